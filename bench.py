@@ -8,7 +8,16 @@ all chains of the rank (re-seeded each time, data and workspaces resident in HBM
 cover seconds of steady-state clocks; per-launch device times (HIP events on the launch stream) are reported as
 min / median / max.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--config 2|3|4|5]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--config 2|3|4|5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` = milliseconds of one timed step, and what the timed launches themselves report).  Everything measured
+or checked beyond that — the legs listed below, sampled clocks, roofline objects — runs only with `--full`.
+
+--dump-outputs DIR: after the timed steps, the results of every analysis of the LAST timed step as DIR/<name>.npy (float64,
+repetition axis in global repetition order; leading axis = the step's launches): what a caller of Plan.fetch receives.  Inputs
+and seeds depend on the arguments only, so two builds can be compared output for output.  Above 64 MB in
+all, a fixed seeded sample of the repetitions is written, with its indices as DIR/rep_index.npy.
 
 `value` is config 2 AS NAMED: one 50-repetition analysis on the chip at a time (one plan, one stream; the next analysis is queued
 while the previous one's results are fetched).  The throughput of a SERIES of data sets — two plans on streams of their own whose
@@ -22,7 +31,7 @@ repetitions (50 / 200 / 400 / 100) are sharded over the ranks (mcsas_amd.dist.sh
 repetition index either way; nothing in an analysis needs another rank (no data-path collective): one all-gather (RCCL)
 after the timed region puts the last analysis together.
 
-Prints ONE JSON line (rank 0); besides the contract's keys: `roofline` (the SURVEY 8d byte model — 40 Q bytes per MC step —
+Prints ONE JSON line (rank 0); with --full, besides the contract's keys: `roofline` (the SURVEY 8d byte model — 40 Q bytes per MC step —
 against the HBM peak for the tick kernels of ONE analysis by themselves: HIP-event time of analyses run alone on one stream,
 `launch_ms_solo`; with the memory-side traffic of the committed FETCH/WRITE passes as `traffic`), `launch_ms` /
 `launch_ms_effective` (per-analysis event times in the timed region, where two streams share the chip, and the timed region
@@ -318,6 +327,43 @@ class DryPlan(object):
         return res
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def last_step_outputs(kept, n_total, use_dist):
+    """--dump-outputs: the results of the last timed step's analyses (`kept`: (launch number, ChainResults)), repetition axis first
+    and in global repetition order (all ranks' blocks put together: called on EVERY rank), stacked over the step's launches."""
+    from mcsas_amd import dist as mdist
+    per_launch = []
+    for _, res in sorted(kept, key=lambda e: e[0]):
+        local = dict(contribs=np.moveaxis(res.contribs, 2, 0), fit=res.fit.T, chisq=res.chisq, scaling=res.scaling,
+                     background=res.background)
+        for name in ("num_iter", "num_moves"):
+            if hasattr(res, name):
+                local[name] = getattr(res, name)
+        local = {k: np.asarray(v, dtype=np.float64) for k, v in local.items()}
+        per_launch.append(mdist.gather_results(local, n_total, force=True) if use_dist else local)
+    return {k: np.stack([d[k] for d in per_launch]) for k in (per_launch[0] if per_launch else {})}
+
+
+def write_outputs(out_dir, outputs, cap=DUMP_CAP_BYTES):
+    """DIR/<name>.npy per array (float64).  Above `cap` bytes in all: the same fixed, seeded sample of repetitions (axis 1) from every
+    array, its indices as DIR/rep_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.size * 8 for a in outputs.values())
+    index_path = os.path.join(out_dir, "rep_index.npy")
+    if total > cap:
+        n_reps = next(iter(outputs.values())).shape[1]
+        keep = max(1, int(n_reps * cap // total))
+        idx = np.sort(np.random.RandomState(20250101).choice(n_reps, keep, replace=False))
+        outputs = {k: a[:, idx] for k, a in outputs.items()}
+        np.save(index_path, idx.astype(np.float64))
+    elif os.path.exists(index_path):
+        os.remove(index_path)
+    for k, a in outputs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -346,6 +392,12 @@ def main():
     ap.add_argument("--no-many-chains", action="store_true", help="skip the wave-per-chain run (8192 chains)")
     ap.add_argument("--inflight", type=int, default=2, help="result slots used per plan (analyses of one plan in flight); 1 = fetch before the next launch")
     ap.add_argument("--dump", default="", help="rank 0: write the gathered arrays of the last launch to this .npz (tests)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0: write the results of every analysis of the last timed step to DIR/<name>.npy (float64, <= 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: clocks, roofline objects, the series / strong-scaling / "
+                         "named-totals / per-config legs, the convergence runs, quick-start, many-chains and the CPU baselines "
+                         "(the --no-* options above select among them)")
     args = ap.parse_args()
 
     world_env = os.environ.get("WORLD_SIZE")
@@ -426,7 +478,9 @@ def main():
     launch_ms = []
     gathered = {}
     pending = []
-    state = {"mc": 0, "res": None, "n": 0, "gather_ms": None}
+    launch_no = {}                                  # (plan, slot) in flight -> its launch number
+    kept = []                                       # --dump-outputs: the results of the last timed step's launches
+    state = {"mc": 0, "res": None, "n": 0, "gather_ms": None, "keep_from": None}
 
     def retire():
         k, slot = pending.pop(0)
@@ -435,13 +489,17 @@ def main():
         launch_ms.append(pl.last_ms)
         state["mc"] += pl.total_steps
         state["res"] = res
+        n = launch_no.pop((k, slot))
+        if state["keep_from"] is not None and n >= state["keep_from"]:
+            kept.append((n, res))
         return res
 
     def one_launch(seed):
         k, slot = lanes[state["n"] % len(lanes)]
-        state["n"] += 1
         while (k, slot) in pending or len(pending) >= len(lanes):   # (a slot's previous analysis must be home before it is written again)
             retire()
+        launch_no[(k, slot)] = state["n"]
+        state["n"] += 1
         pl = plans[k]
         pl.reseed(seed, first)
         if dry:
@@ -489,7 +547,9 @@ def main():
     barrier()
     del launch_ms[:]
     state["mc"] = 0
-    sampler = ClockSampler(dev_index) if (not dry and rank == 0) else None
+    if args.dump_outputs and args.steps > 0:
+        state["keep_from"] = state["n"] + (args.steps - 1) * lps
+    sampler = ClockSampler(dev_index) if (args.full and not dry and rank == 0) else None
     if sampler:
         sampler.__enter__()
     t0 = time.perf_counter()
@@ -504,12 +564,13 @@ def main():
     dt_local = dt
     mc_total, res = state["mc"], state["res"]
     gather_last()
+    outputs = last_step_outputs(kept, n_total, use_dist) if args.dump_outputs else None
     # The dominant kernel by itself, for the roofline objects.  One stream (the default): an analysis' HIP events bracket its own
     # tick kernels only, the per-analysis event times ARE the kernel's.  Several streams (--streams 2): the events bracket the other
     # streams' kernels too, so a few analyses are run ALONE behind the timed region (that is also what the committed rocprofv3
     # passes characterise: tools/profile.sh runs --streams 1 --inflight 1).
     solo_ms = []
-    if not dry and len(plans) > 1:
+    if args.full and not dry and len(plans) > 1:
         for i in range(8):
             plan.reseed(seed + i, first); plan.launch(); plan.fetch(want_arrays=False)
             if i >= 2:
@@ -517,11 +578,11 @@ def main():
     # A SERIES of data sets (gui/calc.py:271-330; mcsas_amd.run_series(overlap=True)): two plans on streams of their own, two result
     # slots each, launch order A0 B0 A1 B1 — an analysis' scan-bound first ticks run beside another's producer-bound last ones.
     series = None
-    if not dry and len(plans) == 1 and world == 1 and args.config == 2 and not args.no_series:
+    if args.full and not dry and len(plans) == 1 and world == 1 and args.config == 2 and not args.no_series:
         series = series_two_streams(engine, torch, setup, q, I, sigma, st, first, seed + 100)
     # Strong scaling of config 2 beside the weak headline: its 50 repetitions IN ALL, sharded over the ranks (6-7 chains per GPU)
     strong = None
-    if not dry and world > 1 and args.config == 2 and args.scaling == "weak":
+    if args.full and not dry and world > 1 and args.config == 2 and args.scaling == "weak":
         f2, r2 = mdist.shard_reps(wl["reps_total"], world, rank)
         st2 = engine.Settings(n_contrib=ncontrib, n_reps=r2, max_iter=mc_steps, conv_crit=0.0, max_retries=0, seed=20250101,
                               rep_offset=f2, device=dev_index, waves_per_chain=args.waves, exec_mode=args.mode)
@@ -548,7 +609,7 @@ def main():
                           "by the per-tick latency of the pipeline (3.1 ms for 7 chains against 3.4 for 50 on one GPU), not by throughput"}
         pl2.close()
     totals = None
-    if args.config == 2 and not args.no_configs and (not dry or os.environ.get("MCSAS_BENCH_DRY_CONFIGS") == "1"):
+    if args.full and args.config == 2 and not args.no_configs and (not dry or os.environ.get("MCSAS_BENCH_DRY_CONFIGS") == "1"):
         totals = named_totals(dev_index, world, rank, use_dist, backend, dry, barrier)
     ranks_seen = 1
     if use_dist:
@@ -563,6 +624,8 @@ def main():
     if rank == 0:
         if args.dump:
             np.savez(args.dump, **gathered)
+        if outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
         lm = np.array(launch_ms) if launch_ms else np.zeros(1)
         overlapped = len(plans) > 1
         launch_eff_s = dt_local / max(len(launch_ms), 1)                               # this rank's timed region / its analyses
@@ -589,11 +652,12 @@ def main():
                                   "span the other streams' kernels as well: effective_ms is the timed region / analyses" % len(plans) if overlapped else
                                   " (one stream: the analysis' own tick kernels)")},
             "launch_ms_effective": launch_eff_s * 1e3,
-            "launch_ms_solo": {"n": len(solo_ms), "mean": float(np.mean(solo_ms)), "min": float(np.min(solo_ms)), "max": float(np.max(solo_ms)),
-                               "note": "analyses run alone on one stream behind the timed region: the kernel time the roofline objects use"} if solo_ms else
-                              {"n": int(len(lm)), "mean": float(lm.mean()), "min": float(lm.min()), "max": float(lm.max()),
-                               "note": "= launch_ms: one stream, an analysis' events bracket its own kernels only"},
         }
+        if args.full:
+            out["launch_ms_solo"] = ({"n": len(solo_ms), "mean": float(np.mean(solo_ms)), "min": float(np.min(solo_ms)), "max": float(np.max(solo_ms)),
+                                      "note": "analyses run alone on one stream behind the timed region: the kernel time the roofline objects use"} if solo_ms else
+                                     {"n": int(len(lm)), "mean": float(lm.mean()), "min": float(lm.min()), "max": float(lm.max()),
+                                      "note": "= launch_ms: one stream, an analysis' events bracket its own kernels only"})
         if sampler:
             out["clocks"] = sampler.summary()
         if state["gather_ms"]:
@@ -609,6 +673,7 @@ def main():
         if not dry:
             out["final_chisq_median"] = float(np.median(res.chisq))
             out["chisq_of_truth"] = wl["chisq_of_truth"]
+        if args.full and not dry:
             # SURVEY 8d streaming model: 40*Q bytes per MC step against the HBM peak.  Chain state (q, I, sigma, ft)
             # actually stays on chip, so this is an algorithmic figure; `traffic` is what the memory-side
             # counters saw for the same command in the committed profile named in `traffic_source`.
@@ -637,21 +702,22 @@ def main():
                                    profile_taken_on_these_kernel_sources=bool(pm) and pm.get("csrc_sha16") == kernel_sources_sha16())
         # outside the timed region: the same repetitions run the way McSAS.analyse runs them — convergenceCriterion 1 (BASELINE),
         # maxIterations 1e5, one attempt — -> final chi² and how many got there, to be read against chisq_of_truth.
-        if not dry and not args.no_convergence_run:
+        full = args.full and not dry
+        if full and not args.no_convergence_run:
             out["convergence_run"] = convergence_run(engine, setup, q, I, sigma, ncontrib, reps, first, dev_index, wl["chisq_of_truth"], args.mode)
-        if not dry and not args.no_convergence_run and world == 1 and args.config == 2:
+        if full and not args.no_convergence_run and world == 1 and args.config == 2:
             out["calc_breakdown"] = calc_breakdown(wl, dev_index)
             out["quickstart"] = quickstart(dev_index)
             out["python_only_model"] = python_only_model(wl, dev_index)
-        if not dry and not args.no_configs and not args.totals_only and world == 1 and args.config == 2:
+        if full and not args.no_configs and not args.totals_only and world == 1 and args.config == 2:
             out["configs"] = other_configs(dev_index)
             for k, e in (totals or {}).items():                  # the named totals on ONE GPU: the denominator of a 1 -> N ratio
                 out["configs"][k]["strong_total"] = e
         elif totals:                                             # N > 1 (or the CPU dry run): configs 3-5 as named, whole node
             out["configs"] = totals
-        if not dry and not args.no_many_chains and not args.no_configs and world == 1 and args.config == 2:
+        if full and not args.no_many_chains and not args.no_configs and world == 1 and args.config == 2:
             out["many_chains"] = many_chains(wl, dev_index)
-        if not dry and not args.no_cpu_baseline and world == 1 and args.config == 2:   # the CPU baseline is timed at N = 1 only
+        if full and not args.no_cpu_baseline and world == 1 and args.config == 2:   # the CPU baseline is timed at N = 1 only
             lo, hi = np.pi / q.max(), np.pi / q.min()
             out["cpu_baseline"] = cpu_baseline(q, I, sigma, lo, hi)
             # BASELINE.md §3 per config: the C oracle timed on each workload's shape and the chains' final chi² GPU vs CPU on identical

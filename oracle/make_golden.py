@@ -1107,6 +1107,77 @@ def gen_moments_edge_cases():
             print("G19", k, out[k])
 
 
+def gen_reference_objects():
+    """G20: what the reference's OWN model objects expose once configured through their own setters (the CONFIGS of
+    tests/test_model_declarations.py): per parameter what setup_from_model reads (value, isActive, valueRange, activeRange,
+    generator), and 64 draws of generateParameters after np.random.seed(5); plus a model of the user's own written against the
+    reference's plug-in API (a SASModel with numpy formfactor / volume: the Guinier law of a sphere) and its calc() on 40 q."""
+    import json
+    sys.path[len(sys.path):] = [os.path.dirname(HERE), os.path.join(os.path.dirname(HERE), "tests")]
+    from test_model_declarations import CONFIGS, _configure
+    from mcsas.bases.algorithm import numbergenerator as refgen
+    classes = {c.__name__: c for c in (Sphere, CylindersIsotropic, EllipsoidalCoreShell, Kholodenko, EllipsoidsIsotropic,
+                                       SphericalCoreShell, GaussianChain, LMADenseSphere)}
+    gens = {n: getattr(refgen, n) for n in ("RandomUniform", "RandomExponential", "RandomExponential2", "RandomExponential3")}
+    flatten = {}
+    for cls in sorted(CONFIGS):
+        active, fixed, gen_over = CONFIGS[cls]
+        m = _configure(classes[cls](), gens, active, fixed, gen_over)
+        plist = []
+        for p in m.params():
+            v = p()
+            e = dict(name=p.name(), value=float(v) if isinstance(v, (int, float, np.integer, np.floating)) else None,
+                     active=bool(p.isActive()) if callable(getattr(p, "isActive", None)) else None)
+            if e["active"]:
+                e["valueRange"] = [float(x) for x in p.valueRange()]
+                e["activeRange"] = [float(x) for x in p.activeRange()]
+                e["generator"] = p.generator().__name__
+            plist.append(e)
+        np.random.seed(5)
+        draws = np.asarray(m.generateParameters(64), dtype=float)
+        flatten[cls] = dict(params=plist, draws=draws.tolist())
+
+    from mcsas.bases.algorithm import RandomExponential
+    from mcsas.utils.parameter import FitParameter, Parameter
+    from mcsas.bases.model import SASModel
+
+    class GuinierSphere(SASModel):
+        shortName = "Guinier sphere (user model)"
+        parameters = (FitParameter("rg", 5e-9, displayName="radius of gyration", generator=RandomExponential,
+                                   valueRange=(1e-10, 1e-6), activeRange=(1e-9, 1e-7)),
+                      Parameter("sld", 1e14, displayName="contrast", valueRange=(0., np.inf)))
+
+        def __init__(self):
+            super(GuinierSphere, self).__init__()
+            self.rg.setActive(True)
+
+        def volume(self):
+            r = self.rg() * np.sqrt(5. / 3.)
+            return (np.pi * 4. / 3.) * r**3
+
+        def absVolume(self):
+            return self.volume() * self.sld()**2
+
+        def formfactor(self, dataset):
+            q = self.getQ(dataset)
+            return np.exp(-(q * self.rg())**2 / 6.)
+
+    GuinierSphere.factory()
+    m = GuinierSphere()
+    m.rg.setActiveRange((2e-9, 5e-8))
+    q_nm = np.logspace(-2, 0.3, 40)
+    d = SASData(title="syn", rawArray=np.stack([q_nm, np.ones(40), 0.01 * np.ones(40)], axis=1))
+    d.config.nBin.setValue(0); d._reBin()
+    pset = np.array([[3e-9], [1e-8], [4.9e-8], [1e-12], [1.0]])       # the last two are clipped by setValue (valueRange)
+    ref = m.calc(d, pset, 0.6666666)
+    host = dict(q=np.asarray(m.getQ(d), dtype=float).tolist(), pset=pset.tolist(), comp_exp=0.6666666,
+                cumInt=np.asarray(ref.cumInt, dtype=float).tolist(), vset=np.asarray(ref.vset, dtype=float).tolist(),
+                wset=np.asarray(ref.wset, dtype=float).tolist())
+    with open(os.path.join(OUT, "g20_reference_objects.json"), "w") as f:
+        json.dump(dict(flatten=flatten, host_model=host), f, indent=1, sort_keys=True)
+    print("G20 written:", ", ".join(flatten))
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     quiet_logging(None)
@@ -1155,3 +1226,5 @@ if __name__ == "__main__":
         gen_moments_edge_cases()
     if "cylradiso" in which or not sys.argv[1:]:
         gen_cyl_radially_isotropic()
+    if "refobjects" in which or not sys.argv[1:]:
+        gen_reference_objects()

@@ -118,14 +118,36 @@ def test_bench_runs_the_named_totals_of_configs_3_to_5_over_the_ranks(tmp_path):
     """`bench.py --gpus N` with the default --config 2 also runs BASELINE's configs 3-5 as they are named — 200 / 400 / 100
     repetitions IN ALL, sharded over the ranks (mcsas.py:214 is the loop being sharded) — and reports them per config with the ranks
     it saw; the N = 1 line carries the same totals on one rank (the denominator of a 1 -> N ratio).  Dry run: no measurement."""
-    one, _ = _run_bench(tmp_path, 1, [], "t1", {"MCSAS_BENCH_DRY_CONFIGS": "1"})
-    two, _ = _run_bench(tmp_path, 2, [], "t2", {"MCSAS_BENCH_DRY_CONFIGS": "1"})
+    one, _ = _run_bench(tmp_path, 1, ["--full"], "t1", {"MCSAS_BENCH_DRY_CONFIGS": "1"})
+    two, _ = _run_bench(tmp_path, 2, ["--full"], "t2", {"MCSAS_BENCH_DRY_CONFIGS": "1"})
     for k, total in (("3", 200), ("4", 400), ("5", 100)):
         a, b = one["configs"][k], two["configs"][k]
         assert a["reps_total"] == b["reps_total"] == total and a["scaling"] == b["scaling"] == "strong"
         assert a["ranks_seen"] == 1 and a["reps_rank0"] == total
         assert b["ranks_seen"] == 2 and b["reps_rank0"] == total // 2 and b["n_gpus"] == 2
         assert a["value"] is None and b["value"] is None               # dry run: never a measurement
+
+
+def test_bench_dump_outputs_are_the_last_steps_analyses(tmp_path):
+    """--dump-outputs DIR: every analysis of the LAST timed step as DIR/<name>.npy (float64, repetition axis first in global order,
+    leading axis = the step's launches); the same arguments write the same arrays, 2 ranks write what 1 rank writes, and the last
+    entry is the last launch (--dump).  A plain run carries none of the --full legs."""
+    runs = {}
+    for tag, gpus in (("a", 1), ("b", 1), ("c", 2)):
+        d = tmp_path / ("out_" + tag)
+        line, last = _run_bench(tmp_path, gpus, ["--scaling", "strong", "--launches-per-step", "3", "--dump-outputs", str(d)], tag,
+                                {"MCSAS_BENCH_DRY_CONFIGS": "1"})
+        assert "configs" not in line and line["steps"] == 2 and line["ms_per_step"] > 0
+        runs[tag] = ({f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))}, last)
+    a, last = runs["a"]
+    assert set(a) == {"contribs", "fit", "chisq", "scaling", "background"}
+    assert a["contribs"].shape == (3, 50, 400, 1) and a["fit"].shape == (3, 50, 512) and a["chisq"].shape == (3, 50)
+    assert all(v.dtype == np.float64 for v in a.values())
+    for k in a:
+        np.testing.assert_array_equal(a[k][-1], last[k].reshape(a[k][-1].shape))
+        assert not np.array_equal(a[k][0], a[k][-1])                  # three different analyses, not one written three times
+        for other in ("b", "c"):
+            np.testing.assert_array_equal(a[k], runs[other][0][k])
 
 
 def test_bench_refuses_a_world_size_it_was_not_asked_for(tmp_path):

@@ -2,14 +2,14 @@
 
 (1) tests/golden/g10_param_decls.json — written by oracle/make_golden.py from the imported reference: per model
     class every parameter's name, default, valueRange, activeRange, generator and active flag
-    (models/*.py, utils/parameter.py:577-743, bases/algorithm/parameter.py:420-433).  Runs everywhere.
-(2) In the build container only (skipped when /root/reference is absent, e.g. on the GPU box): the reference's
-    OWN model instances, configured through their own setters, go through mcsas_amd's duck-typed
-    `setup_from_model` — the binding INTEGRATION.md describes — and must flatten to the same mcsas_problem
-    fields as the mirror classes configured the same way (bases/model/scatteringmodel.py:117-127)."""
+    (models/*.py, utils/parameter.py:577-743, bases/algorithm/parameter.py:420-433).
+(2) tests/golden/g20_reference_objects.json (oracle/make_golden.py gen_reference_objects): the reference's OWN model
+    instances, configured through their own setters, as mcsas_amd's duck-typed `setup_from_model` — the binding
+    INTEGRATION.md describes — sees them (value, isActive, valueRange, activeRange, generator per parameter).  Stand-ins
+    answering exactly that must flatten to the same mcsas_problem fields as the mirror classes configured the same way
+    (bases/model/scatteringmodel.py:117-127); and the reference's calc() of a model that exists only as Python."""
 import json
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -44,38 +44,39 @@ def test_mirror_declarations_equal_the_reference(cls):
 
 
 # ------------------------------------------------------------------------------------------------------------
-REF_SRC = "/root/reference/src"
+REFOBJ = json.load(open(os.path.join(HERE, "golden", "g20_reference_objects.json")))
 
 
-def _import_reference():
-    """The reference package with the three third-party import stand-ins of SURVEY.md Appendix A."""
-    if not os.path.isdir(REF_SRC):
-        pytest.skip("reference not present (it never travels to the GPU box)")
-    import tempfile
-    d = tempfile.mkdtemp(prefix="mcsas_shim_")
-    os.makedirs(os.path.join(d, "future"))
-    open(os.path.join(d, "future", "__init__.py"), "w").close()
-    with open(os.path.join(d, "future", "standard_library.py"), "w") as f:
-        f.write("def install_aliases(): pass\n")
-    with open(os.path.join(d, "future", "utils.py"), "w") as f:
-        f.write("def with_metaclass(meta, *bases):\n"
-                "    class metaclass(type):\n"
-                "        def __new__(cls, name, this_bases, d): return meta(name, bases, d)\n"
-                "        @classmethod\n"
-                "        def __prepare__(cls, name, this_bases): return meta.__prepare__(name, bases)\n"
-                "    return type.__new__(metaclass, 'temporary_class', (), {})\n")
-    with open(os.path.join(d, "QtWidgets.py"), "w") as f:
-        f.write("class QApplication(object):\n"
-                "    @staticmethod\n"
-                "    def processEvents(): pass\n"
-                "    @staticmethod\n"
-                "    def translate(ctx, s): return s\n")
-    sys.dont_write_bytecode = True
-    sys.path[:0] = [d, REF_SRC]
-    import logging
-    logging.disable(logging.WARNING)
-    import mcsas.models.sphere                      # noqa: F401  (ordinary import errors fail the test loudly)
-    return d
+class _RecordedParameter(object):
+    """A reference parameter object as setup_from_model sees it: p(), name(), isActive(), valueRange(), activeRange(),
+    generator().__name__ — the answers its configured instance gave (G20)."""
+
+    def __init__(self, e):
+        self.e = e
+
+    def __call__(self):
+        return self.e["value"]
+
+    def name(self):
+        return self.e["name"]
+
+    def isActive(self):
+        return bool(self.e["active"])
+
+    def valueRange(self):
+        return tuple(self.e["valueRange"])
+
+    def activeRange(self):
+        return tuple(self.e["activeRange"])
+
+    def generator(self):
+        return type(str(self.e["generator"]), (object,), {})
+
+
+def _recorded_model(cls):
+    """An object of the reference's class name whose params() are the recorded parameters."""
+    params = [_RecordedParameter(e) for e in REFOBJ["flatten"][cls]["params"]]
+    return type(cls, (object,), {"params": lambda self: params})()
 
 
 CONFIGS = {
@@ -108,17 +109,9 @@ def _configure(m, gens, active, fixed, gen_over):
 
 @pytest.mark.parametrize("cls", sorted(CONFIGS))
 def test_reference_model_objects_flatten_like_the_mirror(cls):
-    _import_reference()
-    import importlib
-    from mcsas.bases.algorithm import numbergenerator as refgen
-    modname = {"Sphere": "sphere", "CylindersIsotropic": "cylindersisotropic", "EllipsoidalCoreShell": "ellipsoidalcoreshell",
-               "Kholodenko": "kholodenko", "EllipsoidsIsotropic": "ellipsoidsisotropic", "SphericalCoreShell": "sphericalcoreshell",
-               "GaussianChain": "gaussianchain", "LMADenseSphere": "lmadensesphere"}[cls]
-    RefCls = getattr(importlib.import_module("mcsas.models." + modname), cls)
     active, fixed, gen_over = CONFIGS[cls]
-    ref_gens = {n: getattr(refgen, n) for n in ("RandomUniform", "RandomExponential", "RandomExponential2", "RandomExponential3")}
-    our_gens = {n: getattr(mcsas_amd, n) for n in ref_gens}
-    ref_model = _configure(RefCls(), ref_gens, active, fixed, gen_over)
+    our_gens = {n: getattr(mcsas_amd, n) for n in ("RandomUniform", "RandomExponential", "RandomExponential2", "RandomExponential3")}
+    ref_model = _recorded_model(cls)
     our_model = _configure(getattr(SM, cls)(), our_gens, active, fixed, gen_over)
 
     class X0:                                           # startFromMinimum needs data.x0.limit (mcsas.py:311-315)
@@ -126,14 +119,14 @@ def test_reference_model_objects_flatten_like_the_mirror(cls):
 
     class D:
         x0 = X0()
-    a = SM.setup_from_model(ref_model, D())            # the reference's own instance, duck-typed
+    a = SM.setup_from_model(ref_model, D())            # the reference's own instance (as recorded), duck-typed
     b = our_model.setup(D())
     assert a.model_id == b.model_id and a.active_index == b.active_index and a.gen_kind == b.gen_kind
     for f in ("params", "gen_lo", "gen_hi", "clip_lo", "clip_hi", "start_value"):
         np.testing.assert_array_equal(getattr(a, f), getattr(b, f), err_msg="%s.%s" % (cls, f))
-    # and the reference's generateParameters draws inside the range the kernels are given
-    np.random.seed(5)
-    g = np.asarray(ref_model.generateParameters(64), dtype=float)
+    # and the reference's generateParameters (np.random.seed(5), 64 sets) draws inside the range the kernels are given
+    g = np.asarray(REFOBJ["flatten"][cls]["draws"], dtype=float)
+    assert g.shape == (64, len(active))
     assert (g >= a.gen_lo).all() and (g <= a.gen_hi).all()
 
 
@@ -142,20 +135,16 @@ def test_a_reference_model_that_exists_only_as_python_runs_through_host_rows():
     volume() / absVolume() and nothing else (bases/model/scatteringmodel.py:16-58, sasmodel.py:37-79; here the Guinier law of a
     sphere, which no built-in kernel has) — flattens to the host-rows path (engine.MODEL_HOST: mcsas_hip_analyse_host_rows), and
     the row evaluation the library will call back (scatteringmodels.host_model_calc: set values, calcIntensity, restore) gives
-    the reference's own model.calc() bit for bit and leaves the model's parameter values where they were."""
-    _import_reference()
+    the reference's own model.calc() of the same class (G20) bit for bit and leaves the model's parameter values where they were."""
     import numpy
-    from mcsas.bases.algorithm import RandomExponential
-    from mcsas.utils.parameter import FitParameter, Parameter
-    from mcsas.bases.model import SASModel
-    from mcsas.dataobj.sasdata import SASData
+    from mcsas_amd import RandomExponential, FitParameter, Parameter, SASModel
     from mcsas_amd import engine
 
     class GuinierSphere(SASModel):
         shortName = "Guinier sphere (user model)"
-        parameters = (FitParameter("rg", 5e-9, displayName="radius of gyration", generator=RandomExponential,
-                                   valueRange=(1e-10, 1e-6), activeRange=(1e-9, 1e-7)),
-                      Parameter("sld", 1e14, displayName="contrast", valueRange=(0., numpy.inf)))
+        parameters = (lambda: FitParameter("rg", 5e-9, displayName="radius of gyration", generator=RandomExponential,
+                                           valueRange=(1e-10, 1e-6), activeRange=(1e-9, 1e-7)),     # (the mirror declares factories)
+                      lambda: Parameter("sld", 1e14, displayName="contrast", valueRange=(0., numpy.inf)))
 
         def __init__(self):
             super(GuinierSphere, self).__init__()
@@ -172,21 +161,21 @@ def test_a_reference_model_that_exists_only_as_python_runs_through_host_rows():
             q = self.getQ(dataset)
             return numpy.exp(-(q * self.rg())**2 / 6.)
 
-    GuinierSphere.factory()
     m = GuinierSphere()
     m.rg.setActiveRange((2e-9, 5e-8))
     assert SM.is_host_model(m)
     setup = SM.setup_from_model(m)
     assert setup.model_id == engine.MODEL_HOST and setup.active_index == (0,) and setup.gen_kind == (1,)
     np.testing.assert_array_equal(setup.gen_lo, [2e-9]); np.testing.assert_array_equal(setup.gen_hi, [5e-8])
-    q_nm = np.logspace(-2, 0.3, 40)
-    d = SASData(title="syn", rawArray=np.stack([q_nm, np.ones(40), 0.01 * np.ones(40)], axis=1))
-    d.config.nBin.setValue(0); d._reBin()
-    pset = np.array([[3e-9], [1e-8], [4.9e-8], [1e-12], [1.0]])       # the last two are clipped by setValue (valueRange)
+    ref = REFOBJ["host_model"]
+    q = np.array(ref["q"])
+    d = mcsas_amd.SASData(q, np.ones(40), 0.01 * np.ones(40))
+    np.testing.assert_array_equal(m.getQ(d), q)
+    pset = np.array(ref["pset"])                                       # the last two are clipped by setValue (valueRange)
+    assert pset.shape == (5, 1) and pset[3, 0] == 1e-12 and pset[4, 0] == 1.0
     before = m.rg()
-    ref = m.calc(d, pset, 0.6666666)                                   # the reference's own ScatteringModel.calc
-    cum, v, w, s_, rows = SM.host_model_calc(m, d, pset, 0.6666666, want_rows=True)
+    cum, v, w, s_, rows = SM.host_model_calc(m, d, pset, ref["comp_exp"], want_rows=True)
     assert m.rg() == before
-    np.testing.assert_array_equal(cum, ref.cumInt); np.testing.assert_array_equal(v, ref.vset); np.testing.assert_array_equal(w, ref.wset)
+    np.testing.assert_array_equal(cum, ref["cumInt"]); np.testing.assert_array_equal(v, ref["vset"]); np.testing.assert_array_equal(w, ref["wset"])
     assert rows.shape == (5, 40) and np.isfinite(rows).all()
-    np.testing.assert_array_equal(rows[3], SM.host_model_calc(m, d, [[1e-10]], 0.6666666, want_rows=True)[4][0])   # clipped to the range's edge
+    np.testing.assert_array_equal(rows[3], SM.host_model_calc(m, d, [[1e-10]], ref["comp_exp"], want_rows=True)[4][0])   # clipped to the range's edge

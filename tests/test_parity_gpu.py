@@ -1974,7 +1974,7 @@ def test_bench_named_totals_go_through_rccl(tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "MCSAS_BENCH_DRY", "MCSAS_BENCH_BACKEND"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--launches-per-step", "2",
-           "--mc-steps", "2000", "--no-cpu-baseline", "--no-convergence-run", "--no-series", "--no-many-chains", "--totals-only"]
+           "--mc-steps", "2000", "--no-cpu-baseline", "--no-convergence-run", "--no-series", "--no-many-chains", "--totals-only", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
