@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MCSAS_ABI_VERSION 4
+#define MCSAS_ABI_VERSION 5
 #define MCSAS_MAX_ACTIVE 4   /* active (fitted) parameters per contribution: columns of rset */
 #define MCSAS_MAX_PARAMS 8   /* full parameter vector of a model */
 #define MCSAS_MAX_DEVICES 16 /* devices one mcsas_hip_analyse call may spread its repetitions over */
@@ -239,6 +239,26 @@ int  mcsas_hip_plan_info(mcsas_plan *plan, int32_t info[8]);
 /* change seed / rep_offset between launches without re-uploading anything else */
 int  mcsas_hip_plan_reseed(mcsas_plan *plan, uint64_t seed, int32_t rep_offset);
 void mcsas_hip_plan_destroy(mcsas_plan *plan);
+
+/* ---- several analyses in one launch (ABI 5): a series of data sets (gui/calc.py:271-379) --------------------------------
+ * A series fits the same model with the same settings to many data sets, each with a few repetitions: too few chains per
+ * analysis to fill the chip one wavefront per chain.  The chains of different analyses share nothing, so a batch runs them
+ * together: one launch of the wavefront-per-chain kernel per group of analyses with the same kernel (model, q slots per lane,
+ * row cache), block b = one repetition of one analysis, reading that analysis' own argument block.
+ * mcsas_hip_plan_launch_batch: enqueues the n resident plans on `hip_stream` (slot 0 of each; it first waits for any earlier
+ *   analysis of a plan that is still in flight, as mcsas_hip_plan_launch does).  Every plan must be on the same device, must
+ *   have resolved to MCSAS_EXEC_WAVE, and all must carry the same `stop` pointer (or all NULL); a plan may appear once.
+ *   Otherwise MCSAS_EINVAL and nothing is launched.  The chains of the whole batch watch ONE stop word: a stop forwarded by
+ *   the fetch of any plan of the batch ends every chain.  Afterwards each plan is fetched on its own (mcsas_hip_plan_fetch);
+ *   _last_ms is the device time of its group's launch, _total_steps its own steps; mcsas_hip_plan_reseed between launches holds.
+ * mcsas_hip_analyse_batch: the one-shot form: problems[i] -> results[i] (each sized as for mcsas_hip_analyse).  exec_mode AUTO
+ *   means wave here; PIPELINE / WORKGROUP, n_devices > 1 or nq > 4096 give MCSAS_EINVAL before anything is launched.  A problem
+ *   with n_active == 0 is answered at its place exactly as mcsas_hip_analyse answers it.
+ * Contract: results[i] is IDENTICAL to mcsas_hip_analyse of problems[i] with exec_mode = MCSAS_EXEC_WAVE (same seed /
+ * rep_offset / replay stream): contribs, fit, chisq, scaling, background, num_iter, num_moves, attempts, converged, draws —
+ * whatever the other problems of the batch and their order.  Only `seconds` differs. */
+int mcsas_hip_plan_launch_batch(mcsas_plan *const *plans, int32_t n, void *hip_stream);
+int mcsas_hip_analyse_batch(const mcsas_problem *problems, int32_t n, mcsas_result *results);
 
 /* ---- ScatteringModel.calc(data, pset, compensationExponent) (scatteringmodel.py:79-109) ------
  * Uses problem->{model_id, params, n_active, active_index, clip_*, nq, q, comp_exp, device}.

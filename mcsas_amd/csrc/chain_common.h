@@ -64,6 +64,9 @@ struct ChainArgs {
     ChainOut *out;                     // [n_reps]
 };
 
+// one chain of a batch launch (chain_wave_batch_kernel): repetition `rep` of the analysis whose argument block is sets[set]
+struct ChainRef { int32_t set, rep; };
+
 // McSAS.stop (mcsas.py:357: polled once per step).  The caller's word lives in host memory, and a read of it crosses the host link:
 // microseconds each, served one at a time — 8192 chains looking every 64 steps were measured to spend HALF of a launch queued
 // up on those reads (3.7e8 instead of 7.5e8 steps/s, whatever the q count).  So the chains look at a word in device memory (an L2

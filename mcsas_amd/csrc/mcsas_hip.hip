@@ -460,6 +460,13 @@ static int plugin_wave_function(int model_id, int qpl, bool cache, hipFunction_t
     return plugin_function(model_id, k, {e}, e, fn);
 }
 
+static int plugin_wave_batch_function(int model_id, int qpl, bool cache, hipFunction_t *fn) {
+    char e[128], k[32];
+    snprintf(e, sizeof e, "mcsas::chain_wave_batch_kernel<MCSAS_MODEL_PLUGIN, %d, %s>", qpl, cache ? "true" : "false");
+    snprintf(k, sizeof k, "wave batch %d %d", qpl, cache ? 1 : 0);
+    return plugin_function(model_id, k, {e}, e, fn);
+}
+
 // launch of small kernel `which` (PLUGIN_SMALL_EXPRS) of a plug-in on the null stream; the arguments are passed by address,
 // so their types must be the kernel's parameter types exactly
 template <class... A>
@@ -718,6 +725,25 @@ struct DevPool {
     void release() { for (auto &b : blocks) cached_dev_free(b.first, b.second, dev); blocks.clear(); cur = nullptr; left = 0; }
 };
 
+// What the analyses of one mcsas_hip_plan_launch_batch share, in one device block: the stop relay (one for the whole batch: a relay
+// per analysis would multiply the chains' reads of host memory, chain_common.h: stop_requested), the argument blocks of the analyses
+// and the chain table of the batch kernel, plus the pinned host word McSAS.stop is forwarded into and the staging copy of the block.
+// Every plan of the batch holds a reference; a plan gives it up only once its own analysis is over (plan destroyed or launched
+// again), so the last reference goes when every group of the batch has ended.
+struct BatchShared {
+    int dev = 0;
+    size_t bytes = 0;
+    char *d_block = nullptr;            // [0, 256): relay; then ChainArgs[n]; then ChainRef[chains]
+    char *h_block = nullptr;            // pinned staging copy of d_block (the upload is asynchronous)
+    int32_t *h_stop = nullptr;          // pinned + mapped
+    ~BatchShared() {
+        if (d_block) cached_dev_free(d_block, bytes, dev);
+        cached_host_free(h_block, bytes, hipHostMallocDefault);
+        cached_host_free(h_stop, sizeof(int32_t), hipHostMallocMapped);
+    }
+};
+static int32_t *batch_stop_word(BatchShared *b) { return b->h_stop; }
+
 struct mcsas_plan {
     DevPool pool;
     mcsas_problem prob;
@@ -774,6 +800,8 @@ struct mcsas_plan {
     };
     Slot slots[MCSAS_PLAN_SLOTS];
     int cur_slot = 0;
+    // the batch (mcsas_hip_plan_launch_batch) whose launch wrote slot k, or null: its stop word is the one fetch() forwards to
+    std::shared_ptr<struct BatchShared> batch_of[MCSAS_PLAN_SLOTS];
 };
 
 // make slot k the plan's active view (allocating it on first use)
@@ -807,7 +835,7 @@ static int plan_activate_slot(mcsas_plan *pl, int k) {
 }
 
 // kernel lookups, one translation unit per model (kern_wave.hip / kern_wg.hip)
-#define DECL_K(m) void *mcsas_wave_kernel_m##m(int, bool); void *mcsas_wg_kernel_m##m(int); void *mcsas_wide_kernel_m##m(int); void *mcsas_pipe_tick_kernel_m##m(int, bool);
+#define DECL_K(m) void *mcsas_wave_kernel_m##m(int, bool); void *mcsas_wave_batch_kernel_m##m(int, bool); void *mcsas_wg_kernel_m##m(int); void *mcsas_wide_kernel_m##m(int); void *mcsas_pipe_tick_kernel_m##m(int, bool);
 MCSAS_FOR_MODELS(DECL_K)
 #undef DECL_K
 void *mcsas_pipe_reset_kernel();
@@ -824,6 +852,14 @@ static void *pipe_tick_kernel_for(int model, int qpl, bool rowq) {
 static void *wave_kernel_for(int model, int qpl, bool cache) {
     switch (model) {
 #define CASE_K(m) case m: return mcsas_wave_kernel_m##m(qpl, cache);
+        MCSAS_FOR_MODELS(CASE_K)
+#undef CASE_K
+        default: return nullptr;
+    }
+}
+static void *wave_batch_kernel_for(int model, int qpl, bool cache) {
+    switch (model) {
+#define CASE_K(m) case m: return mcsas_wave_batch_kernel_m##m(qpl, cache);
         MCSAS_FOR_MODELS(CASE_K)
 #undef CASE_K
         default: return nullptr;
@@ -1294,6 +1330,7 @@ extern "C" int mcsas_hip_plan_launch_slot(mcsas_plan *pl, void *hip_stream, int3
     for (int k = 0; k < MCSAS_PLAN_SLOTS; ++k)
         if (k != pl->cur_slot && pl->slots[k].made && pl->slots[k].launched && pl->slots[k].ev1) HIPCHK(hipStreamWaitEvent(st, pl->slots[k].ev1, 0));
     if (pl->launched && pl->ev1) HIPCHK(hipEventSynchronize(pl->ev1));
+    pl->batch_of[pl->cur_slot].reset();
     *pl->h_stop = (pl->prob.stop && *pl->prob.stop) ? 1 : 0;
     pl->stream = st;
     if (pl->mode != MCSAS_EXEC_PIPELINE) HIPCHK(hipMemsetAsync(pl->d_stop_relay, 0, 16, st));   // (the pipeline's ticks get McSAS.stop as a kernel argument)
@@ -1364,11 +1401,12 @@ extern "C" int mcsas_hip_plan_fetch_slot(mcsas_plan *pl, int32_t slot, mcsas_res
     DeviceGuard dev_guard;
     HIPCHK(hipSetDevice(pl->dev));
     // wait, forwarding the caller's stop word to the device-visible one (McSAS.stop, mcsas.py:357)
+    int32_t *const h_stop = pl->batch_of[pl->cur_slot] ? batch_stop_word(pl->batch_of[pl->cur_slot].get()) : pl->h_stop;
     while (pl->prob.stop) {                              // (no stop word: nothing to forward, plain wait below)
         hipError_t q = hipEventQuery(pl->ev1);
         if (q == hipSuccess) break;
         if (q != hipErrorNotReady) return fail(MCSAS_EHIP, "kernel failed: %s", hipGetErrorString(q));
-        if (*pl->prob.stop) *pl->h_stop = 1;
+        if (*pl->prob.stop) *h_stop = 1;
         std::this_thread::sleep_for(std::chrono::microseconds(50));
     }
     HIPCHK(hipEventSynchronize(pl->ev1));
@@ -1471,6 +1509,159 @@ extern "C" int mcsas_hip_plan_last_ms(mcsas_plan *pl, double *ms) {
 extern "C" int mcsas_hip_plan_total_steps(mcsas_plan *pl, int64_t *steps) {
     if (!pl || !steps) return fail(MCSAS_EINVAL, "null argument");
     *steps = pl->last_steps;
+    return MCSAS_OK;
+}
+
+// ------------------------------------------------------------------------------ several analyses in one launch
+// One chain_wave_batch_kernel launch per group of plans that run the same kernel (model, q slots per lane, row cache): block b runs
+// chain table entry b, i.e. one repetition of one plan, with that plan's own argument block.  A chain computes exactly what it
+// computes in the plan's own launch; the plans only share the launch and the stop relay.
+extern "C" int mcsas_hip_plan_launch_batch(mcsas_plan *const *plans, int32_t n, void *hip_stream) {
+    if (!plans || n < 1) return fail(MCSAS_EINVAL, "launch_batch: needs n >= 1 plans (n = %d)", (int)n);
+    for (int i = 0; i < n; ++i) {
+        const mcsas_plan *pl = plans[i];
+        if (!pl) return fail(MCSAS_EINVAL, "launch_batch: plan %d is null", i);
+        if (pl->mode != MCSAS_EXEC_WAVE || pl->wide)
+            return fail(MCSAS_EINVAL, "launch_batch: plan %d runs in exec_mode %d; a batch takes wavefront-per-chain plans only (exec_mode %d)", i, pl->mode, MCSAS_EXEC_WAVE);
+        if (pl->dev != plans[0]->dev) return fail(MCSAS_EINVAL, "launch_batch: plan %d is on device %d, plan 0 on device %d", i, pl->dev, plans[0]->dev);
+        if (pl->prob.stop != plans[0]->prob.stop) return fail(MCSAS_EINVAL, "launch_batch: plan %d has another stop word than plan 0 (all plans of a batch share one, or none has one)", i);
+        for (int j = 0; j < i; ++j)
+            if (plans[j] == pl) return fail(MCSAS_EINVAL, "launch_batch: plan %d is plan %d again", i, j);
+    }
+    DeviceGuard dev_guard;
+    HIPCHK(hipSetDevice(plans[0]->dev));
+    hipStream_t st = (hipStream_t)hip_stream;
+    // the kernel of every plan; groups in order of first appearance
+    std::vector<const void *> fn_of(n);
+    std::vector<int> group_of(n);
+    std::vector<const void *> groups;
+    for (int i = 0; i < n; ++i) {
+        mcsas_plan *pl = plans[i];
+        if (pl->plugin_fn) {
+            hipFunction_t f = nullptr;
+            int rc = plugin_wave_batch_function(pl->prob.model_id, pl->qpl, pl->use_cache != 0, &f);      // (compiled on first use)
+            if (rc) return rc;
+            fn_of[i] = (const void *)f;
+        } else {
+            fn_of[i] = wave_batch_kernel_for(pl->prob.model_id, pl->qpl, pl->use_cache != 0);
+            if (!fn_of[i]) return fail(MCSAS_EINVAL, "launch_batch: no batch kernel for model %d qpl %d", pl->prob.model_id, pl->qpl);
+        }
+        group_of[i] = (int)(std::find(groups.begin(), groups.end(), fn_of[i]) - groups.begin());
+        if (group_of[i] == (int)groups.size()) groups.push_back(fn_of[i]);
+    }
+    // every plan's earlier analyses must be over before its workspaces are written again (as mcsas_hip_plan_launch_slot)
+    for (int i = 0; i < n; ++i) {
+        mcsas_plan *pl = plans[i];
+        int rcs = plan_activate_slot(pl, 0);
+        if (rcs) return rcs;
+        for (int k = 1; k < MCSAS_PLAN_SLOTS; ++k)
+            if (pl->slots[k].made && pl->slots[k].launched && pl->slots[k].ev1) HIPCHK(hipStreamWaitEvent(st, pl->slots[k].ev1, 0));
+        if (pl->launched && pl->ev1) HIPCHK(hipEventSynchronize(pl->ev1));
+    }
+    // the shared block: relay, argument blocks, chain table (group-major, plans in list order, repetitions in order)
+    size_t n_chains = 0;
+    for (int i = 0; i < n; ++i) n_chains += (size_t)plans[i]->prob.n_reps;
+    if (n_chains > 0x7fffffffull) return fail(MCSAS_EINVAL, "launch_batch: %zu chains", n_chains);
+    const size_t off_sets = 256, off_chains = off_sets + (sizeof(ChainArgs) * (size_t)n + 255) / 256 * 256;
+    auto bs = std::make_shared<BatchShared>();
+    bs->dev = plans[0]->dev;
+    bs->bytes = off_chains + sizeof(ChainRef) * n_chains;
+    HIPCHK(cached_dev_malloc((void **)&bs->d_block, bs->bytes));
+    HIPCHK(cached_host_malloc((void **)&bs->h_block, bs->bytes, hipHostMallocDefault));
+    HIPCHK(cached_host_malloc((void **)&bs->h_stop, sizeof(int32_t), hipHostMallocMapped));
+    const volatile int32_t *stop = plans[0]->prob.stop;
+    *bs->h_stop = (stop && *stop) ? 1 : 0;
+    int32_t *d_stop = nullptr;
+    HIPCHK(hipHostGetDevicePointer((void **)&d_stop, bs->h_stop, 0));
+    // the relay starts as the stop word is now: a stop set before the launch is seen by every chain at its first poll (through the
+    // host word alone only the chain that reads it would, the others one poll later)
+    memset(bs->h_block, 0, off_sets);
+    ((int32_t *)bs->h_block)[0] = *bs->h_stop;
+    ChainArgs *h_sets = (ChainArgs *)(bs->h_block + off_sets);
+    ChainRef *h_chains = (ChainRef *)(bs->h_block + off_chains);
+    for (int i = 0; i < n; ++i) {
+        h_sets[i] = plans[i]->args;                                          // (slot 0's outputs, the plan's seed / rep_offset)
+        h_sets[i].stop_flag = d_stop;
+        h_sets[i].stop_relay = (int32_t *)bs->d_block;
+    }
+    std::vector<size_t> g_first(groups.size() + 1, 0), g_lds(groups.size(), 0);
+    for (int i = 0; i < n; ++i) {
+        g_first[group_of[i] + 1] += (size_t)plans[i]->prob.n_reps;
+        g_lds[group_of[i]] = std::max(g_lds[group_of[i]], plans[i]->lds_bytes);
+    }
+    for (size_t g = 0; g < groups.size(); ++g) g_first[g + 1] += g_first[g];
+    {
+        std::vector<size_t> fill(g_first.begin(), g_first.end() - 1);
+        for (int i = 0; i < n; ++i)
+            for (int r = 0; r < plans[i]->prob.n_reps; ++r) h_chains[fill[group_of[i]]++] = ChainRef{i, r};
+    }
+    struct FailGuard {                                    // (an error return below may leave work on `st` that no end event covers)
+        mcsas_plan *const *plans; int n; bool ok = false;
+        ~FailGuard() { if (!ok) for (int i = 0; i < n; ++i) plans[i]->enqueue_failed = true; }
+    } guard{plans, n};
+    for (int i = 0; i < n; ++i) { plans[i]->stream = st; plans[i]->batch_of[0] = bs; }
+    HIPCHK(hipMemcpyAsync(bs->d_block, bs->h_block, bs->bytes, hipMemcpyHostToDevice, st));
+    const ChainArgs *d_sets = (const ChainArgs *)(bs->d_block + off_sets);
+    for (size_t g = 0; g < groups.size(); ++g) {
+        const ChainRef *d_chains = (const ChainRef *)(bs->d_block + off_chains) + g_first[g];
+        const unsigned grid = (unsigned)(g_first[g + 1] - g_first[g]);
+        void *kargs[] = {(void *)&d_sets, (void *)&d_chains};
+        for (int i = 0; i < n; ++i) if (group_of[i] == (int)g) HIPCHK(hipEventRecord(plans[i]->ev0, st));
+        int first = 0;
+        while (group_of[first] != (int)g) ++first;
+        if (plans[first]->plugin_fn) {
+            HIPCHK(hipModuleLaunchKernel((hipFunction_t)groups[g], grid, 1, 1, WAVE, 1, 1, (unsigned)g_lds[g], st, kargs, nullptr));
+        } else {
+            if (g_lds[g] > 64 * 1024) HIPCHK(hipFuncSetAttribute(groups[g], hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_lds[g]));
+            HIPCHK(hipLaunchKernel(groups[g], dim3(grid), dim3(WAVE), kargs, g_lds[g], st));
+        }
+        for (int i = 0; i < n; ++i)
+            if (group_of[i] == (int)g) { HIPCHK(hipEventRecord(plans[i]->ev1, st)); plans[i]->launched = true; }
+    }
+    guard.ok = true;
+    return MCSAS_OK;
+}
+
+// One-shot form: plans in the wavefront-per-chain mode for every problem, one batch launch, results at their places.
+extern "C" int mcsas_hip_analyse_batch(const mcsas_problem *problems, int32_t n, mcsas_result *results) {
+    if (!problems || !results || n < 1) return fail(MCSAS_EINVAL, "analyse_batch: needs n >= 1 problems and results (n = %d)", (int)n);
+    for (int i = 0; i < n; ++i) {
+        const mcsas_problem *p = &problems[i];
+        if (p->struct_size != sizeof(mcsas_problem)) return fail(MCSAS_EINVAL, "analyse_batch: problem %d: mcsas_problem size %u, library expects %zu (ABI mismatch)", i, p->struct_size, sizeof(mcsas_problem));
+        if (results[i].struct_size != sizeof(mcsas_result)) return fail(MCSAS_EINVAL, "analyse_batch: result %d: mcsas_result size mismatch", i);
+        if (p->n_active == 0) continue;                                       // answered at its place below, as mcsas_hip_analyse does
+        if (p->exec_mode != MCSAS_EXEC_AUTO && p->exec_mode != MCSAS_EXEC_WAVE)
+            return fail(MCSAS_EINVAL, "analyse_batch: problem %d asks for exec_mode %d; a batch runs one wavefront per chain (exec_mode 0 or 1)", i, p->exec_mode);
+        if (p->n_devices > 1) return fail(MCSAS_EINVAL, "analyse_batch: problem %d spreads over %d devices; a batch runs on one", i, p->n_devices);
+        if (p->nq > 64 * WAVE) return fail(MCSAS_EINVAL, "analyse_batch: problem %d has nq %d > %d (one wavefront per chain)", i, p->nq, 64 * WAVE);
+    }
+    std::vector<mcsas_plan *> plans;
+    std::vector<int> index;
+    int rc = MCSAS_OK;
+    for (int i = 0; i < n && !rc; ++i) {
+        if (problems[i].n_active == 0) continue;
+        mcsas_problem p = problems[i];
+        p.exec_mode = MCSAS_EXEC_WAVE;
+        p.n_devices = 0;
+        mcsas_plan *pl = nullptr;
+        rc = mcsas_hip_plan_create(&p, &pl);
+        if (rc) { std::string e = g_err; rc = fail(rc, "analyse_batch: problem %d: %s", i, e.c_str()); break; }
+        plans.push_back(pl); index.push_back(i);
+    }
+    if (!rc && !plans.empty()) rc = mcsas_hip_plan_launch_batch(plans.data(), (int32_t)plans.size(), nullptr);
+    if (!rc) {
+        for (size_t k = 0; k < plans.size(); ++k) {
+            const int rk = mcsas_hip_plan_fetch(plans[k], &results[index[k]]);
+            if (rk && !rc) { std::string e = g_err; rc = fail(rk, "analyse_batch: problem %d: %s", index[k], e.c_str()); }
+        }
+    }
+    for (mcsas_plan *pl : plans) mcsas_hip_plan_destroy(pl);
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i)
+        if (problems[i].n_active == 0) {
+            const int r0 = mcsas_hip_analyse(&problems[i], &results[i]);
+            if (r0) return r0;
+        }
     return MCSAS_OK;
 }
 

@@ -274,6 +274,59 @@ def analyse_many(problems, streams=2):
     return out
 
 
+WAVE_MAX_Q = 4096       # q-points one wavefront per chain takes (include/mcsas_hip.h: MCSAS_EXEC_WAVE)
+
+
+def analyse_batch(problems):
+    """Independent analyses — a series of data sets — in ONE wavefront-per-chain launch per kernel (mcsas_hip_analyse_batch,
+    include/mcsas_hip.h): every repetition of every data set is one chain of the same launch, so a series of a few repetitions per
+    data set fills the chip.  `problems` as for analyse_many.  Returns the ChainResults in order; each is identical to analyse() of
+    that problem with exec_mode = EXEC_WAVE (seconds aside), whatever else is in the batch.  Device lists and models without an
+    active parameter run through analyse() at their place; a model that exists only as host code (MODEL_HOST) or a data set of
+    more than WAVE_MAX_Q q-points raises ValueError before anything is launched."""
+    problems = [p if isinstance(p, dict) else dict(model=p[0], q=p[1], intensity=p[2], sigma=p[3], st=p[4]) for p in problems]
+    for i, pr in enumerate(problems):
+        if pr["model"].model_id == MODEL_HOST:
+            raise ValueError("analyse_batch: problem %d: a model that exists only as host code has no device kernel to batch" % i)
+        if np.size(pr["q"]) > WAVE_MAX_Q:
+            raise ValueError("analyse_batch: problem %d has %d q-points; one wavefront per chain takes up to %d"
+                             % (i, np.size(pr["q"]), WAVE_MAX_Q))
+    if not problems:
+        return []
+    out, batched = [None] * len(problems), []
+    for i, pr in enumerate(problems):
+        if not (pr["model"].n_active == 0 or pr["st"].devices):
+            batched.append(i)
+    if batched:
+        lib = _lib.load(tuning=bool(problems[batched[0]]["st"].debug_flags))
+        probs, results = [], []
+        for i in batched:
+            pr = problems[i]
+            probs.append(HipProblem(pr["model"], pr["q"], pr["intensity"], pr["sigma"], pr["st"], pr.get("replay"), pr.get("stop"),
+                                    pr.get("smear")))
+            results.append(ChainResults(pr["st"].n_contrib, pr["model"].n_active, pr["st"].n_reps, len(probs[-1].q)))
+        parr = (Problem * len(probs))(*[p.c for p in probs])
+        rarr = (Result * len(results))(*[r.c for r in results])
+        check(lib.mcsas_hip_analyse_batch(parr, len(probs), rarr), lib)
+        for i, r in zip(batched, results):
+            out[i] = r
+    for i, pr in enumerate(problems):
+        if out[i] is None:
+            out[i] = analyse(pr["model"], pr["q"], pr["intensity"], pr["sigma"], pr["st"], pr.get("replay"), pr.get("stop"), pr.get("smear"))
+    return out
+
+
+def launch_batch(plans, stream=None):
+    """Enqueues resident wavefront-per-chain plans together (mcsas_hip_plan_launch_batch): one launch per group of plans with the
+    same kernel, every plan's slot 0.  Fetch each plan afterwards (Plan.fetch).  All plans on one device, one stop word or none."""
+    plans = list(plans)
+    if not plans:
+        raise ValueError("launch_batch: no plans")
+    lib = plans[0].lib
+    hs = (C.c_void_p * len(plans))(*[p.h.value for p in plans])
+    check(lib.mcsas_hip_plan_launch_batch(hs, len(plans), C.c_void_p(stream or 0)), lib)
+
+
 class Plan:
     """Resident plan: data and workspaces stay in HBM; launch/fetch can be repeated (bench.py)."""
 

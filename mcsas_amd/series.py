@@ -7,22 +7,32 @@ from __future__ import annotations
 from collections import OrderedDict
 
 
-def run_series(algo, datasets, keys=None, replays=None, overlap=False):
+def run_series(algo, datasets, keys=None, replays=None, overlap=False, batch=False):
     """-> (results, series).  `results[i]` is `algo.result[0]` of data set i (None when nothing
     converged); `series[(param, lower, upper, yweight)]` is the list of `(key_i, moments.fields)`.
     `keys`: the series key value of each data set (default: its index).  `replays`: per data set, the uniform
     streams of its repetitions (tests replaying the reference: tests/golden/g15_series.npz).  `overlap`: the data sets' analyses
     run side by side on the device instead of one after the other (same results; algo.seed should be set: an unseeded algo draws a
-    new seed per data set either way)."""
+    new seed per data set either way).  `batch`: the Monte-Carlo part of all data sets runs as ONE batch of wavefront-per-chain
+    chains (engine.analyse_batch; results as each data set's analysis in that mode alone), the rest as with `overlap`; a model that
+    exists only as host code runs one data set after the other instead."""
     if algo.model is None:
         raise ValueError("no model set")
     results, series = [], OrderedDict()
     chains = None
-    if overlap and algo.model.paramCount():
+    from . import engine
+    if batch and algo.model.paramCount():
+        algo.stop = False                                    # (as below: once for the batch)
+        problems = []
+        for i, data in enumerate(datasets):
+            algo.data = data
+            problems.append(algo._problem(replay=None if replays is None else replays[i]))
+        if all(pr["model"].model_id != engine.MODEL_HOST for pr in problems):
+            chains = engine.analyse_batch(problems)
+    elif overlap and algo.model.paramCount():
         algo.stop = False                                    # calc() resets it per data set (mcsas.py:152); here once, for the batch
         # the Monte-Carlo part of every data set first, side by side on the device (engine.analyse_many: the data sets' analyses are
         # independent); the loop below then only stores each result and takes its histograms — the same numbers as one after the other
-        from . import engine
         problems = []
         for i, data in enumerate(datasets):
             algo.data = data
