@@ -5,8 +5,11 @@ is fused).  References: x87 extended precision (64-bit significand) for sin / co
 Cephes J1 for the Bessel function.  The bounds asserted here are the ones fastmath.h states.
 
 What does NOT carry over from the host: the hardware reciprocal / reciprocal-square-root seeds of div_fast and
-rsqrt_fast (v_rcp_f64, v_rsq_f64) are replaced by float-precision stand-ins — both are refined by Newton steps
-whose result does not depend on the seed's last bits; the device versions are exercised by the GPU parity tests."""
+rsqrt_fast (v_rcp_f64, v_rsq_f64) are replaced by float-precision stand-ins.  div_fast's two Newton steps and residual
+correction make its result independent of the seed: the device gives the host's bits.  rsqrt_fast's single correction
+does not: the device result differs from the host build's in the last bit for about a fifth of the arguments (and so
+does j1_core above x = 5, which calls it); both stay within the bounds above.  tests/test_fastmath_device.py runs every
+function here on the device and checks both statements."""
 import ctypes as C
 import os
 import subprocess
@@ -163,3 +166,187 @@ def test_expm1_neg_fast(lib):
     lib.fm_ref_expm1(len(x), P(x), P(hi), P(lo))
     err = np.abs((y - hi) - lo) / np.maximum(ulp_of(hi), 5e-324)
     assert err.max() <= 2.0, (err.max(), x[np.argmax(err)])
+
+
+# ------------------------------------------------------------------------------------------ sin x - x cos x, _n, split J1
+EPS = 2.0**-52                      # ulp(v) <= EPS |v| for every normal double v
+
+
+def tan_x_zeros(ks=None):
+    """The positive roots of tan x = x (the zeros of sin x - x cos x, i.e. of the sphere's form factor), one per
+    k in `ks`, x_k in (k pi, k pi + pi/2), to the nearest double (mpmath, 40 digits), each with its two neighbours."""
+    import mpmath as mp
+    if ks is None:
+        ks = np.unique(np.concatenate([np.arange(1, 201), np.logspace(np.log10(201), np.log10(330000), 100).astype(int)]))
+    with mp.workdps(40):
+        roots = []
+        for k in ks:
+            a = mp.mpf(int(k)) * mp.pi + mp.pi / 2 - mp.mpf(1) / (int(k) * mp.pi + mp.pi / 2)  # 1st-order asymptote
+            roots.append(float(mp.findroot(lambda t: mp.sin(t) - t * mp.cos(t), a)))
+    r = np.array(roots)
+    return np.concatenate([r, np.nextafter(r, np.inf), np.nextafter(r, 0)])
+
+
+def smxc_mp(x, dps=40):
+    """sin x - x cos x of the doubles x, in `dps`-digit arithmetic, rounded to double."""
+    import mpmath as mp
+    with mp.workdps(dps):
+        return np.array([float(mp.sin(mp.mpf(v)) - mp.mpf(v) * mp.cos(mp.mpf(v))) for v in x])
+
+
+def smxc_bound(x, value):
+    """What fma(-x, cos x, sin x) may be off by, with sin x, cos x from sincos_core (the documented equivalent of
+    sin_minus_xcos): each of s, c carries <= 1.6 ulp <= 1.6 EPS |.| of its own value, or 2e-26 absolute where that value
+    is < 1e-9 (the dropped third reduction term); the fma multiplies c's error by |x| and rounds once, so
+      |err| <= 1.6 EPS (|x cos x| + |sin x|) + 2e-26 (1 + |x|) + ulp(value) / 2.
+    It scales with the magnitude of the two TERMS, not with their difference: that is the cancellation at small x and
+    next to the zeros, which the kernel shares with the reference's own expression."""
+    ax = np.abs(x)
+    return 1.6 * EPS * (ax * np.abs(np.cos(x)) + np.abs(np.sin(x))) + 2e-26 * (1 + ax) + 0.5 * np.spacing(np.abs(value))
+
+
+def fm1(lib, fn, x):
+    y = np.empty_like(x)
+    getattr(lib, fn)(len(x), P(x), P(y))
+    return y
+
+
+def smxc_point_sets():
+    s = point_sets()
+    s.pop("handoff")                                             # (callers keep q x below 2^20: no libm branch here)
+    s["handoff"] = np.nextafter(2.0**20, 0) - np.arange(1, 2000) * 2.0**-32
+    s["tan_zeros"] = tan_x_zeros()
+    return s
+
+
+@pytest.mark.parametrize("name", list(smxc_point_sets()))
+def test_sin_minus_xcos_is_the_fma_of_sincos_core(lib, name):
+    """sin_minus_xcos equals fma(-x, cos x, sin x) taken from sincos_core bit for bit; sin_minus_xcos_abs equals it up
+    to the sign (fastmath.h: fma(-x, -c, -s) == -fma(-x, c, s)), so its square is the same double."""
+    x = np.ascontiguousarray(smxc_point_sets()[name])
+    ref = fm1(lib, "fm_sin_minus_xcos_via_core", x)
+    signed = fm1(lib, "fm_sin_minus_xcos", x)
+    absv = fm1(lib, "fm_sin_minus_xcos_abs", x)
+    np.testing.assert_array_equal(signed, ref)
+    np.testing.assert_array_equal(np.abs(absv), np.abs(ref))
+    np.testing.assert_array_equal(absv * absv, ref * ref)
+
+
+@pytest.mark.parametrize("name", list(smxc_point_sets()))
+def test_sin_minus_xcos_within_its_bound(lib, name):
+    """sin_minus_xcos / _abs against x87 (whose own error, ~3 2^-64 (|sin x| + |x cos x|), is 2^-12 of the bound and
+    is added to it) within smxc_bound; on the sets where the difference cancels (tiny / small x, the zeros of
+    tan x = x) also against mpmath at 40 digits."""
+    x = np.ascontiguousarray(smxc_point_sets()[name])
+    hi, lo = np.empty_like(x), np.empty_like(x)
+    lib.fm_ref_sin_minus_xcos(len(x), P(x), P(hi), P(lo))
+    signed = fm1(lib, "fm_sin_minus_xcos", x)
+    absv = fm1(lib, "fm_sin_minus_xcos_abs", x)
+    b = smxc_bound(x, hi) + 4 * 2.0**-64 * (np.abs(x * np.cos(x)) + np.abs(np.sin(x)))
+    err = np.abs((signed - hi) - lo)
+    assert (err / b).max() <= 1.0, (name, (err / b).max(), x[np.argmax(err / b)])
+    erra = np.abs((np.abs(absv) - np.abs(hi)) - np.sign(hi) * lo)
+    assert (erra / b).max() <= 1.0, (name, (erra / b).max())
+    if name in ("tiny", "tan_zeros", "small"):
+        xs = np.ascontiguousarray(x if name != "small" else x[np.abs(x) < 0.1][:3000])
+        ex = smxc_mp(xs)
+        got = fm1(lib, "fm_sin_minus_xcos", xs)
+        r = np.abs(got - ex) / smxc_bound(xs, ex)
+        assert r.max() <= 1.0, (name, r.max(), xs[np.argmax(r)])
+
+
+def test_sin_minus_xcos_small_argument_regime(lib):
+    """The cancellation at small x, stated: for 1e-6 <= x <= 0.1 the value is x^3/3 (1 - x^2/10 + ...) while the bound
+    is ~3.2 EPS x — the RELATIVE error may reach ~10 EPS / x^2, and the evaluation is asked to stay inside that, not to beat
+    it; at x = 1 and beyond the terms and the difference are of one size and the error is a few ulp of the value."""
+    x = np.ascontiguousarray(np.logspace(-6, -1, 400))
+    ex = smxc_mp(x)
+    got = fm1(lib, "fm_sin_minus_xcos", x)
+    assert (np.abs(got - ex) / smxc_bound(x, ex)).max() <= 1.0
+    x = np.ascontiguousarray(np.linspace(1.0, 4.0, 400))
+    ex = smxc_mp(x)
+    got = fm1(lib, "fm_sin_minus_xcos", x)
+    assert (np.abs(got - ex) / np.spacing(np.abs(ex))).max() <= 8.0   # terms <= 4x the value here: 1.6 * 2 * 4 / 2 + 1/2
+
+
+def _pad8(x):
+    return np.ascontiguousarray(np.concatenate([x, np.full((-len(x)) % 8, 1.0)]))
+
+
+@pytest.mark.parametrize("name", list(smxc_point_sets()))
+def test_n_variants_are_bit_identical_to_the_scalar_forms(lib, name):
+    """sincos_poly_n / sincos_core_n / sin_minus_xcos_abs_n at N = 4 and 8 equal sincos_poly / sincos_core /
+    sin_minus_xcos_abs per element, bit for bit (fastmath.h: same operations in the same order per element)."""
+    x = _pad8(smxc_point_sets()[name])
+    n = len(x)
+    s0, c0, q0 = np.empty_like(x), np.empty_like(x), np.empty(n, dtype=np.int32)
+    lib.fm_sincos_poly(n, P(x), P(s0), P(c0), q0.ctypes.data_as(C.POINTER(C.c_int)))
+    sn0, cs0 = sincos(lib, "fm_sincos_core", x)
+    g0 = fm1(lib, "fm_sin_minus_xcos_abs", x)
+    for N in (4, 8):
+        s, c, q = np.empty_like(x), np.empty_like(x), np.empty(n, dtype=np.int32)
+        getattr(lib, "fm_sincos_poly_n%d" % N)(n, P(x), P(s), P(c), q.ctypes.data_as(C.POINTER(C.c_int)))
+        np.testing.assert_array_equal(s.view(np.int64), s0.view(np.int64))
+        np.testing.assert_array_equal(c.view(np.int64), c0.view(np.int64))
+        np.testing.assert_array_equal(q, q0)
+        sn, cs = sincos(lib, "fm_sincos_core_n%d" % N, x)
+        np.testing.assert_array_equal(sn.view(np.int64), sn0.view(np.int64))
+        np.testing.assert_array_equal(cs.view(np.int64), cs0.view(np.int64))
+        g = fm1(lib, "fm_sin_minus_xcos_abs_n%d" % N, x)
+        np.testing.assert_array_equal(g.view(np.int64), g0.view(np.int64))
+
+
+def j1_points():
+    rs = np.random.RandomState(2)
+    x = np.concatenate([rs.uniform(0, 5, 200000), rs.uniform(5, 60, 200000), 10 ** rs.uniform(-6, 6, 200000),
+                        np.nextafter(5.0, 0) - np.arange(100) * 1e-15, 5.0 + np.arange(100) * 1e-15, [5.0],
+                        [3.8317059702075125, 7.015586669815619, 1e-12, 1048575.9]])
+    return np.ascontiguousarray(x[(x > 0) & (x < 2.0**20)])
+
+
+def test_split_j1_ranges_are_j1_core(lib):
+    """j1_core_small (x <= 5) and j1_core_large (x > 5) are j1_core's two branches bit for bit — the interleaved
+    cylinder loop calls them directly when a whole group of arguments is on one side of x = 5."""
+    x = j1_points()
+    core = fm1(lib, "fm_j1_core", x)
+    sm, lg = x <= 5.0, x > 5.0
+    ys = fm1(lib, "fm_j1_core_small", np.ascontiguousarray(x[sm]))
+    yl = fm1(lib, "fm_j1_core_large", np.ascontiguousarray(x[lg]))
+    np.testing.assert_array_equal(ys.view(np.int64), core[sm].view(np.int64))
+    np.testing.assert_array_equal(yl.view(np.int64), core[lg].view(np.int64))
+    from scipy.special import j1
+    assert np.abs(ys - j1(x[sm])).max() <= 5e-16 and np.abs(yl - j1(x[lg])).max() <= 5e-16
+
+
+def hard_division_cases(n=20000, seed=7):
+    """Operand pairs (a, b) whose quotient lies within 2^-54 ulp of the midpoint between two doubles, on either side:
+    b an odd 53-bit integer, c = (2m + 1) the midpoint's numerator with b c = -+1 (mod 2^54) (b is odd, so c = -+b^-1 mod 2^54),
+    a = (b c +- 1) / 2^54 — an integer below 2^53, so a double — and a / b = c / 2^54 +- 1 / (b 2^54); scaled by powers of two.
+    Only a division whose reciprocal carries a relative error far below 2^-54 rounds all of them correctly."""
+    rs = np.random.RandomState(seed)
+    M = 1 << 54
+    A, B = [], []
+    while len(A) < n:
+        b = int(rs.randint(1 << 20, 1 << 31)) << 22 | int(rs.randint(0, 1 << 22)) | 1
+        if not (1 << 52) <= b < (1 << 53):
+            continue
+        s = 1 if len(A) % 2 else -1
+        c = (-s * pow(b, -1, M)) % M
+        if not (1 << 53) <= c < M:
+            continue
+        a, r = divmod(b * c + s, M)
+        assert r == 0 and a < (1 << 53)
+        A.append(float(a)); B.append(float(b))
+    ea, eb = rs.randint(-60, 60, n), rs.randint(-60, 60, n)
+    return np.ascontiguousarray(np.ldexp(A, ea)), np.ascontiguousarray(np.ldexp(B, eb))
+
+
+def test_div_fast_rounds_hard_quotients_correctly(lib):
+    """div_fast = reciprocal seed, two Newton steps, q = a y, residual r = fma(-b, q, a), fma(r, y, q): the last step puts
+    q + (a/b - q)(1 - d) with d the reciprocal's relative error, so it rounds like a/b unless a/b lies within about
+    |a/b - q| d of a midpoint.  After two steps d <= ~(2^-24)^4 (host stand-in seed; the device seed is better): far below
+    the 2^-54 ulp of hard_division_cases, so every one of them comes out correctly rounded (= numpy's IEEE a / b)."""
+    a, b = hard_division_cases()
+    y = np.empty_like(a)
+    lib.fm_div_fast(len(a), P(a), P(b), P(y))
+    np.testing.assert_array_equal(y, a / b)
