@@ -1,0 +1,108 @@
+// host_internal.h — what the host translation units of libmcsas_hip.so share (mcsas_hip.hip: the analysis; host_plugin.hip: the
+// run-time compiler of model plug-ins; host_calls.hip: the one-call entry points).  Host code only: the run-time compiler never sees
+// this file (it is not among the embedded headers).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/mcsas_hip.h"
+#include "chain_common.h"
+
+#pragma GCC visibility push(hidden)
+
+// ------------------------------------------------------------------------------ error plumbing (mcsas_hip.hip)
+extern thread_local std::string g_err;
+int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+#define HIPCHK(expr)                                                                         \
+    do {                                                                                     \
+        hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess)                                                                \
+            return fail(e_ == hipErrorOutOfMemory ? MCSAS_ENOMEM : MCSAS_EHIP, "%s: %s (%s:%d)", \
+                        #expr, hipGetErrorString(e_), __FILE__, __LINE__);                   \
+    } while (0)
+
+int select_device(int device);
+
+// Every entry point that selects a device puts the calling thread's current device back on the way out: a
+// host that shares the HIP runtime (torch with RCCL in bench.py, the hosts of INTEGRATION.md) keeps its own.
+struct DeviceGuard {
+    int prev = -1;
+    DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+    DeviceGuard(const DeviceGuard &) = delete;
+    DeviceGuard &operator=(const DeviceGuard &) = delete;
+};
+
+// ------------------------------------------------------------------------------ the process-level memory cache (mcsas_hip.hip: MemCache)
+hipError_t cached_dev_malloc(void **p, size_t n);
+void cached_dev_free(void *p, size_t n, int d);
+hipError_t cached_host_malloc(void **p, size_t n, unsigned flags);
+void cached_host_free(void *p, size_t n, unsigned flags);
+hipError_t cached_copy_stream(hipStream_t *st);
+
+// scratch arrays of the one-call entry points and of mcsas_hip_analyse_host_rows: from / back to the process-level cache (a
+// histogram() makes a dozen of them)
+template <typename T> struct DevBuf {
+    T *p = nullptr;
+    size_t bytes = 0;
+    int dev = 0;
+    ~DevBuf() {
+        if (!p) return;
+        (void)hipStreamSynchronize(nullptr);       // (hipFree used to wait for the kernels that read it — they run on the null stream —; the cache does not)
+        cached_dev_free(p, bytes, dev);
+    }
+    hipError_t alloc(size_t n) {
+        bytes = (sizeof(T) * (n ? n : 1) + 255) / 256 * 256;
+        (void)hipGetDevice(&dev);
+        return cached_dev_malloc((void **)&p, bytes);
+    }
+};
+
+// ------------------------------------------------------------------------------ models (mcsas_hip.hip)
+// what the host needs to know about a model, read off its Contrib<M> (models.h) — no per-model code outside this table
+struct ModelTraits { int int_div_param, rowtab, row_class; bool can_smear; int (*table_doubles)(int); int contrib_doubles; };
+ModelTraits model_traits(int model_id);
+inline int table_doubles_host(int model_id, int K) { return model_traits(model_id).table_doubles(K); }
+// per-wave scratch for the per-row orientation table (Contrib<M>::ROWTAB * K doubles, models.h); beyond
+// K = 256 the chain kernels evaluate the integrand directly
+inline int rowtab_doubles_host(int model_id, int K) { return K > 256 ? 0 : model_traits(model_id).rowtab * K; }
+int fill_model_args(const mcsas_problem *p, mcsas::ModelArgs *m);
+
+// Device copy of the smearing tables of a problem: locs transposed to [K][stride] (pad columns repeat
+// column 0, like the padded q) and cw[m] = 2 * trapezoid coefficient(q_offset)[m] * weights[m], so that
+// sum_m cw[m] y[m] = 2 trapz(y * weights, x = q_offset) (sasmodel.py:72-73).
+struct SmearDev {
+    double *locs_t = nullptr, *cw = nullptr;
+    ~SmearDev() { if (locs_t) hipFree(locs_t); if (cw) hipFree(cw); }
+    static bool active(const mcsas_problem *p);            // smearing asked for and the model can be smeared (canSmear)
+    static int check(const mcsas_problem *p);              // the refusal of upload(), without a HIP call
+    int upload(const mcsas_problem *p, int stride, mcsas::ModelArgs *m);
+};
+
+// ------------------------------------------------------------------------------ run-time model plug-ins (host_plugin.hip)
+// the chain kernel families; every built-in model has its instances in kern_<family>.hip, a plug-in compiles its own on first use
+enum KernelFamily { KF_WAVE, KF_WAVE_BATCH, KF_WG, KF_WIDE, KF_PIPE_TICK, KF_COUNT };
+enum PluginSmallKernel { PLUGIN_MODEL_ROWS, PLUGIN_OBSERVABILITY, PLUGIN_HIST_ROWS };
+
+inline bool is_plugin_model(int model_id) { return model_id >= MCSAS_MODEL_PLUGIN0 && model_id < MCSAS_MODEL_PLUGIN0 + MCSAS_MAX_PLUGINS; }
+// what a plug-in's text declares (plugin_model.h); false: no such plug-in
+bool plugin_declares(int model_id, int *row_class, bool *can_smear);
+// the family's kernel for `qpl` q slots per lane and the family's flag (row cache / row queue; ignored by the families without one),
+// compiled on first use, as a function of the CURRENT device's module
+int plugin_chain_function(int model_id, KernelFamily family, int qpl, bool flag, hipFunction_t *fn);
+int plugin_small_function(int model_id, PluginSmallKernel which, hipFunction_t *fn);
+
+// launch of a small kernel of a plug-in on the null stream; the arguments are passed by address,
+// so their types must be the kernel's parameter types exactly
+template <class... A>
+static int plugin_small_launch(int model_id, PluginSmallKernel which, dim3 grid, size_t lds, A... args) {
+    hipFunction_t fn = nullptr;
+    int rc = plugin_small_function(model_id, which, &fn);
+    if (rc) return rc;
+    void *ka[] = {(void *)&args...};
+    HIPCHK(hipModuleLaunchKernel(fn, grid.x, grid.y, grid.z, mcsas::WAVE, 1, 1, (unsigned)lds, nullptr, ka, nullptr));
+    return MCSAS_OK;
+}
+
+#pragma GCC visibility pop

@@ -419,7 +419,8 @@ def test_mcsas_front_end_takes_a_device_list():
 def test_mcsas_front_end_device_list_with_an_integral_model_in_auto_mode():
     """mcsas_amd.McSAS(device=[0, 0]) for a model whose rows cost an integral, MCSAS_EXEC_AUTO (it picks the row-queue pipeline on
     every block): the repetition loop of mcsas.py:214-262 split over two plans on two host threads inside the C ABI gives the arrays of
-    one device bit for bit (window fixed by the contribution count, chain id = global repetition index), histogram included."""
+    one device bit for bit (chain id = global repetition index; the window follows each plan's contribution, chain and CU counts —
+    chain_pipe.h: pipe_geometry — and nothing a chain decides depends on it), histogram included."""
     g = load("g16_cyl_free.npz")
     out = []
     for dev in (0, [0, 0]):

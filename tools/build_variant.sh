@@ -1,19 +1,21 @@
 #!/bin/bash
-# usage: [MODELS="0 1"] tools/build_variant.sh <name> [extra hipcc flags]  -> mcsas_amd/lib/libmcsas_<name>.so from the CURRENT sources of the C ABI
-# translation unit and the pipeline kernels of the models in MODELS (default: the sphere; the other objects are taken from build/csrc:
+# usage: [MODELS="0 1"] tools/build_variant.sh <name> [extra hipcc flags]  -> mcsas_amd/lib/libmcsas_<name>.so from the CURRENT sources of the host
+# translation units (mcsas_hip.hip, host_plugin.hip, host_calls.hip) and the pipeline kernels of the models in MODELS (default: the sphere; the other objects are taken from build/csrc:
 # run `make release` first)
 set -e
 cd $(dirname $0)/../mcsas_amd/csrc
 name=$1; shift
 B=../../build/csrc; V=../../build/variant_$name; mkdir -p $V
 F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -Wno-unused-value -I$B $*"
-/opt/rocm/bin/hipcc $F -c -o $V/mcsas_hip.o mcsas_hip.hip &
+make --no-print-directory $B/embedded_headers.inc
+HOST="mcsas_hip host_plugin host_calls"
+for u in $HOST; do /opt/rocm/bin/hipcc $F -c -o $V/$u.o $u.hip & done
 MODELS=${MODELS:-0}
 for m in $MODELS; do /opt/rocm/bin/hipcc $F -DMCSAS_M=$m -c -o $V/kern_pipe_m$m.o kern_pipe.hip & done
 wait
-objs="$V/mcsas_hip.o"
+objs=""; for u in $HOST; do objs="$objs $V/$u.o"; done
 for m in 0 1 2 3 4 5 6 7; do
-  objs="$objs $B/kern_wave_m$m.o $B/kern_wg_m$m.o $B/kern_wide_m$m.o"
+  objs="$objs $B/kern_wave_m$m.o $B/kern_wave_batch_m$m.o $B/kern_wg_m$m.o $B/kern_wide_m$m.o"
   case " $MODELS " in *" $m "*) objs="$objs $V/kern_pipe_m$m.o";; *) objs="$objs $B/kern_pipe_m$m.o";; esac
 done
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../lib/libmcsas_$name.so $objs -lhiprtc
