@@ -21,7 +21,7 @@
 #include "host_internal.h"
 #include "chain_feed.h"     // feed_rows_kernel: chains whose rows the caller evaluates (mcsas_hip_analyse_host_rows)
 #include "chain_wg.h"   // WgGeom / wg_geometry only; the kernels are instantiated in kern_*.hip
-#include "chain_pipe.h" // PipeArgs / pipe_geometry only
+#include "pipe_layout.h" // the pipeline's argument blocks, constants and pipe_geometry (no kernel templates)
 #include "chain_wide.h" // WIDE_* constants only
 #include "auto_table.h" // measured rates of the execution modes (tools/make_auto_table.py)
 #include "model_list.h" // MCSAS_FOR_MODELS: the built-in models
@@ -510,7 +510,7 @@ static int decide_shape(const mcsas_problem *p, const ModelArgs &margs, int n_cu
     }
     const int qpad = wide ? qpl * WAVE * wide_waves : qpl * WAVE;
     if (int rc = SmearDev::check(p)) return rc;
-    // rows that cost a numerical integration each (2: and whose cost varies with the parameter set — chain_pipe.h, pipe_geometry)
+    // rows that cost a numerical integration each (2: and whose cost varies with the parameter set — pipe_layout.h, pipe_geometry)
     const int heavy_rows = std::max(model_traits(p->model_id).row_class, SmearDev::active(p) ? 1 : 0);
     const int contrib_doubles = model_traits(p->model_id).contrib_doubles;
     auto tabd = [&](int waves_per_block) { return table_doubles_block(p->model_id, margs.int_div, waves_per_block); };

@@ -252,6 +252,21 @@ def test_model_plugins_compile_without_a_gpu_and_report_compiler_errors():
         Nameless().setup()
 
 
+def test_embedded_headers_include_only_embedded_headers():
+    """The run-time compiler of model plug-ins sees the files of the Makefile's EMBED list and nothing else (hiprtc gets them from
+    memory): every `#include "x"` inside an embedded file has to name another embedded file, and every header of the pipeline
+    (PIPE_HDRS) has to be in the list.  Text only — a header split that forgets the list compiles everywhere but there."""
+    csrc = os.path.join(ROOT, "mcsas_amd", "csrc")
+    mk = open(os.path.join(csrc, "Makefile")).read().replace("\\\n", " ")
+    embed = dict(item.split("=", 1) for item in re.search(r"^EMBED\s*:=(.*)$", mk, re.M).group(1).split())
+    pipe_hdrs = re.search(r"^PIPE_HDRS\s*:=(.*)$", mk, re.M).group(1).split()
+    assert len(embed) >= 12 and "chain_pipe.h" in embed and set(pipe_hdrs) <= set(embed), (sorted(embed), pipe_hdrs)
+    for name, path in embed.items():
+        assert "$" not in name + path, "EMBED is read as text: spell the files out (%s=%s)" % (name, path)
+        for inc in re.findall(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', open(os.path.join(csrc, path)).read(), re.M):
+            assert os.path.basename(inc) in embed, "%s includes %s, which is not embedded" % (name, inc)
+
+
 def test_committed_counter_profiles_describe_the_committed_kernels():
     """bench.py quotes per-step counters (instructions, memory-side bytes) from the newest profiles/rNN_*.json; tools/pmc_summary.py
     stores a hash of the kernel sources they were taken on, and the bench line reports whether it matches the tree.  Committed state:

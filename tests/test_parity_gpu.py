@@ -420,7 +420,7 @@ def test_mcsas_front_end_device_list_with_an_integral_model_in_auto_mode():
     """mcsas_amd.McSAS(device=[0, 0]) for a model whose rows cost an integral, MCSAS_EXEC_AUTO (it picks the row-queue pipeline on
     every block): the repetition loop of mcsas.py:214-262 split over two plans on two host threads inside the C ABI gives the arrays of
     one device bit for bit (chain id = global repetition index; the window follows each plan's contribution, chain and CU counts —
-    chain_pipe.h: pipe_geometry — and nothing a chain decides depends on it), histogram included."""
+    pipe_layout.h: pipe_geometry — and nothing a chain decides depends on it), histogram included."""
     g = load("g16_cyl_free.npz")
     out = []
     for dev in (0, [0, 0]):
@@ -1454,7 +1454,7 @@ def test_pipeline_tuning_variants_replay_the_reference():
 
 
 def test_pipeline_geometry_follows_the_chain_count():
-    """The pipeline's window is chosen with the chain count and the CU count in hand (chain_pipe.h: pipe_geometry):
+    """The pipeline's window is chosen with the chain count and the CU count in hand (pipe_layout.h: pipe_geometry):
     rows without an integral get more, smaller producer blocks per chain while every block still has a CU of its own
     (the window stays 192 steps at 512 q x 400 contributions: 3 / 4 / 6 rows per producer wave), rows with an integral
     the number of producer blocks that gives the most steps per round of CUs.  Pinned here on a 256-CU MI355X."""

@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: [MODELS="0 1"] tools/build_variant.sh <name> [extra hipcc flags]  -> mcsas_amd/lib/libmcsas_<name>.so from the CURRENT sources of the host
-# translation units (mcsas_hip.hip, host_plugin.hip, host_calls.hip) and the pipeline kernels of the models in MODELS (default: the sphere; the other objects are taken from build/csrc:
+# translation units (mcsas_hip.hip, host_plugin.hip, host_calls.hip) and the pipeline kernels (kern_pipe.hip: chain_pipe.h and the pipe_*.h under it) of the models in MODELS (default: the sphere; the other objects are taken from build/csrc:
 # run `make release` first)
 set -e
 cd $(dirname $0)/../mcsas_amd/csrc
