@@ -1320,15 +1320,16 @@ extern "C" int mcsas_hip_analyse_host_rows(const mcsas_problem *p, mcsas_rows_ca
     fa.first = dmeta.p; fa.count = dmeta.p + R; fa.kind = dmeta.p + 2 * R;
 
     // the chains as the host sees them: where each is in its random stream and in the retry loop of McSAS.analyse (mcsas.py:220-246)
-    struct HostChain { uint64_t draw_pos = 0; int64_t num_iter = 0, total = 0; int attempt = 0, phase = 0 /*0 init due, 1 running, 2 done*/, converged = 0, overflow = 0, stopped = 0; double seconds = 0; };
+    struct HostChain { uint64_t draw_pos = 0; int64_t num_iter = 0, total = 0; int attempt = 0, phase = 0 /*0 init due, 1 running, 2 done*/, converged = 0, stopped = 0; double seconds = 0; };
     std::vector<HostChain> hc(R);
     std::vector<FeedState> hs(R);
     std::vector<int32_t> meta(3 * R);
     std::vector<double> pset(round_rows * P), hrows(round_rows * Q), staged(round_rows * qpad, 0.);
-    auto uniform = [&](size_t r, uint64_t idx, int *ovf) -> double {
+    // (a window is drawn ahead of the decisions: a draw behind the replay stream's end is no error here — the chain may end before
+    // the step that would need it; what was consumed is known when the chain is through, see below)
+    auto uniform = [&](size_t r, uint64_t idx) -> double {
         if (p->replay_stream) {
             if ((int64_t)idx < p->replay_len) return p->replay_stream[r * (size_t)p->replay_len + idx];
-            *ovf = 1;
             return 0.5;
         }
         return philox_uniform_host(p->seed, (uint32_t)(p->rep_offset + (int)r), idx);
@@ -1361,8 +1362,8 @@ extern "C" int mcsas_hip_analyse_host_rows(const mcsas_problem *p, mcsas_rows_ca
                 for (size_t c = 0; c < P; ++c) {
                     double v;
                     if (h.phase == 0) v = p->start_from_minimum ? p->start_value[c]     // mcsas.py:310-317: N draws per parameter, parameter-major
-                                                                : generate((int)c, uniform(r, h.draw_pos + c * N + k, &h.overflow));
-                    else v = generate((int)c, uniform(r, h.draw_pos + (uint64_t)(h.num_iter + (int64_t)k) * P + c, &h.overflow));   // :358
+                                                                : generate((int)c, uniform(r, h.draw_pos + c * N + k));
+                    else v = generate((int)c, uniform(r, h.draw_pos + (uint64_t)(h.num_iter + (int64_t)k) * P + c));   // :358
                     pset[(nrows + k) * P + c] = v;
                 }
             nrows += want;
@@ -1411,7 +1412,9 @@ extern "C" int mcsas_hip_analyse_host_rows(const mcsas_problem *p, mcsas_rows_ca
         if (res->converged) res->converged[r] = hc[r].converged;
         if (res->seconds) res->seconds[r] = hc[r].seconds;
         if (res->draws) res->draws[r] = (int64_t)hc[r].draw_pos;
-        ovf |= hc[r].overflow;
+        // exhausted: a step the chain TOOK needed a draw behind the end — draw_pos counts the initial sets of the attempts that
+        // were made and the steps that were decided, not what was drawn ahead for a window the chain left early
+        if (p->replay_stream && (int64_t)hc[r].draw_pos > p->replay_len) ovf = 1;
     }
     if (ovf) return fail(MCSAS_ESTREAM, "replay stream exhausted (replay_len=%lld)", (long long)p->replay_len);
     return MCSAS_OK;

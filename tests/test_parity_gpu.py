@@ -553,7 +553,9 @@ def test_python_only_model_free_running_retries_and_stop():
 def test_python_only_model_flags_and_stream_end():
     """Host rows with the settings that change mcFit's set-up and fit — startFromMinimum (mcsas.py:310-315: no draws for the initial
     set), no background, positiveBackground — against the numpy oracle on the same replayed stream; and a replay stream that is too
-    short is reported (MCSAS_ESTREAM), as by every other entry point."""
+    short is reported (MCSAS_ESTREAM), as by every other entry point — in both directions: reported if and only if a step the
+    chain took needed a draw behind the stream's end, not for what was drawn ahead for a window the chain left early
+    (tests/test_chain_end_gpu.py pins that for every entry point)."""
     g = load("g4_sphere_q100_fixed.npz")
     q, I, sig = g["data_q"], g["data_I"], g["data_sigma"]
     lo, hi = float(g["spec_lo"][0]), float(g["spec_hi"][0])
