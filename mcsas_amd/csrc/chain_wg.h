@@ -301,7 +301,6 @@ __device__ __forceinline__ void wg_scanner(const ChainArgs &a, const WgGeom &g, 
                 // octet then evaluates step g's decision.  The first accepted step (if any) is applied
                 // and the group restarts behind it — the sequence of decisions is exactly the serial one.
                 const int g = lane & 7;
-                const int gslot = ((g & 1) << 2) | (g & 2) | ((g >> 2) & 1);   // accumulator holding step g (bit-reversed)
                 while (k < kmax) {
                     const int gcount = (kmax - k) < 8 ? (kmax - k) : 8;
                     double acc[8] = {0., 0., 0., 0., 0., 0., 0., 0.};
@@ -316,7 +315,6 @@ __device__ __forceinline__ void wg_scanner(const ChainArgs &a, const WgGeom &g, 
                         }
                     }
                     const double h = wave_sum8_transposed(acc, lane);               // lane g: h of step k+g
-                    (void)gslot;
                     const int kg = (k + g < K) ? k + g : K - 1;
                     const double *sc = sbase + kg * 4;
                     const double SCt = SC + sc[0], SICt = SIC + sc[1], SCCt = SCC + fma(2., h, sc[2]);
