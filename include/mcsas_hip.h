@@ -260,6 +260,34 @@ void mcsas_hip_plan_destroy(mcsas_plan *plan);
 int mcsas_hip_plan_launch_batch(mcsas_plan *const *plans, int32_t n, void *hip_stream);
 int mcsas_hip_analyse_batch(const mcsas_problem *problems, int32_t n, mcsas_result *results);
 
+/* ---- chains started from given contributions (ABI 5, additive): continue a run that ended at maxIterations, refine a result to
+ * a tighter criterion, warm-start a frame of a series from an earlier frame's result -------------------------------------------
+ * `start` is [n_contrib][n_active][rep_stride] in the layout of mcsas_result.contribs, so a fetched result feeds straight back;
+ * repetition r of the plan reads column rep_first + r (0 <= rep_first, rep_first + n_reps <= rep_stride, else MCSAS_EINVAL).
+ * The values are taken as they are and reach the model through the same clipping into the valueRange as any parameter set; they
+ * need not lie inside gen_lo..gen_hi (a warm start under a narrowed active range is legal).  A non-finite value: MCSAS_EINVAL,
+ * its index in mcsas_hip_last_error().
+ * Contract: the FIRST attempt of each repetition is McSAS.mcFit with rset given in place of generateParameters(numContribs)
+ *   (mcsas.py:317).  It consumes no uniforms for the initial set, so the step draws of that attempt start at index 0 of the chain's
+ *   stream, replayed or Philox.  start_from_minimum is overridden for that attempt only.  num_iter counts from 0 and max_iter is
+ *   the budget of THIS call.  Attempts after the first (the retry loop of analyse, mcsas.py:220-246) generate a fresh set exactly
+ *   as they do without a start, draws included.  A start whose chi-squared already meets conv_crit returns itself: num_iter =
+ *   num_moves = draws = 0, attempts = 1, converged = 1, contribs bit-equal to start.
+ * mcsas_hip_plan_set_start: the plan keeps a (transposed) device copy taken at the call; the caller's array may be freed.  Every
+ *   later launch of any slot, mcsas_hip_plan_launch_batch included, copies that block into the slot's parameter sets on the launch
+ *   stream ahead of the kernel and runs the start form of the wavefront kernel.  start == NULL clears it.  A batch groups plans by
+ *   (model, q slots per lane, row cache, start or not): plans with and without a start may share one batch.
+ *   mcsas_hip_plan_reseed and the replay stream are independent of the start.  Only a plan that resolved to MCSAS_EXEC_WAVE takes
+ *   a start; any other: MCSAS_EINVAL naming the mode (the plan stays usable).
+ * mcsas_hip_analyse_from: mcsas_hip_analyse from `start` ([n_contrib][n_active][n_reps]).  MCSAS_EXEC_AUTO means WAVE, as in
+ *   mcsas_hip_analyse_batch; WORKGROUP, PIPELINE and nq > 4096 are refused before a device is touched, and so are a NULL start and
+ *   a non-finite value.  n_active == 0 is answered as mcsas_hip_analyse answers it (start is not read).  n_devices > 1 shards as
+ *   mcsas_hip_analyse does, each block reading its own columns of the one array.
+ * Out of scope: mcsas_hip_analyse_host_rows (models that exist only as host code), and the workgroup, q-split and pipeline
+ *   kernels: a start needs exec_mode = MCSAS_EXEC_WAVE. */
+int mcsas_hip_plan_set_start(mcsas_plan *plan, const double *start, int32_t rep_stride, int32_t rep_first);
+int mcsas_hip_analyse_from(const mcsas_problem *problem, const double *start, mcsas_result *result);
+
 /* ---- ScatteringModel.calc(data, pset, compensationExponent) (scatteringmodel.py:79-109) ------
  * Uses problem->{model_id, params, n_active, active_index, clip_*, nq, q, comp_exp, device}.
  * pset[n][n_active] -> cum_int[nq] (rows summed in order), vset/wset/sset[n], optional

@@ -24,7 +24,7 @@ SYMBOLS = (
     "mcsas_hip_analyse", "mcsas_hip_analyse_host_rows", "mcsas_hip_shard", "mcsas_hip_plan_create", "mcsas_hip_plan_launch", "mcsas_hip_plan_fetch",
     "mcsas_hip_plan_launch_slot", "mcsas_hip_plan_fetch_slot",
     "mcsas_hip_plan_last_ms", "mcsas_hip_plan_total_steps", "mcsas_hip_plan_reseed", "mcsas_hip_plan_info",
-    "mcsas_hip_plan_destroy", "mcsas_hip_plan_launch_batch", "mcsas_hip_analyse_batch", "mcsas_hip_model_calc", "mcsas_hip_bgfit", "mcsas_hip_observability",
+    "mcsas_hip_plan_destroy", "mcsas_hip_plan_launch_batch", "mcsas_hip_analyse_batch", "mcsas_hip_plan_set_start", "mcsas_hip_analyse_from", "mcsas_hip_model_calc", "mcsas_hip_bgfit", "mcsas_hip_observability",
     "mcsas_hip_histogram_prep", "mcsas_hip_histogram", "mcsas_hip_prepare_uncertainty", "mcsas_hip_rebin",
     "mcsas_hip_plugin_compile", "mcsas_hip_plugin_log", "mcsas_hip_release_cached_memory", "mcsas_hip_stream_create", "mcsas_hip_stream_destroy",
     "mcsas_hip_device_count", "mcsas_hip_abi_version", "mcsas_hip_is_tuning_build", "mcsas_hip_last_error",
@@ -131,6 +131,8 @@ def load(tuning=False):
     lib.mcsas_hip_plan_info.argtypes = [C.c_void_p, _i32p]
     lib.mcsas_hip_plan_launch_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]
     lib.mcsas_hip_analyse_batch.argtypes = [C.POINTER(Problem), C.c_int32, C.POINTER(Result)]
+    lib.mcsas_hip_plan_set_start.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_int32]
+    lib.mcsas_hip_analyse_from.argtypes = [C.POINTER(Problem), _dp, C.POINTER(Result)]
     lib.mcsas_hip_plan_destroy.argtypes = [C.c_void_p]
     lib.mcsas_hip_plan_destroy.restype = None
     lib.mcsas_hip_model_calc.argtypes = [C.POINTER(Problem), _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp]

@@ -20,6 +20,18 @@ __global__ __launch_bounds__(64, MCSAS_WAVE_MIN_WAVES(QPL, CACHE)) void chain_wa
     extern __shared__ double lds[];
     const int lane = threadIdx.x;
     const int rep = blockIdx.x;
+    constexpr bool GIVEN = false;
+#include "chain_wave_body.inc"
+}
+
+// The same chain started from a given set (mcsas_hip_plan_set_start): the host has copied the repetition's start into rset ahead of
+// the launch, and the first attempt takes it where chain_wave_kernel generates one (chain_wave_body.inc: GIVEN).
+template <int M, int QPL, bool CACHE>
+__global__ __launch_bounds__(64, MCSAS_WAVE_MIN_WAVES(QPL, CACHE)) void chain_wave_start_kernel(const ChainArgs a) {
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x;
+    const int rep = blockIdx.x;
+    constexpr bool GIVEN = true;
 #include "chain_wave_body.inc"
 }
 
@@ -49,6 +61,23 @@ __global__ __launch_bounds__(64, MCSAS_WAVE_MIN_WAVES(QPL, CACHE)) void chain_wa
     const int set = __builtin_amdgcn_readfirstlane(c.set);
     ChainArgs a = sets[set];                                    // (read whole before the first store)
     chain_args_pointers(a, ((ConstChainArgs *)sets)[set]);
+    constexpr bool GIVEN = false;
+#include "chain_wave_body.inc"
+}
+
+// ... and its start twin: every analysis of such a launch has its start in its rset (plans with and without a start share a batch
+// call, not a launch: the host groups them apart)
+template <int M, int QPL, bool CACHE>
+__global__ __launch_bounds__(64, MCSAS_WAVE_MIN_WAVES(QPL, CACHE)) void chain_wave_batch_start_kernel(const ChainArgs *__restrict__ sets,
+                                                                                                      const ChainRef *__restrict__ chains) {
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x;
+    const ChainRef c = chains[blockIdx.x];
+    const int rep = __builtin_amdgcn_readfirstlane(c.rep);
+    const int set = __builtin_amdgcn_readfirstlane(c.set);
+    ChainArgs a = sets[set];
+    chain_args_pointers(a, ((ConstChainArgs *)sets)[set]);
+    constexpr bool GIVEN = true;
 #include "chain_wave_body.inc"
 }
 

@@ -1,7 +1,8 @@
 // chain_wave_body.inc — the body of one wave-per-chain chain (chain_wave.h), included verbatim by chain_wave_kernel and
-// chain_wave_batch_kernel so that both compile from the same text and the single kernel's code stays what it was.  In scope at
-// the point of inclusion: M, QPL, CACHE (template parameters), `const ChainArgs &a` (the analysis), `const int rep` (its
-// repetition), `lds` (the dynamic LDS) and `const int lane`.
+// chain_wave_batch_kernel (and their start twins) so that all compile from the same text and the single kernel's code stays what
+// it was.  In scope at the point of inclusion: M, QPL, CACHE (template parameters), `const ChainArgs &a` (the analysis),
+// `const int rep` (its repetition), `lds` (the dynamic LDS), `const int lane` and GIVEN (a compile-time bool: the first attempt
+// takes the set the host left in rset instead of generating one, mcsas_hip_plan_set_start; false folds away).
     const int N = a.n_contrib, P = a.model.n_active, qpad = a.qpad;
     double *lq = lds, *lw = lds + qpad, *lwI = lds + 2 * qpad, *lq3 = lds + 3 * qpad, *tab = lds + 4 * qpad;
     for (int i = lane; i < qpad; i += WAVE) {
@@ -28,7 +29,9 @@
     for (int attempt = 0; attempt <= a.max_retries; ++attempt) {
         ++attempts;
         // ------------------------------------------------------------ initial parameter set
-        // generateParameters(N): N draws per active parameter, parameter-major (scatteringmodel.py:117-127)
+        // generateParameters(N): N draws per active parameter, parameter-major (scatteringmodel.py:117-127); a given start
+        // (GIVEN, first attempt only) stands in for it and consumes no draws
+        const bool given = GIVEN && attempt == 0;
 #pragma unroll
         for (int j = 0; j < QPL; ++j) ft[j] = 0.;
         for (int n0 = 0; n0 < N; n0 += WAVE) {
@@ -38,7 +41,8 @@
 #pragma unroll
                 for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)
                     if (p < P) {
-                        if (a.start_from_min) row[p] = a.start_value[p];         // mcsas.py:310-315
+                        if (given) row[p] = rset[(size_t)n * P + p];
+                        else if (a.start_from_min) row[p] = a.start_value[p];    // mcsas.py:310-315
                         else {
                             double u = src.at(draw_pos + (uint64_t)p * N + n, overflow);   // parameter-major
                             row[p] = gen_transform(a.gen_kind[p], u) * (a.gen_hi[p] - a.gen_lo[p]) + a.gen_lo[p];
@@ -64,7 +68,7 @@
                 }
             }
         }
-        if (!a.start_from_min) draw_pos += (uint64_t)N * P;
+        if (!given && !a.start_from_min) draw_pos += (uint64_t)N * P;
 
         // ------------------------------------------------------------ initial fit (mcsas.py:327-343)
         {

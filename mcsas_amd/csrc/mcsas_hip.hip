@@ -261,6 +261,8 @@ struct mcsas_plan {
     size_t lds_bytes = 0;
     double *d_q = nullptr, *d_w = nullptr, *d_wI = nullptr, *d_I = nullptr, *d_q3inv = nullptr;
     double *d_cache = nullptr, *d_replay = nullptr;
+    double *d_start = nullptr;          // [n_reps][n_contrib][n_active], the layout of rset: the set every launch starts from (mcsas_hip_plan_set_start)
+    bool has_start = false;             // ... while this holds; the buffer stays with the plan once made
     int32_t *h_stop = nullptr;          // pinned + mapped: McSAS.stop as the kernels see it
     int32_t *d_stop_relay = nullptr;    // device memory, 16 bytes: the relayed stop word and the time stamp of the last look at h_stop (chain_common.h: stop_requested)
     hipStream_t stream = nullptr;
@@ -330,7 +332,8 @@ static int plan_activate_slot(mcsas_plan *pl, int k) {
 
 // ------------------------------------------------------------------------------ the chain kernels
 // kernel lookups, one translation unit per model and family (kern_*.hip)
-#define DECL_K(m) void *mcsas_wave_kernel_m##m(int, bool); void *mcsas_wave_batch_kernel_m##m(int, bool); void *mcsas_wg_kernel_m##m(int); void *mcsas_wide_kernel_m##m(int); void *mcsas_pipe_tick_kernel_m##m(int, bool);
+#define DECL_K(m) void *mcsas_wave_kernel_m##m(int, bool); void *mcsas_wave_batch_kernel_m##m(int, bool); void *mcsas_wg_kernel_m##m(int); void *mcsas_wide_kernel_m##m(int); void *mcsas_pipe_tick_kernel_m##m(int, bool); \
+                  void *mcsas_wave_start_kernel_m##m(int, bool); void *mcsas_wave_batch_start_kernel_m##m(int, bool);
 MCSAS_FOR_MODELS(DECL_K)
 #undef DECL_K
 void *mcsas_pipe_reset_kernel();
@@ -341,6 +344,7 @@ static void *builtin_kernel(KernelFamily family, int model, int qpl, bool flag) 
 #define CASE_K(m)                                                                                                                   \
     case m:                                                                                                                         \
         return family == KF_WAVE ? mcsas_wave_kernel_m##m(qpl, flag) : family == KF_WAVE_BATCH ? mcsas_wave_batch_kernel_m##m(qpl, flag) \
+             : family == KF_WAVE_START ? mcsas_wave_start_kernel_m##m(qpl, flag) : family == KF_WAVE_BATCH_START ? mcsas_wave_batch_start_kernel_m##m(qpl, flag) \
              : family == KF_WG ? mcsas_wg_kernel_m##m(qpl) : family == KF_WIDE ? mcsas_wide_kernel_m##m(qpl) : mcsas_pipe_tick_kernel_m##m(qpl, flag);
         MCSAS_FOR_MODELS(CASE_K)
 #undef CASE_K
@@ -357,15 +361,21 @@ struct KernelRef {
     enum { ARG2_NONE, ARG2_WG, ARG2_Q3INV } arg2 = ARG2_NONE;
     const void *id() const { return plugin ? (const void *)plugin : entry; }
 };
-// the family of the plan's own launches (mcsas_hip_plan_launch_batch asks for KF_WAVE_BATCH instead)
+// the family of the plan's own launches (mcsas_hip_plan_launch_batch asks for KF_WAVE_BATCH instead); launch_family: the one a
+// launch takes now, i.e. the start twin of the wave families while the plan holds a start (mcsas_hip_plan_set_start)
 static KernelFamily plan_family(const mcsas_plan *pl) {
     if (pl->mode == MCSAS_EXEC_WAVE) return KF_WAVE;
     if (pl->mode == MCSAS_EXEC_PIPELINE) return KF_PIPE_TICK;
     return pl->wide ? KF_WIDE : KF_WG;
 }
+static KernelFamily launch_family(const mcsas_plan *pl, bool batch) {
+    if (batch) return pl->has_start ? KF_WAVE_BATCH_START : KF_WAVE_BATCH;
+    return pl->has_start ? KF_WAVE_START : plan_family(pl);
+}
 static int resolve_kernel(const mcsas_plan *pl, KernelFamily family, KernelRef *k) {
     static const char *const missing[KF_COUNT] = {"no kernel for model %d qpl %d", "launch_batch: no batch kernel for model %d qpl %d", "no kernel for model %d qpl %d",
-                                                  "no q-split kernel for model %d qpl %d", "no pipeline kernel for model %d qpl %d"};
+                                                  "no q-split kernel for model %d qpl %d", "no pipeline kernel for model %d qpl %d",
+                                                  "no start kernel for model %d qpl %d", "launch_batch: no batch start kernel for model %d qpl %d"};
     const int model = pl->prob.model_id;
     const bool flag = family == KF_PIPE_TICK ? pl->pipe.g.rowq != 0 : pl->use_cache != 0;
     *k = KernelRef{};
@@ -794,6 +804,51 @@ extern "C" int mcsas_hip_plan_reseed(mcsas_plan *pl, uint64_t seed, int32_t rep_
     return MCSAS_OK;
 }
 
+// the first non-finite value of the columns [first, first + R) of start[N][P][stride], or MCSAS_OK
+static int check_start_finite(const char *who, const double *start, size_t N, size_t P, size_t stride, size_t first, size_t R) {
+    for (size_t i = 0; i < N * P; ++i)
+        for (size_t r = 0; r < R; ++r)
+            if (!std::isfinite(start[i * stride + first + r]))
+                return fail(MCSAS_EINVAL, "%s: start[%zu][%zu][%zu] (index %zu) is not finite", who, i / P, i % P, first + r, i * stride + first + r);
+    return MCSAS_OK;
+}
+
+static const char *exec_mode_name(int mode) {
+    return mode == MCSAS_EXEC_WAVE ? "MCSAS_EXEC_WAVE" : mode == MCSAS_EXEC_WORKGROUP ? "MCSAS_EXEC_WORKGROUP" : mode == MCSAS_EXEC_PIPELINE ? "MCSAS_EXEC_PIPELINE" : "MCSAS_EXEC_AUTO";
+}
+
+// The set every later launch of the plan starts its repetitions from (include/mcsas_hip.h), kept on the device in the layout of rset;
+// a launch copies it into its slot's rset on the launch stream and runs the start twin of the wave kernel, whose first attempt reads
+// it where the others generate one (chain_wave_body.inc: GIVEN).
+extern "C" int mcsas_hip_plan_set_start(mcsas_plan *pl, const double *start, int32_t rep_stride, int32_t rep_first) {
+    if (!pl) return fail(MCSAS_EINVAL, "set_start: null plan");
+    if (!start) { pl->has_start = false; return MCSAS_OK; }
+    if (pl->mode != MCSAS_EXEC_WAVE || pl->wide)
+        return fail(MCSAS_EINVAL, "set_start: the plan runs in exec_mode %d (%s); a start needs exec_mode = MCSAS_EXEC_WAVE (%d)", pl->mode, exec_mode_name(pl->mode), MCSAS_EXEC_WAVE);
+    const size_t R = pl->prob.n_reps, N = pl->prob.n_contrib, P = pl->prob.n_active;
+    if (rep_first < 0 || (int64_t)rep_first + (int64_t)R > (int64_t)rep_stride)
+        return fail(MCSAS_EINVAL, "set_start: repetitions %d..%lld of a start with %d columns", rep_first, (long long)rep_first + (long long)R - 1, rep_stride);
+    if (int rc = check_start_finite("set_start", start, N, P, (size_t)rep_stride, (size_t)rep_first, R)) return rc;
+    std::vector<double> hr(R * N * P);
+    for (size_t r = 0; r < R; ++r)
+        for (size_t i = 0; i < N * P; ++i) hr[r * N * P + i] = start[i * (size_t)rep_stride + (size_t)rep_first + r];
+    DeviceGuard dev_guard;
+    HIPCHK(hipSetDevice(pl->dev));
+    // (a launch still in flight may not have made its copy of the previous start yet)
+    for (mcsas_plan::Slot &sl : pl->slots)
+        if (sl.launched && sl.ev1) HIPCHK(hipEventSynchronize(sl.ev1));
+    if (!pl->d_start) HIPCHK(pl->pool.get(&pl->d_start, sizeof(double) * hr.size()));
+    HIPCHK(hipMemcpy(pl->d_start, hr.data(), sizeof(double) * hr.size(), hipMemcpyHostToDevice));
+    pl->has_start = true;
+    return MCSAS_OK;
+}
+// the slot's rset takes the start ahead of the kernel, on the launch stream
+static int enqueue_start(mcsas_plan *pl, hipStream_t st) {
+    const size_t bytes = sizeof(double) * (size_t)pl->prob.n_reps * pl->prob.n_contrib * pl->prob.n_active;
+    HIPCHK(hipMemcpyAsync(pl->cur().d_rset, pl->d_start, bytes, hipMemcpyDeviceToDevice, st));
+    return MCSAS_OK;
+}
+
 // marks the plans of a launch that returns early: work of theirs is on the stream that no end event covers (mcsas_hip_plan_destroy)
 struct FailGuard {
     mcsas_plan *const *plans; int n; bool ok = false;
@@ -875,7 +930,7 @@ extern "C" int mcsas_hip_plan_launch_slot(mcsas_plan *pl, void *hip_stream, int3
     if (pl->mode != MCSAS_EXEC_PIPELINE) HIPCHK(hipMemsetAsync(pl->d_stop_relay, 0, 16, st));   // (the pipeline's ticks get McSAS.stop as a kernel argument)
     FailGuard guard{&pl, 1};                              // (any error return below leaves work on `st` that no end event covers)
     KernelRef k;
-    if (int rc = resolve_kernel(pl, plan_family(pl), &k)) return rc;
+    if (int rc = resolve_kernel(pl, launch_family(pl, false), &k)) return rc;
     if (pl->mode == MCSAS_EXEC_PIPELINE) {
         if (int rc = pipeline_launch(pl, k, st)) return rc;
     } else {
@@ -883,6 +938,7 @@ extern "C" int mcsas_hip_plan_launch_slot(mcsas_plan *pl, void *hip_stream, int3
         void *kargs[] = {(void *)&pl->args, k.arg2 == KernelRef::ARG2_WG ? (void *)&pl->wg : (k.arg2 == KernelRef::ARG2_Q3INV ? (void *)&pl->d_q3inv : nullptr)};
         if (int rc = raise_lds_limit(k, pl->lds_bytes)) return rc;
         HIPCHK(hipEventRecord(s.ev0, st));
+        if (pl->has_start) { if (int rc = enqueue_start(pl, st)) return rc; }
         if (int rc = launch_kernel(k, (unsigned)pl->prob.n_reps, kargs, pl->lds_bytes, st)) return rc;
         HIPCHK(hipEventRecord(s.ev1, st));
     }
@@ -1014,7 +1070,7 @@ extern "C" int mcsas_hip_plan_total_steps(mcsas_plan *pl, int64_t *steps) {
 }
 
 // ------------------------------------------------------------------------------ several analyses in one launch
-// One chain_wave_batch_kernel launch per group of plans that run the same kernel (model, q slots per lane, row cache): block b runs
+// One chain_wave_batch_kernel launch per group of plans that run the same kernel (model, q slots per lane, row cache, start or not): block b runs
 // chain table entry b, i.e. one repetition of one plan, with that plan's own argument block.  A chain computes exactly what it
 // computes in the plan's own launch; the plans only share the launch and the stop relay.
 extern "C" int mcsas_hip_plan_launch_batch(mcsas_plan *const *plans, int32_t n, void *hip_stream) {
@@ -1037,7 +1093,7 @@ extern "C" int mcsas_hip_plan_launch_batch(mcsas_plan *const *plans, int32_t n, 
     std::vector<KernelRef> groups;
     for (int i = 0; i < n; ++i) {
         KernelRef k;
-        if (int rc = resolve_kernel(plans[i], KF_WAVE_BATCH, &k)) return rc;
+        if (int rc = resolve_kernel(plans[i], launch_family(plans[i], true), &k)) return rc;
         group_of[i] = (int)(std::find_if(groups.begin(), groups.end(), [&](const KernelRef &g) { return g.id() == k.id(); }) - groups.begin());
         if (group_of[i] == (int)groups.size()) groups.push_back(k);
     }
@@ -1089,6 +1145,8 @@ extern "C" int mcsas_hip_plan_launch_batch(mcsas_plan *const *plans, int32_t n, 
     FailGuard guard{plans, n};                            // (an error return below may leave work on `st` that no end event covers)
     for (int i = 0; i < n; ++i) { plans[i]->stream = st; plans[i]->slots[0].batch_of = bs; }
     HIPCHK(hipMemcpyAsync(bs->d_block, bs->h_block, bs->bytes, hipMemcpyHostToDevice, st));
+    for (int i = 0; i < n; ++i)
+        if (plans[i]->has_start) { if (int rc = enqueue_start(plans[i], st)) return rc; }
     const ChainArgs *d_sets = (const ChainArgs *)(bs->d_block + off_sets);
     for (size_t g = 0; g < groups.size(); ++g) {
         const ChainRef *d_chains = (const ChainRef *)(bs->d_block + off_chains) + g_first[g];
@@ -1147,11 +1205,13 @@ extern "C" int mcsas_hip_analyse_batch(const mcsas_problem *problems, int32_t n,
     return MCSAS_OK;
 }
 
-static int analyse_one(const mcsas_problem *p, mcsas_result *res) {
+// `start` (or null): columns [rep_first, rep_first + n_reps) of start[n_contrib][n_active][rep_stride], mcsas_hip_plan_set_start
+static int analyse_one(const mcsas_problem *p, mcsas_result *res, const double *start = nullptr, int32_t rep_stride = 0, int32_t rep_first = 0) {
     mcsas_plan *pl = nullptr;
     int rc = mcsas_hip_plan_create(p, &pl);
     if (rc) return rc;
-    rc = mcsas_hip_plan_launch(pl, nullptr);
+    if (start) rc = mcsas_hip_plan_set_start(pl, start, rep_stride, rep_first);
+    if (!rc) rc = mcsas_hip_plan_launch(pl, nullptr);
     if (!rc) rc = mcsas_hip_plan_fetch(pl, res);
     mcsas_hip_plan_destroy(pl);
     return rc;
@@ -1169,7 +1229,7 @@ extern "C" int mcsas_hip_shard(int32_t n_reps, int32_t n_devices, int32_t index,
 // McSAS.analyse's repetition loop (mcsas.py:214-262) over several GPUs: one host thread, one plan and one stream per
 // device, each running a contiguous block of repetitions under its global chain ids; every block lands in the caller's
 // (…, numReps) arrays at its place.  No data-path exchange between the devices: the blocks share read-only inputs only.
-static int analyse_sharded(const mcsas_problem *p, mcsas_result *res) {
+static int analyse_sharded(const mcsas_problem *p, mcsas_result *res, const double *start = nullptr) {
     if (res->struct_size != sizeof(mcsas_result)) return fail(MCSAS_EINVAL, "mcsas_result size mismatch");
     const int G = p->n_devices;
     if (G > MCSAS_MAX_DEVICES) return fail(MCSAS_EINVAL, "n_devices %d > %d", G, MCSAS_MAX_DEVICES);
@@ -1205,8 +1265,8 @@ static int analyse_sharded(const mcsas_problem *p, mcsas_result *res) {
         SHBUF(chisq); SHBUF(scaling); SHBUF(background); SHBUF(seconds); SHBUF(num_iter); SHBUF(num_moves); SHBUF(draws);
         SHBUF(attempts); SHBUF(converged);
 #undef SHBUF
-        th.emplace_back([&s]() {
-            s.rc = analyse_one(&s.prob, &s.out);
+        th.emplace_back([&s, start, R]() {
+            s.rc = analyse_one(&s.prob, &s.out, start, (int32_t)R, s.first);   // (every block reads its own columns of the one start)
             if (s.rc) s.err = g_err;                          // (thread-local in the worker)
         });
     }
@@ -1255,6 +1315,26 @@ extern "C" int mcsas_hip_analyse(const mcsas_problem *p, mcsas_result *res) {
     }
     if (p && p->struct_size == sizeof(mcsas_problem) && p->n_devices > 1) return analyse_sharded(p, res);
     return analyse_one(p, res);
+}
+
+// McSAS.analyse with the first attempt of every repetition started from a given set (include/mcsas_hip.h): the wavefront mode only,
+// and every refusal before a device is touched.
+extern "C" int mcsas_hip_analyse_from(const mcsas_problem *p, const double *start, mcsas_result *res) {
+    if (!p || !res) return fail(MCSAS_EINVAL, "analyse_from: null argument");
+    if (p->struct_size != sizeof(mcsas_problem))
+        return fail(MCSAS_EINVAL, "analyse_from: mcsas_problem size %u, library expects %zu (ABI mismatch)", p->struct_size, sizeof(mcsas_problem));
+    if (p->n_active == 0) return mcsas_hip_analyse(p, res);                     // nothing to start: one contribution at fixed values
+    if (!start) return fail(MCSAS_EINVAL, "analyse_from: start is NULL (mcsas_hip_analyse runs without one)");
+    if (p->exec_mode != MCSAS_EXEC_AUTO && p->exec_mode != MCSAS_EXEC_WAVE)
+        return fail(MCSAS_EINVAL, "analyse_from: exec_mode %d (%s) asked; a start needs exec_mode = MCSAS_EXEC_WAVE (%d, or 0)", p->exec_mode, exec_mode_name(p->exec_mode), MCSAS_EXEC_WAVE);
+    if (p->nq > 64 * WAVE) return fail(MCSAS_EINVAL, "analyse_from: nq %d > %d: one wavefront per chain does not take it, and a start needs exec_mode = MCSAS_EXEC_WAVE", p->nq, 64 * WAVE);
+    if (p->n_active < 0 || p->n_active > MCSAS_MAX_ACTIVE) return fail(MCSAS_EINVAL, "n_active %d out of range", p->n_active);
+    if (p->n_contrib < 1 || p->n_reps < 1) return fail(MCSAS_EINVAL, "n_contrib and n_reps must be >= 1");
+    if (int rc = check_start_finite("analyse_from", start, (size_t)p->n_contrib, (size_t)p->n_active, (size_t)p->n_reps, 0, (size_t)p->n_reps)) return rc;
+    mcsas_problem q = *p;
+    q.exec_mode = MCSAS_EXEC_WAVE;
+    if (q.n_devices > 1) return analyse_sharded(&q, res, start);
+    return analyse_one(&q, res, start, q.n_reps, 0);
 }
 
 // ------------------------------------------------------------------------------ rows evaluated by the caller (ABI 4)

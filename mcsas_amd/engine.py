@@ -7,7 +7,7 @@ in libmcsas_hip.so; nothing here evaluates a form factor or a chi-squared on the
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -185,12 +185,39 @@ class ChainResults:
         self.c = r
 
 
-def analyse(model: ModelSetup, q, intensity, sigma, st: Settings, replay=None, stop=None, smear=None) -> ChainResults:
-    """All repetitions of McSAS.analyse (mcsas.py:214-262) in one kernel launch."""
+def _check_start(start, model: ModelSetup, st: Settings, who="analyse"):
+    """The start set of an analysis as a contiguous [n_contrib][n_active][R >= n_reps] array (the layout of ChainResults.contribs);
+    ValueError for a wrong shape or a model that exists only as host code — before any library call."""
+    if model.model_id == MODEL_HOST:
+        raise ValueError("%s: a model that exists only as host code takes no start (a start runs one wavefront per chain)" % who)
+    a = f64(start)
+    if a.ndim != 3 or a.shape[0] != int(st.n_contrib) or a.shape[1] != model.n_active:
+        raise ValueError("%s: start must be (n_contrib, n_active, n_reps) = (%d, %d, >= %d), got %r"
+                         % (who, st.n_contrib, model.n_active, st.n_reps, a.shape))
+    return a
+
+
+def _start_columns(a, st: Settings, rep_first, who="analyse"):
+    if rep_first < 0 or rep_first + int(st.n_reps) > a.shape[2]:
+        raise ValueError("%s: start has %d repetitions, %d..%d asked" % (who, a.shape[2], rep_first, rep_first + int(st.n_reps) - 1))
+
+
+def analyse(model: ModelSetup, q, intensity, sigma, st: Settings, replay=None, stop=None, smear=None, start=None) -> ChainResults:
+    """All repetitions of McSAS.analyse (mcsas.py:214-262) in one kernel launch.  `start`: [n_contrib][n_active][n_reps] (a
+    ChainResults.contribs; further repetitions are ignored), the set the first attempt of every repetition starts from instead of
+    a random one (mcsas_hip_analyse_from, include/mcsas_hip.h) — one wavefront per chain; exec_mode 2 or 3 is refused."""
+    if start is not None and model.n_active > 0:
+        a = _check_start(start, model, st)
+        _start_columns(a, st, 0)
+        if a.shape[2] != int(st.n_reps):
+            a = f64(a[:, :, :int(st.n_reps)])
     lib = _lib.load(tuning=bool(st.debug_flags))
     prob = HipProblem(model, q, intensity, sigma, st, replay, stop, smear)
     res = ChainResults(st.n_contrib, model.n_active, st.n_reps, len(prob.q))
-    check(lib.mcsas_hip_analyse(C.byref(prob.c), C.byref(res.c)), lib)
+    if start is not None and model.n_active > 0:
+        check(lib.mcsas_hip_analyse_from(C.byref(prob.c), as_dp(a), C.byref(res.c)), lib)
+    else:
+        check(lib.mcsas_hip_analyse(C.byref(prob.c), C.byref(res.c)), lib)
     return res
 
 
@@ -243,7 +270,8 @@ def analyse_many(problems, streams=2):
         return hs[k % len(hs)]
 
     def direct(pr):
-        return analyse(pr["model"], pr["q"], pr["intensity"], pr["sigma"], pr["st"], pr.get("replay"), pr.get("stop"), pr.get("smear"))
+        return analyse(pr["model"], pr["q"], pr["intensity"], pr["sigma"], pr["st"], pr.get("replay"), pr.get("stop"), pr.get("smear"),
+                       start=pr.get("start"))
 
     out, pending, launched = [None] * len(problems), [], {}
     try:
@@ -258,7 +286,17 @@ def analyse_many(problems, streams=2):
             while len(pending) >= cap:
                 j, pl = pending.pop(0)
                 out[j] = pl.fetch(); pl.close()
+            if pr.get("start") is not None:                  # (a start runs one wavefront per chain: analyse)
+                if st.exec_mode not in (EXEC_AUTO, EXEC_WAVE):
+                    raise ValueError("analyse_many: problem %d asks for exec_mode %d with a start (0 or 1)" % (i, st.exec_mode))
+                st = replace(st, exec_mode=EXEC_WAVE)
             pl = Plan(pr["model"], pr["q"], pr["intensity"], pr["sigma"], st, pr.get("replay"), pr.get("stop"), pr.get("smear"))
+            if pr.get("start") is not None:
+                try:
+                    pl.set_start(pr["start"])
+                except Exception:
+                    pl.close()
+                    raise
             k = launched.get(st.device, 0); launched[st.device] = k + 1
             pl.launch(stream=stream_for(st.device, k).value)
             pending.append((i, pl))
@@ -283,8 +321,15 @@ def analyse_batch(problems):
     data set fills the chip.  `problems` as for analyse_many.  Returns the ChainResults in order; each is identical to analyse() of
     that problem with exec_mode = EXEC_WAVE (seconds aside), whatever else is in the batch.  Device lists and models without an
     active parameter run through analyse() at their place; a model that exists only as host code (MODEL_HOST) or a data set of
-    more than WAVE_MAX_Q q-points raises ValueError before anything is launched."""
+    more than WAVE_MAX_Q q-points raises ValueError before anything is launched.  A problem may carry a "start" key (see analyse);
+    a batch with one runs through resident plans (Plan.set_start, launch_batch, fetch), the problems without a start included, and
+    each result is then identical to analyse(..., start=...) of that problem."""
     problems = [p if isinstance(p, dict) else dict(model=p[0], q=p[1], intensity=p[2], sigma=p[3], st=p[4]) for p in problems]
+    starts = {}
+    for i, pr in enumerate(problems):
+        if pr.get("start") is not None and pr["model"].n_active > 0:
+            starts[i] = _check_start(pr["start"], pr["model"], pr["st"], "analyse_batch: problem %d" % i)
+            _start_columns(starts[i], pr["st"], 0, "analyse_batch: problem %d" % i)
     for i, pr in enumerate(problems):
         if pr["model"].model_id == MODEL_HOST:
             raise ValueError("analyse_batch: problem %d: a model that exists only as host code has no device kernel to batch" % i)
@@ -297,7 +342,30 @@ def analyse_batch(problems):
     for i, pr in enumerate(problems):
         if not (pr["model"].n_active == 0 or pr["st"].devices):
             batched.append(i)
-    if batched:
+    if batched and any(i in starts for i in batched):
+        plans = []
+        try:
+            for i in batched:
+                pr = problems[i]
+                if pr["st"].exec_mode not in (EXEC_AUTO, EXEC_WAVE):
+                    raise ValueError("analyse_batch: problem %d asks for exec_mode %d; a batch runs one wavefront per chain" % (i, pr["st"].exec_mode))
+                st = replace(pr["st"], exec_mode=EXEC_WAVE)
+                plans.append(Plan(pr["model"], pr["q"], pr["intensity"], pr["sigma"], st, pr.get("replay"), pr.get("stop"), pr.get("smear")))
+                if i in starts:
+                    plans[-1].set_start(starts[i])
+            launch_batch(plans)
+            failure = None
+            for i, pl in zip(batched, plans):                # (every plan is fetched, so that none is destroyed in flight)
+                try:
+                    out[i] = pl.fetch()
+                except _lib.McSASHipError as e:
+                    failure = failure or e
+            if failure is not None:
+                raise failure
+        finally:
+            for pl in plans:
+                pl.close()
+    elif batched:
         lib = _lib.load(tuning=bool(problems[batched[0]]["st"].debug_flags))
         probs, results = [], []
         for i in batched:
@@ -312,7 +380,8 @@ def analyse_batch(problems):
             out[i] = r
     for i, pr in enumerate(problems):
         if out[i] is None:
-            out[i] = analyse(pr["model"], pr["q"], pr["intensity"], pr["sigma"], pr["st"], pr.get("replay"), pr.get("stop"), pr.get("smear"))
+            out[i] = analyse(pr["model"], pr["q"], pr["intensity"], pr["sigma"], pr["st"], pr.get("replay"), pr.get("stop"), pr.get("smear"),
+                             start=pr.get("start"))
     return out
 
 
@@ -346,6 +415,17 @@ class Plan:
         res = ChainResults(st.n_contrib, self.prob.model.n_active, st.n_reps, len(self.prob.q)) if want_arrays else None
         check(self.lib.mcsas_hip_plan_fetch_slot(self.h, C.c_int32(slot), C.byref(res.c) if res is not None else None), self.lib)
         return res
+
+    def set_start(self, contribs, rep_first=0):
+        """Every later launch of this plan (launch_batch included) starts repetition r from contribs[:, :, rep_first + r]
+        ([n_contrib][n_active][R], e.g. a fetched ChainResults.contribs) instead of a random set, for its first attempt
+        (mcsas_hip_plan_set_start).  The plan keeps a copy.  None clears it.  Plans in the wavefront mode only."""
+        if contribs is None:
+            check(self.lib.mcsas_hip_plan_set_start(self.h, None, 0, 0), self.lib)
+            return
+        a = _check_start(contribs, self.prob.model, self.prob.st, "Plan.set_start")
+        _start_columns(a, self.prob.st, int(rep_first), "Plan.set_start")
+        check(self.lib.mcsas_hip_plan_set_start(self.h, as_dp(a), C.c_int32(a.shape[2]), C.c_int32(int(rep_first))), self.lib)
 
     def reseed(self, seed, rep_offset=0):
         check(self.lib.mcsas_hip_plan_reseed(self.h, C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_int32(rep_offset)), self.lib)

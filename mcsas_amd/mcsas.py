@@ -82,7 +82,15 @@ class McSAS(object):
     def stop(self, flag):
         self._stop.value = 1 if flag else 0
 
+    def _check_start_mode(self, start):
+        if start is not None and self.execMode not in (engine.EXEC_AUTO, engine.EXEC_WAVE):
+            raise ValueError("McSAS: a start runs one wavefront per chain; execMode %d was asked (0 or 1)" % self.execMode)
+
     def calc(self, **kwargs):                                # mcsas.py:149-179
+        """`start=`: an [N][P][R] array of contributions, typically an earlier `algo.result[0]['contribs']`: the first attempt of
+        every repetition starts from it instead of a random set — to continue a run that ended at maxIterations, to refine a result
+        to a tighter criterion, or to warm-start from a neighbouring data set's result (see analyse)."""
+        self._check_start_mode(kwargs.get("start"))
         self.result = []
         self.stop = False
         assert self.data is not None
@@ -91,7 +99,7 @@ class McSAS(object):
         if not self.model.paramCount():
             logging.warning("No parameters to analyse given! Breaking up.")
             return
-        self.analyse(replay=kwargs.get("replay"))            # (replay: tests feed the uniform stream the reference consumed)
+        self.analyse(replay=kwargs.get("replay"), start=kwargs.get("start"))   # (replay: tests feed the uniform stream the reference consumed)
         if not len(self.result):
             return
         self.histogram()
@@ -108,7 +116,10 @@ class McSAS(object):
             show_incomplete=self.showIncomplete(), seed=seed, device=self.device, devices=self.devices,
             waves_per_chain=self.wavesPerChain, exec_mode=self.execMode)
 
-    def analyse(self, replay=None):                          # mcsas.py:191-285
+    def analyse(self, replay=None, start=None):              # mcsas.py:191-285
+        """`start`: [numContribs][active parameters][>= numReps] — mcFit's rset of the first attempt of each repetition, in place of
+        generateParameters(numContribs) (mcsas.py:317); later attempts draw a fresh set as always.  A start forces the wavefront mode
+        for this call (include/mcsas_hip.h: mcsas_hip_analyse_from); an explicit execMode of workgroup or pipeline raises ValueError."""
         if self.result is None:
             self.result = []
         data, model = self.data, self.model
@@ -116,7 +127,7 @@ class McSAS(object):
             numContribs, numReps = 1, 1                      # mcsas.py:198-199: nothing active, nothing to fit
         else:
             numContribs, numReps = self.numContribs(), self.numReps()
-        pr = self._problem(numContribs, numReps, replay)
+        pr = self._problem(numContribs, numReps, replay, start)
         if pr["model"].model_id == engine.MODEL_HOST:
             # a model with Python formfactor / volume only: its rows are evaluated here, by the model's own calcIntensity with the
             # set-value-and-restore semantics of ScatteringModel.calc (scatteringmodel.py:86-104); the device does the rest
@@ -128,18 +139,26 @@ class McSAS(object):
                                            replay=pr["replay"], stop=pr["stop"], window=self.hostRowWindow)
         else:
             res = engine.analyse(pr["model"], pr["q"], pr["intensity"], pr["sigma"], pr["st"],
-                                 replay=pr["replay"], stop=pr["stop"], smear=pr["smear"])
+                                 replay=pr["replay"], stop=pr["stop"], smear=pr["smear"], start=pr.get("start"))
         self._store(res, numReps)
 
-    def _problem(self, numContribs=None, numReps=None, replay=None):
-        """What analyse() hands to the library for the current data / model / settings (engine.analyse_many takes a list of these)."""
+    def _problem(self, numContribs=None, numReps=None, replay=None, start=None):
+        """What analyse() hands to the library for the current data / model / settings (engine.analyse_many takes a list of these).
+        With a `start` (see analyse) the problem asks for the wavefront mode and carries the checked array under "start"."""
         data, model = self.data, self.model
         if numContribs is None:
             active = any(isActiveFitParam(p) for p in model.params())
             numContribs, numReps = (self.numContribs(), self.numReps()) if active else (1, 1)
         smear = data.smearArgs(model) if hasattr(data, "smearArgs") else None   # sasmodel.py:56-60
-        return dict(model=setup_from_model(model, data), q=data.q, intensity=data.f.binnedData, sigma=data.f.binnedDataU,
-                    st=self._settings(numContribs, numReps), replay=replay, stop=self._stop, smear=smear)
+        pr = dict(model=setup_from_model(model, data), q=data.q, intensity=data.f.binnedData, sigma=data.f.binnedDataU,
+                  st=self._settings(numContribs, numReps), replay=replay, stop=self._stop, smear=smear)
+        if start is not None and pr["model"].n_active > 0:
+            self._check_start_mode(start)
+            a = engine._check_start(start, pr["model"], pr["st"], "McSAS.analyse")
+            engine._start_columns(a, pr["st"], 0, "McSAS.analyse")
+            pr["st"].exec_mode = engine.EXEC_WAVE
+            pr["start"] = a
+        return pr
 
     def _store(self, res, numReps=None):
         """The second half of analyse() (mcsas.py:221-285): warnings, active values, the result dictionary."""

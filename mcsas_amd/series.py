@@ -7,7 +7,7 @@ from __future__ import annotations
 from collections import OrderedDict
 
 
-def run_series(algo, datasets, keys=None, replays=None, overlap=False, batch=False):
+def run_series(algo, datasets, keys=None, replays=None, overlap=False, batch=False, start=None):
     """-> (results, series).  `results[i]` is `algo.result[0]` of data set i (None when nothing
     converged); `series[(param, lower, upper, yweight)]` is the list of `(key_i, moments.fields)`.
     `keys`: the series key value of each data set (default: its index).  `replays`: per data set, the uniform
@@ -15,9 +15,30 @@ def run_series(algo, datasets, keys=None, replays=None, overlap=False, batch=Fal
     run side by side on the device instead of one after the other (same results; algo.seed should be set: an unseeded algo draws a
     new seed per data set either way).  `batch`: the Monte-Carlo part of all data sets runs as ONE batch of wavefront-per-chain
     chains (engine.analyse_batch; results as each data set's analysis in that mode alone), the rest as with `overlap`; a model that
-    exists only as host code runs one data set after the other instead."""
+    exists only as host code runs one data set after the other instead.
+    `start`: the contributions the first attempt of every repetition starts from (McSAS.analyse: an [N][P][R] array; wavefront
+    mode) — one array for every data set, a list with one entry per data set (None: cold), or "previous": each data set starts from
+    the previous stored result's contributions; the first one, and any after a data set that stored nothing, starts cold.
+    "previous" is sequential by nature: with `batch` or `overlap` it raises ValueError."""
     if algo.model is None:
         raise ValueError("no model set")
+    previous = isinstance(start, str)
+    if previous:
+        if start != "previous":
+            raise ValueError('run_series: start=%r (an array, a list of arrays / None, or "previous")' % (start,))
+        if batch or overlap:
+            raise ValueError('run_series: start="previous" chains each data set to the one before; batch / overlap run them together')
+    datasets = list(datasets)
+    if start is None or previous:
+        starts = [None] * len(datasets)
+    elif isinstance(start, (list, tuple)):
+        if len(start) != len(datasets):
+            raise ValueError("run_series: %d start entries for %d data sets" % (len(start), len(datasets)))
+        starts = list(start)
+    else:
+        starts = [start] * len(datasets)
+    if any(s is not None for s in starts):
+        algo._check_start_mode(True)
     results, series = [], OrderedDict()
     chains = None
     from . import engine
@@ -26,7 +47,7 @@ def run_series(algo, datasets, keys=None, replays=None, overlap=False, batch=Fal
         problems = []
         for i, data in enumerate(datasets):
             algo.data = data
-            problems.append(algo._problem(replay=None if replays is None else replays[i]))
+            problems.append(algo._problem(replay=None if replays is None else replays[i], start=starts[i]))
         if all(pr["model"].model_id != engine.MODEL_HOST for pr in problems):
             chains = engine.analyse_batch(problems)
     elif overlap and algo.model.paramCount():
@@ -36,13 +57,14 @@ def run_series(algo, datasets, keys=None, replays=None, overlap=False, batch=Fal
         problems = []
         for i, data in enumerate(datasets):
             algo.data = data
-            problems.append(algo._problem(replay=None if replays is None else replays[i]))
+            problems.append(algo._problem(replay=None if replays is None else replays[i], start=starts[i]))
         chains = engine.analyse_many(problems)
     for i, data in enumerate(datasets):
         key = i if keys is None else keys[i]
         algo.data = data
         if chains is None:
-            algo.calc(replay=None if replays is None else replays[i])
+            prev = results[-1]["contribs"] if previous and results and results[-1] is not None else None
+            algo.calc(replay=None if replays is None else replays[i], start=prev if previous else starts[i])
         else:
             # (McSAS.stop is left as the analyses saw it: _store tells "stop pressed" from "criterion not reached" by it)
             algo.result = []
