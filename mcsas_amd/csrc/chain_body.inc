@@ -1,23 +1,35 @@
-// chain_wave_body.inc — the body of one wave-per-chain chain (chain_wave.h), included verbatim by chain_wave_kernel and
-// chain_wave_batch_kernel (and their start twins) so that all compile from the same text and the single kernel's code stays what
-// it was.  In scope at the point of inclusion: M, QPL, CACHE (template parameters), `const ChainArgs &a` (the analysis),
-// `const int rep` (its repetition), `lds` (the dynamic LDS), `const int lane` and GIVEN (a compile-time bool: the first attempt
-// takes the set the host left in rset instead of generating one, mcsas_hip_plan_set_start; false folds away).
-    const int N = a.n_contrib, P = a.model.n_active, qpad = a.qpad;
-    double *lq = lds, *lw = lds + qpad, *lwI = lds + 2 * qpad, *lq3 = lds + 3 * qpad, *tab = lds + 4 * qpad;
-    for (int i = lane; i < qpad; i += WAVE) {
-        const double qq = a.q[i];
-        lq[i] = qq; lw[i] = a.w[i]; lwI[i] = a.wI[i]; lq3[i] = 1.0 / (qq * qq * qq);
-    }
-    const QTables qt = make_qtables<M>(a.model, lq, lq3, tab);
-    Contrib<M>::fill_table(a.model, tab, lane, WAVE);
-    __syncthreads();
-
+// chain_body.inc — one Monte-Carlo chain with the running intensity ft in registers (McSAS.mcFit, mcsas.py:287-439; retry loop
+// of McSAS.analyse, :220-246), from its rset pointer to its ChainOut record: initial set, initial fit, batches of 64 proposals,
+// the division-free comparison, the accept bookkeeping, retries, final fit.  Included verbatim, inside the kernel, by the
+// wavefront-per-chain kernels (chain_wave_kernel.inc) and by the q-split workgroup kernel (chain_wide.h), so that both families
+// compile from one text and a change to the step is made once.  Text, not a function or a policy object: either was measured to
+// change the kernels' code (DESIGN §4.1a).
+//
+// In scope at the point of inclusion: M, QPL (template parameters); CACHE (compile-time bool: per-contribution rows are kept in
+// a.cache; false re-evaluates the old row and folds the cache away) and GIVEN (compile-time bool: the first attempt takes the set
+// the host left in rset instead of generating one, mcsas_hip_plan_set_start; false folds away); `const ChainArgs &a` (the
+// analysis), `const int rep` (its repetition), `const int lane` (0..63), `N`, `P`, `qpad` (a.n_contrib, a.model.n_active,
+// a.qpad), `qt` (the QTables of this lane's q-points: RowEval fills slot j of a lane with one of them) — and the hooks below.
+// A hook is a macro the including file defines ahead of the #include and #undef's after it; the ones marked (text) stand for
+// exactly the tokens given, without parentheses of their own, because the sums they are part of keep their order of evaluation.
+//   CHAIN_STATE        declarations: what the sums below keep from one call to the next, if anything (it sits among the chain's own
+//                      state because moving a declaration was measured to change the code)
+//   CHAIN_CACHE_PTR(p) where this thread's `cache` pointer starts, given the repetition's first row p
+//   CHAIN_ROW(r)       (text) offset from `cache` of this lane's slot 0 in row r; slot j is WAVE * j further
+//   CHAIN_Q(j)         (text) index of this lane's slot j into the padded data (a.I, one row of a.fit)
+//   CHAIN_W(j)         w = 1/sigma^2 at slot j
+//   CHAIN_WI(j)        wI = I/sigma^2 at slot j
+//   CHAIN_SUM3(x,y,z)  statement: replaces three per-lane values by their sums over the chain's q-points, the same in every thread
+//   CHAIN_SUM1(x)      expression: that sum of one per-lane value
+//   CHAIN_FIRST        true in one thread per lane index: those write the initial set to rset
+//   CHAIN_LEADER       true in one thread of the chain: it writes an accepted row to rset, and the record
+//   CHAIN_STOP         expression: McSAS.stop has been asked for — one answer for all threads of the chain
     double *rset = a.rset + (size_t)rep * N * P;
-    double *cache = CACHE ? a.cache + (size_t)rep * a.cache_rows * qpad : nullptr;
+    double *cache = CACHE ? CHAIN_CACHE_PTR(a.cache + (size_t)rep * a.cache_rows * qpad) : nullptr;
     DrawSource src{a.replay ? a.replay + (size_t)rep * a.replay_len : nullptr, a.replay_len, a.seed,
                    (uint32_t)(a.rep_offset + rep)};
     int overflow = 0;
+    CHAIN_STATE
     uint64_t draw_pos = 0;                 // uniforms consumed so far by this rep (all attempts)
     const uint64_t t_start = wall_clock64();
 
@@ -47,13 +59,13 @@
                             double u = src.at(draw_pos + (uint64_t)p * N + n, overflow);   // parameter-major
                             row[p] = gen_transform(a.gen_kind[p], u) * (a.gen_hi[p] - a.gen_lo[p]) + a.gen_lo[p];
                         }
-                        rset[(size_t)n * P + p] = row[p];
+                        if (CHAIN_FIRST) rset[(size_t)n * P + p] = row[p];
                     }
             } else {
 #pragma unroll
                 for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p) row[p] = a.gen_lo[p] > 0. ? a.gen_lo[p] : 1e-9;
             }
-            Contrib<M> mine;
+            Contrib<M> mine;                                       // (where a chain has several waves, each prepares all 64: the same numbers)
             mine.prepare(a.model, row);
             // model.calc(data, rset, c): rows accumulated in contribution order (scatteringmodel.py:90-101)
             const int cnt = min(WAVE, N - n0);
@@ -64,7 +76,7 @@
 #pragma unroll
                 for (int j = 0; j < QPL; ++j) {
                     ft[j] += it[j];
-                    if (CACHE) cache[(size_t)(n0 + i) * qpad + lane + WAVE * j] = it[j];
+                    if (CACHE) cache[CHAIN_ROW(n0 + i) + WAVE * j] = it[j];
                 }
             }
         }
@@ -75,10 +87,10 @@
             double s1 = 0., s2 = 0., s3 = 0.;
 #pragma unroll
             for (int j = 0; j < QPL; ++j) {
-                double wt = lw[lane + WAVE * j] * ft[j];
-                s1 += wt; s2 = fma(wt, ft[j], s2); s3 = fma(lwI[lane + WAVE * j], ft[j], s3);
+                double wt = CHAIN_W(j) * ft[j];
+                s1 += wt; s2 = fma(wt, ft[j], s2); s3 = fma(CHAIN_WI(j), ft[j], s3);
             }
-            wave_sum3(s1, s2, s3);
+            CHAIN_SUM3(s1, s2, s3);
             cur = solve_fit(a, s1, s2, s3);
         }
         num_iter = 0; num_moves = 0;
@@ -94,9 +106,9 @@
         bool running = (N > 1);
         while (running) {
             if (!(cur.chi2 > a.conv_crit) || !(num_iter < a.max_iter)) break;
-            if (stop_requested(a)) { stopped = 1; break; }   // (one answer per wave: chain_common.h)
-            // proposals for the next 64 steps, one per lane: generateParameters() draws P uniforms
-            // per step in parameter order (mcsas.py:358)
+            if (CHAIN_STOP) { stopped = 1; break; }
+            // proposals for the next 64 steps, one per lane (the same in every wave of the chain): generateParameters() draws
+            // P uniforms per step in parameter order (mcsas.py:358)
             double prow[MCSAS_MAX_ACTIVE] = {0., 0., 0., 0.};
             int povf = 0;
 #pragma unroll
@@ -118,7 +130,7 @@
                 if (__builtin_amdgcn_readlane(povf, kk)) overflow = 1;
                 double inew[QPL], test[QPL];
                 if (CACHE) {
-                    const double *orow = cache + (size_t)ri * qpad + lane;
+                    const double *orow = cache + CHAIN_ROW(ri);
 #pragma unroll
                     for (int j = 0; j < QPL; ++j) test[j] = orow[WAVE * j];
                 } else {
@@ -138,10 +150,10 @@
                     // instead (the workgroup and pipeline kernels carry d rows), so that ft is the SAME number in all
                     // three modes — at most one ulp per accepted move away from the reference's order
                     test[j] = ft[j] + (inew[j] - test[j]);
-                    double wt = lw[lane + WAVE * j] * test[j];
-                    s1 += wt; s2 = fma(wt, test[j], s2); s3 = fma(lwI[lane + WAVE * j], test[j], s3);
+                    double wt = CHAIN_W(j) * test[j];
+                    s1 += wt; s2 = fma(wt, test[j], s2); s3 = fma(CHAIN_WI(j), test[j], s3);
                 }
-                wave_sum3(s1, s2, s3);
+                CHAIN_SUM3(s1, s2, s3);
                 // s1 = Σ w C, s2 = Σ w C², s3 = Σ w I C of the candidate (mcsas.py:376)
                 double S = a.SII, num = s3, den = s2;
                 if (a.find_bg) {
@@ -155,13 +167,13 @@
 #pragma unroll
                     for (int j = 0; j < QPL; ++j) {
                         ft[j] = test[j];
-                        if (CACHE) cache[(size_t)ri * qpad + lane + WAVE * j] = inew[j];
+                        if (CACHE) cache[CHAIN_ROW(ri) + WAVE * j] = inew[j];
                     }
 #pragma unroll
                     for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)
                         if (p < P) {
                             double val = readlane_f64(prow[p], kk);
-                            if (lane == 0) rset[(size_t)ri * P + p] = val;
+                            if (CHAIN_LEADER) rset[(size_t)ri * P + p] = val;
                         }
                     if (!CACHE) __threadfence_block();   // rset[ri] is re-read by every lane N steps later
                     ++num_moves;
@@ -178,20 +190,19 @@
             double s1 = 0., s2 = 0., s3 = 0.;
 #pragma unroll
             for (int j = 0; j < QPL; ++j) {
-                double wt = lw[lane + WAVE * j] * ft[j];
-                s1 += wt; s2 = fma(wt, ft[j], s2); s3 = fma(lwI[lane + WAVE * j], ft[j], s3);
+                double wt = CHAIN_W(j) * ft[j];
+                s1 += wt; s2 = fma(wt, ft[j], s2); s3 = fma(CHAIN_WI(j), ft[j], s3);
             }
-            wave_sum3(s1, s2, s3);
+            CHAIN_SUM3(s1, s2, s3);
             cur = solve_fit(a, s1, s2, s3);
             // reported chi-squared: direct residual sum, like chiSqr (backgroundscalingfit.py:72-77)
             double rs = 0.;
 #pragma unroll
             for (int j = 0; j < QPL; ++j) {
-                const int i = lane + WAVE * j;
-                double r = a.I[i] - (ft[j] * cur.A + cur.b);
-                rs += lw[i] * r * r;
+                double r = a.I[CHAIN_Q(j)] - (ft[j] * cur.A + cur.b);
+                rs += CHAIN_W(j) * r * r;
             }
-            cur.chi2 = wave_sum(rs) / (double)a.nq;
+            cur.chi2 = CHAIN_SUM1(rs) / (double)a.nq;
         }
         converged = !(cur.chi2 > a.conv_crit);
         if (converged || stopped) break;
@@ -200,9 +211,9 @@
     // ---------------------------------------------------------------- outputs (mcsas.py:428-439)
 #pragma unroll
     for (int j = 0; j < QPL; ++j)
-        a.fit[(size_t)rep * qpad + lane + WAVE * j] = ft[j] * cur.A + cur.b;      // ifinal*sc[0]+sc[1]
+        a.fit[(size_t)rep * qpad + CHAIN_Q(j)] = ft[j] * cur.A + cur.b;           // ifinal*sc[0]+sc[1]
     overflow = __any(overflow);
-    if (lane == 0) {
+    if (CHAIN_LEADER) {
         ChainOut o;
         o.chisq = cur.chi2; o.scaling = cur.A; o.background = cur.b;
         o.seconds = (double)(wall_clock64() - t_start) * 1e-8;                    // 100 MHz counter

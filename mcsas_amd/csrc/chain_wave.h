@@ -6,7 +6,8 @@
 //   LDS       : q, w = 1/sigma^2, wI = I/sigma^2 (read-only, shared by the block), orientation table
 //   HBM       : rset[N][P], cached per-contribution intensity rows [N][qpad] (CACHE), outputs
 // No barriers in the step loop: the three weighted sums are reduced with DPP inside the wave,
-// the accept/reject decision is wave-uniform.
+// the accept/reject decision is wave-uniform.  The chain itself is chain_body.inc, shared with chain_wide.h; the kernels below
+// differ in how they come by their analysis, and chain_wave_kernel.inc is what they do with it.
 #pragma once
 #include "chain_common.h"
 
@@ -21,18 +22,18 @@ __global__ __launch_bounds__(64, MCSAS_WAVE_MIN_WAVES(QPL, CACHE)) void chain_wa
     const int lane = threadIdx.x;
     const int rep = blockIdx.x;
     constexpr bool GIVEN = false;
-#include "chain_wave_body.inc"
+#include "chain_wave_kernel.inc"
 }
 
 // The same chain started from a given set (mcsas_hip_plan_set_start): the host has copied the repetition's start into rset ahead of
-// the launch, and the first attempt takes it where chain_wave_kernel generates one (chain_wave_body.inc: GIVEN).
+// the launch, and the first attempt takes it where chain_wave_kernel generates one (chain_body.inc: GIVEN).
 template <int M, int QPL, bool CACHE>
 __global__ __launch_bounds__(64, MCSAS_WAVE_MIN_WAVES(QPL, CACHE)) void chain_wave_start_kernel(const ChainArgs a) {
     extern __shared__ double lds[];
     const int lane = threadIdx.x;
     const int rep = blockIdx.x;
     constexpr bool GIVEN = true;
-#include "chain_wave_body.inc"
+#include "chain_wave_kernel.inc"
 }
 
 // Every pointer of an argument block points into device (or mapped host) memory, i.e. the global address space.  The compiler
@@ -62,7 +63,7 @@ __global__ __launch_bounds__(64, MCSAS_WAVE_MIN_WAVES(QPL, CACHE)) void chain_wa
     ChainArgs a = sets[set];                                    // (read whole before the first store)
     chain_args_pointers(a, ((ConstChainArgs *)sets)[set]);
     constexpr bool GIVEN = false;
-#include "chain_wave_body.inc"
+#include "chain_wave_kernel.inc"
 }
 
 // ... and its start twin: every analysis of such a launch has its start in its rset (plans with and without a start share a batch
@@ -78,7 +79,7 @@ __global__ __launch_bounds__(64, MCSAS_WAVE_MIN_WAVES(QPL, CACHE)) void chain_wa
     ChainArgs a = sets[set];
     chain_args_pointers(a, ((ConstChainArgs *)sets)[set]);
     constexpr bool GIVEN = true;
-#include "chain_wave_body.inc"
+#include "chain_wave_kernel.inc"
 }
 
 }  // namespace mcsas

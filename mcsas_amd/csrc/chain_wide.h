@@ -1,7 +1,8 @@
 // chain_wide.h — one workgroup = one Monte-Carlo chain, the q-points split over its waves: the kernel for data sets with
 // more than 1024 q-points (un-binned files, nBin = 0: dataobj/dataconfig.py:99; McSAS.analyse takes any data.count,
-// mcsas.py:210).  Same chain as chain_wave.h (McSAS.mcFit, mcsas.py:287-439; retry loop of McSAS.analyse, :220-246), same
-// arithmetic per q-point; what differs is where a q-point lives and how the three weighted sums of a step are put together.
+// mcsas.py:210).  Same chain as chain_wave.h (McSAS.mcFit, mcsas.py:287-439; retry loop of McSAS.analyse, :220-246), compiled from
+// the same text (chain_body.inc); what differs is where a q-point lives and how the three weighted sums of a step are put
+// together, and this file holds that and nothing of the step.
 //
 // Layout: NW = blockDim.x / 64 waves (<= 8), qpad = 64 * QPL * NW; wave v owns the q slice [64 QPL v, 64 QPL (v + 1)):
 // q index i = 64 (QPL v + j) + lane, j = register slot.  ft, w, wI of the slice live in registers; q and 1/q^3 in LDS when
@@ -31,6 +32,22 @@ __device__ __forceinline__ void wide_sum3(double &s1, double &s2, double &s3, do
     par ^= 1;
 }
 
+// ... and of one
+__device__ __forceinline__ double wide_sum1(double s, double *part, int &par, int wave, int lane, int NW) {
+    double z1 = 0., z2 = 0.;
+    wide_sum3(s, z1, z2, part, par, wave, lane, NW);
+    return s;
+}
+
+// McSAS.stop: one thread looks, everybody acts on what it saw (a wave of its own could see the word change between two waves'
+// reads and leave the others at the next barrier)
+__device__ __forceinline__ bool wide_stop(const ChainArgs &a, int32_t *stop_word, int tid) {
+    if (!a.stop_flag) return false;
+    if (tid == 0) *stop_word = stop_requested(a) ? 1 : 0;
+    __syncthreads();
+    return *stop_word != 0;
+}
+
 template <int M, int QPL>
 __global__ __launch_bounds__(WIDE_MAX_WAVES * 64) void chain_wide_kernel(const ChainArgs a, const double *q3inv_glb) {
     extern __shared__ double lds[];
@@ -58,185 +75,32 @@ __global__ __launch_bounds__(WIDE_MAX_WAVES * 64) void chain_wide_kernel(const C
 #pragma unroll
     for (int j = 0; j < QPL; ++j) { lw[j] = a.w[q0 + lane + WAVE * j]; lwI[j] = a.wI[q0 + lane + WAVE * j]; }
 
-    double *rset = a.rset + (size_t)rep * N * P;
-    double *cache = a.cache + (size_t)rep * a.cache_rows * qpad + q0 + lane;     // this lane's column of the rows
-    DrawSource src{a.replay ? a.replay + (size_t)rep * a.replay_len : nullptr, a.replay_len, a.seed,
-                   (uint32_t)(a.rep_offset + rep)};
-    int overflow = 0, par = 0;
-    uint64_t draw_pos = 0;
-    const uint64_t t_start = wall_clock64();
-
-    double ft[QPL];
-    FitResult cur{1.0, 0.0, 0.0};
-    int64_t num_iter = 0, num_moves = 0, total_steps = 0;
-    int attempts = 0, converged = 0, stopped = 0;
-
-    for (int attempt = 0; attempt <= a.max_retries; ++attempt) {
-        ++attempts;
-        // ------------------------------------------------------------ initial parameter set (scatteringmodel.py:117-127)
-#pragma unroll
-        for (int j = 0; j < QPL; ++j) ft[j] = 0.;
-        for (int n0 = 0; n0 < N; n0 += WAVE) {
-            const int n = n0 + lane;
-            double row[MCSAS_MAX_ACTIVE] = {0., 0., 0., 0.};
-            if (n < N) {
-#pragma unroll
-                for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)
-                    if (p < P) {
-                        if (a.start_from_min) row[p] = a.start_value[p];         // mcsas.py:310-315
-                        else {
-                            double u = src.at(draw_pos + (uint64_t)p * N + n, overflow);   // parameter-major
-                            row[p] = gen_transform(a.gen_kind[p], u) * (a.gen_hi[p] - a.gen_lo[p]) + a.gen_lo[p];
-                        }
-                        if (wave == 0) rset[(size_t)n * P + p] = row[p];
-                    }
-            } else {
-#pragma unroll
-                for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p) row[p] = a.gen_lo[p] > 0. ? a.gen_lo[p] : 1e-9;
-            }
-            Contrib<M> mine;                                       // (every wave prepares all 64: the same numbers)
-            mine.prepare(a.model, row);
-            const int cnt = min(WAVE, N - n0);
-            for (int i = 0; i < cnt; ++i) {                        // rows accumulated in contribution order (scatteringmodel.py:90-101)
-                const Contrib<M> c = mine.bcast(__builtin_amdgcn_readfirstlane(i));
-                double it[QPL];
-                RowEval<M, QPL>::run(c, qt, lane, it);
-#pragma unroll
-                for (int j = 0; j < QPL; ++j) {
-                    ft[j] += it[j];
-                    cache[(size_t)(n0 + i) * qpad + WAVE * j] = it[j];
-                }
-            }
-        }
-        if (!a.start_from_min) draw_pos += (uint64_t)N * P;
-
-        // ------------------------------------------------------------ initial fit (mcsas.py:327-343)
-        {
-            double s1 = 0., s2 = 0., s3 = 0.;
-#pragma unroll
-            for (int j = 0; j < QPL; ++j) {
-                double wt = lw[j] * ft[j];
-                s1 += wt; s2 = fma(wt, ft[j], s2); s3 = fma(lwI[j], ft[j], s3);
-            }
-            wide_sum3(s1, s2, s3, part, par, wave, lane, NW);
-            cur = solve_fit(a, s1, s2, s3);
-        }
-        num_iter = 0; num_moves = 0;
-        int ri = 0;
-        // division-free comparison as in chain_wave.h: chi²_t < chi²  <=>  num² > (S - X) den
-        const double nqd = (double)a.nq, invSw = 1.0 / a.Sw, SIoSw = a.SI / a.Sw, Scen = a.SII - a.SI * a.SI / a.Sw;
-        double X = cur.chi2 * nqd;
-
-        // ------------------------------------------------------------ MC loop (mcsas.py:354-404)
-        bool running = (N > 1);
-        while (running) {
-            if (!(cur.chi2 > a.conv_crit) || !(num_iter < a.max_iter)) break;
-            // McSAS.stop: one thread looks, everybody acts on what it saw (a wave of its own could see the word change
-            // between two waves' reads and leave the others at the next barrier)
-            if (a.stop_flag) {
-                if (tid == 0) *stop_word = stop_requested(a) ? 1 : 0;
-                __syncthreads();
-                if (*stop_word) { stopped = 1; break; }
-            }
-            // proposals for the next 64 steps, one per lane (mcsas.py:358), the same in every wave
-            double prow[MCSAS_MAX_ACTIVE] = {0., 0., 0., 0.};
-            int povf = 0;
-#pragma unroll
-            for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)
-                if (p < P) {
-                    double u = 0.5;
-                    if (num_iter + lane < a.max_iter)
-                        u = src.at(draw_pos + (uint64_t)(num_iter + lane) * P + p, povf);
-                    prow[p] = gen_transform(a.gen_kind[p], u) * (a.gen_hi[p] - a.gen_lo[p]) + a.gen_lo[p];
-                }
-            Contrib<M> prop;
-            prop.prepare(a.model, prow);
-
-            for (int k = 0; k < WAVE; ++k) {
-                if (!(cur.chi2 > a.conv_crit) || !(num_iter < a.max_iter)) { running = false; break; }
-                const int kk = __builtin_amdgcn_readfirstlane(k);
-                const Contrib<M> cnew = prop.bcast(kk);
-                if (__builtin_amdgcn_readlane(povf, kk)) overflow = 1;
-                double inew[QPL], test[QPL];
-                const double *orow = cache + (size_t)ri * qpad;
-#pragma unroll
-                for (int j = 0; j < QPL; ++j) test[j] = orow[WAVE * j];
-                RowEval<M, QPL>::run(cnew, qt, lane, inew);
-                double s1 = 0., s2 = 0., s3 = 0.;
-#pragma unroll
-                for (int j = 0; j < QPL; ++j) {
-                    test[j] = ft[j] + (inew[j] - test[j]);        // ft + d, d = new - old: as in every execution mode (chain_wave.h)
-                    double wt = lw[j] * test[j];
-                    s1 += wt; s2 = fma(wt, test[j], s2); s3 = fma(lwI[j], test[j], s3);
-                }
-                wide_sum3(s1, s2, s3, part, par, wave, lane, NW);
-                double S = a.SII, num = s3, den = s2;
-                if (a.find_bg) {
-                    const double numc = fma(-SIoSw, s1, s3), denc = fma(-(s1 * invSw), s1, s2);
-                    const bool neg_b = a.pos_bg && (fma(a.SI, denc, -(numc * s1)) < 0.);
-                    if (!neg_b) { S = Scen; num = numc; den = denc; }
-                }
-                if (num * num > (S - X) * den) {                                   // mcsas.py:379-390
-                    X = S - num * num / den;
-                    cur.chi2 = X / nqd;
-#pragma unroll
-                    for (int j = 0; j < QPL; ++j) {
-                        ft[j] = test[j];
-                        cache[(size_t)ri * qpad + WAVE * j] = inew[j];
-                    }
-#pragma unroll
-                    for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)
-                        if (p < P) {
-                            double val = readlane_f64(prow[p], kk);
-                            if (tid == 0) rset[(size_t)ri * P + p] = val;
-                        }
-                    ++num_moves;
-                }
-                ri = (ri + 1 == N) ? 0 : ri + 1;                                   // mcsas.py:403-404
-                ++num_iter;
-            }
-        }
-        draw_pos += (uint64_t)num_iter * P;
-        total_steps += num_iter;
-
-        // ------------------------------------------------------------ final fit on ft (mcsas.py:424-426)
-        {
-            double s1 = 0., s2 = 0., s3 = 0.;
-#pragma unroll
-            for (int j = 0; j < QPL; ++j) {
-                double wt = lw[j] * ft[j];
-                s1 += wt; s2 = fma(wt, ft[j], s2); s3 = fma(lwI[j], ft[j], s3);
-            }
-            wide_sum3(s1, s2, s3, part, par, wave, lane, NW);
-            cur = solve_fit(a, s1, s2, s3);
-            // reported chi-squared: direct residual sum, like chiSqr (backgroundscalingfit.py:72-77)
-            double rs = 0., z1 = 0., z2 = 0.;
-#pragma unroll
-            for (int j = 0; j < QPL; ++j) {
-                double r = a.I[q0 + lane + WAVE * j] - (ft[j] * cur.A + cur.b);
-                rs += lw[j] * r * r;
-            }
-            wide_sum3(rs, z1, z2, part, par, wave, lane, NW);
-            cur.chi2 = rs / (double)a.nq;
-        }
-        converged = !(cur.chi2 > a.conv_crit);
-        if (converged || stopped) break;
-    }
-
-    // ---------------------------------------------------------------- outputs (mcsas.py:428-439)
-#pragma unroll
-    for (int j = 0; j < QPL; ++j)
-        a.fit[(size_t)rep * qpad + q0 + lane + WAVE * j] = ft[j] * cur.A + cur.b;
-    overflow = __any(overflow);
-    if (tid == 0) {
-        ChainOut o;
-        o.chisq = cur.chi2; o.scaling = cur.A; o.background = cur.b;
-        o.seconds = (double)(wall_clock64() - t_start) * 1e-8;
-        o.num_iter = num_iter; o.num_moves = num_moves; o.draws = (int64_t)draw_pos;
-        o.total_steps = total_steps;
-        o.attempts = attempts; o.converged = converged; o.stream_overflow = overflow; o.stopped = stopped;
-        a.out[rep] = o;
-    }
+    // the chain itself is chain_wave.h's (chain_body.inc), with a wave's slice of the q-points: the slice's column folded into the
+    // cache pointer, w and wI from the registers above, sums over the workgroup, the row cache always on and no given start
+    constexpr bool CACHE = true, GIVEN = false;
+#define CHAIN_STATE int par = 0;
+#define CHAIN_CACHE_PTR(p) (p + q0 + lane)
+#define CHAIN_ROW(r) (size_t)(r) * qpad
+#define CHAIN_Q(j) q0 + lane + WAVE * j
+#define CHAIN_W(j) lw[j]
+#define CHAIN_WI(j) lwI[j]
+#define CHAIN_SUM3(x, y, z) wide_sum3(x, y, z, part, par, wave, lane, NW)
+#define CHAIN_SUM1(x) wide_sum1(x, part, par, wave, lane, NW)
+#define CHAIN_FIRST (wave == 0)
+#define CHAIN_LEADER (tid == 0)
+#define CHAIN_STOP wide_stop(a, stop_word, tid)
+#include "chain_body.inc"
+#undef CHAIN_STATE
+#undef CHAIN_CACHE_PTR
+#undef CHAIN_ROW
+#undef CHAIN_Q
+#undef CHAIN_W
+#undef CHAIN_WI
+#undef CHAIN_SUM3
+#undef CHAIN_SUM1
+#undef CHAIN_FIRST
+#undef CHAIN_LEADER
+#undef CHAIN_STOP
 }
 
 }  // namespace mcsas

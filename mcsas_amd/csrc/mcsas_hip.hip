@@ -819,7 +819,7 @@ static const char *exec_mode_name(int mode) {
 
 // The set every later launch of the plan starts its repetitions from (include/mcsas_hip.h), kept on the device in the layout of rset;
 // a launch copies it into its slot's rset on the launch stream and runs the start twin of the wave kernel, whose first attempt reads
-// it where the others generate one (chain_wave_body.inc: GIVEN).
+// it where the others generate one (chain_body.inc: GIVEN).
 extern "C" int mcsas_hip_plan_set_start(mcsas_plan *pl, const double *start, int32_t rep_stride, int32_t rep_first) {
     if (!pl) return fail(MCSAS_EINVAL, "set_start: null plan");
     if (!start) { pl->has_start = false; return MCSAS_OK; }

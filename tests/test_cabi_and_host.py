@@ -267,6 +267,56 @@ def test_embedded_headers_include_only_embedded_headers():
             assert os.path.basename(inc) in embed, "%s includes %s, which is not embedded" % (name, inc)
 
 
+def test_chain_body_hooks_are_defined_and_undefined_around_every_inclusion(tmp_path):
+    """chain_body.inc is one chain's text for the wave and the q-split kernels; what differs between them reaches it as CHAIN_*
+    macros.  Text: in every file that includes it, exactly the hooks the body names are defined at the #include, and none of them
+    is still defined at any other #include or at the end of the file.  Compiler (syntax only, no GPU, no hiprtc): the four chain
+    headers in the order of the plug-in compiler's translation unit (host_plugin.hip), the one unit in which both families meet
+    and a leaked hook is a redefinition (a warning to the compiler: an error here)."""
+    import shutil
+    csrc = os.path.join(ROOT, "mcsas_amd", "csrc")
+    code = lambda text: re.sub(r"//[^\n]*", "", text)
+    hooks = set(re.findall(r"\bCHAIN_[A-Z0-9_]+\b", code(open(os.path.join(csrc, "chain_body.inc")).read())))
+    assert len(hooks) >= 5, hooks
+    includers = []
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".h", ".inc", ".hip")):
+            continue
+        defined, inclusions = set(), 0
+        for line in code(open(os.path.join(csrc, name)).read()).split("\n"):
+            m = re.match(r"\s*#\s*(define|undef|include)\s+[\"<]?([\w./]+)", line)
+            if not m:
+                continue
+            what, arg = m.groups()
+            if what == "define" and arg.startswith("CHAIN_"):
+                assert arg not in defined, "%s defines %s twice" % (name, arg)
+                defined.add(arg)
+            elif what == "undef":
+                defined.discard(arg)
+            elif what == "include" and arg == "chain_body.inc":
+                assert defined == hooks, "%s: missing %s, unknown %s" % (name, sorted(hooks - defined), sorted(defined - hooks))
+                inclusions += 1
+            elif what == "include":
+                assert not defined, "%s: %s still defined at #include %s" % (name, sorted(defined), arg)
+        assert not defined, "%s leaves %s defined" % (name, sorted(defined))
+        if inclusions:
+            includers.append(name)
+    assert includers == ["chain_wave_kernel.inc", "chain_wide.h"], includers
+
+    order = re.search(r'#include \\"plugin_model.h\\"\\n((?:#include \\"chain_\w+\.h\\"\\n)+)',
+                      open(os.path.join(csrc, "host_plugin.hip")).read()).group(1)
+    order = re.findall(r"chain_\w+\.h", order)
+    assert order == ["chain_wave.h", "chain_wg.h", "chain_wide.h", "chain_pipe.h"], order
+    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc: the include order of the plug-in unit is compiled on the GPU by hiprtc only")
+    unit = tmp_path / "plugin_order.hip"
+    unit.write_text("#include <hip/hip_runtime.h>\n" + "".join('#include "%s"\n' % h for h in order))
+    r = subprocess.run([hipcc, "-fsyntax-only", "--offload-arch=gfx950", "-std=c++17", "-Werror=macro-redefined", "-I", csrc, "-I", os.path.join(ROOT, "include"),
+                        str(unit)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+
+
 def test_committed_counter_profiles_describe_the_committed_kernels():
     """bench.py quotes per-step counters (instructions, memory-side bytes) from the newest profiles/rNN_*.json; tools/pmc_summary.py
     stores a hash of the kernel sources they were taken on, and the bench line reports whether it matches the tree.  Committed state:
