@@ -275,16 +275,19 @@ int mcsas_hip_analyse_batch(const mcsas_problem *problems, int32_t n, mcsas_resu
  *   num_moves = draws = 0, attempts = 1, converged = 1, contribs bit-equal to start.
  * mcsas_hip_plan_set_start: the plan keeps a (transposed) device copy taken at the call; the caller's array may be freed.  Every
  *   later launch of any slot, mcsas_hip_plan_launch_batch included, copies that block into the slot's parameter sets on the launch
- *   stream ahead of the kernel and runs the start form of the wavefront kernel.  start == NULL clears it.  A batch groups plans by
+ *   stream ahead of the kernel and runs the start form of the plan's kernel.  start == NULL clears it.  A batch groups plans by
  *   (model, q slots per lane, row cache, start or not): plans with and without a start may share one batch.
- *   mcsas_hip_plan_reseed and the replay stream are independent of the start.  Only a plan that resolved to MCSAS_EXEC_WAVE takes
- *   a start; any other: MCSAS_EINVAL naming the mode (the plan stays usable).
+ *   mcsas_hip_plan_reseed and the replay stream are independent of the start.  A plan that resolved to MCSAS_EXEC_WAVE takes a
+ *   start, and so does one that resolved to the q-split workgroup kernel (MCSAS_EXEC_WORKGROUP with more than 1024 q-points; not
+ *   in a batch, which takes WAVE plans only); any other: MCSAS_EINVAL naming the mode (the plan stays usable).
  * mcsas_hip_analyse_from: mcsas_hip_analyse from `start` ([n_contrib][n_active][n_reps]).  MCSAS_EXEC_AUTO means WAVE, as in
- *   mcsas_hip_analyse_batch; WORKGROUP, PIPELINE and nq > 4096 are refused before a device is touched, and so are a NULL start and
- *   a non-finite value.  n_active == 0 is answered as mcsas_hip_analyse answers it (start is not read).  n_devices > 1 shards as
+ *   mcsas_hip_analyse_batch, whatever nq is: with AUTO or WAVE nq > 4096 is refused.  MCSAS_EXEC_WORKGROUP takes a start for
+ *   1025...16384 q-points (the q-split kernel, the only one beyond 4096) and is refused up to 1024 (the workgroup-window kernel);
+ *   PIPELINE is refused.  Every refusal comes before a device is touched, and so do those of a NULL start and a non-finite
+ *   value.  n_active == 0 is answered as mcsas_hip_analyse answers it (start is not read).  n_devices > 1 shards as
  *   mcsas_hip_analyse does, each block reading its own columns of the one array.
- * Out of scope: mcsas_hip_analyse_host_rows (models that exist only as host code), and the workgroup, q-split and pipeline
- *   kernels: a start needs exec_mode = MCSAS_EXEC_WAVE. */
+ * Out of scope: mcsas_hip_analyse_host_rows (models that exist only as host code), the workgroup-window kernel (MCSAS_EXEC_WORKGROUP
+ *   up to 1024 q-points) and the pipeline. */
 int mcsas_hip_plan_set_start(mcsas_plan *plan, const double *start, int32_t rep_stride, int32_t rep_first);
 int mcsas_hip_analyse_from(const mcsas_problem *problem, const double *start, mcsas_result *result);
 

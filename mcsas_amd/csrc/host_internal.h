@@ -81,9 +81,10 @@ struct SmearDev {
 };
 
 // ------------------------------------------------------------------------------ run-time model plug-ins (host_plugin.hip)
-// the chain kernel families; every built-in model has its instances in kern_<family>.hip (the two start families, the wave and
-// wave-batch kernels whose first attempt takes a given set, share kern_wave_start.hip), a plug-in compiles its own on first use
-enum KernelFamily { KF_WAVE, KF_WAVE_BATCH, KF_WG, KF_WIDE, KF_PIPE_TICK, KF_WAVE_START, KF_WAVE_BATCH_START, KF_COUNT };
+// the chain kernel families; every built-in model has its instances in kern_<family>.hip (the two wave start families, the wave and
+// wave-batch kernels whose first attempt takes a given set, share kern_wave_start.hip; the q-split one is kern_wide_start.hip), a
+// plug-in compiles its own on first use
+enum KernelFamily { KF_WAVE, KF_WAVE_BATCH, KF_WG, KF_WIDE, KF_PIPE_TICK, KF_WAVE_START, KF_WAVE_BATCH_START, KF_WIDE_START, KF_COUNT };
 enum PluginSmallKernel { PLUGIN_MODEL_ROWS, PLUGIN_OBSERVABILITY, PLUGIN_HIST_ROWS };
 
 inline bool is_plugin_model(int model_id) { return model_id >= MCSAS_MODEL_PLUGIN0 && model_id < MCSAS_MODEL_PLUGIN0 + MCSAS_MAX_PLUGINS; }

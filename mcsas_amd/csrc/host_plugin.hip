@@ -151,7 +151,8 @@ int plugin_chain_function(int model_id, KernelFamily family, int qpl, bool flag,
     static const struct { const char *kernel, *key; bool flagged; } FAMILY[KF_COUNT] = {
         {"chain_wave_kernel", "wave", true}, {"chain_wave_batch_kernel", "wave batch", true}, {"chain_wg_kernel", "wg", false},
         {"chain_wide_kernel", "wide", false}, {"pipe_tick_kernel", "pipe", true},
-        {"chain_wave_start_kernel", "wave start", true}, {"chain_wave_batch_start_kernel", "wave batch start", true}};
+        {"chain_wave_start_kernel", "wave start", true}, {"chain_wave_batch_start_kernel", "wave batch start", true},
+        {"chain_wide_start_kernel", "wide start", false}};
     char e[128], k[32];
     if (FAMILY[family].flagged) {
         snprintf(e, sizeof e, "mcsas::%s<MCSAS_MODEL_PLUGIN, %d, %s>", FAMILY[family].kernel, qpl, flag ? "true" : "false");

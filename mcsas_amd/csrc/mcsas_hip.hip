@@ -333,7 +333,7 @@ static int plan_activate_slot(mcsas_plan *pl, int k) {
 // ------------------------------------------------------------------------------ the chain kernels
 // kernel lookups, one translation unit per model and family (kern_*.hip)
 #define DECL_K(m) void *mcsas_wave_kernel_m##m(int, bool); void *mcsas_wave_batch_kernel_m##m(int, bool); void *mcsas_wg_kernel_m##m(int); void *mcsas_wide_kernel_m##m(int); void *mcsas_pipe_tick_kernel_m##m(int, bool); \
-                  void *mcsas_wave_start_kernel_m##m(int, bool); void *mcsas_wave_batch_start_kernel_m##m(int, bool);
+                  void *mcsas_wave_start_kernel_m##m(int, bool); void *mcsas_wave_batch_start_kernel_m##m(int, bool); void *mcsas_wide_start_kernel_m##m(int);
 MCSAS_FOR_MODELS(DECL_K)
 #undef DECL_K
 void *mcsas_pipe_reset_kernel();
@@ -345,7 +345,8 @@ static void *builtin_kernel(KernelFamily family, int model, int qpl, bool flag) 
     case m:                                                                                                                         \
         return family == KF_WAVE ? mcsas_wave_kernel_m##m(qpl, flag) : family == KF_WAVE_BATCH ? mcsas_wave_batch_kernel_m##m(qpl, flag) \
              : family == KF_WAVE_START ? mcsas_wave_start_kernel_m##m(qpl, flag) : family == KF_WAVE_BATCH_START ? mcsas_wave_batch_start_kernel_m##m(qpl, flag) \
-             : family == KF_WG ? mcsas_wg_kernel_m##m(qpl) : family == KF_WIDE ? mcsas_wide_kernel_m##m(qpl) : mcsas_pipe_tick_kernel_m##m(qpl, flag);
+             : family == KF_WG ? mcsas_wg_kernel_m##m(qpl) : family == KF_WIDE ? mcsas_wide_kernel_m##m(qpl)                              \
+             : family == KF_WIDE_START ? mcsas_wide_start_kernel_m##m(qpl) : mcsas_pipe_tick_kernel_m##m(qpl, flag);
         MCSAS_FOR_MODELS(CASE_K)
 #undef CASE_K
         default: return nullptr;
@@ -362,7 +363,8 @@ struct KernelRef {
     const void *id() const { return plugin ? (const void *)plugin : entry; }
 };
 // the family of the plan's own launches (mcsas_hip_plan_launch_batch asks for KF_WAVE_BATCH instead); launch_family: the one a
-// launch takes now, i.e. the start twin of the wave families while the plan holds a start (mcsas_hip_plan_set_start)
+// launch takes now, i.e. the start twin of the wave and q-split families while the plan holds a start (mcsas_hip_plan_set_start
+// gives one to no other plan)
 static KernelFamily plan_family(const mcsas_plan *pl) {
     if (pl->mode == MCSAS_EXEC_WAVE) return KF_WAVE;
     if (pl->mode == MCSAS_EXEC_PIPELINE) return KF_PIPE_TICK;
@@ -370,17 +372,20 @@ static KernelFamily plan_family(const mcsas_plan *pl) {
 }
 static KernelFamily launch_family(const mcsas_plan *pl, bool batch) {
     if (batch) return pl->has_start ? KF_WAVE_BATCH_START : KF_WAVE_BATCH;
-    return pl->has_start ? KF_WAVE_START : plan_family(pl);
+    if (!pl->has_start) return plan_family(pl);
+    return pl->wide ? KF_WIDE_START : KF_WAVE_START;
 }
 static int resolve_kernel(const mcsas_plan *pl, KernelFamily family, KernelRef *k) {
     static const char *const missing[KF_COUNT] = {"no kernel for model %d qpl %d", "launch_batch: no batch kernel for model %d qpl %d", "no kernel for model %d qpl %d",
                                                   "no q-split kernel for model %d qpl %d", "no pipeline kernel for model %d qpl %d",
-                                                  "no start kernel for model %d qpl %d", "launch_batch: no batch start kernel for model %d qpl %d"};
+                                                  "no start kernel for model %d qpl %d", "launch_batch: no batch start kernel for model %d qpl %d",
+                                                  "no q-split start kernel for model %d qpl %d"};
     const int model = pl->prob.model_id;
     const bool flag = family == KF_PIPE_TICK ? pl->pipe.g.rowq != 0 : pl->use_cache != 0;
     *k = KernelRef{};
-    k->block = family == KF_PIPE_TICK ? PIPE_BLOCK : (family == KF_WG || family == KF_WIDE ? WAVE * pl->waves : WAVE);
-    k->arg2 = family == KF_WG ? KernelRef::ARG2_WG : (family == KF_WIDE ? KernelRef::ARG2_Q3INV : KernelRef::ARG2_NONE);
+    const bool q_split = family == KF_WIDE || family == KF_WIDE_START;
+    k->block = family == KF_PIPE_TICK ? PIPE_BLOCK : (family == KF_WG || q_split ? WAVE * pl->waves : WAVE);
+    k->arg2 = family == KF_WG ? KernelRef::ARG2_WG : (q_split ? KernelRef::ARG2_Q3INV : KernelRef::ARG2_NONE);
     if (is_plugin_model(model)) {
         if (pl->plugin_fn && family == plan_family(pl)) { k->plugin = pl->plugin_fn; return MCSAS_OK; }      // (looked up when the plan was made)
         return plugin_chain_function(model, family, pl->qpl, flag, &k->plugin);                             // (compiled on first use of this q count)
@@ -818,13 +823,15 @@ static const char *exec_mode_name(int mode) {
 }
 
 // The set every later launch of the plan starts its repetitions from (include/mcsas_hip.h), kept on the device in the layout of rset;
-// a launch copies it into its slot's rset on the launch stream and runs the start twin of the wave kernel, whose first attempt reads
-// it where the others generate one (chain_body.inc: GIVEN).
+// a launch copies it into its slot's rset on the launch stream and runs the start twin of the plan's kernel, whose first attempt reads
+// it where the others generate one (chain_body.inc: GIVEN).  The wavefront-per-chain and the q-split kernels have such a twin; the
+// workgroup-window kernel (up to 1024 q-points) and the pipeline have none, and their plans refuse.
 extern "C" int mcsas_hip_plan_set_start(mcsas_plan *pl, const double *start, int32_t rep_stride, int32_t rep_first) {
     if (!pl) return fail(MCSAS_EINVAL, "set_start: null plan");
     if (!start) { pl->has_start = false; return MCSAS_OK; }
-    if (pl->mode != MCSAS_EXEC_WAVE || pl->wide)
-        return fail(MCSAS_EINVAL, "set_start: the plan runs in exec_mode %d (%s); a start needs exec_mode = MCSAS_EXEC_WAVE (%d)", pl->mode, exec_mode_name(pl->mode), MCSAS_EXEC_WAVE);
+    if (pl->mode != MCSAS_EXEC_WAVE && !pl->wide)
+        return fail(MCSAS_EINVAL, "set_start: the plan runs in exec_mode %d (%s) with %d q-points; a start needs exec_mode = MCSAS_EXEC_WAVE (%d), or MCSAS_EXEC_WORKGROUP (%d) with more than %d q-points",
+                    pl->mode, exec_mode_name(pl->mode), pl->prob.nq, MCSAS_EXEC_WAVE, MCSAS_EXEC_WORKGROUP, 16 * WAVE);
     const size_t R = pl->prob.n_reps, N = pl->prob.n_contrib, P = pl->prob.n_active;
     if (rep_first < 0 || (int64_t)rep_first + (int64_t)R > (int64_t)rep_stride)
         return fail(MCSAS_EINVAL, "set_start: repetitions %d..%lld of a start with %d columns", rep_first, (long long)rep_first + (long long)R - 1, rep_stride);
@@ -1317,22 +1324,27 @@ extern "C" int mcsas_hip_analyse(const mcsas_problem *p, mcsas_result *res) {
     return analyse_one(p, res);
 }
 
-// McSAS.analyse with the first attempt of every repetition started from a given set (include/mcsas_hip.h): the wavefront mode only,
-// and every refusal before a device is touched.
+// McSAS.analyse with the first attempt of every repetition started from a given set (include/mcsas_hip.h): one wavefront per chain,
+// or, where MCSAS_EXEC_WORKGROUP is asked for more than 1024 q-points, the q-split kernel; every refusal before a device is touched.
 extern "C" int mcsas_hip_analyse_from(const mcsas_problem *p, const double *start, mcsas_result *res) {
     if (!p || !res) return fail(MCSAS_EINVAL, "analyse_from: null argument");
     if (p->struct_size != sizeof(mcsas_problem))
         return fail(MCSAS_EINVAL, "analyse_from: mcsas_problem size %u, library expects %zu (ABI mismatch)", p->struct_size, sizeof(mcsas_problem));
     if (p->n_active == 0) return mcsas_hip_analyse(p, res);                     // nothing to start: one contribution at fixed values
     if (!start) return fail(MCSAS_EINVAL, "analyse_from: start is NULL (mcsas_hip_analyse runs without one)");
-    if (p->exec_mode != MCSAS_EXEC_AUTO && p->exec_mode != MCSAS_EXEC_WAVE)
-        return fail(MCSAS_EINVAL, "analyse_from: exec_mode %d (%s) asked; a start needs exec_mode = MCSAS_EXEC_WAVE (%d, or 0)", p->exec_mode, exec_mode_name(p->exec_mode), MCSAS_EXEC_WAVE);
-    if (p->nq > 64 * WAVE) return fail(MCSAS_EINVAL, "analyse_from: nq %d > %d: one wavefront per chain does not take it, and a start needs exec_mode = MCSAS_EXEC_WAVE", p->nq, 64 * WAVE);
+    const bool q_split = p->exec_mode == MCSAS_EXEC_WORKGROUP && p->nq > 16 * WAVE;      // (decide_shape: the q-split kernel, whatever waves_per_chain says)
+    if (p->exec_mode != MCSAS_EXEC_AUTO && p->exec_mode != MCSAS_EXEC_WAVE && !q_split)
+        return fail(MCSAS_EINVAL, "analyse_from: exec_mode %d (%s) asked with %d q-points; a start needs exec_mode = MCSAS_EXEC_WAVE (%d, or 0), or MCSAS_EXEC_WORKGROUP (%d) with more than %d q-points",
+                    p->exec_mode, exec_mode_name(p->exec_mode), p->nq, MCSAS_EXEC_WAVE, MCSAS_EXEC_WORKGROUP, 16 * WAVE);
+    if (p->nq > WIDE_MAX_WAVES * WAVE * 32) return fail(MCSAS_EINVAL, "analyse_from: nq %d > %d is not supported", p->nq, WIDE_MAX_WAVES * WAVE * 32);
+    if (!q_split && p->nq > 64 * WAVE)
+        return fail(MCSAS_EINVAL, "analyse_from: nq %d > %d: one wavefront per chain does not take it, and with exec_mode %d a start runs one wavefront per chain; "
+                    "MCSAS_EXEC_WORKGROUP (%d) takes a start for %d...%d q-points", p->nq, 64 * WAVE, p->exec_mode, MCSAS_EXEC_WORKGROUP, 16 * WAVE + 1, WIDE_MAX_WAVES * WAVE * 32);
     if (p->n_active < 0 || p->n_active > MCSAS_MAX_ACTIVE) return fail(MCSAS_EINVAL, "n_active %d out of range", p->n_active);
     if (p->n_contrib < 1 || p->n_reps < 1) return fail(MCSAS_EINVAL, "n_contrib and n_reps must be >= 1");
     if (int rc = check_start_finite("analyse_from", start, (size_t)p->n_contrib, (size_t)p->n_active, (size_t)p->n_reps, 0, (size_t)p->n_reps)) return rc;
     mcsas_problem q = *p;
-    q.exec_mode = MCSAS_EXEC_WAVE;
+    q.exec_mode = q_split ? MCSAS_EXEC_WORKGROUP : MCSAS_EXEC_WAVE;
     if (q.n_devices > 1) return analyse_sharded(&q, res, start);
     return analyse_one(&q, res, start, q.n_reps, 0);
 }

@@ -205,7 +205,8 @@ def _start_columns(a, st: Settings, rep_first, who="analyse"):
 def analyse(model: ModelSetup, q, intensity, sigma, st: Settings, replay=None, stop=None, smear=None, start=None) -> ChainResults:
     """All repetitions of McSAS.analyse (mcsas.py:214-262) in one kernel launch.  `start`: [n_contrib][n_active][n_reps] (a
     ChainResults.contribs; further repetitions are ignored), the set the first attempt of every repetition starts from instead of
-    a random one (mcsas_hip_analyse_from, include/mcsas_hip.h) — one wavefront per chain; exec_mode 2 or 3 is refused."""
+    a random one (mcsas_hip_analyse_from, include/mcsas_hip.h) — one wavefront per chain, or with exec_mode 2 and more than
+    WG_MAX_Q q-points the q-split workgroup kernel (the only one beyond WAVE_MAX_Q); exec_mode 2 below that and 3 are refused."""
     if start is not None and model.n_active > 0:
         a = _check_start(start, model, st)
         _start_columns(a, st, 0)
@@ -286,10 +287,13 @@ def analyse_many(problems, streams=2):
             while len(pending) >= cap:
                 j, pl = pending.pop(0)
                 out[j] = pl.fetch(); pl.close()
-            if pr.get("start") is not None:                  # (a start runs one wavefront per chain: analyse)
-                if st.exec_mode not in (EXEC_AUTO, EXEC_WAVE):
-                    raise ValueError("analyse_many: problem %d asks for exec_mode %d with a start (0 or 1)" % (i, st.exec_mode))
-                st = replace(st, exec_mode=EXEC_WAVE)
+            if pr.get("start") is not None:                  # (a start runs one wavefront per chain or the q-split kernel: analyse)
+                q_split = st.exec_mode == EXEC_WORKGROUP and np.size(pr["q"]) > WG_MAX_Q
+                if st.exec_mode not in (EXEC_AUTO, EXEC_WAVE) and not q_split:
+                    raise ValueError("analyse_many: problem %d asks for exec_mode %d with a start and %d q-points (0 or 1, or 2 with more than %d q-points)"
+                                     % (i, st.exec_mode, np.size(pr["q"]), WG_MAX_Q))
+                if not q_split:
+                    st = replace(st, exec_mode=EXEC_WAVE)
             pl = Plan(pr["model"], pr["q"], pr["intensity"], pr["sigma"], st, pr.get("replay"), pr.get("stop"), pr.get("smear"))
             if pr.get("start") is not None:
                 try:
@@ -313,6 +317,7 @@ def analyse_many(problems, streams=2):
 
 
 WAVE_MAX_Q = 4096       # q-points one wavefront per chain takes (include/mcsas_hip.h: MCSAS_EXEC_WAVE)
+WG_MAX_Q = 1024         # ... and the workgroup-window kernel; beyond, MCSAS_EXEC_WORKGROUP is the q-split kernel, which takes a start
 
 
 def analyse_batch(problems):
@@ -419,7 +424,8 @@ class Plan:
     def set_start(self, contribs, rep_first=0):
         """Every later launch of this plan (launch_batch included) starts repetition r from contribs[:, :, rep_first + r]
         ([n_contrib][n_active][R], e.g. a fetched ChainResults.contribs) instead of a random set, for its first attempt
-        (mcsas_hip_plan_set_start).  The plan keeps a copy.  None clears it.  Plans in the wavefront mode only."""
+        (mcsas_hip_plan_set_start).  The plan keeps a copy.  None clears it.  Plans in the wavefront mode, and workgroup plans of more
+        than WG_MAX_Q q-points (the q-split kernel); the others refuse."""
         if contribs is None:
             check(self.lib.mcsas_hip_plan_set_start(self.h, None, 0, 0), self.lib)
             return

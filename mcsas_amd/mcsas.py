@@ -82,9 +82,23 @@ class McSAS(object):
     def stop(self, flag):
         self._stop.value = 1 if flag else 0
 
-    def _check_start_mode(self, start):
-        if start is not None and self.execMode not in (engine.EXEC_AUTO, engine.EXEC_WAVE):
-            raise ValueError("McSAS: a start runs one wavefront per chain; execMode %d was asked (0 or 1)" % self.execMode)
+    def _check_start_mode(self, start, data=None):
+        """The execution mode a started analysis of `data` (default: the current data) asks for, or None without a start: one wavefront per chain up
+        to engine.WAVE_MAX_Q points; the q-split workgroup kernel where execMode asks for it with more than engine.WG_MAX_Q points,
+        and beyond WAVE_MAX_Q also where execMode leaves the choice open (no other kernel takes such data).  ValueError otherwise."""
+        if start is None:
+            return None
+        data = self.data if data is None else data
+        nq = 0 if data is None else int(np.size(data.q))
+        if self.execMode == engine.EXEC_WORKGROUP and nq > engine.WG_MAX_Q:
+            return engine.EXEC_WORKGROUP
+        if self.execMode not in (engine.EXEC_AUTO, engine.EXEC_WAVE):
+            raise ValueError("McSAS: a start runs one wavefront per chain, or a workgroup per chain with more than %d points; "
+                             "execMode %d was asked with %d points (0 or 1, or 2 beyond %d points)"
+                             % (engine.WG_MAX_Q, self.execMode, nq, engine.WG_MAX_Q))
+        if self.execMode == engine.EXEC_AUTO and nq > engine.WAVE_MAX_Q:
+            return engine.EXEC_WORKGROUP
+        return engine.EXEC_WAVE
 
     def calc(self, **kwargs):                                # mcsas.py:149-179
         """`start=`: an [N][P][R] array of contributions, typically an earlier `algo.result[0]['contribs']`: the first attempt of
@@ -118,8 +132,9 @@ class McSAS(object):
 
     def analyse(self, replay=None, start=None):              # mcsas.py:191-285
         """`start`: [numContribs][active parameters][>= numReps] — mcFit's rset of the first attempt of each repetition, in place of
-        generateParameters(numContribs) (mcsas.py:317); later attempts draw a fresh set as always.  A start forces the wavefront mode
-        for this call (include/mcsas_hip.h: mcsas_hip_analyse_from); an explicit execMode of workgroup or pipeline raises ValueError."""
+        generateParameters(numContribs) (mcsas.py:317); later attempts draw a fresh set as always.  A start runs one wavefront per chain
+        for this call, or the q-split workgroup kernel (_check_start_mode; include/mcsas_hip.h: mcsas_hip_analyse_from); an explicit
+        execMode of pipeline, or of workgroup with up to 1024 points, raises ValueError."""
         if self.result is None:
             self.result = []
         data, model = self.data, self.model
@@ -144,7 +159,7 @@ class McSAS(object):
 
     def _problem(self, numContribs=None, numReps=None, replay=None, start=None):
         """What analyse() hands to the library for the current data / model / settings (engine.analyse_many takes a list of these).
-        With a `start` (see analyse) the problem asks for the wavefront mode and carries the checked array under "start"."""
+        With a `start` (see analyse) the problem asks for the mode of _check_start_mode and carries the checked array under "start"."""
         data, model = self.data, self.model
         if numContribs is None:
             active = any(isActiveFitParam(p) for p in model.params())
@@ -153,10 +168,10 @@ class McSAS(object):
         pr = dict(model=setup_from_model(model, data), q=data.q, intensity=data.f.binnedData, sigma=data.f.binnedDataU,
                   st=self._settings(numContribs, numReps), replay=replay, stop=self._stop, smear=smear)
         if start is not None and pr["model"].n_active > 0:
-            self._check_start_mode(start)
+            mode = self._check_start_mode(start)
             a = engine._check_start(start, pr["model"], pr["st"], "McSAS.analyse")
             engine._start_columns(a, pr["st"], 0, "McSAS.analyse")
-            pr["st"].exec_mode = engine.EXEC_WAVE
+            pr["st"].exec_mode = mode
             pr["start"] = a
         return pr
 

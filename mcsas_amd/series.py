@@ -17,7 +17,7 @@ def run_series(algo, datasets, keys=None, replays=None, overlap=False, batch=Fal
     chains (engine.analyse_batch; results as each data set's analysis in that mode alone), the rest as with `overlap`; a model that
     exists only as host code runs one data set after the other instead.
     `start`: the contributions the first attempt of every repetition starts from (McSAS.analyse: an [N][P][R] array; wavefront
-    mode) — one array for every data set, a list with one entry per data set (None: cold), or "previous": each data set starts from
+    mode, or the q-split workgroup kernel beyond 1024 points: McSAS._check_start_mode) — one array for every data set, a list with one entry per data set (None: cold), or "previous": each data set starts from
     the previous stored result's contributions; the first one, and any after a data set that stored nothing, starts cold.
     "previous" is sequential by nature: with `batch` or `overlap` it raises ValueError."""
     if algo.model is None:
@@ -37,8 +37,8 @@ def run_series(algo, datasets, keys=None, replays=None, overlap=False, batch=Fal
         starts = list(start)
     else:
         starts = [start] * len(datasets)
-    if any(s is not None for s in starts):
-        algo._check_start_mode(True)
+    for data, s in zip(datasets, starts):                    # (what no kernel starts is refused before anything runs)
+        algo._check_start_mode(s, data)
     results, series = [], OrderedDict()
     chains = None
     from . import engine

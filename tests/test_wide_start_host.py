@@ -1,0 +1,137 @@
+"""A start for the q-split workgroup kernel (MCSAS_EXEC_WORKGROUP with more than 1024 q-points): what can be checked without a GPU
+— the refusals and acceptances that are made before a device is touched, in Python and in the library, and the tables a new kernel
+family has to be entered into."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import mcsas_amd
+from mcsas_amd import _lib, engine
+from helpers import make_models
+from test_start_host import MCSAS_EINVAL, _data, _from, _problem
+
+MCSAS_OK, MCSAS_ENODEV = 0, -2
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mcsas_amd", "csrc")
+
+
+class _LibraryReached(Exception):
+    pass
+
+
+def _stub_library(monkeypatch):
+    """_lib.load replaced for the duration: reaching it means every check made in Python has passed."""
+    def load(*a, **k):
+        raise _LibraryReached()
+    monkeypatch.setattr(_lib, "load", load)
+
+
+def _algo(nq, **kw):
+    q, I, sig = _data(nq)
+    algo = mcsas_amd.McSAS.factory()(seed=1, **kw)
+    algo.numContribs.setValue(8); algo.numReps.setValue(3); algo.maxIterations.setValue(10)
+    algo.model, _ = make_models("sphere", [2e-9], [3e-7])
+    algo.data = mcsas_amd.SASData(q, I, sig)
+    return algo
+
+
+def test_front_end_takes_the_workgroup_mode_beyond_1024_points(monkeypatch):
+    _stub_library(monkeypatch)
+    good = np.full((8, 1, 3), 5e-8)
+    with pytest.raises(_LibraryReached):
+        _algo(1500, execMode=engine.EXEC_WORKGROUP).calc(start=good)
+    with pytest.raises(ValueError, match="execMode"):
+        _algo(40, execMode=engine.EXEC_WORKGROUP).calc(start=good)
+    with pytest.raises(ValueError, match="execMode"):
+        _algo(1024, execMode=engine.EXEC_WORKGROUP).calc(start=good)
+    with pytest.raises(ValueError, match="execMode"):
+        _algo(1500, execMode=engine.EXEC_PIPELINE).calc(start=good)
+    # the mode a started problem asks for: one wavefront per chain while it takes the data, the workgroup mode where nothing else does
+    for nq, mode, asked in ((1500, engine.EXEC_AUTO, engine.EXEC_WAVE), (1500, engine.EXEC_WORKGROUP, engine.EXEC_WORKGROUP),
+                            (4096, engine.EXEC_AUTO, engine.EXEC_WAVE), (4097, engine.EXEC_AUTO, engine.EXEC_WORKGROUP),
+                            (4097, engine.EXEC_WAVE, engine.EXEC_WAVE), (40, engine.EXEC_AUTO, engine.EXEC_WAVE)):
+        algo = _algo(nq, execMode=mode)
+        assert algo._problem(start=good)["st"].exec_mode == asked, (nq, mode)
+        assert algo._problem()["st"].exec_mode == mode, (nq, mode)              # (without a start: what was set)
+    # a series checks each data set against its own size
+    algo = _algo(40, execMode=engine.EXEC_WORKGROUP)
+    with pytest.raises(ValueError, match="execMode"):
+        mcsas_amd.run_series(algo, [_algo(1500).data, _algo(40).data], start=good)
+
+
+def test_analyse_many_with_a_start_and_the_workgroup_mode(monkeypatch):
+    m, _ = make_models("sphere", [2e-9], [3e-7])
+    st = engine.Settings(n_contrib=8, n_reps=3, max_iter=10, exec_mode=engine.EXEC_WORKGROUP)
+    q, I, sig = _data(40)
+    monkeypatch.setattr(_lib, "load", lambda *a, **k: None)      # (asked for at the top of the call; the check must need nothing of it)
+    with pytest.raises(ValueError, match="exec_mode 2"):
+        engine.analyse_many([dict(model=m.setup(), q=q, intensity=I, sigma=sig, st=st, start=np.full((8, 1, 3), 5e-8))])
+
+
+def test_analyse_from_takes_the_workgroup_mode_beyond_1024_q():
+    """Past the argument checks means as far as the device: MCSAS_ENODEV where there is none, and with one the ten steps run."""
+    start = np.full((8, 1, 2), 5e-8)
+    for nq in (1500, 5000):
+        prob, res = _problem(nq=nq, exec_mode=engine.EXEC_WORKGROUP)
+        rc, msg = _from(prob, start, res)
+        assert rc in (MCSAS_ENODEV, MCSAS_OK), (rc, msg)
+    prob, res = _problem(nq=20000, exec_mode=engine.EXEC_WORKGROUP)
+    rc, msg = _from(prob, start, res)
+    assert rc == MCSAS_EINVAL and "20000" in msg and "16384" in msg, msg
+    # the message of the wave limit names the way out
+    prob, res = _problem(nq=5000)
+    rc, msg = _from(prob, start, res)
+    assert rc == MCSAS_EINVAL and "MCSAS_EXEC_WORKGROUP" in msg and "1025" in msg and "16384" in msg, msg
+    # refusals that stay: the workgroup-window kernel's q range, a non-finite start in the new path
+    prob, res = _problem(nq=1024, exec_mode=engine.EXEC_WORKGROUP)
+    rc, msg = _from(prob, start, res)
+    assert rc == MCSAS_EINVAL and "MCSAS_EXEC_WORKGROUP" in msg and "1024" in msg, msg
+    bad = start.copy()
+    bad[5, 0, 1] = np.nan
+    prob, res = _problem(nq=1500, exec_mode=engine.EXEC_WORKGROUP)
+    rc, msg = _from(prob, bad, res)
+    assert rc == MCSAS_EINVAL and "not finite" in msg, msg
+
+
+def _code(name):
+    return re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, name)).read())
+
+
+def test_the_new_family_is_entered_in_every_table():
+    families = re.search(r"enum\s+KernelFamily\s*\{([^}]*)\}", _code("host_internal.h")).group(1).replace(" ", "").split(",")
+    assert families[-1] == "KF_COUNT" and "KF_WIDE_START" in families[:-1] and len(set(families)) == len(families)
+    n = len(families) - 1
+    table = re.search(r"FAMILY\[KF_COUNT\]\s*=\s*\{(.*?)\};", _code("host_plugin.hip"), re.S).group(1)
+    rows = re.findall(r'\{\s*"(\w+)"\s*,\s*"([\w ]+)"\s*,\s*(?:true|false)\s*\}', table)
+    assert len(rows) == n and rows[families.index("KF_WIDE_START")][0] == "chain_wide_start_kernel", rows
+    assert len({key for _, key in rows}) == n                                    # (the program keys tell the families apart)
+    missing = re.search(r"missing\[KF_COUNT\]\s*=\s*\{(.*?)\};", _code("mcsas_hip.hip"), re.S).group(1)
+    assert len(re.findall(r'"[^"]*"', missing)) == n, missing
+    # one translation unit per model, and the lookup the host links against
+    assert "chain_wide_start_kernel<MCSAS_M, 8>" in _code("kern_wide_start.hip")
+    make = open(os.path.join(CSRC, "Makefile")).read()
+    assert "kern_wide_start_m$(m).o" in make and re.search(r"kern_wide_start_m%\.o:\s*kern_wide_start\.hip \$\(WIDE_HDRS\)", make)
+
+
+def test_every_included_text_is_embedded_for_the_plugin_compiler():
+    """What a kernel header includes by name must be among the texts the run-time compiler is handed (Makefile: EMBED), and a
+    dependency of the units that compile it."""
+    make = open(os.path.join(CSRC, "Makefile")).read()
+    embed = re.search(r"^EMBED :=(.*?)\n(?!\s)", make, re.S | re.M).group(1)
+    embedded = set(re.findall(r"([\w.]+)=", embed))
+    assert "chain_wide.h" in embedded
+    todo, seen = ["chain_wave.h", "chain_wg.h", "chain_wide.h", "chain_pipe.h", "small_kernels.h", "plugin_model.h"], set()
+    while todo:
+        name = todo.pop()
+        if name in seen:
+            continue
+        seen.add(name)
+        assert name in embedded or name == "mcsas_hip.h", name
+        path = os.path.join(CSRC, name)
+        if os.path.exists(path):
+            todo += [os.path.basename(x) for x in re.findall(r'#\s*include\s+"([\w./]+)"', _code(name))]
+    incs = [x for x in seen if x.endswith(".inc")]
+    assert "chain_wide_prologue.inc" in incs and "chain_body.inc" in incs
+    wide_hdrs = re.search(r"^WIDE_HDRS :=(.*)$", make, re.M).group(1).split()
+    assert set(re.findall(r'#\s*include\s+"([\w.]+\.inc)"', _code("chain_wide.h"))) <= set(wide_hdrs)
