@@ -16,23 +16,13 @@ namespace mcsas {
 // waves per SIMD the chain kernels are built for (the batch kernel below keeps its single twin's)
 #define MCSAS_WAVE_MIN_WAVES(QPL, CACHE) (((QPL) < 8 || ((QPL) == 8 && (CACHE))) ? 2 : 1)
 
-template <int M, int QPL, bool CACHE>
+// GIVEN: the chain is started from a given set (mcsas_hip_plan_set_start): the host has copied the repetition's start into rset
+// ahead of the launch, and the first attempt takes it where the cold kernel generates one (chain_body.inc: GIVEN).
+template <int M, int QPL, bool CACHE, bool GIVEN>
 __global__ __launch_bounds__(64, MCSAS_WAVE_MIN_WAVES(QPL, CACHE)) void chain_wave_kernel(const ChainArgs a) {
     extern __shared__ double lds[];
     const int lane = threadIdx.x;
     const int rep = blockIdx.x;
-    constexpr bool GIVEN = false;
-#include "chain_wave_kernel.inc"
-}
-
-// The same chain started from a given set (mcsas_hip_plan_set_start): the host has copied the repetition's start into rset ahead of
-// the launch, and the first attempt takes it where chain_wave_kernel generates one (chain_body.inc: GIVEN).
-template <int M, int QPL, bool CACHE>
-__global__ __launch_bounds__(64, MCSAS_WAVE_MIN_WAVES(QPL, CACHE)) void chain_wave_start_kernel(const ChainArgs a) {
-    extern __shared__ double lds[];
-    const int lane = threadIdx.x;
-    const int rep = blockIdx.x;
-    constexpr bool GIVEN = true;
 #include "chain_wave_kernel.inc"
 }
 
@@ -52,7 +42,9 @@ __device__ __forceinline__ void chain_args_pointers(ChainArgs &a, ConstChainArgs
 // analysis sets[chains[b].set] (ChainRef: chain_common.h) with the same body.  The entry and the index are wave-uniform by
 // construction; saying so (readfirstlane) lets the compiler read the argument block with scalar loads at the start, as it reads a
 // kernel argument.  Both tables are read-only here: every result goes through the analysis' own output pointers.
-template <int M, int QPL, bool CACHE>
+// GIVEN: every analysis of such a launch has its start in its rset (plans with and without a start share a batch call, not a launch:
+// the host groups them apart).
+template <int M, int QPL, bool CACHE, bool GIVEN>
 __global__ __launch_bounds__(64, MCSAS_WAVE_MIN_WAVES(QPL, CACHE)) void chain_wave_batch_kernel(const ChainArgs *__restrict__ sets,
                                                                                                 const ChainRef *__restrict__ chains) {
     extern __shared__ double lds[];
@@ -62,23 +54,6 @@ __global__ __launch_bounds__(64, MCSAS_WAVE_MIN_WAVES(QPL, CACHE)) void chain_wa
     const int set = __builtin_amdgcn_readfirstlane(c.set);
     ChainArgs a = sets[set];                                    // (read whole before the first store)
     chain_args_pointers(a, ((ConstChainArgs *)sets)[set]);
-    constexpr bool GIVEN = false;
-#include "chain_wave_kernel.inc"
-}
-
-// ... and its start twin: every analysis of such a launch has its start in its rset (plans with and without a start share a batch
-// call, not a launch: the host groups them apart)
-template <int M, int QPL, bool CACHE>
-__global__ __launch_bounds__(64, MCSAS_WAVE_MIN_WAVES(QPL, CACHE)) void chain_wave_batch_start_kernel(const ChainArgs *__restrict__ sets,
-                                                                                                      const ChainRef *__restrict__ chains) {
-    extern __shared__ double lds[];
-    const int lane = threadIdx.x;
-    const ChainRef c = chains[blockIdx.x];
-    const int rep = __builtin_amdgcn_readfirstlane(c.rep);
-    const int set = __builtin_amdgcn_readfirstlane(c.set);
-    ChainArgs a = sets[set];
-    chain_args_pointers(a, ((ConstChainArgs *)sets)[set]);
-    constexpr bool GIVEN = true;
 #include "chain_wave_kernel.inc"
 }
 

@@ -48,51 +48,44 @@ __device__ __forceinline__ bool wide_stop(const ChainArgs &a, int32_t *stop_word
     return *stop_word != 0;
 }
 
-template <int M, int QPL>
-__global__ __launch_bounds__(WIDE_MAX_WAVES * 64) void chain_wide_kernel(const ChainArgs a, const double *q3inv_glb) {
-#include "chain_wide_prologue.inc"
-
-    // the chain itself is chain_wave.h's (chain_body.inc), with a wave's slice of the q-points: the slice's column folded into the
-    // cache pointer, w and wI from the registers above, sums over the workgroup, the row cache always on and no given start
-    constexpr bool CACHE = true, GIVEN = false;
-#define CHAIN_STATE int par = 0;
-#define CHAIN_CACHE_PTR(p) (p + q0 + lane)
-#define CHAIN_ROW(r) (size_t)(r) * qpad
-#define CHAIN_Q(j) q0 + lane + WAVE * j
-#define CHAIN_W(j) lw[j]
-#define CHAIN_WI(j) lwI[j]
-#define CHAIN_SUM3(x, y, z) wide_sum3(x, y, z, part, par, wave, lane, NW)
-#define CHAIN_SUM1(x) wide_sum1(x, part, par, wave, lane, NW)
-#define CHAIN_FIRST (wave == 0)
-#define CHAIN_LEADER (tid == 0)
-#define CHAIN_STOP wide_stop(a, stop_word, tid)
-#include "chain_body.inc"
-#undef CHAIN_STATE
-#undef CHAIN_CACHE_PTR
-#undef CHAIN_ROW
-#undef CHAIN_Q
-#undef CHAIN_W
-#undef CHAIN_WI
-#undef CHAIN_SUM3
-#undef CHAIN_SUM1
-#undef CHAIN_FIRST
-#undef CHAIN_LEADER
-#undef CHAIN_STOP
-}
-
-// The same chain started from a given set (mcsas_hip_plan_set_start): the host has copied the repetition's start into rset ahead of
-// the launch, and the first attempt takes it where chain_wide_kernel generates one (chain_body.inc: GIVEN).  Here several waves run
-// that branch.  In the first attempt every wave reads rset[n * P + p] while wave 0 (CHAIN_FIRST) stores what it has just read back
+// GIVEN: the chain is started from a given set (mcsas_hip_plan_set_start): the host has copied the repetition's start into rset
+// ahead of the launch, and the first attempt takes it where the cold kernel generates one (chain_body.inc: GIVEN).  Here several waves
+// run that branch.  In the first attempt every wave reads rset[n * P + p] while wave 0 (CHAIN_FIRST) stores what it has just read back
 // to the same address: the same 8-byte value, bit for bit, in one aligned store, so a reader gets that value whichever side of the
 // store it lands on.  No other access to rset crosses a wave boundary without a barrier: an accepted row is written by thread 0 and
 // read by nobody during the attempt (the row cache is always on), and the fresh set of a retry is written by wave 0, which reaches
 // it only through the barriers of the attempt before (the sums of its initial and final fits), behind every wave's last read of the
 // start; nobody reads that set back.
-template <int M, int QPL>
-__global__ __launch_bounds__(WIDE_MAX_WAVES * 64) void chain_wide_start_kernel(const ChainArgs a, const double *q3inv_glb) {
-#include "chain_wide_prologue.inc"
+template <int M, int QPL, bool GIVEN>
+__global__ __launch_bounds__(WIDE_MAX_WAVES * 64) void chain_wide_kernel(const ChainArgs a, const double *q3inv_glb) {
+    extern __shared__ double lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NW = blockDim.x >> 6;
+    const int rep = blockIdx.x;
+    const int N = a.n_contrib, P = a.model.n_active, qpad = a.qpad;
+    const int q0 = wave * QPL * WAVE;                              // first q index of this wave's slice
+    double *part = lds, *tab = lds + WIDE_PART_DOUBLES;
+    int32_t *stop_word = reinterpret_cast<int32_t *>(part + 2 * WIDE_MAX_WAVES * 4);
+    // the model's tables and the per-wave row scratch (make_qtables finds the latter behind the former)
+    int tabd = Contrib<M>::table_doubles(a.model.int_div);
+    if constexpr (Contrib<M>::ROWTAB > 0) { if (a.model.use_rowtab) tabd += NW * Contrib<M>::ROWTAB * a.model.int_div; }
+    const double *qsrc = a.q, *q3src = q3inv_glb;
+    if (a.pad1) {                                                  // q and 1/q^3 fit in LDS
+        double *lq = tab + tabd, *lq3 = lq + qpad;
+        for (int i = tid; i < qpad; i += blockDim.x) { lq[i] = a.q[i]; lq3[i] = q3inv_glb[i]; }
+        qsrc = lq; q3src = lq3;
+    }
+    Contrib<M>::fill_table(a.model, tab, tid, blockDim.x);
+    if (tid == 0) *stop_word = 0;
+    __syncthreads();
+    QTables qt = make_qtables<M>(a.model, qsrc + q0, q3src + q0, tab);
+    if (qt.locs_t) qt.locs_t += q0;                                // smearing: evaluation points of this slice
+    double lw[QPL], lwI[QPL];
+#pragma unroll
+    for (int j = 0; j < QPL; ++j) { lw[j] = a.w[q0 + lane + WAVE * j]; lwI[j] = a.wI[q0 + lane + WAVE * j]; }
 
-    constexpr bool CACHE = true, GIVEN = true;
+    // the chain itself is chain_wave.h's (chain_body.inc), with a wave's slice of the q-points: the slice's column folded into the
+    // cache pointer, w and wI from the registers above, sums over the workgroup and the row cache always on
+    constexpr bool CACHE = true;
 #define CHAIN_STATE int par = 0;
 #define CHAIN_CACHE_PTR(p) (p + q0 + lane)
 #define CHAIN_ROW(r) (size_t)(r) * qpad

@@ -81,18 +81,19 @@ struct SmearDev {
 };
 
 // ------------------------------------------------------------------------------ run-time model plug-ins (host_plugin.hip)
-// the chain kernel families; every built-in model has its instances in kern_<family>.hip (the two wave start families, the wave and
-// wave-batch kernels whose first attempt takes a given set, share kern_wave_start.hip; the q-split one is kern_wide_start.hip), a
-// plug-in compiles its own on first use
-enum KernelFamily { KF_WAVE, KF_WAVE_BATCH, KF_WG, KF_WIDE, KF_PIPE_TICK, KF_WAVE_START, KF_WAVE_BATCH_START, KF_WIDE_START, KF_COUNT };
+// the chain kernel families.  A kernel is (family, given): the wave, wave-batch and q-split families have a second form whose first
+// attempt takes a given set (mcsas_hip_plan_set_start), the workgroup-window and pipeline families have none.  Every built-in model
+// has its instances in kern_*.hip (the started ones in kern_wave_start.hip and kern_wide_start.hip), a plug-in compiles its own on
+// first use
+enum KernelFamily { KF_WAVE, KF_WAVE_BATCH, KF_WG, KF_WIDE, KF_PIPE_TICK, KF_COUNT };
 enum PluginSmallKernel { PLUGIN_MODEL_ROWS, PLUGIN_OBSERVABILITY, PLUGIN_HIST_ROWS };
 
 inline bool is_plugin_model(int model_id) { return model_id >= MCSAS_MODEL_PLUGIN0 && model_id < MCSAS_MODEL_PLUGIN0 + MCSAS_MAX_PLUGINS; }
 // what a plug-in's text declares (plugin_model.h); false: no such plug-in
 bool plugin_declares(int model_id, int *row_class, bool *can_smear);
-// the family's kernel for `qpl` q slots per lane and the family's flag (row cache / row queue; ignored by the families without one),
-// compiled on first use, as a function of the CURRENT device's module
-int plugin_chain_function(int model_id, KernelFamily family, int qpl, bool flag, hipFunction_t *fn);
+// the family's kernel for `qpl` q slots per lane, the family's flag (row cache / row queue; ignored by the families without one)
+// and `given`, compiled on first use, as a function of the CURRENT device's module
+int plugin_chain_function(int model_id, KernelFamily family, int qpl, bool flag, bool given, hipFunction_t *fn);
 int plugin_small_function(int model_id, PluginSmallKernel which, hipFunction_t *fn);
 
 // launch of a small kernel of a plug-in on the null stream; the arguments are passed by address,

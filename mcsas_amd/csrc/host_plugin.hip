@@ -146,21 +146,18 @@ int plugin_small_function(int model_id, PluginSmallKernel which, hipFunction_t *
     const std::vector<std::string> exprs(PLUGIN_SMALL_EXPRS, PLUGIN_SMALL_EXPRS + 3);
     return plugin_function(model_id, "small", exprs, exprs[which], fn);
 }
-int plugin_chain_function(int model_id, KernelFamily family, int qpl, bool flag, hipFunction_t *fn) {
-    // the kernel template, the program key, and whether the family has a flag (row cache / row queue) as its last template argument
-    static const struct { const char *kernel, *key; bool flagged; } FAMILY[KF_COUNT] = {
-        {"chain_wave_kernel", "wave", true}, {"chain_wave_batch_kernel", "wave batch", true}, {"chain_wg_kernel", "wg", false},
-        {"chain_wide_kernel", "wide", false}, {"pipe_tick_kernel", "pipe", true},
-        {"chain_wave_start_kernel", "wave start", true}, {"chain_wave_batch_start_kernel", "wave batch start", true},
-        {"chain_wide_start_kernel", "wide start", false}};
-    char e[128], k[32];
-    if (FAMILY[family].flagged) {
-        snprintf(e, sizeof e, "mcsas::%s<MCSAS_MODEL_PLUGIN, %d, %s>", FAMILY[family].kernel, qpl, flag ? "true" : "false");
-        snprintf(k, sizeof k, "%s %d %d", FAMILY[family].key, qpl, flag ? 1 : 0);
-    } else {
-        snprintf(e, sizeof e, "mcsas::%s<MCSAS_MODEL_PLUGIN, %d>", FAMILY[family].kernel, qpl);
-        snprintf(k, sizeof k, "%s %d", FAMILY[family].key, qpl);
-    }
+int plugin_chain_function(int model_id, KernelFamily family, int qpl, bool flag, bool given, hipFunction_t *fn) {
+    // the kernel template, the program key, and which template arguments the family has behind <model, qpl>: its flag (row cache /
+    // row queue), then whether the first attempt takes a given set
+    static const struct { const char *kernel, *key; bool flagged, startable; } FAMILY[KF_COUNT] = {
+        {"chain_wave_kernel", "wave", true, true}, {"chain_wave_batch_kernel", "wave batch", true, true}, {"chain_wg_kernel", "wg", false, false},
+        {"chain_wide_kernel", "wide", false, true}, {"pipe_tick_kernel", "pipe", true, false}};
+    const auto &f = FAMILY[family];
+    if (given && !f.startable) return fail(MCSAS_EINVAL, "no %s start kernel for model %d qpl %d", f.key, model_id, qpl);
+    // (started and cold kernels are programs of their own, each compiled when first asked for)
+    const std::string e = std::string("mcsas::") + f.kernel + "<MCSAS_MODEL_PLUGIN, " + std::to_string(qpl) + (f.flagged ? (flag ? ", true" : ", false") : "")
+                          + (f.startable ? (given ? ", true" : ", false") : "") + ">";
+    const std::string k = std::string(f.key) + (given ? " start " : " ") + std::to_string(qpl) + (f.flagged ? (flag ? " 1" : " 0") : "");
     return plugin_function(model_id, k, {e}, e, fn);
 }
 

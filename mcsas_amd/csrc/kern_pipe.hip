@@ -1,11 +1,7 @@
 // kern_pipe.hip — instantiates the pipeline tick kernel for ONE model (-DMCSAS_M=<id>) and, for
 // model 0 only, the model-independent reset kernel.
 #include "chain_pipe.h"
-#ifndef MCSAS_M
-#error "compile with -DMCSAS_M=<model id>"
-#endif
-#define CAT_(a, b) a##b
-#define CAT(a, b) CAT_(a, b)
+#include "kern_lookup.h"
 using namespace mcsas;
 
 // rowq: the kernel whose producers pull rows from a queue (rows with an integral, smeared models); the models without an integral

@@ -1,26 +1,7 @@
-// kern_wave_batch.hip — instantiates the batch form of the wave-per-chain kernel (chain_wave_batch_kernel: several analyses in
-// one launch) for ONE model (-DMCSAS_M=<id>), for the same q-slot / row-cache pairs as kern_wave.hip.  Exports a lookup the host
-// code links against.
+// kern_wave_batch.hip — the batch form of the wave-per-chain kernel (several analyses in one launch) of one model, for the same
+// q-slot / row-cache pairs as kern_wave.hip (kern_lookup.h).
 #include "chain_wave.h"
-#ifndef MCSAS_M
-#error "compile with -DMCSAS_M=<model id>"
-#endif
-#define CAT_(a, b) a##b
-#define CAT(a, b) CAT_(a, b)
+#include "kern_lookup.h"
 using namespace mcsas;
 
-template <int QPL> static void *pick(bool cache) {
-    return cache ? (void *)chain_wave_batch_kernel<MCSAS_M, QPL, true> : (void *)chain_wave_batch_kernel<MCSAS_M, QPL, false>;
-}
-void *CAT(mcsas_wave_batch_kernel_m, MCSAS_M)(int qpl, bool cache) {
-    switch (qpl) {
-        case 1: return pick<1>(cache);
-        case 2: return pick<2>(cache);
-        case 4: return pick<4>(cache);
-        case 8: return pick<8>(cache);
-        case 16: return pick<16>(cache);
-        case 32: return cache ? (void *)chain_wave_batch_kernel<MCSAS_M, 32, true> : nullptr;
-        case 64: return cache ? (void *)chain_wave_batch_kernel<MCSAS_M, 64, true> : nullptr;
-        default: return nullptr;
-    }
-}
+MCSAS_WAVE_LOOKUP(mcsas_wave_batch_kernel_m, pick, chain_wave_batch_kernel, false)

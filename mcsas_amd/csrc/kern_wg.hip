@@ -1,13 +1,9 @@
 // kern_wg.hip — instantiates the workgroup-per-chain kernels for ONE model (-DMCSAS_M=<id>).
 #include "chain_wg.h"
-#ifndef MCSAS_M
-#error "compile with -DMCSAS_M=<model id>"
-#endif
-#define CAT_(a, b) a##b
-#define CAT(a, b) CAT_(a, b)
+#include "kern_lookup.h"
 using namespace mcsas;
 
-void *CAT(mcsas_wg_kernel_m, MCSAS_M)(int qpl) {
+void *CAT(mcsas_wg_kernel_m, MCSAS_M)(int qpl, bool) {
     switch (qpl) {
         case 1: return (void *)chain_wg_kernel<MCSAS_M, 1>;
         case 2: return (void *)chain_wg_kernel<MCSAS_M, 2>;

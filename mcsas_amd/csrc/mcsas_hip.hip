@@ -331,27 +331,19 @@ static int plan_activate_slot(mcsas_plan *pl, int k) {
 }
 
 // ------------------------------------------------------------------------------ the chain kernels
-// kernel lookups, one translation unit per model and family (kern_*.hip)
-#define DECL_K(m) void *mcsas_wave_kernel_m##m(int, bool); void *mcsas_wave_batch_kernel_m##m(int, bool); void *mcsas_wg_kernel_m##m(int); void *mcsas_wide_kernel_m##m(int); void *mcsas_pipe_tick_kernel_m##m(int, bool); \
-                  void *mcsas_wave_start_kernel_m##m(int, bool); void *mcsas_wave_batch_start_kernel_m##m(int, bool); void *mcsas_wide_start_kernel_m##m(int);
+// A kernel is (family, given): given = the first attempt takes the plan's start (mcsas_hip_plan_set_start).  The lookups of the
+// built-in models, one per model, family and given (kern_*.hip; all `void *(int qpl, bool flag)`, flag: with the row cache (wave
+// families) / rows pulled from a queue (pipeline tick)); null where the family has no start form.
+typedef void *KernelLookup(int qpl, bool flag);
+#define DECL_K(m) KernelLookup mcsas_wave_kernel_m##m, mcsas_wave_kernel_given_m##m, mcsas_wave_batch_kernel_m##m, mcsas_wave_batch_kernel_given_m##m, \
+                               mcsas_wg_kernel_m##m, mcsas_wide_kernel_m##m, mcsas_wide_kernel_given_m##m, mcsas_pipe_tick_kernel_m##m;
+#define ROW_K(m) {{mcsas_wave_kernel_m##m, mcsas_wave_kernel_given_m##m}, {mcsas_wave_batch_kernel_m##m, mcsas_wave_batch_kernel_given_m##m}, \
+                  {mcsas_wg_kernel_m##m, nullptr}, {mcsas_wide_kernel_m##m, mcsas_wide_kernel_given_m##m}, {mcsas_pipe_tick_kernel_m##m, nullptr}},
 MCSAS_FOR_MODELS(DECL_K)
+static KernelLookup *const BUILTIN[MCSAS_MODEL_COUNT][KF_COUNT][2] = {MCSAS_FOR_MODELS(ROW_K)};
 #undef DECL_K
+#undef ROW_K
 void *mcsas_pipe_reset_kernel();
-
-// the instance of a built-in model; `flag`: with the row cache (wave families) / rows pulled from a queue (pipeline tick)
-static void *builtin_kernel(KernelFamily family, int model, int qpl, bool flag) {
-    switch (model) {
-#define CASE_K(m)                                                                                                                   \
-    case m:                                                                                                                         \
-        return family == KF_WAVE ? mcsas_wave_kernel_m##m(qpl, flag) : family == KF_WAVE_BATCH ? mcsas_wave_batch_kernel_m##m(qpl, flag) \
-             : family == KF_WAVE_START ? mcsas_wave_start_kernel_m##m(qpl, flag) : family == KF_WAVE_BATCH_START ? mcsas_wave_batch_start_kernel_m##m(qpl, flag) \
-             : family == KF_WG ? mcsas_wg_kernel_m##m(qpl) : family == KF_WIDE ? mcsas_wide_kernel_m##m(qpl)                              \
-             : family == KF_WIDE_START ? mcsas_wide_start_kernel_m##m(qpl) : mcsas_pipe_tick_kernel_m##m(qpl, flag);
-        MCSAS_FOR_MODELS(CASE_K)
-#undef CASE_K
-        default: return nullptr;
-    }
-}
 
 // What a launch needs: the kernel (built-in models: the host handle of the __global__ function; plug-ins: the function of this
 // device's module), the block size, and which second kernel argument the family takes after its argument block.
@@ -362,37 +354,33 @@ struct KernelRef {
     enum { ARG2_NONE, ARG2_WG, ARG2_Q3INV } arg2 = ARG2_NONE;
     const void *id() const { return plugin ? (const void *)plugin : entry; }
 };
-// the family of the plan's own launches (mcsas_hip_plan_launch_batch asks for KF_WAVE_BATCH instead); launch_family: the one a
-// launch takes now, i.e. the start twin of the wave and q-split families while the plan holds a start (mcsas_hip_plan_set_start
-// gives one to no other plan)
+// the family of the plan's own launches; a batch (mcsas_hip_plan_launch_batch) runs the plan's chains in KF_WAVE_BATCH instead.  Either
+// way a launch takes the started kernel of its family while the plan holds a start (mcsas_hip_plan_set_start gives one to plans of
+// the wave and q-split families only).
 static KernelFamily plan_family(const mcsas_plan *pl) {
     if (pl->mode == MCSAS_EXEC_WAVE) return KF_WAVE;
     if (pl->mode == MCSAS_EXEC_PIPELINE) return KF_PIPE_TICK;
     return pl->wide ? KF_WIDE : KF_WG;
 }
-static KernelFamily launch_family(const mcsas_plan *pl, bool batch) {
-    if (batch) return pl->has_start ? KF_WAVE_BATCH_START : KF_WAVE_BATCH;
-    if (!pl->has_start) return plan_family(pl);
-    return pl->wide ? KF_WIDE_START : KF_WAVE_START;
-}
-static int resolve_kernel(const mcsas_plan *pl, KernelFamily family, KernelRef *k) {
-    static const char *const missing[KF_COUNT] = {"no kernel for model %d qpl %d", "launch_batch: no batch kernel for model %d qpl %d", "no kernel for model %d qpl %d",
-                                                  "no q-split kernel for model %d qpl %d", "no pipeline kernel for model %d qpl %d",
-                                                  "no start kernel for model %d qpl %d", "launch_batch: no batch start kernel for model %d qpl %d",
-                                                  "no q-split start kernel for model %d qpl %d"};
+static int resolve_kernel(const mcsas_plan *pl, KernelFamily family, bool given, KernelRef *k) {
+    static const char *const name[KF_COUNT] = {"", "batch ", "", "q-split ", "pipeline "};
     const int model = pl->prob.model_id;
     const bool flag = family == KF_PIPE_TICK ? pl->pipe.g.rowq != 0 : pl->use_cache != 0;
     *k = KernelRef{};
-    const bool q_split = family == KF_WIDE || family == KF_WIDE_START;
-    k->block = family == KF_PIPE_TICK ? PIPE_BLOCK : (family == KF_WG || q_split ? WAVE * pl->waves : WAVE);
-    k->arg2 = family == KF_WG ? KernelRef::ARG2_WG : (q_split ? KernelRef::ARG2_Q3INV : KernelRef::ARG2_NONE);
+    k->block = family == KF_PIPE_TICK ? PIPE_BLOCK : (family == KF_WG || family == KF_WIDE ? WAVE * pl->waves : WAVE);
+    k->arg2 = family == KF_WG ? KernelRef::ARG2_WG : (family == KF_WIDE ? KernelRef::ARG2_Q3INV : KernelRef::ARG2_NONE);
     if (is_plugin_model(model)) {
-        if (pl->plugin_fn && family == plan_family(pl)) { k->plugin = pl->plugin_fn; return MCSAS_OK; }      // (looked up when the plan was made)
-        return plugin_chain_function(model, family, pl->qpl, flag, &k->plugin);                             // (compiled on first use of this q count)
+        if (pl->plugin_fn && family == plan_family(pl) && !given) { k->plugin = pl->plugin_fn; return MCSAS_OK; }   // (looked up when the plan was made)
+        return plugin_chain_function(model, family, pl->qpl, flag, given, &k->plugin);                           // (compiled on first use of this q count)
     }
-    k->entry = builtin_kernel(family, model, pl->qpl, flag);
-    if (!k->entry) return fail(MCSAS_EINVAL, missing[family], model, pl->qpl);
+    KernelLookup *const lookup = model >= 0 && model < MCSAS_MODEL_COUNT ? BUILTIN[model][family][given] : nullptr;
+    k->entry = lookup ? lookup(pl->qpl, flag) : nullptr;
+    if (!k->entry) return fail(MCSAS_EINVAL, "%sno %s%skernel for model %d qpl %d", family == KF_WAVE_BATCH ? "launch_batch: " : "", name[family], given ? "start " : "", model, pl->qpl);
     return MCSAS_OK;
+}
+// the kernel a launch of the plan takes now
+static int launch_kernel_of(const mcsas_plan *pl, bool batch, KernelRef *k) {
+    return resolve_kernel(pl, batch ? KF_WAVE_BATCH : plan_family(pl), pl->has_start, k);
 }
 // one launch of `grid` blocks; built-in kernels get their dynamic LDS limit raised when they need more than the default 64 KiB
 static int launch_kernel(const KernelRef &k, unsigned grid, void **kargs, size_t lds, hipStream_t st) {
@@ -706,7 +694,7 @@ static int choose_kernel(mcsas_plan *pl) {
     const KernelFamily family = plan_family(pl);
     if (is_plugin_model(model) || family == KF_WAVE || family == KF_WIDE) {
         KernelRef k;
-        if (int rc = resolve_kernel(pl, family, &k)) return rc;
+        if (int rc = resolve_kernel(pl, family, false, &k)) return rc;
         pl->plugin_fn = k.plugin;
     }
     if (family == KF_WAVE) {
@@ -823,8 +811,8 @@ static const char *exec_mode_name(int mode) {
 }
 
 // The set every later launch of the plan starts its repetitions from (include/mcsas_hip.h), kept on the device in the layout of rset;
-// a launch copies it into its slot's rset on the launch stream and runs the start twin of the plan's kernel, whose first attempt reads
-// it where the others generate one (chain_body.inc: GIVEN).  The wavefront-per-chain and the q-split kernels have such a twin; the
+// a launch copies it into its slot's rset on the launch stream and runs the started form of the plan's kernel, whose first attempt reads
+// it where the cold one generates a set (chain_body.inc: GIVEN).  The wavefront-per-chain and the q-split kernels have such a form; the
 // workgroup-window kernel (up to 1024 q-points) and the pipeline have none, and their plans refuse.
 extern "C" int mcsas_hip_plan_set_start(mcsas_plan *pl, const double *start, int32_t rep_stride, int32_t rep_first) {
     if (!pl) return fail(MCSAS_EINVAL, "set_start: null plan");
@@ -937,7 +925,7 @@ extern "C" int mcsas_hip_plan_launch_slot(mcsas_plan *pl, void *hip_stream, int3
     if (pl->mode != MCSAS_EXEC_PIPELINE) HIPCHK(hipMemsetAsync(pl->d_stop_relay, 0, 16, st));   // (the pipeline's ticks get McSAS.stop as a kernel argument)
     FailGuard guard{&pl, 1};                              // (any error return below leaves work on `st` that no end event covers)
     KernelRef k;
-    if (int rc = resolve_kernel(pl, launch_family(pl, false), &k)) return rc;
+    if (int rc = launch_kernel_of(pl, false, &k)) return rc;
     if (pl->mode == MCSAS_EXEC_PIPELINE) {
         if (int rc = pipeline_launch(pl, k, st)) return rc;
     } else {
@@ -1100,7 +1088,7 @@ extern "C" int mcsas_hip_plan_launch_batch(mcsas_plan *const *plans, int32_t n, 
     std::vector<KernelRef> groups;
     for (int i = 0; i < n; ++i) {
         KernelRef k;
-        if (int rc = resolve_kernel(plans[i], launch_family(plans[i], true), &k)) return rc;
+        if (int rc = launch_kernel_of(plans[i], true, &k)) return rc;
         group_of[i] = (int)(std::find_if(groups.begin(), groups.end(), [&](const KernelRef &g) { return g.id() == k.id(); }) - groups.begin());
         if (group_of[i] == (int)groups.size()) groups.push_back(k);
     }

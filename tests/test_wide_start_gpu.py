@@ -1,5 +1,5 @@
 """Chains of the q-split workgroup kernel (csrc/chain_wide.h: more than 1024 q-points, one workgroup per chain) started from given
-contributions: chain_wide_start_kernel behind mcsas_hip_analyse_from / mcsas_hip_plan_set_start with MCSAS_EXEC_WORKGROUP, and
+contributions: chain_wide_kernel<M, QPL, true> behind mcsas_hip_analyse_from / mcsas_hip_plan_set_start with MCSAS_EXEC_WORKGROUP, and
 behind McSAS.calc(start=) on un-binned data.
 
 The machinery is tests/test_start_gpu.py's, by import: the reference of a started chain is the oracle's own mc_fit with its first

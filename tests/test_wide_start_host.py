@@ -99,19 +99,31 @@ def _code(name):
 
 
 def test_the_new_family_is_entered_in_every_table():
+    """A kernel is (family, given): five families, one row each in the plug-in compiler's table, the started q-split kernels compiled
+    by a unit of their own, and no copy of a kernel template for the start."""
     families = re.search(r"enum\s+KernelFamily\s*\{([^}]*)\}", _code("host_internal.h")).group(1).replace(" ", "").split(",")
-    assert families[-1] == "KF_COUNT" and "KF_WIDE_START" in families[:-1] and len(set(families)) == len(families)
+    assert families[-1] == "KF_COUNT" and "KF_WIDE" in families[:-1] and len(set(families)) == len(families)
     n = len(families) - 1
     table = re.search(r"FAMILY\[KF_COUNT\]\s*=\s*\{(.*?)\};", _code("host_plugin.hip"), re.S).group(1)
-    rows = re.findall(r'\{\s*"(\w+)"\s*,\s*"([\w ]+)"\s*,\s*(?:true|false)\s*\}', table)
-    assert len(rows) == n and rows[families.index("KF_WIDE_START")][0] == "chain_wide_start_kernel", rows
+    rows = re.findall(r'\{\s*"(\w+)"\s*,\s*"([\w ]+)"\s*(?:,\s*(?:true|false)\s*)+\}', table)
+    assert len(rows) == n and rows[families.index("KF_WIDE")][0] == "chain_wide_kernel", rows
+    assert len(re.findall(r"\{[^{}]*\}", table)) == n, table                    # (no row of another shape)
     assert len({key for _, key in rows}) == n                                    # (the program keys tell the families apart)
-    missing = re.search(r"missing\[KF_COUNT\]\s*=\s*\{(.*?)\};", _code("mcsas_hip.hip"), re.S).group(1)
-    assert len(re.findall(r'"[^"]*"', missing)) == n, missing
-    # one translation unit per model, and the lookup the host links against
-    assert "chain_wide_start_kernel<MCSAS_M, 8>" in _code("kern_wide_start.hip")
+    # the built-in models: one row of lookups per family, cold and started, for every model of the list
+    row_k = re.search(r"#define ROW_K\(m\)(.*?)\n(?!\s)", _code("mcsas_hip.hip").replace("\\\n", " "), re.S).group(1)
+    pairs = re.findall(r"\{\s*(\w+)##m\s*,\s*(\w+##m|nullptr)\s*\}", row_k)
+    assert len(pairs) == n, row_k
+    assert pairs[families.index("KF_WIDE")] == ("mcsas_wide_kernel_m", "mcsas_wide_kernel_given_m##m"), pairs
+    assert re.search(r"BUILTIN\[MCSAS_MODEL_COUNT\]\[KF_COUNT\]\[2\]\s*=\s*\{\s*MCSAS_FOR_MODELS\(ROW_K\)\s*\}", _code("mcsas_hip.hip"))
+    # one translation unit per model, and the lookup the host links against: the started instances of the shared table
+    assert re.search(r"MCSAS_WIDE_LOOKUP\(\s*mcsas_wide_kernel_given_m\s*,\s*chain_wide_kernel\s*,\s*true\s*\)", _code("kern_wide_start.hip"))
+    lookup = re.search(r"#define MCSAS_WIDE_LOOKUP\(LOOKUP, KERNEL, GIVEN\)(.*?)\n(?!\s)", _code("kern_lookup.h").replace("\\\n", " "), re.S).group(1)
+    assert "KERNEL<MCSAS_M, 8, GIVEN>" in lookup and "CAT(LOOKUP, MCSAS_M)" in lookup
     make = open(os.path.join(CSRC, "Makefile")).read()
     assert "kern_wide_start_m$(m).o" in make and re.search(r"kern_wide_start_m%\.o:\s*kern_wide_start\.hip \$\(WIDE_HDRS\)", make)
+    # the start is a template parameter, not a second template
+    for name in sorted(os.listdir(CSRC)):
+        assert "_start_kernel" not in open(os.path.join(CSRC, name)).read(), name
 
 
 def test_every_included_text_is_embedded_for_the_plugin_compiler():
@@ -132,6 +144,6 @@ def test_every_included_text_is_embedded_for_the_plugin_compiler():
         if os.path.exists(path):
             todo += [os.path.basename(x) for x in re.findall(r'#\s*include\s+"([\w./]+)"', _code(name))]
     incs = [x for x in seen if x.endswith(".inc")]
-    assert "chain_wide_prologue.inc" in incs and "chain_body.inc" in incs
+    assert "chain_wave_kernel.inc" in incs and "chain_body.inc" in incs
     wide_hdrs = re.search(r"^WIDE_HDRS :=(.*)$", make, re.M).group(1).split()
     assert set(re.findall(r'#\s*include\s+"([\w.]+\.inc)"', _code("chain_wide.h"))) <= set(wide_hdrs)

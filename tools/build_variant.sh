@@ -13,10 +13,10 @@ for u in $HOST; do /opt/rocm/bin/hipcc $F -c -o $V/$u.o $u.hip & done
 MODELS=${MODELS:-0}
 for m in $MODELS; do /opt/rocm/bin/hipcc $F -DMCSAS_M=$m -c -o $V/kern_pipe_m$m.o kern_pipe.hip & done
 wait
-objs=""; for u in $HOST; do objs="$objs $V/$u.o"; done
-for m in 0 1 2 3 4 5 6 7; do
-  objs="$objs $B/kern_wave_m$m.o $B/kern_wave_batch_m$m.o $B/kern_wg_m$m.o $B/kern_wide_m$m.o"
-  case " $MODELS " in *" $m "*) objs="$objs $V/kern_pipe_m$m.o";; *) objs="$objs $B/kern_pipe_m$m.o";; esac
+# the release library's object list (Makefile: print-objs), with the objects compiled above in place of the release ones
+objs=""
+for o in $(make --no-print-directory print-objs BUILD=$B); do
+  if [ -e $V/$(basename $o) ]; then objs="$objs $V/$(basename $o)"; else objs="$objs $o"; fi
 done
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../lib/libmcsas_$name.so $objs -lhiprtc
 ls -la ../lib/libmcsas_$name.so
