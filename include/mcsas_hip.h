@@ -342,6 +342,22 @@ typedef struct mcsas_histogram_spec {
 int mcsas_hip_histogram(const mcsas_problem *problem, const double *contribs, int32_t n_hist,
                         const mcsas_histogram_spec *specs, double *scaling, double *fractions, double *out);
 
+/* ---- McSAS.histogram() of a series: n_sets data sets in one call --------------------------------------------------------------
+ * Set s means exactly mcsas_hip_histogram(&problems[s], contribs[s], n_hist[s], specs[s], scaling[s], fractions[s], out[s]) — the
+ * same layouts, fractions[s] (or the table `fractions`) may be NULL — and every array of every set is that single call's bit for
+ * bit, whatever else is in the batch and in whatever order.  What it saves is the calls: ONE packed upload, ONE launch per kernel
+ * over the (set, repetition) blocks of all sets (the model's rows: one launch per built-in model present) and ONE packed download.
+ *   e.g. a series' histograms after mcsas_hip_analyse_batch: mcsas_hip_histogram_batch(n, problems, contribs, n_hist, specs, sc, fr, out);
+ * Refused with MCSAS_EINVAL before a device is touched, the message naming the set (and the histogram): n_sets < 0, a NULL table,
+ * whatever mcsas_hip_histogram refuses of a set (n_contrib > 4096 among it), sets that name different devices.  n_sets == 0: MCSAS_OK.
+ * Memory: the sets are taken in order, in chunks whose rows (n_contrib * n_reps * nq doubles per set) fit 2 GiB, or
+ * MCSAS_HIP_HIST_BATCH_MB MiB (environment, read at every call, fractions allowed); the kernels run once per chunk.  A set whose
+ * rows alone exceed that, and a set of a plug-in model (the run-time compiler has no batch form of its rows kernel), runs in its
+ * place through mcsas_hip_histogram. */
+int mcsas_hip_histogram_batch(int32_t n_sets, const mcsas_problem *problems, const double *const *contribs,
+                              const int32_t *n_hist, const mcsas_histogram_spec *const *specs,
+                              double *const *scaling, double *const *fractions, double *const *out);
+
 /* ---- input preparation ----------------------------------------------------------
  * DataObj._prepareUncertainty (dataobj/dataobj.py:204-227): sigma_out = max(sigma_raw, fu_min * I),
  * fu_min * I when sigma_raw is NULL (no uncertainty column), +inf where that is not finite. */

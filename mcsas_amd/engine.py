@@ -535,30 +535,64 @@ def histogram_device(model: ModelSetup, q, intensity, sigma, contribs, comp_exp,
     Returns (scaling[2][R], fractions dict like mcsas.histogram's {'vol': (vf, mv), ...}, per histogram a dict with
     bins[n_bin][R], obs[n_bin][R], cdf[n_bin][R], moments[5][R])."""
     lib = _lib.load()
-    contribs = f64(contribs)
-    N, P, R = contribs.shape
-    st = Settings(n_contrib=N, n_reps=R, comp_exp=comp_exp, device=device, find_background=find_background,
-                  positive_background=positive_background)
-    prob = HipProblem(model, q, intensity, sigma, st, smear=smear)
-    arr = (_lib.HistogramSpec * max(len(specs), 1))()
-    keep, n_out = [], 0
-    for h, sp in enumerate(specs):
-        e = f64(sp["edges"]).ravel()
-        keep.append(e)
-        arr[h].param_index = int(sp["param_index"]); arr[h].weighting = YWEIGHT_INDEX[sp["yweight"]]
-        arr[h].n_bin = len(e) - 1; arr[h].lower = float(sp["lower"]); arr[h].upper = float(sp["upper"]); arr[h].edges = as_dp(e)
-        n_out += 3 * (len(e) - 1) * R + 5 * R
-    sc = np.zeros((2, R)); frac = np.zeros((8, N, R)); out = np.zeros(max(n_out, 1))
-    check(lib.mcsas_hip_histogram(C.byref(prob.c), as_dp(contribs), len(specs), arr, as_dp(sc), as_dp(frac), as_dp(out)), lib)
-    fractions = dict(vol=(frac[0], frac[4]), num=(frac[1], frac[5]), int=(frac[2], frac[6]), surf=(frac[3], frac[7]))
-    hists, off = [], 0
-    for sp, e in zip(specs, keep):
-        nb = len(e) - 1
-        blk = out[off:off + 3 * nb * R + 5 * R]
-        hists.append(dict(bins=blk[:nb * R].reshape(nb, R), obs=blk[nb * R:2 * nb * R].reshape(nb, R),
-                          cdf=blk[2 * nb * R:3 * nb * R].reshape(nb, R), moments=blk[3 * nb * R:].reshape(5, R)))
-        off += 3 * nb * R + 5 * R
-    return sc, fractions, hists
+    call = _HistogramCall(model, q, intensity, sigma, contribs, comp_exp, specs, find_background, positive_background, device, smear)
+    check(lib.mcsas_hip_histogram(C.byref(call.prob.c), as_dp(call.contribs), len(call.specs), call.arr, as_dp(call.sc), as_dp(call.frac),
+                                  as_dp(call.out)), lib)
+    return call.unpack()
+
+
+class _HistogramCall:
+    """The arguments of one mcsas_hip_histogram call (or of one set of mcsas_hip_histogram_batch) and the arrays it fills; owns
+    every numpy buffer the C structures point at."""
+
+    def __init__(self, model, q, intensity, sigma, contribs, comp_exp, specs, find_background=True, positive_background=False,
+                 device=-1, smear=None):
+        self.contribs = f64(contribs)
+        N, P, R = self.contribs.shape
+        st = Settings(n_contrib=N, n_reps=R, comp_exp=comp_exp, device=device, find_background=find_background,
+                      positive_background=positive_background)
+        self.prob = HipProblem(model, q, intensity, sigma, st, smear=smear)
+        self.specs = list(specs)
+        self.arr = (_lib.HistogramSpec * max(len(self.specs), 1))()
+        self.edges, n_out = [], 0
+        for h, sp in enumerate(self.specs):
+            e = f64(sp["edges"]).ravel()
+            self.edges.append(e)
+            a = self.arr[h]
+            a.param_index = int(sp["param_index"]); a.weighting = YWEIGHT_INDEX[sp["yweight"]]
+            a.n_bin = len(e) - 1; a.lower = float(sp["lower"]); a.upper = float(sp["upper"]); a.edges = as_dp(e)
+            n_out += 3 * (len(e) - 1) * R + 5 * R
+        self.sc = np.zeros((2, R)); self.frac = np.zeros((8, N, R)); self.out = np.zeros(max(n_out, 1))
+
+    def unpack(self):
+        frac, out, R = self.frac, self.out, self.contribs.shape[2]
+        fractions = dict(vol=(frac[0], frac[4]), num=(frac[1], frac[5]), int=(frac[2], frac[6]), surf=(frac[3], frac[7]))
+        hists, off = [], 0
+        for e in self.edges:
+            nb = len(e) - 1
+            blk = out[off:off + 3 * nb * R + 5 * R]
+            hists.append(dict(bins=blk[:nb * R].reshape(nb, R), obs=blk[nb * R:2 * nb * R].reshape(nb, R),
+                              cdf=blk[2 * nb * R:3 * nb * R].reshape(nb, R), moments=blk[3 * nb * R:].reshape(5, R)))
+            off += 3 * nb * R + 5 * R
+        return self.sc, fractions, hists
+
+
+def histogram_device_batch(items):
+    """histogram_device for a list of data sets in one library call (mcsas_hip_histogram_batch): one upload, one launch per kernel
+    over all sets, one download.  Each item is histogram_device's arguments, as a dict by name (model, q, intensity, sigma, contribs,
+    comp_exp, specs, find_background, positive_background, device, smear) or as a tuple in that order; all on one device.
+    Returns, per item, histogram_device's triple — the same arrays bit for bit."""
+    lib = _lib.load()
+    calls = [_HistogramCall(**it) if isinstance(it, dict) else _HistogramCall(*it) for it in items]   # (kept alive to the end of the call)
+    n = len(calls)
+    if n:
+        dpp = C.POINTER(C.c_double) * n
+        probs = (Problem * n)(*[c.prob.c for c in calls])
+        n_hist = (C.c_int32 * n)(*[len(c.specs) for c in calls])
+        specs = (C.POINTER(_lib.HistogramSpec) * n)(*[C.cast(c.arr, C.POINTER(_lib.HistogramSpec)) for c in calls])
+        check(lib.mcsas_hip_histogram_batch(n, probs, dpp(*[as_dp(c.contribs) for c in calls]), n_hist, specs, dpp(*[as_dp(c.sc) for c in calls]),
+                                            dpp(*[as_dp(c.frac) for c in calls]), dpp(*[as_dp(c.out) for c in calls])), lib)
+    return [c.unpack() for c in calls]
 
 
 def prepare_uncertainty(intensity, sigma_raw, fu_min, device=-1):

@@ -241,15 +241,8 @@ class McSAS(object):
         # limits, the fractions, and per configured histogram the bins, CDF and moments of every repetition — their mean / std over
         # the repetitions is taken here.  (More than engine.HISTOGRAM_MAX_CONTRIBS contributions: the two-step path below.)
         if numContribs <= engine.HISTOGRAM_MAX_CONTRIBS:
-            todo = [(pi, h) for pi, param in enumerate(model.activeParams()) for h in param.histograms()]
-            specs = [h.deviceSpec(pi) for pi, h in todo]
-            scalingFactors, fractions, res = engine.histogram_device(
-                setup, data.q, data.f.binnedData, sig, contribs, c, specs, self.findBackground.value(),
-                self.positiveBackground.value(), device=self.device, smear=smear)
-            self.result[0]['scalingFactors'] = scalingFactors
-            self.fractions = fractions
-            for (pi, h), r in zip(todo, res):
-                h.setFromDevice(r)
+            item = self._histogram_item(setup, smear, contribs)
+            self._histogram_from_device(engine.histogram_device(**item))
             return
         # model.calc, the scale/background fit and the N single-row visibility limits of every repetition
         # (:552, :559, :575-590): one library call for all of them
@@ -257,6 +250,31 @@ class McSAS(object):
             setup, data.q, data.f.binnedData, sig, contribs, c, self.findBackground.value(),
             self.positiveBackground.value(), device=self.device, smear=smear)
         self._histogram_tail(contribs, scalingFactors, vsets, wsets, ssets, mv)
+
+    def _histogram_todo(self):
+        return [(pi, h) for pi, param in enumerate(self.model.activeParams()) for h in param.histograms()]
+
+    def _histogram_item(self, setup=None, smear=None, contribs=None):
+        """engine.histogram_device's arguments (by name) for the stored result with the current data, model and histograms
+        (run_series hands a list of these to engine.histogram_device_batch)."""
+        data, model = self.data, self.model
+        if setup is None:
+            setup = setup_from_model(model, data)
+            smear = data.smearArgs(model) if hasattr(data, "smearArgs") else None
+        if contribs is None:
+            contribs = self.result[0]['contribs']
+        return dict(model=setup, q=data.q, intensity=data.f.binnedData, sigma=np.array(data.f.binnedDataU, dtype=float),
+                    contribs=contribs, comp_exp=self.compensationExponent(),
+                    specs=[h.deviceSpec(pi) for pi, h in self._histogram_todo()], find_background=self.findBackground.value(),
+                    positive_background=self.positiveBackground.value(), device=self.device, smear=smear)
+
+    def _histogram_from_device(self, triple):
+        """Takes over what engine.histogram_device returned for the stored result."""
+        scalingFactors, fractions, res = triple
+        self.result[0]['scalingFactors'] = scalingFactors
+        self.fractions = fractions
+        for (pi, h), r in zip(self._histogram_todo(), res):
+            h.setFromDevice(r)
 
     def _histogram_tail(self, contribs, scalingFactors, vsets, wsets, ssets, mv):
         """mcsas.py:561-615 from the per-contribution volumes / weights / surfaces and visibility limits of every repetition."""

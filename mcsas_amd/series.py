@@ -7,7 +7,19 @@ from __future__ import annotations
 from collections import OrderedDict
 
 
-def run_series(algo, datasets, keys=None, replays=None, overlap=False, batch=False, start=None):
+# what run_series(batch_histograms=None) does where a batched pass is possible (the measurement behind it)
+BATCH_HISTOGRAMS_DEFAULT = True
+
+
+def _histograms_batchable(algo, engine):
+    """A batched histogram pass needs what McSAS.histogram()'s one-call device path needs: a device model, and no more than
+    engine.HISTOGRAM_MAX_CONTRIBS contributions."""
+    from .scatteringmodels import setup_from_model
+    return (algo.data is not None and setup_from_model(algo.model, algo.data).model_id != engine.MODEL_HOST
+            and algo.numContribs() <= engine.HISTOGRAM_MAX_CONTRIBS)
+
+
+def run_series(algo, datasets, keys=None, replays=None, overlap=False, batch=False, start=None, batch_histograms=None):
     """-> (results, series).  `results[i]` is `algo.result[0]` of data set i (None when nothing
     converged); `series[(param, lower, upper, yweight)]` is the list of `(key_i, moments.fields)`.
     `keys`: the series key value of each data set (default: its index).  `replays`: per data set, the uniform
@@ -19,7 +31,12 @@ def run_series(algo, datasets, keys=None, replays=None, overlap=False, batch=Fal
     `start`: the contributions the first attempt of every repetition starts from (McSAS.analyse: an [N][P][R] array; wavefront
     mode, or the q-split workgroup kernel beyond 1024 points: McSAS._check_start_mode) — one array for every data set, a list with one entry per data set (None: cold), or "previous": each data set starts from
     the previous stored result's contributions; the first one, and any after a data set that stored nothing, starts cold.
-    "previous" is sequential by nature: with `batch` or `overlap` it raises ValueError."""
+    "previous" is sequential by nature: with `batch` or `overlap` it raises ValueError.
+    `batch_histograms`: with `batch` or `overlap` the chains are done before the first result is stored; True then stores every data
+    set's result first and takes all their histograms in ONE library call (engine.histogram_device_batch — the arrays of each data
+    set's own McSAS.histogram() call, bit for bit), e.g. `run_series(algo, datasets, batch=True, batch_histograms=True)`; False calls
+    McSAS.histogram() per data set.  None: BATCH_HISTOGRAMS_DEFAULT.  A model that exists only as host code, more than
+    engine.HISTOGRAM_MAX_CONTRIBS contributions, and the sequential path (neither `batch` nor `overlap`) keep the call per data set."""
     if algo.model is None:
         raise ValueError("no model set")
     previous = isinstance(start, str)
@@ -59,10 +76,32 @@ def run_series(algo, datasets, keys=None, replays=None, overlap=False, batch=Fal
             algo.data = data
             problems.append(algo._problem(replay=None if replays is None else replays[i], start=starts[i]))
         chains = engine.analyse_many(problems)
+    if batch_histograms is None:
+        batch_histograms = BATCH_HISTOGRAMS_DEFAULT
+    stored = None
+    if chains is not None and batch_histograms and _histograms_batchable(algo, engine):
+        # the chains are done: store every data set's result, take all their histograms in ONE library call
+        # (engine.histogram_device_batch: each set's arrays are those of its own McSAS.histogram() call), then go on as below
+        stored, items = [], []
+        for i, data in enumerate(datasets):
+            algo.data = data
+            algo.result = []
+            algo._store(chains[i])
+            stored.append(algo.result)
+            if len(algo.result):
+                if all(algo.result[0]['contribs'].shape):    # (histogram() leaves an empty result alone)
+                    items.append((i, algo._histogram_item()))
+                if algo.stop:                                # (the loop below ends here)
+                    break
+        device = dict(zip([i for i, _ in items], engine.histogram_device_batch([it for _, it in items])))
     for i, data in enumerate(datasets):
         key = i if keys is None else keys[i]
         algo.data = data
-        if chains is None:
+        if stored is not None:
+            algo.result, algo.details = stored[i], chains[i]
+            if i in device:
+                algo._histogram_from_device(device[i])
+        elif chains is None:
             prev = results[-1]["contribs"] if previous and results and results[-1] is not None else None
             algo.calc(replay=None if replays is None else replays[i], start=prev if previous else starts[i])
         else:

@@ -11,7 +11,9 @@ Per shape, MC steps per second of
   analyse_batch  every chain of every data set in one wavefront-per-chain launch (wall, plans created and fetched included)
   batch_device   resident plans, engine.launch_batch, device time of the launch (HIP events)
   single_wave    the upper bound: one wave-mode plan with the same total chain count on ONE data set, device time
-Shape a also runs run_series(batch=True) end to end and reports the share of its wall time spent in McSAS.histogram().
+Shape a also runs run_series(batch=True) end to end, with the histograms per data set and in one batched pass (batch_histograms),
+and reports median and spread of the wall time, the share of it in the histograms and the split of that into the library call and
+the Python around it; one McSAS.histogram() at config 2's shape is timed the same way (--hist-only: these two alone).
 Every timed quantity is repeated until at least a second has been timed (after a warm-up run), and 16 chains of different data
 sets from the timed batch are checked against the plain-C oracle on the same Philox streams.
 
@@ -123,8 +125,38 @@ def run_shape(key, steps, check):
     return out, model, data
 
 
-def series_wall(model, data, steps):
-    """run_series(batch=True) end to end over shape a's data sets; share of the wall time in McSAS.histogram()."""
+def stats(xs):
+    """median and spread (largest minus smallest) of the repeats"""
+    xs = sorted(float(x) for x in xs)
+    return dict(median=xs[len(xs) // 2] if len(xs) % 2 else 0.5 * (xs[len(xs) // 2 - 1] + xs[len(xs) // 2]), spread=xs[-1] - xs[0], n=len(xs))
+
+
+class Stopwatch:
+    """Adds up the time spent inside the callables it wraps (one wrapped callable inside another counts once)."""
+
+    def __init__(self):
+        self.s, self.depth = 0.0, 0
+
+    def wrap(self, fn):
+        def timed(*a, **k):
+            t0 = time.perf_counter()
+            self.depth += 1
+            try:
+                return fn(*a, **k)
+            finally:
+                self.depth -= 1
+                if self.depth == 0:
+                    self.s += time.perf_counter() - t0
+        return timed
+
+
+def series_wall(model, data, steps, repeats=7):
+    """run_series(batch=True) end to end over shape a's data sets, `repeats` times after a warm-up run, in this process: wall time,
+    the time in McSAS.histogram() (the call per data set) or in engine.histogram_device_batch (the batched pass), and how much of
+    either is spent inside the library call — the rest is the Python around it: setup_from_model, the histogram records,
+    Histogram.setFromDevice and its Moments.  One entry per value of batch_histograms the installed run_series knows."""
+    import inspect
+    from mcsas_amd import _lib, series
     q = data[0][0]
     model.radius.histograms().append(mcsas_amd.Histogram(model.radius, np.pi / q.max(), np.pi / q.min(), binCount=50, xscale='log',
                                                          yweight='vol'))
@@ -133,23 +165,64 @@ def series_wall(model, data, steps):
     algo.numContribs.setValue(SHAPES["a"]["n"]); algo.numReps.setValue(SHAPES["a"]["reps"]); algo.maxIterations.setValue(steps)
     algo.convergenceCriterion.setValue(0.0); algo.maxRetries.setValue(0); algo.showIncomplete.setValue(True)
     algo.model = model
-    spent = [0.0]
-    hist = algo.histogram
+    lib = _lib.load()
+    in_hist, in_lib, in_apply = Stopwatch(), Stopwatch(), Stopwatch()
+    algo.histogram = in_hist.wrap(algo.histogram)
+    lib.mcsas_hip_histogram = in_lib.wrap(lib.mcsas_hip_histogram)
+    modes = {"per_data_set": {}}
+    if "batch_histograms" in inspect.signature(mcsas_amd.run_series).parameters:
+        modes = {"per_data_set": dict(batch_histograms=False), "batched": dict(batch_histograms=True)}
+        lib.mcsas_hip_histogram_batch = in_lib.wrap(lib.mcsas_hip_histogram_batch)
+        engine.histogram_device_batch = in_hist.wrap(engine.histogram_device_batch)
+        algo._histogram_item = in_hist.wrap(algo._histogram_item)
+        algo._histogram_from_device = in_apply.wrap(algo._histogram_from_device)
+    out = dict(data_sets=len(datasets), repeats=repeats)
+    for name, kw in modes.items():
+        mcsas_amd.run_series(algo, datasets, batch=True, **kw)             # (warm-up)
+        wall, hist, libs = [], [], []
+        for _ in range(repeats):
+            in_hist.s = in_lib.s = in_apply.s = 0.0
+            t0 = time.perf_counter()
+            results, _series = mcsas_amd.run_series(algo, datasets, batch=True, **kw)
+            wall.append(time.perf_counter() - t0)
+            # (the per-data-set loop applies the results inside histogram(); the batched pass applies them in the loop after it)
+            hist.append(in_hist.s + (in_apply.s if name == "batched" else 0.0)); libs.append(in_lib.s)
+            assert all(r is not None for r in results)
+        out[name] = dict(wall_s=stats(wall), histogram_s=stats(hist), library_s=stats(libs), python_s=stats([h - l for h, l in zip(hist, libs)]),
+                         histogram_share=stats([h / w for h, w in zip(hist, wall)]),
+                         library_share_of_histogram=stats([l / h for h, l in zip(hist, libs)]))
+    if "batched" in out:
+        gain = out["per_data_set"]["wall_s"]["median"] - out["batched"]["wall_s"]["median"]
+        out["gain_s"] = gain
+        out["batched_is_faster_beyond_spread"] = bool(gain > max(out["per_data_set"]["wall_s"]["spread"], out["batched"]["wall_s"]["spread"]))
+        out["default_batch_histograms"] = bool(series.BATCH_HISTOGRAMS_DEFAULT)
+    return out
 
-    def timed_hist(*a, **k):
+
+def single_histogram(repeats=9):
+    """One McSAS.histogram() at config 2's shape (50 repetitions x 400 contributions x 512 q, one 50-bin histogram), seeded
+    contributions: seconds per call of the whole method and of the library call in it."""
+    from bench import synthetic_data
+    from mcsas_amd import _lib
+    q, I, sig = synthetic_data(512)
+    lo, hi = np.pi / q.max(), np.pi / q.min()
+    model = mcsas_amd.Sphere(); model.radius.setActiveRange((lo, hi))
+    model.radius.histograms().append(mcsas_amd.Histogram(model.radius, lo, hi, binCount=50, xscale='log', yweight='vol'))
+    algo = mcsas_amd.McSAS(seed=5)
+    algo.model = model
+    algo.data = mcsas_amd.SASData(q, I, sig)
+    algo.result = [dict(contribs=np.exp(np.random.RandomState(5).uniform(np.log(lo), np.log(hi), (400, 1, 50))))]
+    lib = _lib.load()
+    in_lib = Stopwatch()
+    lib.mcsas_hip_histogram = in_lib.wrap(lib.mcsas_hip_histogram)
+    algo.histogram()                                                      # (warm-up)
+    wall, libs = [], []
+    for _ in range(repeats):
+        in_lib.s = 0.0
         t0 = time.perf_counter()
-        try:
-            return hist(*a, **k)
-        finally:
-            spent[0] += time.perf_counter() - t0
-    algo.histogram = timed_hist
-    mcsas_amd.run_series(algo, datasets, batch=True)                 # (warm-up)
-    spent[0] = 0.0
-    t0 = time.perf_counter()
-    results, _ = mcsas_amd.run_series(algo, datasets, batch=True)
-    wall = time.perf_counter() - t0
-    assert all(r is not None for r in results)
-    return dict(data_sets=len(datasets), wall_s=wall, histogram_s=spent[0], histogram_share=spent[0] / wall)
+        algo.histogram()
+        wall.append(time.perf_counter() - t0); libs.append(in_lib.s)
+    return dict(shape="512 q x 400 contributions x 50 reps, one 50-bin histogram", histogram_s=stats(wall), library_s=stats(libs))
 
 
 def main():
@@ -157,13 +230,22 @@ def main():
     ap.add_argument("--steps", type=int, default=20000)
     ap.add_argument("--shapes", default="a,b")
     ap.add_argument("--no-check", action="store_true")
+    ap.add_argument("--hist-only", action="store_true", help="only the histogram measurements: run_series over shape a and the single call at config 2's shape")
     args = ap.parse_args()
     line = dict(metric="series_batch", steps=args.steps, shapes={})
+    if args.hist_only:
+        q = dataset(SHAPES["a"]["nq"], 0)[0]
+        model = mcsas_amd.Sphere(); model.radius.setActiveRange((np.pi / q.max(), np.pi / q.min()))
+        line["single_histogram_config2"] = single_histogram()
+        line["run_series_batch"] = series_wall(model, [dataset(SHAPES["a"]["nq"], d) for d in range(SHAPES["a"]["sets"])], args.steps)
+        print(json.dumps(line))
+        return
     for key in args.shapes.split(","):
         res, model, data = run_shape(key, args.steps, not args.no_check)
         line["shapes"][key] = res
         if key == "a":
             line["run_series_batch"] = series_wall(model, data, args.steps)
+    line["single_histogram_config2"] = single_histogram()
     print(json.dumps(line))
 
 
