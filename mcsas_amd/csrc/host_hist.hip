@@ -1,0 +1,612 @@
+// host_hist.hip — McSAS.histogram() on the device: the hist_* kernels, their batch forms and the entry points mcsas_hip_histogram_prep,
+// mcsas_hip_histogram and mcsas_hip_histogram_batch.  What makes a set acceptable (check_hist_set), how a set lies in the staging
+// blocks (HistSizes, pack_hist_set, unpack_hist_set) and how many repetitions share a block of rows (hist_rep_chunk) are each said
+// once here, for the single call and the batch alike.  Nothing here knows about plans.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "host_internal.h"
+#include "small_kernels.h"   // hist_rows_kernel, hist_rows_batch_kernel, HistSetDev
+#include "model_list.h"      // MCSAS_FOR_MODELS: the built-in models
+
+using namespace mcsas;
+
+// ------------------------------------------------------------------------------ kernels
+// The arithmetic of each kernel is a device function of one (data set, repetition): the single call's kernel hands it its own
+// arguments, the batch kernel (further down) what its set's record says.
+
+// min over q of sigma*vf / (A*I_c(q)), I_c != 0 (mcsas.py:582-590) from the stored row of contribution c of repetition r
+__device__ __forceinline__ void hist_obs_body(int nq, const double *sigma, int R, int c, int r, const double *row, const double *scaling,
+                                              const double *vset, const double *wset, double *min_req) {
+    const double A = scaling[r];
+    const double vf = wset[(size_t)c * R + r] * A / vset[(size_t)c * R + r];      // modeldata.py:57-61
+    double best = INFINITY;
+    for (int k = threadIdx.x; k < nq; k += WAVE) {
+        const double scaled = A * row[k];
+        if (scaled != 0.) best = fmin(best, (sigma[k] * vf) / scaled);
+    }
+    best = wave_min(best);
+    if (threadIdx.x == 0) min_req[(size_t)c * R + r] = best;
+}
+__global__ __launch_bounds__(64) void hist_obs_kernel(int nq, const double *sigma, int N, int R, int r0, const double *rows,
+                                                      const double *scaling, const double *vset, const double *wset, double *min_req) {
+    const int c = blockIdx.x, rl = blockIdx.y, r = r0 + rl;
+    hist_obs_body(nq, sigma, R, c, r, rows + ((size_t)rl * N + c) * nq, scaling, vset, wset, min_req);
+}
+
+// cum[k] = sum_n rows[n][k] of one repetition in contribution order (scatteringmodel.py:101): one thread per q, loads in batches of 8
+__device__ __forceinline__ void hist_colsum_body(int nq, int N, int k, const double *rows, double *cum) {
+    if (k >= nq) return;
+    const double *base = rows + k;
+    double s = 0.;
+    int n = 0;
+    for (; n + 8 <= N; n += 8) {
+        double v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = base[(size_t)(n + i) * nq];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s += v[i];
+    }
+    for (; n < N; ++n) s += base[(size_t)n * nq];
+    cum[k] = s;
+}
+__global__ void hist_colsum_kernel(int nq, int N, const double *rows, double *cum) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x, rl = blockIdx.y;
+    hist_colsum_body(nq, N, k, rows + (size_t)rl * N * nq, cum + (size_t)rl * nq);
+}
+// the closed-form scale / background fit (mcsas.py:559) of repetition r against its summed intensity `cum`: one wave
+__device__ __forceinline__ void hist_fit_cum_body(int nq, const double *I, const double *sigma, int R, int r, const double *cum,
+                                                  int find_bg, int pos_bg, double *scaling) {
+    const int lane = threadIdx.x;
+    double sw = 0, si = 0, sii = 0, sc = 0, scc = 0, sic = 0;
+    for (int k = lane; k < nq; k += WAVE) {
+        const double C = cum[k];
+        const double e = sigma[k] == 0.0 ? 1.0 : sigma[k];
+        const double w = 1.0 / (e * e);
+        sw += w; si += w * I[k]; sii += w * I[k] * I[k];
+        sc += w * C; scc += w * C * C; sic += w * I[k] * C;
+    }
+    wave_sum3(sw, si, sii); wave_sum3(sc, scc, sic);
+    ChainArgs a{};
+    a.Sw = sw; a.SI = si; a.SII = sii; a.nq = nq; a.find_bg = find_bg; a.pos_bg = pos_bg;
+    const FitResult f = solve_fit(a, sc, scc, sic);
+    if (lane == 0) { scaling[r] = f.A; scaling[R + r] = f.b; }
+}
+__global__ __launch_bounds__(64) void hist_fit_cum_kernel(int nq, const double *I, const double *sigma, int R, int r0, const double *cum,
+                                                          int find_bg, int pos_bg, double *scaling) {
+    const int rl = blockIdx.x;
+    hist_fit_cum_body(nq, I, sigma, R, r0 + rl, cum + (size_t)rl * nq, find_bg, pos_bg, scaling);
+}
+// fractions and their visibility limits, normalised per repetition (mcsas.py:561-604): frac8 = [vf nf qf sf | mv mn mq ms][N][R].
+// One wave per rep; the three totals are taken by one lane each, over the contributions in order (builtin sum()).
+__device__ __forceinline__ void hist_fractions_body(int N, int R, int r, const double *scaling, const double *vset, const double *wset,
+                                                    const double *sset, const double *mv, double *frac8) {
+    __shared__ double tot[3];
+    const int lane = threadIdx.x;
+    const size_t NR = (size_t)N * R;
+    const double A = scaling[r];
+    double *vf = frac8, *nf = frac8 + NR, *qf = frac8 + 2 * NR, *sf = frac8 + 3 * NR;
+    double *omv = frac8 + 4 * NR, *mn = frac8 + 5 * NR, *mq = frac8 + 6 * NR, *ms = frac8 + 7 * NR;
+    for (int c = lane; c < N; c += WAVE) {
+        const size_t i = (size_t)c * R + r;
+        const double v = vset[i], w = wset[i], s = sset[i], m = mv[i];
+        const double vfc = w * A / v;                          // modeldata.py:57-61
+        const double nfc = vfc / v, mnc = m / v;               // mcsas.py:567-571, :591-594
+        vf[i] = vfc; nf[i] = nfc; qf[i] = vfc * v; sf[i] = nfc * s;
+        omv[i] = m; mn[i] = mnc; mq[i] = mnc * m * m; ms[i] = mnc * s;
+    }
+    __syncthreads();
+    if (lane < 3) {
+        const double *src = lane == 0 ? nf : (lane == 1 ? qf : sf);
+        double t = 0.;
+        for (int c = 0; c < N; ++c) t += src[(size_t)c * R + r];
+        tot[lane] = t;
+    }
+    __syncthreads();
+    const double tn = tot[0], tq = tot[1], ts = tot[2];
+    for (int c = lane; c < N; c += WAVE) {
+        const size_t i = (size_t)c * R + r;
+        if (tn != 0.) { nf[i] /= tn; mn[i] /= tn; }           // :596-604
+        if (tq != 0.) { qf[i] /= tq; mq[i] /= tq; }
+        if (ts != 0.) { sf[i] /= ts; ms[i] /= ts; }
+    }
+}
+__global__ __launch_bounds__(64) void hist_fractions_kernel(int N, int R, const double *scaling, const double *vset, const double *wset,
+                                                            const double *sset, const double *mv, double *frac8) {
+    hist_fractions_body(N, R, blockIdx.x, scaling, vset, wset, sset, mv, frac8);
+}
+struct HistSpecDev { int32_t pidx, weight, nb, pad; int64_t edge_off, out_off; double lo, hi; };
+// One wave per (histogram, repetition).  The repetition's parameter values, fractions and limits are staged in LDS (hl: 3 N doubles);
+// lane b owns bin b (64 bins per pass) and walks the contributions in order; the cumulative distribution and the moments are
+// sequential sums again, taken by one lane (two for skew and kurtosis).  utils/parameter.py:84-122, :441-479.
+__device__ __forceinline__ void hist_bins_body(int N, int P, int R, int r, const HistSpecDev s, const double *contribs, const double *frac8,
+                                               const double *edges_all, double *out, double *hl) {
+    __shared__ double mom[8];
+    const int lane = threadIdx.x, nb = s.nb;
+    const size_t NR = (size_t)N * R;
+    const double *fr = frac8 + (size_t)s.weight * NR, *lim = frac8 + (size_t)(4 + s.weight) * NR;
+    const double *edges = edges_all + s.edge_off;
+    double *bins = out + s.out_off, *obs = bins + (size_t)nb * R, *cdf = obs + (size_t)nb * R, *mo = cdf + (size_t)nb * R;
+    double *lx = hl, *lf = hl + N, *ll = hl + 2 * (size_t)N;
+    for (int c = lane; c < N; c += WAVE) {
+        lx[c] = contribs[((size_t)c * P + s.pidx) * R + r];
+        lf[c] = fr[(size_t)c * R + r]; ll[c] = lim[(size_t)c * R + r];
+    }
+    __syncthreads();
+    const double last = nb > 0 ? edges[nb] : 0.;
+    for (int b0 = 0; b0 < nb; b0 += WAVE) {
+        const int b = b0 + lane;
+        if (b < nb) {
+            const double elo = edges[b], ehi = edges[b + 1];
+            double sb = 0., so = 0., cnt = 0.;
+            for (int c = 0; c < N; ++c) {
+                const double x = lx[c];
+                if (x >= elo && x < ehi && x < last) { sb += lf[c]; so += ll[c]; cnt += 1.; }
+            }
+            bins[(size_t)b * R + r] = (sb != sb) ? 0. : sb;    // bins[isnan(bins)] = 0
+            obs[(size_t)b * R + r] = cnt > 0. ? so / cnt : 0.;
+        }
+    }
+    __syncthreads();
+    if (lane == 0) {
+        double run = 0., top = -__builtin_inf();
+        for (int b = 0; b < nb; ++b) { run += bins[(size_t)b * R + r]; cdf[(size_t)b * R + r] = run; top = fmax(top, run); }
+        for (int b = 0; b < nb; ++b) cdf[(size_t)b * R + r] = (top == 0.) ? 0. : cdf[(size_t)b * R + r] / top;
+    }
+    // moments: total, mean, variance by lane 32 (runs beside lane 0's distribution), then skew / kurtosis by lanes 32 / 33
+    if (lane == 32) {
+        double tot = 0., m1 = 0.;
+        int any = 0;
+        for (int c = 0; c < N; ++c) { const double x = lx[c]; const bool ok = x > s.lo && x < s.hi; any |= ok; tot += ok ? lf[c] : 0.; }
+        for (int c = 0; c < N; ++c) { const double x = lx[c]; const bool ok = x > s.lo && x < s.hi; m1 += ok ? x * lf[c] : 0.; }
+        if (tot != 0.) m1 /= tot;
+        double v2 = 0.;
+        for (int c = 0; c < N; ++c) { const double x = lx[c], d = x - m1; const bool ok = x > s.lo && x < s.hi; v2 += ok ? (d * d) * lf[c] : 0.; }
+        const double var = v2 / tot, sg = sqrt(fabs(var));
+        mom[0] = tot; mom[1] = m1; mom[2] = var; mom[3] = sg; mom[4] = (double)any;
+    }
+    __syncthreads();
+    if (lane == 32 || lane == 33) {
+        const double tot = mom[0], m1 = mom[1], sg = mom[3];
+        const bool any = mom[4] != 0., ok3 = any && (tot * sg) != 0.;      // (utils/parameter.py:106-107: only an exact zero is skipped; NaN goes on)
+        const double sg2 = sg * sg;
+        double acc = 0.;
+        for (int c = 0; c < N; ++c) {
+            const double x = lx[c], d = x - m1, d2 = d * d;
+            const bool ok = x > s.lo && x < s.hi;
+            acc += ok ? (lane == 32 ? d2 * d : d2 * d2) * lf[c] : 0.;
+        }
+        const double val = ok3 ? acc / (tot * (lane == 32 ? sg2 * sg : sg2 * sg2)) : 0.;
+        mo[(size_t)(3 + (lane - 32)) * R + r] = val;
+        if (lane == 32) { mo[r] = any ? tot : 0.; mo[(size_t)R + r] = any ? m1 : 0.; mo[(size_t)2 * R + r] = any ? mom[2] : 0.; }
+    }
+}
+__global__ __launch_bounds__(64) void hist_bins_kernel(int N, int P, int R, const double *contribs, const double *frac8, const double *edges_all,
+                                                       const HistSpecDev *specs, double *out) {
+    extern __shared__ double hl[];
+    hist_bins_body(N, P, R, blockIdx.y, specs[blockIdx.x], contribs, frac8, edges_all, out, hl);
+}
+
+// ---- the same for a batch of data sets (mcsas_hip_histogram_batch): one launch each over the (set, repetition) blocks of a chunk.
+// A set's record (HistSetDev, small_kernels.h) says where its arrays lie in the packed upload `in`, the packed download `back` and
+// the scratch blocks; blockIdx.x picks the (set, repetition), blockIdx.y runs to the chunk's largest extent (contributions, q blocks,
+// histograms): a block beyond its own set's returns on its index alone, ahead of any barrier.
+struct HistSetView {
+    const HistSetDev &s;
+    const int r;
+    const size_t NR;
+    __device__ HistSetView(const HistSetDev *sets, const ChainRef *blocks)
+        : s(sets[__builtin_amdgcn_readfirstlane(blocks[blockIdx.x].set)]), r(__builtin_amdgcn_readfirstlane(blocks[blockIdx.x].rep)),
+          NR((size_t)s.N * s.R) {}
+    __device__ double *scaling(double *back) const { return back + s.back_off; }
+    __device__ double *frac8(double *back) const { return back + s.back_off + 2 * (size_t)s.R; }
+    __device__ double *out(double *back) const { return back + s.back_off + 2 * (size_t)s.R + 8 * NR; }
+};
+__global__ void hist_colsum_batch_kernel(const HistSetDev *__restrict__ sets, const ChainRef *__restrict__ blocks, const double *rows, double *cum) {
+    const HistSetView v(sets, blocks);
+    const HistSetDev &s = v.s;
+    if ((int)(blockIdx.y * blockDim.x) >= s.nq) return;
+    hist_colsum_body(s.nq, s.N, blockIdx.y * blockDim.x + threadIdx.x, rows + s.rows_off + (size_t)v.r * s.N * s.nq, cum + s.cum_off + (size_t)v.r * s.nq);
+}
+__global__ __launch_bounds__(64) void hist_fit_cum_batch_kernel(const HistSetDev *__restrict__ sets, const ChainRef *__restrict__ blocks,
+                                                                const double *__restrict__ in, const double *cum, double *back) {
+    const HistSetView v(sets, blocks);
+    const HistSetDev &s = v.s;
+    hist_fit_cum_body(s.nq, in + s.I_off, in + s.sg_off, s.R, v.r, cum + s.cum_off + (size_t)v.r * s.nq, s.find_bg, s.pos_bg, v.scaling(back));
+}
+__global__ __launch_bounds__(64) void hist_obs_batch_kernel(const HistSetDev *__restrict__ sets, const ChainRef *__restrict__ blocks,
+                                                            const double *__restrict__ in, const double *rows, const double *back, double *vws) {
+    const HistSetView v(sets, blocks);
+    const HistSetDev &s = v.s;
+    const int c = blockIdx.y;
+    if (c >= s.N) return;
+    double *w = vws + s.vws_off;
+    hist_obs_body(s.nq, in + s.sg_off, s.R, c, v.r, rows + s.rows_off + ((size_t)v.r * s.N + c) * s.nq, back + s.back_off, w, w + v.NR, w + 3 * v.NR);
+}
+__global__ __launch_bounds__(64) void hist_fractions_batch_kernel(const HistSetDev *__restrict__ sets, const ChainRef *__restrict__ blocks,
+                                                                  const double *vws, double *back) {
+    const HistSetView v(sets, blocks);
+    const HistSetDev &s = v.s;
+    const double *w = vws + s.vws_off;
+    hist_fractions_body(s.N, s.R, v.r, v.scaling(back), w, w + v.NR, w + 2 * v.NR, w + 3 * v.NR, v.frac8(back));
+}
+// histograms [h0, h0 + gridDim.y) of every set that has that many
+__global__ __launch_bounds__(64) void hist_bins_batch_kernel(const HistSetDev *__restrict__ sets, const ChainRef *__restrict__ blocks, int h0,
+                                                             const double *__restrict__ in, double *back) {
+    extern __shared__ double hl[];
+    const HistSetView v(sets, blocks);
+    const HistSetDev &s = v.s;
+    const int h = h0 + blockIdx.y;
+    if (h >= s.n_hist) return;
+    const HistSpecDev *specs = reinterpret_cast<const HistSpecDev *>(in + s.spec_off);
+    hist_bins_body(s.N, s.P, s.R, v.r, specs[h], in + s.c_off, v.frac8(back), in + s.edge_off, v.out(back), hl);
+}
+
+// ------------------------------------------------------------------------------ one set: what is acceptable, and where it lies
+// The staging blocks of a set, in doubles.  Going in: [q | I | sigma | contribs | edges | specs] — the edges of its histograms one after
+// the other, then their HistSpecDev records, whose edge_off / out_off count from the set's own edges and outputs.  Coming back:
+// [scaling 2R | fractions 8NR | out].  The *_off are the places of the parts in their block; the device reads the coming-back ones
+// through HistSetView.
+struct HistSizes {
+    size_t n_edges = 0, n_out = 0;                             // edges and output doubles of all the set's histograms
+    size_t I_off = 0, sg_off = 0, c_off = 0, edge_off = 0, spec_off = 0, n_in = 0, frac_off = 0, out_off = 0, n_back = 0;
+    size_t rows = 0;                                           // the rows of all repetitions: N R Q
+};
+// a histogram's outputs: bins, observability and cumulative distribution [n_bin][R] each, then the moments [5][R] (hist_bins_body)
+static size_t hist_out_doubles(int n_bin, size_t R) { return (size_t)3 * n_bin * R + 5 * R; }
+
+// Every check of a set that needs no device; fills the model arguments and the sizes.
+static int check_hist_set(const mcsas_problem *p, const double *contribs, int n_hist, const mcsas_histogram_spec *specs, double *scaling, double *out,
+                          ModelArgs *m, HistSizes *sz) {
+    if (!p || !contribs || !scaling || !p->q || !p->intensity || !p->sigma || p->nq < 1 || p->n_contrib < 1 || p->n_reps < 1 || n_hist < 0 ||
+        (n_hist > 0 && (!specs || !out)))
+        return fail(MCSAS_EINVAL, "bad argument");
+    if (p->n_contrib > 4096) return fail(MCSAS_EINVAL, "mcsas_hip_histogram stages a repetition's contributions in LDS: n_contrib %d > 4096 (use mcsas_hip_histogram_prep)", p->n_contrib);
+    if (int rc = fill_model_args(p, m)) return rc;
+    if (int rc = SmearDev::check(p)) return rc;
+    const size_t Q = p->nq, P = p->n_active, N = p->n_contrib, R = p->n_reps;
+    *sz = HistSizes{};
+    for (int h = 0; h < n_hist; ++h) {
+        const mcsas_histogram_spec &sp = specs[h];
+        if (sp.n_bin < 0 || sp.n_bin > (1 << 20) || sp.param_index < 0 || sp.param_index >= (int)std::max<size_t>(P, 1) || sp.weighting < 0 || sp.weighting > 3 ||
+            (sp.n_bin > 0 && !sp.edges) || P == 0)
+            return fail(MCSAS_EINVAL, "histogram %d: param_index %d, weighting %d, n_bin %d", h, sp.param_index, sp.weighting, sp.n_bin);
+        sz->n_edges += (size_t)sp.n_bin + 1;
+        sz->n_out += hist_out_doubles(sp.n_bin, R);
+    }
+    sz->I_off = Q; sz->sg_off = 2 * Q; sz->c_off = 3 * Q; sz->edge_off = sz->c_off + N * P * R; sz->spec_off = sz->edge_off + sz->n_edges;
+    sz->n_in = sz->spec_off + (sizeof(HistSpecDev) * (size_t)n_hist + 7) / 8;
+    sz->frac_off = 2 * R; sz->out_off = sz->frac_off + 8 * N * R; sz->n_back = sz->out_off + sz->n_out; sz->rows = N * R * Q;
+    return MCSAS_OK;
+}
+
+// a checked set's going-in block
+static void pack_hist_set(double *dst, const mcsas_problem *p, const double *contribs, int n_hist, const mcsas_histogram_spec *specs, const HistSizes &sz) {
+    const size_t Q = p->nq, R = p->n_reps;
+    memcpy(dst, p->q, sizeof(double) * Q);
+    memcpy(dst + sz.I_off, p->intensity, sizeof(double) * Q);
+    memcpy(dst + sz.sg_off, p->sigma, sizeof(double) * Q);
+    memcpy(dst + sz.c_off, contribs, sizeof(double) * (sz.edge_off - sz.c_off));
+    HistSpecDev *hs = reinterpret_cast<HistSpecDev *>(dst + sz.spec_off);
+    size_t e_off = 0, o_off = 0;
+    for (int h = 0; h < n_hist; ++h) {
+        const mcsas_histogram_spec &sp = specs[h];
+        memcpy(dst + sz.edge_off + e_off, sp.edges, sizeof(double) * ((size_t)sp.n_bin + 1));
+        hs[h] = HistSpecDev{sp.param_index, sp.weighting, sp.n_bin, 0, (int64_t)e_off, (int64_t)o_off, sp.lower, sp.upper};
+        e_off += (size_t)sp.n_bin + 1; o_off += hist_out_doubles(sp.n_bin, R);
+    }
+}
+
+// a set's results out of its coming-back block (fractions may be NULL)
+static void unpack_hist_set(const double *src, const HistSizes &sz, double *scaling, double *fractions, double *out) {
+    memcpy(scaling, src, sizeof(double) * sz.frac_off);
+    if (fractions) memcpy(fractions, src + sz.frac_off, sizeof(double) * (sz.out_off - sz.frac_off));
+    if (sz.n_out) memcpy(out, src + sz.out_off, sizeof(double) * sz.n_out);
+}
+
+// a pinned staging block from the process-level cache
+struct Pinned {
+    double *p = nullptr; size_t bytes = 0;
+    ~Pinned() { cached_host_free(p, bytes, hipHostMallocDefault); }
+    hipError_t alloc(size_t n) { bytes = sizeof(double) * n; return cached_host_malloc((void **)&p, bytes, hipHostMallocDefault); }
+};
+// Every early return after the first asynchronous copy leaves copies / kernels queued on the null stream: this guard, declared after
+// the staging blocks and so destroyed before them, waits for what is queued before they go back to the cache, where the next call
+// would overwrite them under the DMA.
+struct SyncGuard { bool armed = true; ~SyncGuard() { if (armed) (void)hipStreamSynchronize(nullptr); } };
+
+// The rows of a block of repetitions stay in HBM between the kernels: how many repetitions share a block of at most ~8 GB.
+static size_t hist_rep_chunk(size_t N, size_t Q, size_t R) { return std::max<size_t>(1, std::min<size_t>(R, ((size_t)8 << 30) / (N * Q * sizeof(double)))); }
+
+// ------------------------------------------------------------------------------ one set: mcsas_hip_histogram_prep, mcsas_hip_histogram
+// hist_rows_kernel of the problem's model for repetitions [r0, r0 + grid.y) on the null stream
+static int launch_hist_rows(const mcsas_problem *p, const ModelArgs &m, dim3 grid, size_t lds, const double *dq, int N, int R, int r0,
+                            const double *dc, double *drows, double *dv, double *dw, double *ds) {
+    switch (p->model_id) {
+#define CASE_K(mm) case mm: hist_rows_kernel<mm><<<grid, WAVE, lds>>>(m, p->nq, dq, N, R, r0, dc, drows, dv, dw, ds); break;
+        MCSAS_FOR_MODELS(CASE_K)
+#undef CASE_K
+        default:
+            if (!is_plugin_model(p->model_id)) return fail(MCSAS_EINVAL, "model %d", p->model_id);
+            if (int rc = plugin_small_launch(p->model_id, PLUGIN_HIST_ROWS, grid, lds, m, (int)p->nq, dq, N, R, r0, dc, drows, dv, dw, ds)) return rc;
+    }
+    HIPCHK(hipGetLastError());
+    return MCSAS_OK;
+}
+// The first half of histogram() for all repetitions, a chunk of them at a time: per repetition the rows with their volumes, weights
+// and surfaces, cumInt = the sum of the rows in contribution order (scatteringmodel.py:101), the closed-form scale / background fit
+// (mcsas.py:559) and the visibility limits.  drows holds chunk * N * Q doubles, dcum chunk * Q; dsc is [2][R], the others [N][R].
+static int launch_hist_reps(const mcsas_problem *p, const ModelArgs &m, size_t chunk, const double *dq, const double *dI, const double *dsg,
+                            const double *dc, double *drows, double *dcum, double *dsc, double *dv, double *dw, double *ds, double *dm) {
+    const size_t Q = p->nq, N = p->n_contrib, R = p->n_reps;
+    const size_t lds = sizeof(double) * table_doubles_host(p->model_id, m.int_div);
+    for (size_t r0 = 0; r0 < R; r0 += chunk) {
+        const unsigned nr = (unsigned)std::min(chunk, R - r0);
+        const dim3 grid((unsigned)N, nr);
+        if (int rc = launch_hist_rows(p, m, grid, lds, dq, (int)N, (int)R, (int)r0, dc, drows, dv, dw, ds)) return rc;
+        hist_colsum_kernel<<<dim3((unsigned)((Q + 255) / 256), nr), 256>>>(p->nq, (int)N, drows, dcum);
+        HIPCHK(hipGetLastError());
+        hist_fit_cum_kernel<<<nr, WAVE>>>(p->nq, dI, dsg, (int)R, (int)r0, dcum, p->find_background != 0, p->positive_background != 0, dsc);
+        HIPCHK(hipGetLastError());
+        hist_obs_kernel<<<grid, WAVE>>>(p->nq, dsg, (int)N, (int)R, (int)r0, drows, dsc, dv, dw, dm);
+        HIPCHK(hipGetLastError());
+    }
+    return MCSAS_OK;
+}
+
+extern "C" int mcsas_hip_histogram_prep(const mcsas_problem *p, const double *contribs, double *scaling, double *vset,
+                                        double *wset, double *sset, double *min_req_vol) {
+    if (!p || !contribs || !scaling || !vset || !wset || !sset || !min_req_vol || !p->q || !p->intensity || !p->sigma ||
+        p->nq < 1 || p->n_contrib < 1 || p->n_reps < 1)
+        return fail(MCSAS_EINVAL, "bad argument");
+    ModelArgs m;
+    if (int rc = fill_model_args(p, &m)) return rc;
+    DeviceGuard dev_guard;
+    if (int rc = select_device(p->device)) return rc;
+    const size_t Q = p->nq, P = p->n_active, N = p->n_contrib, R = p->n_reps;
+    const size_t chunk = hist_rep_chunk(N, Q, R);
+    DevBuf<double> dq, dI, dsg, dc, drows, dcum, dsc, dv, dw, ds, dm;
+    HIPCHK(dq.alloc(Q)); HIPCHK(dI.alloc(Q)); HIPCHK(dsg.alloc(Q)); HIPCHK(dc.alloc(N * P * R)); HIPCHK(drows.alloc(chunk * N * Q));
+    HIPCHK(dcum.alloc(chunk * Q)); HIPCHK(dsc.alloc(2 * R)); HIPCHK(dv.alloc(N * R)); HIPCHK(dw.alloc(N * R)); HIPCHK(ds.alloc(N * R)); HIPCHK(dm.alloc(N * R));
+    HIPCHK(hipMemcpy(dq.p, p->q, sizeof(double) * Q, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dI.p, p->intensity, sizeof(double) * Q, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dsg.p, p->sigma, sizeof(double) * Q, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dc.p, contribs, sizeof(double) * N * P * R, hipMemcpyHostToDevice));
+    SmearDev smear;
+    if (int rc = smear.upload(p, p->nq, &m)) return rc;
+    if (int rc = launch_hist_reps(p, m, chunk, dq.p, dI.p, dsg.p, dc.p, drows.p, dcum.p, dsc.p, dv.p, dw.p, ds.p, dm.p)) return rc;
+    HIPCHK(hipMemcpy(scaling, dsc.p, sizeof(double) * 2 * R, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(vset, dv.p, sizeof(double) * N * R, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(wset, dw.p, sizeof(double) * N * R, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sset, ds.p, sizeof(double) * N * R, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(min_req_vol, dm.p, sizeof(double) * N * R, hipMemcpyDeviceToHost));
+    return MCSAS_OK;
+}
+
+// McSAS.histogram() complete (include/mcsas_hip.h): ONE packed upload (data vectors, parameter sets, bin edges, histogram records) from
+// a pinned staging block, the kernels back to back on the null stream, ONE packed download — a call costs two transfers and no
+// allocation once its block sizes have been seen (MemCache).  Every refusal of the set itself comes before a device is touched.
+extern "C" int mcsas_hip_histogram(const mcsas_problem *p, const double *contribs, int32_t n_hist, const mcsas_histogram_spec *specs,
+                                   double *scaling, double *fractions, double *out) {
+    ModelArgs m; HistSizes sz;
+    if (int rc = check_hist_set(p, contribs, n_hist, specs, scaling, out, &m, &sz)) return rc;
+    DeviceGuard dev_guard;
+    if (int rc = select_device(p->device)) return rc;
+    const size_t Q = p->nq, P = p->n_active, N = p->n_contrib, R = p->n_reps, NR = N * R;
+    const size_t chunk = hist_rep_chunk(N, Q, R);
+    DevBuf<double> din, dback, drows, dcum, dvws;
+    HIPCHK(din.alloc(sz.n_in)); HIPCHK(dback.alloc(sz.n_back)); HIPCHK(drows.alloc(chunk * N * Q)); HIPCHK(dcum.alloc(chunk * Q)); HIPCHK(dvws.alloc(4 * NR));
+    Pinned hin, hback;
+    HIPCHK(hin.alloc(sz.n_in)); HIPCHK(hback.alloc(sz.n_back));
+    SyncGuard sync_guard;
+    pack_hist_set(hin.p, p, contribs, n_hist, specs, sz);
+    HIPCHK(hipMemcpyAsync(din.p, hin.p, hin.bytes, hipMemcpyHostToDevice, nullptr));
+    const double *dq = din.p, *dI = din.p + sz.I_off, *dsg = din.p + sz.sg_off, *dc = din.p + sz.c_off, *dedges = din.p + sz.edge_off;
+    const HistSpecDev *dspecs = reinterpret_cast<const HistSpecDev *>(din.p + sz.spec_off);
+    double *dsc = dback.p, *dfrac = dback.p + sz.frac_off, *dout = dback.p + sz.out_off;
+    double *dv = dvws.p, *dw = dvws.p + NR, *ds = dvws.p + 2 * NR, *dm = dvws.p + 3 * NR;
+    SmearDev smear;
+    if (int rc = smear.upload(p, p->nq, &m)) return rc;
+    if (int rc = launch_hist_reps(p, m, chunk, dq, dI, dsg, dc, drows.p, dcum.p, dsc, dv, dw, ds, dm)) return rc;
+    hist_fractions_kernel<<<(unsigned)R, WAVE>>>((int)N, (int)R, dsc, dv, dw, ds, dm, dfrac);
+    HIPCHK(hipGetLastError());
+    if (n_hist > 0) {
+        if (sizeof(double) * 3 * N > 64 * 1024)
+            HIPCHK(hipFuncSetAttribute((const void *)hist_bins_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * 3 * N)));
+        hist_bins_kernel<<<dim3((unsigned)n_hist, (unsigned)R), WAVE, sizeof(double) * 3 * N>>>((int)N, (int)P, (int)R, dc, dfrac, dedges, dspecs, dout);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(hback.p, dback.p, hback.bytes, hipMemcpyDeviceToHost, nullptr));
+    HIPCHK(hipStreamSynchronize(nullptr));
+    sync_guard.armed = false;
+    unpack_hist_set(hback.p, sz, scaling, fractions, out);
+    return MCSAS_OK;
+}
+
+// ------------------------------------------------------------------------------ a batch of sets: mcsas_hip_histogram_batch
+// hist_rows_batch_kernel of built-in model `model_id` over the grid.x blocks that `dblocks` begins with
+static int launch_hist_rows_batch(int model_id, dim3 grid, size_t lds, const HistSetDev *dsets, const ChainRef *dblocks, const double *din,
+                                  double *drows, double *dvws) {
+    switch (model_id) {
+#define CASE_K(mm) case mm: hist_rows_batch_kernel<mm><<<grid, WAVE, lds>>>(dsets, dblocks, din, drows, dvws); break;
+        MCSAS_FOR_MODELS(CASE_K)
+#undef CASE_K
+        default: return fail(MCSAS_EINVAL, "model %d has no batch kernel", model_id);
+    }
+    HIPCHK(hipGetLastError());
+    return MCSAS_OK;
+}
+
+// the rows budget of a batch chunk: 2 GiB, or MCSAS_HIP_HIST_BATCH_MB (a number of MiB, fractions allowed) — read at every call
+static size_t hist_batch_budget() {
+    double mb = 2048.;
+    if (const char *e = getenv("MCSAS_HIP_HIST_BATCH_MB")) { char *end = nullptr; const double v = strtod(e, &end); if (end != e && v >= 0. && v < 1e9) mb = v; }
+    return (size_t)(mb * 1048576.);
+}
+
+// A set of the batch: the caller's arguments for it and what check_hist_set made of them.  single: it runs through
+// mcsas_hip_histogram; otherwise rec is its record, and the *_off are where its blocks begin in the upload, the download and the
+// scratch blocks (rows and cum: of its chunk).
+struct HistBatchSet {
+    const mcsas_problem *p; const double *contribs; int n_hist; const mcsas_histogram_spec *specs; double *scaling, *fractions, *out;
+    ModelArgs m; HistSizes sz; bool single; int rec; size_t in_off, back_off, vws_off, rows_off, cum_off;
+};
+// sets [first, end), none of them single; their (set, repetition) blocks [blk_first, blk_first + n_blk) of the block table; the
+// doubles of their rows and summed intensities; their largest extents
+struct HistChunk { size_t first, end; size_t blk_first = 0, n_blk = 0, rows = 0, cum = 0, maxN = 0, maxQ = 0, maxH = 0; };
+// The staging layout of a batch (doubles): in = per batched set its going-in block, then the records, then the block table; back = per
+// batched set its coming-back block.
+struct HistBatchPlan {
+    std::vector<HistChunk> chunks;
+    size_t n_rec = 0, n_blk = 0, n_in = 0, n_back = 0, n_vws = 0, max_rows = 0, max_cum = 0;
+    size_t rec_d() const { return (sizeof(HistSetDev) * n_rec + 7) / 8; }
+    size_t in_total() const { return n_in + rec_d() + (sizeof(ChainRef) * n_blk + 7) / 8; }
+};
+struct HistBatchDev { const HistSetDev *sets; const ChainRef *blocks; double *in, *back, *rows, *cum, *vws; };
+
+// Chunks of consecutive batched sets whose rows fit the budget (a single set closes the chunk before it); numbers the records.  The
+// block table keeps a chunk's blocks together.
+static HistBatchPlan plan_hist_chunks(std::vector<HistBatchSet> &sets, size_t budget) {
+    HistBatchPlan pl;
+    for (size_t s = 0; s < sets.size(); ++s) {
+        HistBatchSet &t = sets[s];
+        if (t.single) continue;
+        const size_t R = t.p->n_reps, N = t.p->n_contrib, Q = t.p->nq;
+        const bool open = !pl.chunks.empty() && pl.chunks.back().end == s && (pl.chunks.back().rows + t.sz.rows) * sizeof(double) <= budget;
+        if (!open) pl.chunks.push_back(HistChunk{s, s});
+        HistChunk &c = pl.chunks.back();
+        t.rec = (int)pl.n_rec++;
+        t.in_off = pl.n_in; t.back_off = pl.n_back; t.vws_off = pl.n_vws; t.rows_off = c.rows; t.cum_off = c.cum;
+        c.end = s + 1; c.rows += t.sz.rows; c.cum += R * Q; c.n_blk += R;
+        c.maxN = std::max(c.maxN, N); c.maxQ = std::max(c.maxQ, Q); c.maxH = std::max<size_t>(c.maxH, t.n_hist);
+        pl.n_in += t.sz.n_in; pl.n_back += t.sz.n_back; pl.n_vws += 4 * N * R;
+        pl.max_rows = std::max(pl.max_rows, c.rows); pl.max_cum = std::max(pl.max_cum, c.cum);
+    }
+    for (HistChunk &c : pl.chunks) { c.blk_first = pl.n_blk; pl.n_blk += c.n_blk; }
+    return pl;
+}
+
+// Fills the upload block `hin`: every batched set's going-in block and record (its smearing tables go to the device here), and the
+// block table, a chunk's blocks model by model (hist_rows runs once per model; the other kernels take the chunk whole).
+static int pack_hist_batch(const HistBatchPlan &pl, std::vector<HistBatchSet> &sets, std::vector<SmearDev> &smears, double *hin) {
+    HistSetDev *recs = reinterpret_cast<HistSetDev *>(hin + pl.n_in);
+    ChainRef *blks = reinterpret_cast<ChainRef *>(hin + pl.n_in + pl.rec_d());
+    for (const HistChunk &c : pl.chunks) {
+        for (size_t s = c.first; s < c.end; ++s) {
+            HistBatchSet &t = sets[s];
+            const mcsas_problem *p = t.p; const HistSizes &sz = t.sz; const size_t w = t.in_off;
+            HistSetDev &d = recs[t.rec];
+            memset(&d, 0, sizeof d);
+            if (int rc = smears[t.rec].upload(p, p->nq, &t.m)) return rc;
+            d.model = t.m;
+            d.nq = p->nq; d.N = p->n_contrib; d.P = p->n_active; d.R = p->n_reps; d.n_hist = t.n_hist;
+            d.find_bg = p->find_background != 0; d.pos_bg = p->positive_background != 0;
+            d.q_off = (int64_t)w; d.I_off = (int64_t)(w + sz.I_off); d.sg_off = (int64_t)(w + sz.sg_off); d.c_off = (int64_t)(w + sz.c_off);
+            d.edge_off = (int64_t)(w + sz.edge_off); d.spec_off = (int64_t)(w + sz.spec_off);
+            d.back_off = (int64_t)t.back_off; d.rows_off = (int64_t)t.rows_off; d.cum_off = (int64_t)t.cum_off; d.vws_off = (int64_t)t.vws_off;
+            pack_hist_set(hin + w, p, t.contribs, t.n_hist, t.specs, sz);
+        }
+        size_t nb = c.blk_first;
+        for (int mid = 0; mid < MCSAS_MODEL_COUNT; ++mid)
+            for (size_t s = c.first; s < c.end; ++s)
+                if (sets[s].p->model_id == mid)
+                    for (int r = 0; r < sets[s].p->n_reps; ++r) blks[nb++] = ChainRef{sets[s].rec, r};
+    }
+    return MCSAS_OK;
+}
+
+// the kernels of one chunk on the null stream: one launch each over the chunk's blocks (hist_rows: one per model in it)
+static int launch_hist_chunk(const std::vector<HistBatchSet> &sets, const HistChunk &c, const HistBatchDev &d) {
+    const ChainRef *cb = d.blocks + c.blk_first;
+    size_t g_first = 0;
+    for (int mid = 0; mid < MCSAS_MODEL_COUNT; ++mid) {
+        size_t g_blk = 0, g_N = 0, lds = 0;
+        for (size_t t = c.first; t < c.end; ++t)
+            if (sets[t].p->model_id == mid) {
+                g_blk += sets[t].p->n_reps; g_N = std::max<size_t>(g_N, sets[t].p->n_contrib);
+                lds = std::max(lds, sizeof(double) * table_doubles_host(mid, sets[t].m.int_div));
+            }
+        if (!g_blk) continue;
+        if (int rc = launch_hist_rows_batch(mid, dim3((unsigned)g_blk, (unsigned)g_N), lds, d.sets, cb + g_first, d.in, d.rows, d.vws)) return rc;
+        g_first += g_blk;
+    }
+    const unsigned nb = (unsigned)c.n_blk;
+    hist_colsum_batch_kernel<<<dim3(nb, (unsigned)((c.maxQ + 255) / 256)), 256>>>(d.sets, cb, d.rows, d.cum);
+    HIPCHK(hipGetLastError());
+    hist_fit_cum_batch_kernel<<<nb, WAVE>>>(d.sets, cb, d.in, d.cum, d.back);
+    HIPCHK(hipGetLastError());
+    hist_obs_batch_kernel<<<dim3(nb, (unsigned)c.maxN), WAVE>>>(d.sets, cb, d.in, d.rows, d.back, d.vws);
+    HIPCHK(hipGetLastError());
+    hist_fractions_batch_kernel<<<nb, WAVE>>>(d.sets, cb, d.vws, d.back);
+    HIPCHK(hipGetLastError());
+    if (c.maxH > 0) {
+        const size_t lds = sizeof(double) * 3 * c.maxN;
+        if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)hist_bins_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        for (size_t h0 = 0; h0 < c.maxH; h0 += 65535) {      // (a grid's y extent ends at 65535)
+            hist_bins_batch_kernel<<<dim3(nb, (unsigned)std::min<size_t>(65535, c.maxH - h0)), WAVE, lds>>>(d.sets, cb, (int)h0, d.in, d.back);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    return MCSAS_OK;
+}
+
+// McSAS.histogram() of a batch of data sets (include/mcsas_hip.h).  Every refusal comes before a device is touched.  The sets are
+// taken in order, in chunks whose rows fit the budget; a chunk is one launch per kernel.  A plug-in model's set, and one whose rows
+// alone exceed the budget, closes the chunk before it and runs through mcsas_hip_histogram.
+extern "C" int mcsas_hip_histogram_batch(int32_t n_sets, const mcsas_problem *problems, const double *const *contribs, const int32_t *n_hist,
+                                         const mcsas_histogram_spec *const *specs, double *const *scaling, double *const *fractions,
+                                         double *const *out) {
+    if (n_sets < 0) return fail(MCSAS_EINVAL, "histogram_batch: n_sets %d", n_sets);
+    if (n_sets == 0) return MCSAS_OK;
+    if (!problems || !contribs || !n_hist || !specs || !scaling || !out)
+        return fail(MCSAS_EINVAL, "histogram_batch: NULL table (problems, contribs, n_hist, specs, scaling and out are needed; fractions may be NULL)");
+    std::vector<HistBatchSet> sets((size_t)n_sets);
+    const size_t budget = hist_batch_budget();
+    for (int s = 0; s < n_sets; ++s) {
+        HistBatchSet &t = sets[s] = HistBatchSet{&problems[s], contribs[s], n_hist[s], specs[s], scaling[s], fractions ? fractions[s] : nullptr, out[s]};
+        if (t.p->device != problems[0].device)
+            return fail(MCSAS_EINVAL, "histogram_batch: set %d names device %d, set 0 device %d: one device per batch", s, t.p->device, problems[0].device);
+        const int rc = check_hist_set(t.p, t.contribs, t.n_hist, t.specs, t.scaling, t.out, &t.m, &t.sz);
+        if (rc) { const std::string why = g_err; return fail(rc, "histogram_batch: set %d: %s", s, why.c_str()); }
+        t.single = is_plugin_model(t.p->model_id) || t.sz.rows * sizeof(double) > budget;
+    }
+    DeviceGuard dev_guard;
+    if (int rc = select_device(problems[0].device)) return rc;
+    const HistBatchPlan pl = plan_hist_chunks(sets, budget);
+    std::vector<SmearDev> smears(pl.n_rec);                    // (freed after the guard below has waited for the kernels)
+    DevBuf<double> din, dback, drows, dcum, dvws;
+    Pinned hin, hback;
+    SyncGuard sync_guard;
+    if (pl.n_rec) {
+        HIPCHK(din.alloc(pl.in_total())); HIPCHK(dback.alloc(pl.n_back)); HIPCHK(drows.alloc(pl.max_rows)); HIPCHK(dcum.alloc(pl.max_cum)); HIPCHK(dvws.alloc(pl.n_vws));
+        HIPCHK(hin.alloc(pl.in_total())); HIPCHK(hback.alloc(pl.n_back));
+        if (int rc = pack_hist_batch(pl, sets, smears, hin.p)) return rc;
+        HIPCHK(hipMemcpyAsync(din.p, hin.p, hin.bytes, hipMemcpyHostToDevice, nullptr));
+    }
+    const HistBatchDev dev{reinterpret_cast<const HistSetDev *>(din.p + pl.n_in), reinterpret_cast<const ChainRef *>(din.p + pl.n_in + pl.rec_d()),
+                           din.p, dback.p, drows.p, dcum.p, dvws.p};
+    size_t next_chunk = 0;
+    for (int s = 0; s < n_sets; ++s) {
+        const HistBatchSet &t = sets[s];
+        if (t.single) {
+            const int rc = mcsas_hip_histogram(t.p, t.contribs, t.n_hist, t.specs, t.scaling, t.fractions, t.out);
+            if (rc) { const std::string why = g_err; return fail(rc, "histogram_batch: set %d: %s", s, why.c_str()); }
+        } else if (next_chunk < pl.chunks.size() && pl.chunks[next_chunk].first == (size_t)s) {   // (otherwise: inside a chunk already launched)
+            if (int rc = launch_hist_chunk(sets, pl.chunks[next_chunk++], dev)) return rc;
+        }
+    }
+    if (pl.n_rec) {
+        HIPCHK(hipMemcpyAsync(hback.p, dback.p, hback.bytes, hipMemcpyDeviceToHost, nullptr));
+        HIPCHK(hipStreamSynchronize(nullptr));
+    }
+    sync_guard.armed = false;
+    for (const HistBatchSet &t : sets)
+        if (!t.single) unpack_hist_set(hback.p + t.back_off, t.sz, t.scaling, t.fractions, t.out);
+    return MCSAS_OK;
+}
+

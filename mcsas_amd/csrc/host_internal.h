@@ -1,6 +1,6 @@
 // host_internal.h — what the host translation units of libmcsas_hip.so share (mcsas_hip.hip: the analysis; host_plugin.hip: the
-// run-time compiler of model plug-ins; host_calls.hip: the one-call entry points).  Host code only: the run-time compiler never sees
-// this file (it is not among the embedded headers).
+// run-time compiler of model plug-ins; host_calls.hip: the small one-call entry points; host_hist.hip: McSAS.histogram()).  Host code
+// only: the run-time compiler never sees this file (it is not among the embedded headers).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,7 +1,7 @@
 // mcsas_hip.hip — libmcsas_hip.so: C ABI (include/mcsas_hip.h) over the gfx950 chain kernels.  This unit holds the analysis: plans,
 // launches, fetches, batches, sharding, rows evaluated by the caller, streams and the ABI queries; the run-time compiler of model
-// plug-ins is host_plugin.hip, the one-call entry points (model.calc, histogram, input preparation) are host_calls.hip, and what the
-// three share is host_internal.h.
+// plug-ins is host_plugin.hip, the small one-call entry points (model.calc, input preparation) are host_calls.hip, McSAS.histogram()
+// is host_hist.hip, and what the four share is host_internal.h.
 // Built only for MI355X (gfx950); there is no CPU path in here.
 #include <hip/hip_runtime.h>
 

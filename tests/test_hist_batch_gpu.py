@@ -256,3 +256,29 @@ def test_run_series_with_batched_histograms_equals_the_call_per_data_set():
         _assert_same_series(batched, per_set, kw)
         _assert_same_series(batched, sequential, (kw, "sequential"))
         _assert_same_series(_series_run(**kw), per_set, (kw, "default"))
+
+
+@pytest.mark.parametrize("find_background,positive_background", [(True, False), (False, False), (True, True)])
+@pytest.mark.parametrize("nq", [1, 63, 65])
+@pytest.mark.parametrize("N", [7, 8, 9])
+def test_histogram_prep_equals_the_device_histogram(N, nq, find_background, positive_background):
+    """mcsas_hip_histogram_prep and mcsas_hip_histogram take a repetition's summed intensity, its scale fit and its visibility limits
+    through the same kernels: the scaling and the limits are the same bits.  N around the eight-at-a-time column sum (its tail, an
+    exact fill, one over), nq around the 64 lanes of the q loops; three repetitions.  Radii inside pi / q and positive uncertainties:
+    no limit is a NaN, which would be equal to anything here — but for a single point fitted with a background, where scale and
+    background are 0 / 0 by construction and only the equality is asserted."""
+    R = 3
+    q = np.geomspace(1e8, 3e9, nq)
+    lo, hi = np.pi / 3e9, np.pi / 1e8
+    m = mcsas_amd.Sphere(); m.radius.setActiveRange((lo, hi))
+    rs = np.random.RandomState(100 * N + nq)
+    I, sig = 1.0 + rs.rand(nq), 0.1 + rs.rand(nq)
+    contribs = rs.uniform(lo, hi, (N, 1, R))
+    flags = dict(find_background=find_background, positive_background=positive_background)
+    prep = engine.histogram_prep(m.setup(), q, I, sig, contribs, C_EXP, **flags)
+    scaling, fractions, hists = engine.histogram_device(m.setup(), q, I, sig, contribs, C_EXP, [], **flags)
+    assert prep[0].shape == (2, R) and prep[4].shape == (N, R) and hists == []
+    if nq > 1 or not find_background:
+        assert not np.isnan(prep[0]).any() and not np.isnan(prep[4]).any()
+    np.testing.assert_array_equal(prep[0], scaling)
+    np.testing.assert_array_equal(prep[4], fractions["vol"][1])

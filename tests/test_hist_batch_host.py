@@ -1,5 +1,5 @@
-"""mcsas_hip_histogram_batch without a GPU: the declaration, the export, and every refusal — each before a device is touched, each
-naming the set it is about."""
+"""mcsas_hip_histogram_batch and mcsas_hip_histogram without a GPU: the declaration, the export, and every refusal — each before a
+device is touched, the batch's naming the set it is about and otherwise the single call's word for word."""
 import ctypes as C
 import os
 import re
@@ -47,6 +47,52 @@ def _run(calls, n_sets=None, null=None, patch=None):
     rc = lib.mcsas_hip_histogram_batch(n if n_sets is None else n_sets, tables["problems"], tables["contribs"], tables["n_hist"], tables["specs"],
                                        tables["scaling"], tables["fractions"], tables["out"])
     return rc, lib.mcsas_hip_last_error().decode()
+
+
+def _run_single(call, null_contribs=False):
+    """(return code, last error) of mcsas_hip_histogram over one set"""
+    lib = _lib.load()
+    rc = lib.mcsas_hip_histogram(C.byref(call.prob.c), None if null_contribs else _lib.as_dp(call.contribs), len(call.specs), call.arr,
+                                 _lib.as_dp(call.sc), _lib.as_dp(call.frac), _lib.as_dp(call.out))
+    return rc, lib.mcsas_hip_last_error().decode()
+
+
+def _set(obj, name, value):
+    setattr(obj, name, value)
+
+
+# what makes a set unacceptable: (how the valid set of _call is spoilt, the single call's message)
+REFUSALS = {
+    "no contributions": (None, "bad argument"),
+    "nq = 0": (lambda c: _set(c.prob.c, "nq", 0), "bad argument"),
+    "n_contrib = 4097": (None, "mcsas_hip_histogram stages a repetition's contributions in LDS: n_contrib 4097 > 4096 (use mcsas_hip_histogram_prep)"),
+    "weighting = 7": (lambda c: _set(c.arr[1], "weighting", 7), "histogram 1: param_index 0, weighting 7, n_bin 3"),
+    "param_index = 1": (lambda c: _set(c.arr[1], "param_index", 1), "histogram 1: param_index 1, weighting 0, n_bin 3"),   # (one active parameter)
+    "n_bin = -1": (lambda c: _set(c.arr[0], "n_bin", -1), "histogram 0: param_index 0, weighting 0, n_bin -1"),
+    "no edges": (lambda c: _set(c.arr[0], "edges", DPP()), "histogram 0: param_index 0, weighting 0, n_bin 4"),
+    "model_id = 77": (lambda c: _set(c.prob.c, "model_id", 77), "unknown model_id 77"),
+    "smear_nk = 1": (lambda c: _set(c.prob.c, "smear_nk", 1), "smearing: smear_nk 1 (2..4096) needs locs, q_offset and weights"),
+}
+
+
+@pytest.mark.parametrize("case", list(REFUSALS))
+def test_the_single_call_refuses_before_a_device_and_a_batch_of_one_says_the_same(case):
+    """Every refusal of a set is MCSAS_EINVAL (never MCSAS_ENODEV: no device is looked for) with the single call's wording, and the
+    same set as a batch of one is refused with the same code and "histogram_batch: set 0: " before the same sentence: one validator."""
+    spoil, wording = REFUSALS[case]
+    call = _call(n_contrib=4097, n_reps=1, nq=4, n_bins=()) if case == "n_contrib = 4097" else _call()
+    if spoil:
+        spoil(call)
+    null = case == "no contributions"
+    rc, msg = _run_single(call, null_contribs=null)
+    assert rc == EINVAL, (rc, msg)
+    assert msg == wording
+
+    def no_contribs(tables):
+        tables["contribs"][0] = DPP()
+    brc, bmsg = _run([call], patch=no_contribs if null else None)
+    assert brc == rc
+    assert bmsg == "histogram_batch: set 0: " + msg
 
 
 def test_header_declares_the_batch_call_at_abi_5_and_the_library_exports_it():
@@ -108,14 +154,17 @@ def test_sets_on_different_devices_are_refused():
 
 
 def test_a_valid_batch_reaches_the_device_selection():
-    """No GPU here: MCSAS_ENODEV says that validation passed and the call got as far as selecting a device (what the single call
-    answers here as well).  engine.histogram_device_batch raises it; an empty list needs no device."""
+    """No GPU here: MCSAS_ENODEV says that validation passed and the call got as far as selecting a device; the single call answers
+    the same for each of the sets.  engine.histogram_device_batch raises it; an empty list needs no device."""
     if _lib.load().mcsas_hip_device_count() > 0:
         pytest.skip("a GPU is present")
     calls = [_call(), _call(n_contrib=4096, n_reps=1, nq=4, n_bins=()), _call(n_bins=())]
     rc, msg = _run(calls)
     assert rc == ENODEV, msg
     assert _run(calls, null="fractions")[0] == ENODEV          # (fractions may be NULL)
+    for call in calls:
+        rc, msg = _run_single(call)
+        assert rc == ENODEV, msg
     c = calls[0]
     with pytest.raises(_lib.McSASHipError) as e:
         engine.histogram_device_batch([dict(model=c.prob.model, q=c.prob.q, intensity=c.prob.I, sigma=c.prob.sigma, contribs=c.contribs,
