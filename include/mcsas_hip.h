@@ -291,6 +291,42 @@ int mcsas_hip_analyse_batch(const mcsas_problem *problems, int32_t n, mcsas_resu
 int mcsas_hip_plan_set_start(mcsas_plan *plan, const double *start, int32_t rep_stride, int32_t rep_first);
 int mcsas_hip_analyse_from(const mcsas_problem *problem, const double *start, mcsas_result *result);
 
+/* ---- the accepted moves of a chain (ABI 5, additive): what the reference prints while mcFit runs ("good iter ...: Chisqr= ...",
+ * mcsas.py:385-390), so that a caller sees whether a fit was still improving, had stalled or was cut off by maxIterations ---------
+ * One wavefront per chain only (MCSAS_EXEC_WAVE), cold or started (the start functions above).  Per repetition the trace holds the
+ * moves of its LAST attempt, because num_iter and num_moves are that attempt's too: a retry (mcsas.py:220-246) starts it again.
+ * Records kept: the first min(count, capacity) moves, in order; entries from there on are step = -1, chisq = NaN, values = NaN.
+ *   count is always the full number of moves (== mcsas_result.num_moves), whatever the capacity.
+ * The trace only observes: with a trace set, every array of mcsas_result except `seconds` is bit for bit that of the same call
+ *   without one (mcsas_hip_analyse with MCSAS_EXEC_WAVE, or with a start the from-form of it); start, the reseed call, the replay
+ *   stream and `stop` behave as they do without a trace.  Cost: one bounds test and 2 + n_active stores per ACCEPTED move, nothing
+ *   in a rejected step.  Measured once (one MI355X, Sphere 512 q x 400 contributions x 256 repetitions x 20000 steps, 1205 moves
+ *   per chain, capacity 4096): 26.87 ms of kernel against 26.50 ms untraced, +1.4 %, where two untraced runs differed by 0.004 ms
+ *   (profiles/r17_summary.md) — small, but more than the noise: leave the trace off where it is not read.
+ * mcsas_hip_plan_set_trace: for a plan that resolved to MCSAS_EXEC_WAVE; any other: MCSAS_EINVAL naming the mode (the plan stays
+ *   usable).  Every later launch of either slot runs the traced form of the plan's kernel, cold or started, and each slot owns its
+ *   trace buffers.  capacity >= 1 and n_reps * capacity * (16 + 8 n_active) bytes <= 2 GiB, else MCSAS_EINVAL; capacity 0 clears.
+ *   mcsas_hip_plan_launch_batch refuses a plan with a trace (MCSAS_EINVAL, nothing is launched).
+ * mcsas_hip_plan_fetch_trace: after the slot's result has been fetched.  MCSAS_EINVAL if the plan has no trace, if
+ *   trace->capacity differs from the plan's, on a NULL array or a wrong struct_size, or if the slot's launch was not traced.
+ * mcsas_hip_analyse_traced: the one-shot form; `start` as for the from-form above, or NULL for a cold run.  MCSAS_EXEC_AUTO means
+ *   WAVE; WORKGROUP, PIPELINE, nq > 4096 and n_devices > 1 are refused, and so are a NULL trace, a NULL array in it, capacity < 1,
+ *   a wrong struct_size and a non-finite start value — every refusal before a device is touched.  n_active == 0 is answered as
+ *   mcsas_hip_analyse answers it, with count[0] = 0.
+ * Out of scope (each refuses): batches, the q-split, workgroup-window and pipeline kernels, mcsas_hip_analyse_host_rows. */
+typedef struct mcsas_trace {
+    uint32_t struct_size;  /* sizeof(mcsas_trace) */
+    int32_t  capacity;     /* records kept per repetition */
+    int64_t *count;        /* [n_reps] accepted moves of the last attempt (== mcsas_result.num_moves) */
+    double  *chisq0;       /* [n_reps] reduced chi-squared of that attempt's initial set (mcsas.py:343-344) */
+    int64_t *step;         /* [capacity][n_reps] numIter at which move i was accepted (0-based; contribution = step % n_contrib) */
+    double  *chisq;        /* [capacity][n_reps] conval after the move: the number the chain compares with conv_crit (mcsas.py:379) */
+    double  *values;       /* [capacity][n_active][n_reps] the accepted parameter set rt, as written to rset (mcsas.py:381) */
+} mcsas_trace;
+int mcsas_hip_plan_set_trace(mcsas_plan *plan, int32_t capacity);
+int mcsas_hip_plan_fetch_trace(mcsas_plan *plan, int32_t slot, mcsas_trace *trace);
+int mcsas_hip_analyse_traced(const mcsas_problem *problem, const double *start, mcsas_result *result, mcsas_trace *trace);
+
 /* ---- ScatteringModel.calc(data, pset, compensationExponent) (scatteringmodel.py:79-109) ------
  * Uses problem->{model_id, params, n_active, active_index, clip_*, nq, q, comp_exp, device}.
  * pset[n][n_active] -> cum_int[nq] (rows summed in order), vset/wset/sset[n], optional

@@ -24,7 +24,8 @@ SYMBOLS = (
     "mcsas_hip_analyse", "mcsas_hip_analyse_host_rows", "mcsas_hip_shard", "mcsas_hip_plan_create", "mcsas_hip_plan_launch", "mcsas_hip_plan_fetch",
     "mcsas_hip_plan_launch_slot", "mcsas_hip_plan_fetch_slot",
     "mcsas_hip_plan_last_ms", "mcsas_hip_plan_total_steps", "mcsas_hip_plan_reseed", "mcsas_hip_plan_info",
-    "mcsas_hip_plan_destroy", "mcsas_hip_plan_launch_batch", "mcsas_hip_analyse_batch", "mcsas_hip_plan_set_start", "mcsas_hip_analyse_from", "mcsas_hip_model_calc", "mcsas_hip_bgfit", "mcsas_hip_observability",
+    "mcsas_hip_plan_destroy", "mcsas_hip_plan_launch_batch", "mcsas_hip_analyse_batch", "mcsas_hip_plan_set_start", "mcsas_hip_analyse_from",
+    "mcsas_hip_plan_set_trace", "mcsas_hip_plan_fetch_trace", "mcsas_hip_analyse_traced", "mcsas_hip_model_calc", "mcsas_hip_bgfit", "mcsas_hip_observability",
     "mcsas_hip_histogram_prep", "mcsas_hip_histogram", "mcsas_hip_histogram_batch", "mcsas_hip_prepare_uncertainty", "mcsas_hip_rebin",
     "mcsas_hip_plugin_compile", "mcsas_hip_plugin_log", "mcsas_hip_release_cached_memory", "mcsas_hip_stream_create", "mcsas_hip_stream_destroy",
     "mcsas_hip_device_count", "mcsas_hip_abi_version", "mcsas_hip_is_tuning_build", "mcsas_hip_last_error",
@@ -83,6 +84,14 @@ class Result(C.Structure):
     ]
 
 
+class Trace(C.Structure):
+    """mcsas_trace (include/mcsas_hip.h): the accepted moves of every repetition's last attempt."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("capacity", C.c_int32),
+        ("count", _i64p), ("chisq0", _dp), ("step", _i64p), ("chisq", _dp), ("values", _dp),
+    ]
+
+
 class McSASHipError(RuntimeError):
     def __init__(self, code, message):
         super().__init__("libmcsas_hip error %d: %s" % (code, message))
@@ -133,6 +142,9 @@ def load(tuning=False):
     lib.mcsas_hip_analyse_batch.argtypes = [C.POINTER(Problem), C.c_int32, C.POINTER(Result)]
     lib.mcsas_hip_plan_set_start.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_int32]
     lib.mcsas_hip_analyse_from.argtypes = [C.POINTER(Problem), _dp, C.POINTER(Result)]
+    lib.mcsas_hip_plan_set_trace.argtypes = [C.c_void_p, C.c_int32]
+    lib.mcsas_hip_plan_fetch_trace.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Trace)]
+    lib.mcsas_hip_analyse_traced.argtypes = [C.POINTER(Problem), _dp, C.POINTER(Result), C.POINTER(Trace)]
     lib.mcsas_hip_plan_destroy.argtypes = [C.c_void_p]
     lib.mcsas_hip_plan_destroy.restype = None
     lib.mcsas_hip_model_calc.argtypes = [C.POINTER(Problem), _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp]

@@ -24,6 +24,9 @@
 //   CHAIN_FIRST        true in one thread per lane index: those write the initial set to rset
 //   CHAIN_LEADER       true in one thread of the chain: it writes an accepted row to rset, and the record
 //   CHAIN_STOP         expression: McSAS.stop has been asked for — one answer for all threads of the chain
+//   CHAIN_TRACE_START(c)          statement, or nothing: an attempt starts with reduced chi² c of its initial set (mcsas.py:343-344)
+//   CHAIN_TRACE_MOVE(i, s, c, k)  statement, or nothing: move i of the attempt was accepted at step s and left reduced chi² c; its
+//                      values are lane k of prow (mcsas.py:385-390).  Only the traced wave kernels (chain_wave.h) put anything here
     double *rset = a.rset + (size_t)rep * N * P;
     double *cache = CACHE ? CHAIN_CACHE_PTR(a.cache + (size_t)rep * a.cache_rows * qpad) : nullptr;
     DrawSource src{a.replay ? a.replay + (size_t)rep * a.replay_len : nullptr, a.replay_len, a.seed,
@@ -93,6 +96,7 @@
             CHAIN_SUM3(s1, s2, s3);
             cur = solve_fit(a, s1, s2, s3);
         }
+        CHAIN_TRACE_START(cur.chi2)
         num_iter = 0; num_moves = 0;
         int ri = 0;
         // The comparison chi²_t < chi² (mcsas.py:379) is made without divisions, as in the other kernels:
@@ -176,6 +180,7 @@
                             if (CHAIN_LEADER) rset[(size_t)ri * P + p] = val;
                         }
                     if (!CACHE) __threadfence_block();   // rset[ri] is re-read by every lane N steps later
+                    CHAIN_TRACE_MOVE(num_moves, num_iter, cur.chi2, kk)
                     ++num_moves;
                 }
                 ri = (ri + 1 == N) ? 0 : ri + 1;                                   // mcsas.py:403-404

@@ -67,6 +67,17 @@ struct ChainArgs {
 // one chain of a batch launch (chain_wave_batch_kernel): repetition `rep` of the analysis whose argument block is sets[set]
 struct ChainRef { int32_t set, rep; };
 
+// Where a traced wave kernel (chain_wave.h: chain_wave_trace_kernel) records the accepted moves of a chain's last attempt: its second
+// kernel argument, not a part of ChainArgs (a field there changes every chain kernel's object).  Move i of repetition
+// r is entry r * capacity + i; moves from `capacity` on are counted (ChainOut::num_moves) and not recorded.
+struct TraceArgs {
+    int64_t *step;                     // [n_reps][capacity] numIter at which the move was accepted
+    double  *chisq;                    // [n_reps][capacity] reduced chi² after it
+    double  *values;                   // [n_reps][capacity][n_active] the set written to rset
+    double  *chisq0;                   // [n_reps] reduced chi² of the attempt's initial set
+    int32_t  capacity, pad;
+};
+
 // McSAS.stop (mcsas.py:357: polled once per step).  The caller's word lives in host memory, and a read of it crosses the host link:
 // microseconds each, served one at a time — 8192 chains looking every 64 steps were measured to spend HALF of a launch queued
 // up on those reads (3.7e8 instead of 7.5e8 steps/s, whatever the q count).  So the chains look at a word in device memory (an L2

@@ -16,6 +16,10 @@ namespace mcsas {
 // waves per SIMD the chain kernels are built for (the batch kernel below keeps its single twin's)
 #define MCSAS_WAVE_MIN_WAVES(QPL, CACHE) (((QPL) < 8 || ((QPL) == 8 && (CACHE))) ? 2 : 1)
 
+// the trace hooks of chain_wave_kernel.inc: nothing in the kernels of this file, except in chain_wave_trace_kernel
+#define MCSAS_WAVE_TRACE_START(c)
+#define MCSAS_WAVE_TRACE_MOVE(i, s, c, k)
+
 // GIVEN: the chain is started from a given set (mcsas_hip_plan_set_start): the host has copied the repetition's start into rset
 // ahead of the launch, and the first attempt takes it where the cold kernel generates one (chain_body.inc: GIVEN).
 template <int M, int QPL, bool CACHE, bool GIVEN>
@@ -56,5 +60,34 @@ __global__ __launch_bounds__(64, MCSAS_WAVE_MIN_WAVES(QPL, CACHE)) void chain_wa
     chain_args_pointers(a, ((ConstChainArgs *)sets)[set]);
 #include "chain_wave_kernel.inc"
 }
+
+#undef MCSAS_WAVE_TRACE_START
+#undef MCSAS_WAVE_TRACE_MOVE
+
+// The traced form of chain_wave_kernel (mcsas_hip_plan_set_trace): the same chain, and lane 0 also records the accepted moves of the
+// last attempt in the repetition's part of `t` (TraceArgs, chain_common.h) — the reference reports them as it goes, mcsas.py:385-390.
+// An attempt's start writes the chi² of its initial set; move i of the attempt overwrites record i of the attempt before, so what is
+// left at the end are the records of the last attempt (its count is ChainOut::num_moves) and, behind them, stale ones the host
+// drops.  One bounds test and 2 + P stores per accepted move; nothing in a rejected step.  Nothing the chain computes reads `t`.
+#define MCSAS_WAVE_TRACE_START(c) if (lane == 0) t.chisq0[rep] = c;
+#define MCSAS_WAVE_TRACE_MOVE(i, s, c, k)                                                                              \
+    if (i < (int64_t)t.capacity) {                                                                                     \
+        const size_t rec = (size_t)rep * (size_t)t.capacity + (size_t)i;                                               \
+        _Pragma("unroll") for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)                                                   \
+            if (p < P) {                                                                                               \
+                const double tv = readlane_f64(prow[p], k);                                                            \
+                if (lane == 0) t.values[rec * P + p] = tv;                                                             \
+            }                                                                                                          \
+        if (lane == 0) { t.step[rec] = s; t.chisq[rec] = c; }                                                          \
+    }
+template <int M, int QPL, bool CACHE, bool GIVEN>
+__global__ __launch_bounds__(64, MCSAS_WAVE_MIN_WAVES(QPL, CACHE)) void chain_wave_trace_kernel(const ChainArgs a, const TraceArgs t) {
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x;
+    const int rep = blockIdx.x;
+#include "chain_wave_kernel.inc"
+}
+#undef MCSAS_WAVE_TRACE_START
+#undef MCSAS_WAVE_TRACE_MOVE
 
 }  // namespace mcsas

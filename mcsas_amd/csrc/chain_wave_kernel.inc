@@ -2,7 +2,8 @@
 // tables, then the chain (chain_body.inc) with the q-points of a wave: q index lane + 64 j in slot j, w and wI read from LDS, sums
 // by DPP inside the wave, every lane a first-wave lane and lane 0 the leader.  Included verbatim so that all four compile from the
 // same text.  In scope at the point of inclusion: M, QPL, CACHE (template parameters), GIVEN (compile-time bool),
-// `const ChainArgs &a`, `const int rep`, `lds` (the dynamic LDS), `const int lane`.
+// `const ChainArgs &a`, `const int rep`, `lds` (the dynamic LDS), `const int lane` — and the two macros MCSAS_WAVE_TRACE_START /
+// MCSAS_WAVE_TRACE_MOVE, which stand for nothing except in the traced kernel (chain_wave.h sets them).
     const int N = a.n_contrib, P = a.model.n_active, qpad = a.qpad;
     double *lq = lds, *lw = lds + qpad, *lwI = lds + 2 * qpad, *lq3 = lds + 3 * qpad, *tab = lds + 4 * qpad;
     for (int i = lane; i < qpad; i += WAVE) {
@@ -24,6 +25,8 @@
 #define CHAIN_FIRST true
 #define CHAIN_LEADER (lane == 0)
 #define CHAIN_STOP stop_requested(a)                        // (one answer per wave: chain_common.h)
+#define CHAIN_TRACE_START(c) MCSAS_WAVE_TRACE_START(c)
+#define CHAIN_TRACE_MOVE(i, s, c, k) MCSAS_WAVE_TRACE_MOVE(i, s, c, k)
 #include "chain_body.inc"
 #undef CHAIN_STATE
 #undef CHAIN_CACHE_PTR
@@ -36,3 +39,5 @@
 #undef CHAIN_FIRST
 #undef CHAIN_LEADER
 #undef CHAIN_STOP
+#undef CHAIN_TRACE_START
+#undef CHAIN_TRACE_MOVE

@@ -97,6 +97,8 @@ __global__ __launch_bounds__(WIDE_MAX_WAVES * 64) void chain_wide_kernel(const C
 #define CHAIN_FIRST (wave == 0)
 #define CHAIN_LEADER (tid == 0)
 #define CHAIN_STOP wide_stop(a, stop_word, tid)
+#define CHAIN_TRACE_START(c)                                // (no trace in this family)
+#define CHAIN_TRACE_MOVE(i, s, c, k)
 #include "chain_body.inc"
 #undef CHAIN_STATE
 #undef CHAIN_CACHE_PTR
@@ -109,6 +111,8 @@ __global__ __launch_bounds__(WIDE_MAX_WAVES * 64) void chain_wide_kernel(const C
 #undef CHAIN_FIRST
 #undef CHAIN_LEADER
 #undef CHAIN_STOP
+#undef CHAIN_TRACE_START
+#undef CHAIN_TRACE_MOVE
 }
 
 }  // namespace mcsas

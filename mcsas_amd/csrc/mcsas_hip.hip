@@ -263,6 +263,7 @@ struct mcsas_plan {
     double *d_cache = nullptr, *d_replay = nullptr;
     double *d_start = nullptr;          // [n_reps][n_contrib][n_active], the layout of rset: the set every launch starts from (mcsas_hip_plan_set_start)
     bool has_start = false;             // ... while this holds; the buffer stays with the plan once made
+    int32_t trace_capacity = 0;         // > 0: every launch runs the traced kernel and keeps this many moves per repetition (mcsas_hip_plan_set_trace)
     int32_t *h_stop = nullptr;          // pinned + mapped: McSAS.stop as the kernels see it
     int32_t *d_stop_relay = nullptr;    // device memory, 16 bytes: the relayed stop word and the time stamp of the last look at h_stop (chain_common.h: stop_requested)
     hipStream_t stream = nullptr;
@@ -295,6 +296,12 @@ struct mcsas_plan {
         int64_t last_steps = 0;
         // the batch (mcsas_hip_plan_launch_batch) whose launch wrote this slot, or null: its stop word is the one fetch() forwards to
         std::shared_ptr<BatchShared> batch_of;
+        // the trace of the slot's last launch (mcsas_hip_plan_set_trace): one device block of its own, made by the first traced launch
+        // of the slot, given back when the trace is cleared or resized and with the plan
+        TraceArgs trace{};
+        char *d_trace = nullptr;
+        size_t trace_bytes = 0;
+        bool traced = false;            // the launch that `launched` stands for ran the traced kernel
     };
     Slot slots[MCSAS_PLAN_SLOTS];
     int cur_slot = 0;
@@ -336,9 +343,11 @@ static int plan_activate_slot(mcsas_plan *pl, int k) {
 // families) / rows pulled from a queue (pipeline tick)); null where the family has no start form.
 typedef void *KernelLookup(int qpl, bool flag);
 #define DECL_K(m) KernelLookup mcsas_wave_kernel_m##m, mcsas_wave_kernel_given_m##m, mcsas_wave_batch_kernel_m##m, mcsas_wave_batch_kernel_given_m##m, \
-                               mcsas_wg_kernel_m##m, mcsas_wide_kernel_m##m, mcsas_wide_kernel_given_m##m, mcsas_pipe_tick_kernel_m##m;
+                               mcsas_wg_kernel_m##m, mcsas_wide_kernel_m##m, mcsas_wide_kernel_given_m##m, mcsas_pipe_tick_kernel_m##m, \
+                               mcsas_wave_trace_kernel_m##m, mcsas_wave_trace_kernel_given_m##m;
 #define ROW_K(m) {{mcsas_wave_kernel_m##m, mcsas_wave_kernel_given_m##m}, {mcsas_wave_batch_kernel_m##m, mcsas_wave_batch_kernel_given_m##m}, \
-                  {mcsas_wg_kernel_m##m, nullptr}, {mcsas_wide_kernel_m##m, mcsas_wide_kernel_given_m##m}, {mcsas_pipe_tick_kernel_m##m, nullptr}},
+                  {mcsas_wg_kernel_m##m, nullptr}, {mcsas_wide_kernel_m##m, mcsas_wide_kernel_given_m##m}, {mcsas_pipe_tick_kernel_m##m, nullptr}, \
+                  {mcsas_wave_trace_kernel_m##m, mcsas_wave_trace_kernel_given_m##m}},
 MCSAS_FOR_MODELS(DECL_K)
 static KernelLookup *const BUILTIN[MCSAS_MODEL_COUNT][KF_COUNT][2] = {MCSAS_FOR_MODELS(ROW_K)};
 #undef DECL_K
@@ -351,26 +360,26 @@ struct KernelRef {
     void *entry = nullptr;
     hipFunction_t plugin = nullptr;
     unsigned block = 0;
-    enum { ARG2_NONE, ARG2_WG, ARG2_Q3INV } arg2 = ARG2_NONE;
+    enum { ARG2_NONE, ARG2_WG, ARG2_Q3INV, ARG2_TRACE } arg2 = ARG2_NONE;
     const void *id() const { return plugin ? (const void *)plugin : entry; }
 };
 // the family of the plan's own launches; a batch (mcsas_hip_plan_launch_batch) runs the plan's chains in KF_WAVE_BATCH instead.  Either
 // way a launch takes the started kernel of its family while the plan holds a start (mcsas_hip_plan_set_start gives one to plans of
-// the wave and q-split families only).
+// the wave and q-split families only), and a wave plan with a trace (mcsas_hip_plan_set_trace) the traced family.
 static KernelFamily plan_family(const mcsas_plan *pl) {
-    if (pl->mode == MCSAS_EXEC_WAVE) return KF_WAVE;
+    if (pl->mode == MCSAS_EXEC_WAVE) return pl->trace_capacity > 0 ? KF_WAVE_TRACE : KF_WAVE;
     if (pl->mode == MCSAS_EXEC_PIPELINE) return KF_PIPE_TICK;
     return pl->wide ? KF_WIDE : KF_WG;
 }
 static int resolve_kernel(const mcsas_plan *pl, KernelFamily family, bool given, KernelRef *k) {
-    static const char *const name[KF_COUNT] = {"", "batch ", "", "q-split ", "pipeline "};
+    static const char *const name[KF_COUNT] = {"", "batch ", "", "q-split ", "pipeline ", "traced "};
     const int model = pl->prob.model_id;
     const bool flag = family == KF_PIPE_TICK ? pl->pipe.g.rowq != 0 : pl->use_cache != 0;
     *k = KernelRef{};
     k->block = family == KF_PIPE_TICK ? PIPE_BLOCK : (family == KF_WG || family == KF_WIDE ? WAVE * pl->waves : WAVE);
-    k->arg2 = family == KF_WG ? KernelRef::ARG2_WG : (family == KF_WIDE ? KernelRef::ARG2_Q3INV : KernelRef::ARG2_NONE);
+    k->arg2 = family == KF_WG ? KernelRef::ARG2_WG : (family == KF_WIDE ? KernelRef::ARG2_Q3INV : (family == KF_WAVE_TRACE ? KernelRef::ARG2_TRACE : KernelRef::ARG2_NONE));
     if (is_plugin_model(model)) {
-        if (pl->plugin_fn && family == plan_family(pl) && !given) { k->plugin = pl->plugin_fn; return MCSAS_OK; }   // (looked up when the plan was made)
+        if (pl->plugin_fn && family == plan_family(pl) && family != KF_WAVE_TRACE && !given) { k->plugin = pl->plugin_fn; return MCSAS_OK; }   // (looked up when the plan was made)
         return plugin_chain_function(model, family, pl->qpl, flag, given, &k->plugin);                           // (compiled on first use of this q count)
     }
     KernelLookup *const lookup = model >= 0 && model < MCSAS_MODEL_COUNT ? BUILTIN[model][family][given] : nullptr;
@@ -411,6 +420,7 @@ extern "C" void mcsas_hip_plan_destroy(mcsas_plan *pl) {
     for (mcsas_plan::Slot &sl : pl->slots) {              // (a slot that was never made, or only half made, holds nulls)
         cached_host_free(sl.h_done, sizeof(int32_t), hipHostMallocMapped);
         cached_host_free(sl.h_pipeargs, sizeof(PipeArgs), hipHostMallocDefault);
+        if (sl.d_trace) cached_dev_free(sl.d_trace, sl.trace_bytes, pl->dev);
         if (sl.ev0) hipEventDestroy(sl.ev0);
         if (sl.ev1) hipEventDestroy(sl.ev1);
     }
@@ -844,6 +854,102 @@ static int enqueue_start(mcsas_plan *pl, hipStream_t st) {
     return MCSAS_OK;
 }
 
+// ------------------------------------------------------------------------------ the trace of a wave plan (include/mcsas_hip.h)
+// bytes of one slot's trace block: step, chisq and values of `capacity` moves per repetition
+static size_t trace_record_bytes(size_t R, size_t capacity, size_t P) { return R * capacity * (16 + 8 * P); }
+static const size_t TRACE_MAX_BYTES = (size_t)2 << 30;
+static void drop_slot_trace(mcsas_plan *pl, mcsas_plan::Slot &sl) {
+    if (sl.d_trace) cached_dev_free(sl.d_trace, sl.trace_bytes, pl->dev);
+    sl.d_trace = nullptr; sl.trace_bytes = 0; sl.trace = TraceArgs{}; sl.traced = false;
+}
+// the slot's trace block for the plan's capacity: [step | chisq | values | chisq0], made on the slot's first traced launch
+static int make_slot_trace(mcsas_plan *pl, mcsas_plan::Slot &sl) {
+    if (sl.d_trace && sl.trace.capacity == pl->trace_capacity) return MCSAS_OK;
+    drop_slot_trace(pl, sl);
+    const size_t R = pl->prob.n_reps, K = (size_t)pl->trace_capacity, P = pl->prob.n_active;
+    const size_t bytes = (trace_record_bytes(R, K, P) + 8 * R + 255) / 256 * 256;
+    HIPCHK(cached_dev_malloc((void **)&sl.d_trace, bytes));
+    sl.trace_bytes = bytes;
+    sl.trace.step = (int64_t *)sl.d_trace;
+    sl.trace.chisq = (double *)(sl.d_trace + 8 * R * K);
+    sl.trace.values = (double *)(sl.d_trace + 16 * R * K);
+    sl.trace.chisq0 = (double *)(sl.d_trace + (16 + 8 * P) * R * K);
+    sl.trace.capacity = pl->trace_capacity; sl.trace.pad = 0;
+    return MCSAS_OK;
+}
+
+extern "C" int mcsas_hip_plan_set_trace(mcsas_plan *pl, int32_t capacity) {
+    if (!pl) return fail(MCSAS_EINVAL, "set_trace: null plan");
+    if (capacity < 0) return fail(MCSAS_EINVAL, "set_trace: capacity %d (>= 1, or 0 to clear the trace)", (int)capacity);
+    if (capacity > 0) {
+        if (pl->mode != MCSAS_EXEC_WAVE || pl->wide)
+            return fail(MCSAS_EINVAL, "set_trace: the plan runs in exec_mode %d (%s); a trace needs exec_mode = MCSAS_EXEC_WAVE (%d)", pl->mode, exec_mode_name(pl->mode), MCSAS_EXEC_WAVE);
+        const size_t R = pl->prob.n_reps, P = pl->prob.n_active;
+        if ((size_t)capacity > TRACE_MAX_BYTES / (R * (16 + 8 * P)))
+            return fail(MCSAS_EINVAL, "set_trace: %d repetitions x capacity %d x %zu bytes per move exceed 2 GiB", pl->prob.n_reps, (int)capacity, 16 + 8 * P);
+    }
+    DeviceGuard dev_guard;
+    HIPCHK(hipSetDevice(pl->dev));
+    if (capacity != pl->trace_capacity) {
+        // (a launch still in flight writes the blocks that go back to the cache here)
+        for (mcsas_plan::Slot &sl : pl->slots)
+            if (sl.launched && sl.ev1) HIPCHK(hipEventSynchronize(sl.ev1));
+        for (mcsas_plan::Slot &sl : pl->slots) drop_slot_trace(pl, sl);
+    }
+    if (capacity > 0) {                                   // a shape without a traced kernel is refused here, as the plan's own is at its creation
+        const int32_t before = pl->trace_capacity;
+        pl->trace_capacity = capacity;
+        KernelRef k;
+        const int rc = is_plugin_model(pl->prob.model_id) ? MCSAS_OK : resolve_kernel(pl, KF_WAVE_TRACE, pl->has_start, &k);
+        if (rc) { pl->trace_capacity = before; return rc; }
+    }
+    pl->trace_capacity = capacity;
+    return MCSAS_OK;
+}
+
+static int check_trace_arrays(const char *who, const mcsas_trace *tr) {
+    if (!tr) return fail(MCSAS_EINVAL, "%s: trace is NULL", who);
+    if (tr->struct_size != sizeof(mcsas_trace)) return fail(MCSAS_EINVAL, "%s: mcsas_trace size %u, library expects %zu", who, tr->struct_size, sizeof(mcsas_trace));
+    if (tr->capacity < 1) return fail(MCSAS_EINVAL, "%s: trace capacity %d (>= 1)", who, (int)tr->capacity);
+    if (!tr->count || !tr->chisq0 || !tr->step || !tr->chisq || !tr->values)
+        return fail(MCSAS_EINVAL, "%s: trace array %s is NULL", who, !tr->count ? "count" : !tr->chisq0 ? "chisq0" : !tr->step ? "step" : !tr->chisq ? "chisq" : "values");
+    return MCSAS_OK;
+}
+
+extern "C" int mcsas_hip_plan_fetch_trace(mcsas_plan *pl, int32_t slot, mcsas_trace *tr) {
+    if (!pl) return fail(MCSAS_EINVAL, "fetch_trace: null plan");
+    if (pl->trace_capacity < 1) return fail(MCSAS_EINVAL, "fetch_trace: the plan has no trace (mcsas_hip_plan_set_trace)");
+    if (int rc = check_trace_arrays("fetch_trace", tr)) return rc;
+    if (tr->capacity != pl->trace_capacity) return fail(MCSAS_EINVAL, "fetch_trace: trace capacity %d, the plan's is %d", (int)tr->capacity, (int)pl->trace_capacity);
+    if (slot < 0 || slot >= MCSAS_PLAN_SLOTS) return fail(MCSAS_EINVAL, "fetch_trace: slot %d (0..%d)", (int)slot, MCSAS_PLAN_SLOTS - 1);
+    mcsas_plan::Slot &s = pl->slots[slot];
+    if (!s.launched || !s.traced || !s.d_trace) return fail(MCSAS_EINVAL, "fetch_trace: slot %d holds no traced launch", (int)slot);
+    DeviceGuard dev_guard;
+    HIPCHK(hipSetDevice(pl->dev));
+    HIPCHK(hipEventSynchronize(s.ev1));
+    const size_t R = pl->prob.n_reps, K = (size_t)pl->trace_capacity, P = pl->prob.n_active;
+    std::vector<ChainOut> ho(R);
+    HIPCHK(hipMemcpy(ho.data(), s.d_out, sizeof(ChainOut) * R, hipMemcpyDeviceToHost));
+    std::vector<char> h(trace_record_bytes(R, K, P) + 8 * R);
+    HIPCHK(hipMemcpy(h.data(), s.d_trace, h.size(), hipMemcpyDeviceToHost));
+    const int64_t *hstep = (const int64_t *)h.data();
+    const double *hchi = (const double *)(h.data() + 8 * R * K), *hval = (const double *)(h.data() + 16 * R * K);
+    const double *hchi0 = (const double *)(h.data() + (16 + 8 * P) * R * K);
+    const double nan = std::nan("");
+    // [rep][capacity] -> the caller's [capacity][n_reps]; what lies behind the last attempt's moves is an earlier attempt's or nothing
+    for (size_t r = 0; r < R; ++r) {
+        const int64_t moves = ho[r].num_moves;
+        tr->count[r] = moves; tr->chisq0[r] = hchi0[r];
+        for (size_t i = 0; i < K; ++i) {
+            const bool kept = (int64_t)i < moves;
+            tr->step[i * R + r] = kept ? hstep[r * K + i] : -1;
+            tr->chisq[i * R + r] = kept ? hchi[r * K + i] : nan;
+            for (size_t p = 0; p < P; ++p) tr->values[(i * P + p) * R + r] = kept ? hval[(r * K + i) * P + p] : nan;
+        }
+    }
+    return MCSAS_OK;
+}
+
 // marks the plans of a launch that returns early: work of theirs is on the stream that no end event covers (mcsas_hip_plan_destroy)
 struct FailGuard {
     mcsas_plan *const *plans; int n; bool ok = false;
@@ -930,12 +1036,15 @@ extern "C" int mcsas_hip_plan_launch_slot(mcsas_plan *pl, void *hip_stream, int3
         if (int rc = pipeline_launch(pl, k, st)) return rc;
     } else {
         // the argument block by value, then what the family takes besides (a plug-in: the same arguments, through its code-object module)
-        void *kargs[] = {(void *)&pl->args, k.arg2 == KernelRef::ARG2_WG ? (void *)&pl->wg : (k.arg2 == KernelRef::ARG2_Q3INV ? (void *)&pl->d_q3inv : nullptr)};
+        if (k.arg2 == KernelRef::ARG2_TRACE) { if (int rc = make_slot_trace(pl, s)) return rc; }
+        void *kargs[] = {(void *)&pl->args, k.arg2 == KernelRef::ARG2_WG ? (void *)&pl->wg : (k.arg2 == KernelRef::ARG2_Q3INV ? (void *)&pl->d_q3inv
+                                            : (k.arg2 == KernelRef::ARG2_TRACE ? (void *)&s.trace : nullptr))};
         if (int rc = raise_lds_limit(k, pl->lds_bytes)) return rc;
         HIPCHK(hipEventRecord(s.ev0, st));
         if (pl->has_start) { if (int rc = enqueue_start(pl, st)) return rc; }
         if (int rc = launch_kernel(k, (unsigned)pl->prob.n_reps, kargs, pl->lds_bytes, st)) return rc;
         HIPCHK(hipEventRecord(s.ev1, st));
+        s.traced = k.arg2 == KernelRef::ARG2_TRACE;
     }
     s.launched = true; guard.ok = true;
     return MCSAS_OK;
@@ -1075,6 +1184,8 @@ extern "C" int mcsas_hip_plan_launch_batch(mcsas_plan *const *plans, int32_t n, 
         if (!pl) return fail(MCSAS_EINVAL, "launch_batch: plan %d is null", i);
         if (pl->mode != MCSAS_EXEC_WAVE || pl->wide)
             return fail(MCSAS_EINVAL, "launch_batch: plan %d runs in exec_mode %d; a batch takes wavefront-per-chain plans only (exec_mode %d)", i, pl->mode, MCSAS_EXEC_WAVE);
+        if (pl->trace_capacity > 0)
+            return fail(MCSAS_EINVAL, "launch_batch: plan %d has a trace (mcsas_hip_plan_set_trace, capacity %d); a batch records none: clear it, or launch the plan alone", i, (int)pl->trace_capacity);
         if (pl->dev != plans[0]->dev) return fail(MCSAS_EINVAL, "launch_batch: plan %d is on device %d, plan 0 on device %d", i, pl->dev, plans[0]->dev);
         if (pl->prob.stop != plans[0]->prob.stop) return fail(MCSAS_EINVAL, "launch_batch: plan %d has another stop word than plan 0 (all plans of a batch share one, or none has one)", i);
         for (int j = 0; j < i; ++j)
@@ -1151,7 +1262,7 @@ extern "C" int mcsas_hip_plan_launch_batch(mcsas_plan *const *plans, int32_t n, 
         if (int rc = raise_lds_limit(groups[g], g_lds[g])) return rc;
         if (int rc = launch_kernel(groups[g], grid, kargs, g_lds[g], st)) return rc;
         for (int i = 0; i < n; ++i)
-            if (group_of[i] == (int)g) { HIPCHK(hipEventRecord(plans[i]->cur().ev1, st)); plans[i]->cur().launched = true; }
+            if (group_of[i] == (int)g) { HIPCHK(hipEventRecord(plans[i]->cur().ev1, st)); plans[i]->cur().launched = true; plans[i]->cur().traced = false; }
     }
     guard.ok = true;
     return MCSAS_OK;
@@ -1335,6 +1446,47 @@ extern "C" int mcsas_hip_analyse_from(const mcsas_problem *p, const double *star
     q.exec_mode = q_split ? MCSAS_EXEC_WORKGROUP : MCSAS_EXEC_WAVE;
     if (q.n_devices > 1) return analyse_sharded(&q, res, start);
     return analyse_one(&q, res, start, q.n_reps, 0);
+}
+
+// mcsas_hip_analyse (MCSAS_EXEC_WAVE), or mcsas_hip_analyse_from when a start is given, with the accepted moves of every repetition's
+// last attempt (include/mcsas_hip.h); every refusal before a device is touched.
+extern "C" int mcsas_hip_analyse_traced(const mcsas_problem *p, const double *start, mcsas_result *res, mcsas_trace *tr) {
+    if (!p || !res) return fail(MCSAS_EINVAL, "analyse_traced: null argument");
+    if (p->struct_size != sizeof(mcsas_problem))
+        return fail(MCSAS_EINVAL, "analyse_traced: mcsas_problem size %u, library expects %zu (ABI mismatch)", p->struct_size, sizeof(mcsas_problem));
+    if (int rc = check_trace_arrays("analyse_traced", tr)) return rc;
+    if (p->n_active == 0) {                                                    // one contribution at fixed values: no move is ever made
+        const int rc = mcsas_hip_analyse(p, res);
+        if (!rc) tr->count[0] = 0;
+        return rc;
+    }
+    if (p->exec_mode != MCSAS_EXEC_AUTO && p->exec_mode != MCSAS_EXEC_WAVE)
+        return fail(MCSAS_EINVAL, "analyse_traced: exec_mode %d (%s) asked; a trace needs exec_mode = MCSAS_EXEC_WAVE (%d, or 0)", p->exec_mode, exec_mode_name(p->exec_mode), MCSAS_EXEC_WAVE);
+    if (p->nq > 64 * WAVE) return fail(MCSAS_EINVAL, "analyse_traced: nq %d > %d: one wavefront per chain does not take it, and only that kernel keeps a trace", p->nq, 64 * WAVE);
+    if (p->n_devices > 1) return fail(MCSAS_EINVAL, "analyse_traced: n_devices %d: a trace is kept on one device", p->n_devices);
+    if (p->n_active < 0 || p->n_active > MCSAS_MAX_ACTIVE) return fail(MCSAS_EINVAL, "n_active %d out of range", p->n_active);
+    if (p->n_contrib < 1 || p->n_reps < 1) return fail(MCSAS_EINVAL, "n_contrib and n_reps must be >= 1");
+    if ((size_t)tr->capacity > TRACE_MAX_BYTES / ((size_t)p->n_reps * (16 + 8 * (size_t)p->n_active)))
+        return fail(MCSAS_EINVAL, "analyse_traced: %d repetitions x capacity %d x %d bytes per move exceed 2 GiB", p->n_reps, (int)tr->capacity, 16 + 8 * p->n_active);
+    if (start) { if (int rc = check_start_finite("analyse_traced", start, (size_t)p->n_contrib, (size_t)p->n_active, (size_t)p->n_reps, 0, (size_t)p->n_reps)) return rc; }
+    mcsas_problem q = *p;
+    q.exec_mode = MCSAS_EXEC_WAVE;
+    q.n_devices = 0;
+    mcsas_plan *pl = nullptr;
+    int rc = mcsas_hip_plan_create(&q, &pl);
+    if (rc) return rc;
+    if (start) rc = mcsas_hip_plan_set_start(pl, start, q.n_reps, 0);
+    if (!rc) rc = mcsas_hip_plan_set_trace(pl, tr->capacity);
+    if (!rc) rc = mcsas_hip_plan_launch(pl, nullptr);
+    if (!rc) rc = mcsas_hip_plan_fetch(pl, res);
+    // (a replay stream that ran out is reported by the fetch; the trace of what ran is still the caller's)
+    if (!rc || rc == MCSAS_ESTREAM) {
+        const std::string e = g_err;
+        const int rt = mcsas_hip_plan_fetch_trace(pl, 0, tr);
+        if (rt) rc = rt; else g_err = e;
+    }
+    mcsas_hip_plan_destroy(pl);
+    return rc;
 }
 
 // ------------------------------------------------------------------------------ rows evaluated by the caller (ABI 4)

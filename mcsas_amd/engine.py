@@ -183,6 +183,47 @@ class ChainResults:
         r.seconds = as_dp(self.seconds)
         r.draws = self.draws.ctypes.data_as(C.POINTER(C.c_int64))
         self.c = r
+        self.trace = None                 # a ChainTrace where the analysis was asked for one (analyse(trace=K), Plan.set_trace)
+
+
+class ChainTrace:
+    """numpy-backed `mcsas_trace`: per repetition the accepted moves of its last attempt (what the reference logs as "good iter",
+    mcsas.py:385-390).  count[R] = all moves made (== num_moves), chisq0[R] = reduced chi-squared of the attempt's initial set;
+    the first min(count, capacity) moves: step[K][R] (numIter of the move; contribution = step % n_contrib), chisq[K][R] (conval
+    after it), values[K][P][R] (the accepted set); entries behind them are -1 / NaN."""
+
+    def __init__(self, capacity, n_active, n_reps):
+        self.capacity = int(capacity)
+        self.count = np.zeros(n_reps, dtype=np.int64); self.chisq0 = np.full(n_reps, np.nan)
+        self.step = np.full((self.capacity, n_reps), -1, dtype=np.int64)
+        self.chisq = np.full((self.capacity, n_reps), np.nan)
+        self.values = np.full((self.capacity, n_active, n_reps), np.nan)
+        t = _lib.Trace()
+        t.struct_size = C.sizeof(_lib.Trace)
+        t.capacity = self.capacity
+        t.count = self.count.ctypes.data_as(C.POINTER(C.c_int64)); t.chisq0 = as_dp(self.chisq0)
+        t.step = self.step.ctypes.data_as(C.POINTER(C.c_int64)); t.chisq = as_dp(self.chisq); t.values = as_dp(self.values)
+        self.c = t
+
+    def asdict(self):
+        return dict(count=self.count, chisq0=self.chisq0, step=self.step, chisq=self.chisq, values=self.values)
+
+
+def _check_trace(trace, model: ModelSetup, st: Settings, nq, who="analyse"):
+    """The capacity of a trace as an int; ValueError where no traced kernel exists for the analysis — before any library call: a trace
+    is kept by the wavefront-per-chain kernel, on one device."""
+    k = int(trace)
+    if k < 1:
+        raise ValueError("%s: trace is the number of moves kept per repetition (>= 1), got %r" % (who, trace))
+    if model.model_id == MODEL_HOST:
+        raise ValueError("%s: a model that exists only as host code keeps no trace (a trace runs one wavefront per chain)" % who)
+    if st.exec_mode not in (EXEC_AUTO, EXEC_WAVE):
+        raise ValueError("%s: a trace runs one wavefront per chain; exec_mode %d was asked (0 or 1)" % (who, st.exec_mode))
+    if nq > WAVE_MAX_Q:
+        raise ValueError("%s: %d q-points; a trace runs one wavefront per chain, which takes up to %d" % (who, nq, WAVE_MAX_Q))
+    if st.devices:
+        raise ValueError("%s: a trace is kept on one device; a device list %r was given" % (who, tuple(st.devices)))
+    return k
 
 
 def _check_start(start, model: ModelSetup, st: Settings, who="analyse"):
@@ -202,11 +243,15 @@ def _start_columns(a, st: Settings, rep_first, who="analyse"):
         raise ValueError("%s: start has %d repetitions, %d..%d asked" % (who, a.shape[2], rep_first, rep_first + int(st.n_reps) - 1))
 
 
-def analyse(model: ModelSetup, q, intensity, sigma, st: Settings, replay=None, stop=None, smear=None, start=None) -> ChainResults:
+def analyse(model: ModelSetup, q, intensity, sigma, st: Settings, replay=None, stop=None, smear=None, start=None, trace=None) -> ChainResults:
     """All repetitions of McSAS.analyse (mcsas.py:214-262) in one kernel launch.  `start`: [n_contrib][n_active][n_reps] (a
     ChainResults.contribs; further repetitions are ignored), the set the first attempt of every repetition starts from instead of
     a random one (mcsas_hip_analyse_from, include/mcsas_hip.h) — one wavefront per chain, or with exec_mode 2 and more than
-    WG_MAX_Q q-points the q-split workgroup kernel (the only one beyond WAVE_MAX_Q); exec_mode 2 below that and 3 are refused."""
+    WG_MAX_Q q-points the q-split workgroup kernel (the only one beyond WAVE_MAX_Q); exec_mode 2 below that and 3 are refused.
+    `trace`: K >= 1 keeps the first K accepted moves of every repetition's last attempt in the result's .trace (a ChainTrace;
+    mcsas_hip_analyse_traced): one wavefront per chain, cold or from a start; every other array is what it is without a trace."""
+    if trace is not None:
+        trace = _check_trace(trace, model, st, int(np.size(q)))
     if start is not None and model.n_active > 0:
         a = _check_start(start, model, st)
         _start_columns(a, st, 0)
@@ -215,7 +260,11 @@ def analyse(model: ModelSetup, q, intensity, sigma, st: Settings, replay=None, s
     lib = _lib.load(tuning=bool(st.debug_flags))
     prob = HipProblem(model, q, intensity, sigma, st, replay, stop, smear)
     res = ChainResults(st.n_contrib, model.n_active, st.n_reps, len(prob.q))
-    if start is not None and model.n_active > 0:
+    if trace is not None:
+        res.trace = ChainTrace(trace, model.n_active, st.n_reps)
+        given = as_dp(a) if start is not None and model.n_active > 0 else None
+        check(lib.mcsas_hip_analyse_traced(C.byref(prob.c), given, C.byref(res.c), C.byref(res.trace.c)), lib)
+    elif start is not None and model.n_active > 0:
         check(lib.mcsas_hip_analyse_from(C.byref(prob.c), as_dp(a), C.byref(res.c)), lib)
     else:
         check(lib.mcsas_hip_analyse(C.byref(prob.c), C.byref(res.c)), lib)
@@ -409,6 +458,7 @@ class Plan:
         self.prob = HipProblem(model, q, intensity, sigma, st, replay, stop, smear)
         self.h = C.c_void_p()
         check(self.lib.mcsas_hip_plan_create(C.byref(self.prob.c), C.byref(self.h)), self.lib)
+        self.trace_capacity = 0
 
     def launch(self, stream=None, slot=0):
         """Enqueues one analysis.  `slot`: which of the plan's result sets (mcsas_hip.h: MCSAS_PLAN_SLOTS) it writes — launch
@@ -419,7 +469,23 @@ class Plan:
         st = self.prob.st
         res = ChainResults(st.n_contrib, self.prob.model.n_active, st.n_reps, len(self.prob.q)) if want_arrays else None
         check(self.lib.mcsas_hip_plan_fetch_slot(self.h, C.c_int32(slot), C.byref(res.c) if res is not None else None), self.lib)
+        if res is not None and self.trace_capacity:
+            res.trace = self.fetch_trace(slot)
         return res
+
+    def set_trace(self, capacity):
+        """Every later launch of this plan keeps the first `capacity` accepted moves of every repetition's last attempt, per slot
+        (mcsas_hip_plan_set_trace); fetch() then fills ChainResults.trace.  0 or None clears it.  Plans in the wavefront mode; the
+        others refuse, and so does launch_batch for a plan with a trace."""
+        k = int(capacity or 0)
+        check(self.lib.mcsas_hip_plan_set_trace(self.h, C.c_int32(k)), self.lib)
+        self.trace_capacity = k
+
+    def fetch_trace(self, slot=0, capacity=None):
+        """The trace of the slot's last launch (mcsas_hip_plan_fetch_trace), after its fetch()."""
+        tr = ChainTrace(self.trace_capacity if capacity is None else capacity, self.prob.model.n_active, self.prob.st.n_reps)
+        check(self.lib.mcsas_hip_plan_fetch_trace(self.h, C.c_int32(slot), C.byref(tr.c)), self.lib)
+        return tr
 
     def set_start(self, contribs, rep_first=0):
         """Every later launch of this plan (launch_batch included) starts repetition r from contribs[:, :, rep_first + r]

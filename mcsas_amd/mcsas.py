@@ -100,11 +100,34 @@ class McSAS(object):
             return engine.EXEC_WORKGROUP
         return engine.EXEC_WAVE
 
+    def _check_trace_mode(self, trace, data=None):
+        """The execution mode a traced analysis of `data` (default: the current data) asks for, or None without a trace: one wavefront
+        per chain, the only kernel that keeps a trace (include/mcsas_hip.h: mcsas_hip_analyse_traced).  ValueError where execMode asks
+        for another, for more than engine.WAVE_MAX_Q points, for a model that exists only as host code and for a device list."""
+        if trace is None:
+            return None
+        data = self.data if data is None else data
+        nq = 0 if data is None else int(np.size(data.q))
+        if int(trace) < 1:
+            raise ValueError("McSAS: trace is the number of moves kept per repetition (>= 1), got %r" % (trace,))
+        if self.execMode not in (engine.EXEC_AUTO, engine.EXEC_WAVE):
+            raise ValueError("McSAS: a trace runs one wavefront per chain; execMode %d was asked (0 or 1)" % self.execMode)
+        if nq > engine.WAVE_MAX_Q:
+            raise ValueError("McSAS: %d points; a trace runs one wavefront per chain, which takes up to %d" % (nq, engine.WAVE_MAX_Q))
+        if self.devices:
+            raise ValueError("McSAS: a trace is kept on one device; the device list %r was given" % (self.devices,))
+        if self.model is not None and setup_from_model(self.model, data).model_id == engine.MODEL_HOST:
+            raise ValueError("McSAS: a model that exists only as host code keeps no trace (it runs through host-evaluated rows)")
+        return engine.EXEC_WAVE
+
     def calc(self, **kwargs):                                # mcsas.py:149-179
-        """`start=`: an [N][P][R] array of contributions, typically an earlier `algo.result[0]['contribs']`: the first attempt of
+        """`trace=K`: keeps the first K accepted moves of every repetition (step, chi-squared, new values: what the reference logs
+        as "good iter", mcsas.py:385-390) under `algo.result[0]['trace']`; combines with `start=`.
+        `start=`: an [N][P][R] array of contributions, typically an earlier `algo.result[0]['contribs']`: the first attempt of
         every repetition starts from it instead of a random set — to continue a run that ended at maxIterations, to refine a result
         to a tighter criterion, or to warm-start from a neighbouring data set's result (see analyse)."""
         self._check_start_mode(kwargs.get("start"))
+        self._check_trace_mode(kwargs.get("trace"))
         self.result = []
         self.stop = False
         assert self.data is not None
@@ -113,7 +136,7 @@ class McSAS(object):
         if not self.model.paramCount():
             logging.warning("No parameters to analyse given! Breaking up.")
             return
-        self.analyse(replay=kwargs.get("replay"), start=kwargs.get("start"))   # (replay: tests feed the uniform stream the reference consumed)
+        self.analyse(replay=kwargs.get("replay"), start=kwargs.get("start"), trace=kwargs.get("trace"))   # (replay: tests feed the uniform stream the reference consumed)
         if not len(self.result):
             return
         self.histogram()
@@ -130,11 +153,14 @@ class McSAS(object):
             show_incomplete=self.showIncomplete(), seed=seed, device=self.device, devices=self.devices,
             waves_per_chain=self.wavesPerChain, exec_mode=self.execMode)
 
-    def analyse(self, replay=None, start=None):              # mcsas.py:191-285
+    def analyse(self, replay=None, start=None, trace=None):  # mcsas.py:191-285
         """`start`: [numContribs][active parameters][>= numReps] — mcFit's rset of the first attempt of each repetition, in place of
         generateParameters(numContribs) (mcsas.py:317); later attempts draw a fresh set as always.  A start runs one wavefront per chain
         for this call, or the q-split workgroup kernel (_check_start_mode; include/mcsas_hip.h: mcsas_hip_analyse_from); an explicit
-        execMode of pipeline, or of workgroup with up to 1024 points, raises ValueError."""
+        execMode of pipeline, or of workgroup with up to 1024 points, raises ValueError.
+        `trace`: K >= 1 stores the first K accepted moves of every repetition's last attempt under result[0]['trace'] (count, chisq0,
+        step[K][R], chisq[K][R], values[K][P][R]: engine.ChainTrace); one wavefront per chain (_check_trace_mode)."""
+        self._check_trace_mode(trace)
         if self.result is None:
             self.result = []
         data, model = self.data, self.model
@@ -143,6 +169,10 @@ class McSAS(object):
         else:
             numContribs, numReps = self.numContribs(), self.numReps()
         pr = self._problem(numContribs, numReps, replay, start)
+        if trace is not None:
+            if pr.get("start") is not None and pr["st"].exec_mode != engine.EXEC_WAVE:
+                raise ValueError("McSAS: this start runs the q-split workgroup kernel, which keeps no trace")
+            pr["st"].exec_mode = engine.EXEC_WAVE
         if pr["model"].model_id == engine.MODEL_HOST:
             # a model with Python formfactor / volume only: its rows are evaluated here, by the model's own calcIntensity with the
             # set-value-and-restore semantics of ScatteringModel.calc (scatteringmodel.py:86-104); the device does the rest
@@ -154,8 +184,10 @@ class McSAS(object):
                                            replay=pr["replay"], stop=pr["stop"], window=self.hostRowWindow)
         else:
             res = engine.analyse(pr["model"], pr["q"], pr["intensity"], pr["sigma"], pr["st"],
-                                 replay=pr["replay"], stop=pr["stop"], smear=pr["smear"], start=pr.get("start"))
+                                 replay=pr["replay"], stop=pr["stop"], smear=pr["smear"], start=pr.get("start"), trace=trace)
         self._store(res, numReps)
+        if trace is not None and res.trace is not None and len(self.result):
+            self.result[0]['trace'] = res.trace.asdict()
 
     def _problem(self, numContribs=None, numReps=None, replay=None, start=None):
         """What analyse() hands to the library for the current data / model / settings (engine.analyse_many takes a list of these).
