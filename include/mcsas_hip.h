@@ -209,6 +209,34 @@ typedef int (*mcsas_rows_callback)(void *user, int32_t n, const double *pset, do
 int mcsas_hip_analyse_host_rows(const mcsas_problem *problem, mcsas_rows_callback rows_cb, void *user, int32_t window,
                                 mcsas_result *result);
 
+/* ---- the same, with the rows of a round produced ON THE DEVICE by the caller (additive to ABI 5) -------------------------
+ * For a model the caller has as device code of its own (torch tensor lines, a kernel of a C caller): the proposals of a round are
+ * generated on the device (csrc/chain_feed.h: feed_draw_kernel — the draw source, generator transform and expression of the chain
+ * kernels, so the values are bit for bit those of MCSAS_EXEC_WAVE for the same seed or replay stream) straight into d_pset, the
+ * caller fills the rows of the whole round in d_rows, and feed_rows_kernel decides on them where they lie.  Nothing of a round
+ * crosses the bus but the round's metadata (up) and the chains' state (down).
+ *   d_pset [capacity_rows][n_active], d_rows [capacity_rows][row_stride]: the CALLER's device memory on problem->device;
+ *     row_stride = nq rounded up to 64.  The library zeroes d_rows once, at the start of the call.
+ *   rows_cb(user, n): d_pset[0..n) holds the round's parameter sets (activeParams() order, NOT yet clipped), complete on the device
+ *     when the callback is entered; the callback fills columns 0..nq of rows 0..n of d_rows and nothing else (the padding columns
+ *     stay zero), complete on the device when it returns; return 0, anything else aborts with MCSAS_ECALLBACK.  Calling thread only.
+ *   mcsas_hip_device_rows_shape (touches no device): *min_rows = max(n_contrib, window) is the least capacity_rows (one chain per
+ *     round); *useful_rows = min(n_reps * min_rows, 256 MiB / (row_stride * 8)), never below min_rows, is the most a round uses;
+ *     *row_stride as above.  window < 1: 64.  Any of the three may be NULL.
+ * Refused before a device is touched: NULL problem / rows_cb / result / d_pset / d_rows, a wrong struct_size, capacity_rows <
+ * min_rows, and everything mcsas_hip_analyse_host_rows refuses of a problem; after the device is selected: a buffer that is not
+ * device memory of that device (MCSAS_EINVAL, no kernel is launched on it).  A failed host allocation: MCSAS_ENOMEM.
+ * Everything else — the fields of problem that are read, the retry loop, stop, the replay rule (a draw behind the stream's end is
+ * 0.5; MCSAS_ESTREAM only if a step a chain TOOK needed one), result — is mcsas_hip_analyse_host_rows.
+ * Measured once (one MI355X, 2026-10-19; profiles/device_rows_ab.md): a Sphere typed as a Python model, 100 q x 200 contributions x
+ * 10 repetitions x 20 000 steps, window 64: 8.81 us of wall time per step through mcsas_hip_analyse_host_rows (numpy), 0.438 us
+ * through this entry point (the same model in torch), 20 times faster; the device run is bound by its rounds (0.28 ms each). */
+typedef int (*mcsas_device_rows_callback)(void *user, int32_t n);
+int mcsas_hip_device_rows_shape(const mcsas_problem *problem, int32_t window, int64_t *min_rows, int64_t *useful_rows,
+                                int32_t *row_stride);
+int mcsas_hip_analyse_device_rows(const mcsas_problem *problem, double *d_pset, double *d_rows, int64_t capacity_rows,
+                                  mcsas_device_rows_callback rows_cb, void *user, int32_t window, mcsas_result *result);
+
 /* ---- resident plan: same work split so that inputs/workspaces live in HBM across runs ------- */
 typedef struct mcsas_plan mcsas_plan;
 int  mcsas_hip_plan_create(const mcsas_problem *problem, mcsas_plan **plan);

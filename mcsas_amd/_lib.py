@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("MCSAS_HIP_LIB") or os.path.join(os.path.dirname(os.pa
 
 # every symbol include/mcsas_hip.h declares (tests check that the library exports all of them)
 SYMBOLS = (
-    "mcsas_hip_analyse", "mcsas_hip_analyse_host_rows", "mcsas_hip_shard", "mcsas_hip_plan_create", "mcsas_hip_plan_launch", "mcsas_hip_plan_fetch",
+    "mcsas_hip_analyse", "mcsas_hip_analyse_host_rows", "mcsas_hip_device_rows_shape", "mcsas_hip_analyse_device_rows", "mcsas_hip_shard", "mcsas_hip_plan_create", "mcsas_hip_plan_launch", "mcsas_hip_plan_fetch",
     "mcsas_hip_plan_launch_slot", "mcsas_hip_plan_fetch_slot",
     "mcsas_hip_plan_last_ms", "mcsas_hip_plan_total_steps", "mcsas_hip_plan_reseed", "mcsas_hip_plan_info",
     "mcsas_hip_plan_destroy", "mcsas_hip_plan_launch_batch", "mcsas_hip_analyse_batch", "mcsas_hip_plan_set_start", "mcsas_hip_analyse_from",
@@ -38,6 +38,8 @@ _i32p = C.POINTER(C.c_int32)
 
 # mcsas_rows_callback (include/mcsas_hip.h): int cb(void *user, int32_t n, const double *pset, double *rows)
 RowsCallback = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, _dp, _dp)
+# mcsas_device_rows_callback: int cb(void *user, int32_t n) — the sets and rows lie in the caller's device buffers
+DeviceRowsCallback = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32)
 
 
 class HistogramSpec(C.Structure):
@@ -128,6 +130,9 @@ def load(tuning=False):
     lib.mcsas_hip_device_count.restype = C.c_int
     lib.mcsas_hip_analyse.argtypes = [C.POINTER(Problem), C.POINTER(Result)]
     lib.mcsas_hip_analyse_host_rows.argtypes = [C.POINTER(Problem), RowsCallback, C.c_void_p, C.c_int32, C.POINTER(Result)]
+    lib.mcsas_hip_device_rows_shape.argtypes = [C.POINTER(Problem), C.c_int32, _i64p, _i64p, _i32p]
+    lib.mcsas_hip_analyse_device_rows.argtypes = [C.POINTER(Problem), C.c_void_p, C.c_void_p, C.c_int64, DeviceRowsCallback, C.c_void_p,
+                                                  C.c_int32, C.POINTER(Result)]
     lib.mcsas_hip_shard.argtypes = [C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p]
     lib.mcsas_hip_plan_create.argtypes = [C.POINTER(Problem), C.POINTER(C.c_void_p)]
     lib.mcsas_hip_plan_launch.argtypes = [C.c_void_p, C.c_void_p]

@@ -1,4 +1,5 @@
-// chain_feed.h — Monte-Carlo chains whose intensity rows are evaluated by the HOST (mcsas_hip_analyse_host_rows).
+// chain_feed.h — Monte-Carlo chains whose intensity rows are evaluated by the CALLER: on the host (mcsas_hip_analyse_host_rows), or
+// on the device into a buffer of the caller's (mcsas_hip_analyse_device_rows; feed_draw_kernel below generates the proposals there).
 //
 // The reference's plug-in contract is a ScatteringModel subclass whose formfactor / volume are Python
 // (bases/model/scatteringmodel.py:16-58, sasmodel.py:46-79).  A proposal depends on the random stream only, never on the state
@@ -120,6 +121,38 @@ __global__ __launch_bounds__(64) void feed_rows_kernel(const FeedArgs f) {
         s.converged = !(s.chi2 > a.conv_crit);
     }
     if (lane == 0) f.state[rep] = s;
+}
+
+// The proposals of a round, generated on the device into the caller's buffer (mcsas_hip_analyse_device_rows): for every chain that
+// has rows in the round the `count` parameter sets feed_rows_kernel will decide on, pset[(first + k) * P + c].  The draw source, the
+// generator transform and the expression are those of the chain kernels (chain_body.inc: the initial set parameter-major, P draws
+// per step after it), compiled with the same flags, so a value is bit for bit what MCSAS_EXEC_WAVE proposes at the same place of the
+// same stream.  pos[rep] is where the chain's attempt starts in its stream, pos[n_reps + rep] the steps it has taken (the host's
+// bookkeeping between rounds).  A draw behind a replay stream's end is 0.5 and latches nothing: whether a step the chain TOOK
+// needed one is known to the host when the chain is through.  One block per chain, thread k strides over the chain's rows.
+__global__ __launch_bounds__(64) void feed_draw_kernel(const FeedArgs f, double *pset, const int64_t *pos) {
+    const ChainArgs &a = f.c;
+    const int rep = blockIdx.x;
+    const int n = f.count[rep], kind = f.kind[rep];
+    if (n == 0 || kind == FEED_END) return;
+    const int N = a.n_contrib, P = a.model.n_active;
+    const DrawSource src{a.replay ? a.replay + (size_t)rep * a.replay_len : nullptr, a.replay_len, a.seed,
+                         (uint32_t)(a.rep_offset + rep)};
+    const uint64_t draw_pos = (uint64_t)pos[rep];
+    const int64_t num_iter = pos[a.n_reps + rep];
+    double *out = pset + (size_t)f.first[rep] * P;
+    int overflow = 0;
+    for (int k = threadIdx.x; k < n; k += WAVE)
+        for (int c = 0; c < P; ++c) {
+            double v;
+            if (kind == FEED_INIT && a.start_from_min) v = a.start_value[c];          // mcsas.py:310-315
+            else {
+                const double u = kind == FEED_INIT ? src.at(draw_pos + (uint64_t)c * N + k, overflow)      // parameter-major
+                                                   : src.at(draw_pos + (uint64_t)(num_iter + k) * P + c, overflow);   // mcsas.py:358
+                v = gen_transform(a.gen_kind[c], u) * (a.gen_hi[c] - a.gen_lo[c]) + a.gen_lo[c];
+            }
+            out[(size_t)k * P + c] = v;
+        }
 }
 
 }  // namespace mcsas

@@ -17,7 +17,7 @@ from ._lib import MAX_ACTIVE, MAX_DEVICES, MAX_PARAMS, Problem, Result, as_dp, c
 MODEL_SPHERE, MODEL_CYL_ISO, MODEL_ELL_CS, MODEL_KHOLODENKO = 0, 1, 2, 3
 MODEL_ELL_ISO, MODEL_SPH_CS, MODEL_GAUSS_CHAIN, MODEL_LMA_SPHERE = 4, 5, 6, 7
 MODEL_PLUGIN0 = 64      # first id of a run-time model plug-in (include/mcsas_hip.h: MCSAS_MODEL_PLUGIN0)
-MODEL_HOST = -1         # a model that exists only as host code (Python formfactor / volume): rows through analyse_host_rows
+MODEL_HOST = -1         # a model that exists only as host code (Python formfactor / volume: rows through analyse_host_rows; torch calcIntensityBatch: analyse_device_rows)
 
 
 class PluginCompileError(ValueError):
@@ -293,6 +293,78 @@ def analyse_host_rows(model: ModelSetup, q, intensity, sigma, st: Settings, row_
             return 1
 
     rc = lib.mcsas_hip_analyse_host_rows(C.byref(prob.c), _lib.RowsCallback(cb), None, int(window), C.byref(res.c))
+    if failure:
+        raise failure[0]
+    check(rc, lib)
+    return res
+
+
+def device_rows_shape(model: ModelSetup, q, st: Settings, window=64):
+    """(min_rows, useful_rows, row_stride) of analyse_device_rows for this problem (mcsas_hip_device_rows_shape; no device is touched):
+    the least and the most rows of a round, and the row pitch of the rows buffer (the q count rounded up to 64)."""
+    q = f64(q).ravel()
+    return _rows_shape(_lib.load(), HipProblem(model, q, np.ones_like(q), np.ones_like(q), st), window)
+
+
+def _rows_shape(lib, prob, window):
+    lo, hi, stride = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    check(lib.mcsas_hip_device_rows_shape(C.byref(prob.c), int(window), C.byref(lo), C.byref(hi), C.byref(stride)), lib)
+    return lo.value, hi.value, stride.value
+
+
+def _one_hip_runtime():
+    """A torch wheel brings a HIP runtime of its own.  Loaded after torch, libmcsas_hip.so binds to that one (same soname) and a
+    tensor is device memory to both; loaded before torch, it has bound to the system's runtime, the process holds two, and memory
+    of the one is unknown to the other.  RuntimeError then, instead of an analysis on buffers the library cannot see."""
+    try:
+        with open("/proc/self/maps") as f:
+            paths = {line.split()[-1] for line in f if "libamdhip64.so" in line}
+    except OSError:
+        return
+    if len(paths) > 1:
+        raise RuntimeError("analyse_device_rows: this process holds two HIP runtimes (%s): the library was loaded before torch. "
+                           "Import torch before the first call into mcsas_amd" % ", ".join(sorted(paths)))
+
+
+def analyse_device_rows(model: ModelSetup, q, intensity, sigma, st: Settings, row_fn, replay=None, stop=None, window=64,
+                        capacity=None) -> ChainResults:
+    """McSAS.analyse for a model whose rows the caller computes ON THE DEVICE with torch (mcsas_hip_analyse_device_rows,
+    include/mcsas_hip.h): the library generates the proposals of a round into a torch tensor, `row_fn(pset[n][n_active],
+    rows[n][nq])` fills the rows view in place, or returns a tensor [n][nq] that is copied into it, and the device does the rest
+    of mcFit on the rows where they lie.  pset is not yet clipped.  `capacity`: rows of the two tensors (default: the most a round
+    uses, device_rows_shape).  torch is imported here, not with the package."""
+    import torch                                 # (ahead of the library's first load: see _one_hip_runtime)
+    lib = _lib.load()
+    _one_hip_runtime()
+    prob = HipProblem(model, q, intensity, sigma, st, replay, stop, None)
+    prob.c.model_id = MODEL_HOST
+    nq, P = len(prob.q), model.n_active
+    min_rows, useful_rows, stride = _rows_shape(lib, prob, window)
+    capacity = int(useful_rows if capacity is None else capacity)
+    if capacity < min_rows:
+        raise ValueError("analyse_device_rows: capacity %d < %d rows, what one chain's round takes (max(n_contrib, window))" % (capacity, min_rows))
+    res = ChainResults(st.n_contrib, P, st.n_reps, nq)
+    device = torch.device("cuda", torch.cuda.current_device() if st.device < 0 else int(st.device))
+    pset = torch.empty((capacity, P), dtype=torch.float64, device=device)
+    rows = torch.empty((capacity, stride), dtype=torch.float64, device=device)
+    torch.cuda.synchronize(device)               # (the library works on the null stream of its own)
+    failure = []
+
+    def cb(user, n):
+        try:
+            with torch.cuda.device(device):
+                view = rows[:n, :nq]
+                out = row_fn(pset[:n], view)
+                if out is not None and out is not view:
+                    view.copy_(torch.as_tensor(out, dtype=torch.float64, device=device).reshape(n, nq))
+                torch.cuda.current_stream(device).synchronize()
+            return 0
+        except BaseException as e:           # (an exception must not cross the C frame: hand it over and re-raise below)
+            failure.append(e)
+            return 1
+
+    rc = lib.mcsas_hip_analyse_device_rows(C.byref(prob.c), C.c_void_p(pset.data_ptr()), C.c_void_p(rows.data_ptr()), capacity,
+                                           _lib.DeviceRowsCallback(cb), None, int(window), C.byref(res.c))
     if failure:
         raise failure[0]
     check(rc, lib)

@@ -16,7 +16,8 @@ import numpy as np
 
 from . import engine
 from .parameter import isActiveFitParam
-from .scatteringmodels import setup_from_model, host_model_calc
+from .scatteringmodels import (setup_from_model, host_model_calc, is_batch_model, batch_model_calc, batch_clip,
+                               refuse_batch_smearing)
 
 
 class _Setting(object):
@@ -177,11 +178,24 @@ class McSAS(object):
             # a model with Python formfactor / volume only: its rows are evaluated here, by the model's own calcIntensity with the
             # set-value-and-restore semantics of ScatteringModel.calc (scatteringmodel.py:86-104); the device does the rest
             c = self.compensationExponent()
+            if is_batch_model(model):
+                # ... or with calcIntensityBatch in torch: the rows of a whole round in one call on the device, where the library
+                # generated the proposals and decides on them (mcsas_hip_analyse_device_rows); the clipping of setValue on a copy
+                refuse_batch_smearing(model, data)
+                qdev = []
 
-            def rows(pset):
-                return host_model_calc(model, data, pset, c, want_rows=True)[4]
-            res = engine.analyse_host_rows(pr["model"], pr["q"], pr["intensity"], pr["sigma"], pr["st"], rows,
-                                           replay=pr["replay"], stop=pr["stop"], window=self.hostRowWindow)
+                def rows_on_device(pset, out):
+                    if not qdev:
+                        import torch
+                        qdev.append(torch.as_tensor(np.ascontiguousarray(pr["q"], dtype=np.float64), device=pset.device).reshape(-1))
+                    return model.calcIntensityBatch(qdev[0], batch_clip(model, pset), c)[0]
+                res = engine.analyse_device_rows(pr["model"], pr["q"], pr["intensity"], pr["sigma"], pr["st"], rows_on_device,
+                                                 replay=pr["replay"], stop=pr["stop"], window=self.hostRowWindow)
+            else:
+                def rows(pset):
+                    return host_model_calc(model, data, pset, c, want_rows=True)[4]
+                res = engine.analyse_host_rows(pr["model"], pr["q"], pr["intensity"], pr["sigma"], pr["st"], rows,
+                                               replay=pr["replay"], stop=pr["stop"], window=self.hostRowWindow)
         else:
             res = engine.analyse(pr["model"], pr["q"], pr["intensity"], pr["sigma"], pr["st"],
                                  replay=pr["replay"], stop=pr["stop"], smear=pr["smear"], start=pr.get("start"), trace=trace)
@@ -257,8 +271,21 @@ class McSAS(object):
             scalingFactors = np.zeros((2, numReps))
             vsets = np.zeros((numContribs, numReps)); wsets = np.zeros((numContribs, numReps)); ssets = np.zeros((numContribs, numReps))
             mv = np.zeros((numContribs, numReps))
+            # (a batch model: the sets of a block of repetitions in one calcIntensityBatch call, at most ~256 MB of rows at a time)
+            batch = is_batch_model(model)
+            per_block = max(1, (256 << 20) // (8 * data.count * numContribs)) if batch else 1
             for ri in range(numReps):
-                cum, vsets[:, ri], wsets[:, ri], ssets[:, ri], rows = host_model_calc(model, data, contribs[:, :, ri], c, want_rows=True)
+                if batch:
+                    if ri % per_block == 0:
+                        r1 = min(numReps, ri + per_block)
+                        sets = np.ascontiguousarray(np.moveaxis(contribs[:, :, ri:r1], 2, 0)).reshape((r1 - ri) * numContribs, -1)
+                        block = [a.reshape(r1 - ri, numContribs, -1) for a in batch_model_calc(model, data, sets, c, want_rows=True,
+                                                                                             device=self.device)[1:]]
+                    k = ri % per_block
+                    vsets[:, ri], wsets[:, ri], ssets[:, ri], rows = block[0][k, :, 0], block[1][k, :, 0], block[2][k, :, 0], block[3][k]
+                    cum = np.cumsum(rows, axis=0)[-1]        # (rows added in order, scatteringmodel.py:90-101)
+                else:
+                    cum, vsets[:, ri], wsets[:, ri], ssets[:, ri], rows = host_model_calc(model, data, contribs[:, :, ri], c, want_rows=True)
                 sc, _, _ = engine.bgfit(data.f.binnedData, sig, cum, self.findBackground.value(), self.positiveBackground.value(),
                                         num_params=model.activeParamCount(), device=self.device)
                 scalingFactors[:, ri] = sc

@@ -81,6 +81,8 @@ class ScatteringModel(object):
 
     def calc(self, data, pset, compensationExponent=None):   # scatteringmodel.py:79-105, on the GPU
         if is_host_model(self):                              # a model of the user's own with Python formfactor / volume only
+            if is_batch_model(self):                         # ... or with calcIntensityBatch: all sets in one call on the device
+                return self.getModelData(*batch_model_calc(self, data, np.asarray(pset, dtype=float), compensationExponent)[:4])
             return self.getModelData(*host_model_calc(self, data, np.asarray(pset, dtype=float), compensationExponent)[:4])
         q = data.q if hasattr(data, "q") else np.asarray(data)
         smear = data.smearArgs(self) if hasattr(data, "smearArgs") else None    # sasmodel.py:56-60
@@ -369,9 +371,55 @@ def is_host_model(model) -> bool:
         return False
     if isinstance(getattr(model, "hipSource", None), str) or type(model).__name__ in SHIPPED_PLUGINS:
         return False
-    if isinstance(model, ScatteringModel):                  # our mirror base: the subclass must bring formfactor AND volume
+    if isinstance(model, ScatteringModel):                  # our mirror base: the subclass must bring formfactor AND volume,
+        if is_batch_model(model):                           # or the batch form of calcIntensity in torch
+            return True
         return type(model).formfactor is not ScatteringModel.formfactor and type(model).volume is not ScatteringModel.volume
     return callable(getattr(model, "calcIntensity", None))  # the reference's own classes: ABCMeta enforces the rest
+
+
+def is_batch_model(model) -> bool:
+    """A host model that brings `calcIntensityBatch(q, pset, compensationExponent) -> (it[n, nq], v[n], w[n], s[n])`: the batch form
+    of calcIntensity (bases/model/sasmodel.py:46-79) on torch tensors of the device.  q is float64 [nq], pset [n, activeParamCount()]
+    already clipped into each parameter's valueRange; inactive parameters are read from the model.  Its rows are computed on the
+    device for a whole round of proposals at once (mcsas_hip_analyse_device_rows)."""
+    return callable(getattr(model, "calcIntensityBatch", None))
+
+
+def refuse_batch_smearing(model, data):
+    """Smearing is not part of the batch contract: refuse the data whose smearing calcIntensity would apply (sasmodel.py:56-60)."""
+    if hasattr(data, "smearArgs") and data.smearArgs(model) is not None:
+        raise NotImplementedError("model %s computes its rows with calcIntensityBatch, which does not smear; this data's smearing "
+                                  "would apply to it (canSmear): switch it off, or write formfactor / volume" % type(model).__name__)
+
+
+def batch_clip(model, pset):
+    """A copy of the torch parameter sets pset[n, P] clipped into each active parameter's valueRange, as Parameter.setValue does per
+    value (bases/algorithm/parameter.py:405-414)."""
+    import torch
+    ranges = [p.valueRange() for p in model.activeParams()]
+    lo = torch.tensor([float(r[0]) for r in ranges], dtype=pset.dtype, device=pset.device)
+    hi = torch.tensor([float(r[1]) for r in ranges], dtype=pset.dtype, device=pset.device)
+    return torch.maximum(torch.minimum(pset, hi), lo)
+
+
+def batch_model_calc(model, data, pset, compensationExponent, want_rows=False, device=None):
+    """ScatteringModel.calc for a batch model: one calcIntensityBatch call over all parameter sets on the device.  -> (cumInt, vset, wset, sset, rows or None) as numpy arrays, like host_model_calc."""
+    refuse_batch_smearing(model, data)
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None or int(device) < 0 else int(device))
+    q = torch.as_tensor(np.ascontiguousarray(data.q if hasattr(data, "q") else data, dtype=np.float64), device=dev).reshape(-1)
+    P = len(model.activeParams())
+    ps = torch.as_tensor(np.ascontiguousarray(pset, dtype=np.float64).reshape(-1, P), device=dev)
+    if not len(ps):
+        return np.zeros(0), np.zeros(0), np.zeros(0), np.zeros(0), (np.zeros((0, len(q))) if want_rows else None)
+    it, v, w, s = model.calcIntensityBatch(q, batch_clip(model, ps), compensationExponent)
+    n = len(ps)
+    one = torch.ones(n, dtype=torch.float64, device=dev)
+    it = torch.as_tensor(it, dtype=torch.float64, device=dev).reshape(n, len(q))
+    v, w, s = (torch.as_tensor(x, dtype=torch.float64, device=dev) * one for x in (v, w, s))
+    cum = it.sum(dim=0)                                      # (torch's order of addition, not the row order of scatteringmodel.py:90-101)
+    return (cum.cpu().numpy(), v.cpu().numpy(), w.cpu().numpy(), s.cpu().numpy(), it.cpu().numpy() if want_rows else None)
 
 
 def host_model_calc(model, data, pset, compensationExponent, want_rows=False):
