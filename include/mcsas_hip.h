@@ -321,27 +321,34 @@ int mcsas_hip_analyse_from(const mcsas_problem *problem, const double *start, mc
 
 /* ---- the accepted moves of a chain (ABI 5, additive): what the reference prints while mcFit runs ("good iter ...: Chisqr= ...",
  * mcsas.py:385-390), so that a caller sees whether a fit was still improving, had stalled or was cut off by maxIterations ---------
- * One wavefront per chain only (MCSAS_EXEC_WAVE), cold or started (the start functions above).  Per repetition the trace holds the
- * moves of its LAST attempt, because num_iter and num_moves are that attempt's too: a retry (mcsas.py:220-246) starts it again.
+ * One wavefront per chain (MCSAS_EXEC_WAVE), or the q-split workgroup kernel (MCSAS_EXEC_WORKGROUP with 1025...16384 q-points:
+ * the only kernel beyond 4096), cold or started (the start functions above).  Per repetition the trace holds the moves of its
+ * LAST attempt, because num_iter and num_moves are that attempt's too: a retry (mcsas.py:220-246) starts it again.
  * Records kept: the first min(count, capacity) moves, in order; entries from there on are step = -1, chisq = NaN, values = NaN.
  *   count is always the full number of moves (== mcsas_result.num_moves), whatever the capacity.
  * The trace only observes: with a trace set, every array of mcsas_result except `seconds` is bit for bit that of the same call
- *   without one (mcsas_hip_analyse with MCSAS_EXEC_WAVE, or with a start the from-form of it); start, the reseed call, the replay
- *   stream and `stop` behave as they do without a trace.  Cost: one bounds test and 2 + n_active stores per ACCEPTED move, nothing
- *   in a rejected step.  Measured once (one MI355X, Sphere 512 q x 400 contributions x 256 repetitions x 20000 steps, 1205 moves
- *   per chain, capacity 4096): 26.87 ms of kernel against 26.50 ms untraced, +1.4 %, where two untraced runs differed by 0.004 ms
- *   (profiles/r17_summary.md) — small, but more than the noise: leave the trace off where it is not read.
- * mcsas_hip_plan_set_trace: for a plan that resolved to MCSAS_EXEC_WAVE; any other: MCSAS_EINVAL naming the mode (the plan stays
- *   usable).  Every later launch of either slot runs the traced form of the plan's kernel, cold or started, and each slot owns its
- *   trace buffers.  capacity >= 1 and n_reps * capacity * (16 + 8 n_active) bytes <= 2 GiB, else MCSAS_EINVAL; capacity 0 clears.
- *   mcsas_hip_plan_launch_batch refuses a plan with a trace (MCSAS_EINVAL, nothing is launched).
+ *   without one (mcsas_hip_analyse in the same mode, or with a start the from-form of it); start, the reseed call, the replay
+ *   stream and `stop` behave as they do without a trace.  Cost: one bounds test and 2 + n_active stores per ACCEPTED move,
+ *   nothing in a rejected step.  Measured once (one MI355X, Sphere 512 q x 400 contributions x 256 repetitions x 20000 steps,
+ *   1205 moves per chain, capacity 4096): 26.87 ms of kernel against 26.50 ms untraced, +1.4 %, where two untraced runs differed
+ *   by 0.004 ms (profiles/r17_summary.md) — small, but more than the noise: leave the trace off where it is not read.  The
+ *   q-split kernel (thread 0 of the workgroup writes; Sphere 2048 q x 300 contributions x 256 repetitions x 20000 steps, capacity
+ *   4096): 45.13 ms of kernel against 46.26 ms untraced, a ratio of 0.975 — the traced kernel was 2.5 % FASTER, where two
+ *   untraced runs differed by 0.22 ms; more than the noise, cause not established (profiles/r19_summary.md): there a trace costs
+ *   nothing measurable.
+ * mcsas_hip_plan_set_trace: for a plan that resolved to MCSAS_EXEC_WAVE or to the q-split kernel (MCSAS_EXEC_WORKGROUP with more
+ *   than 1024 q-points); any other: MCSAS_EINVAL naming the mode (the plan stays usable).  Every later launch of either slot runs
+ *   the traced form of the plan's kernel, cold or started, and each slot owns its trace buffers.  capacity >= 1 and n_reps *
+ *   capacity * (16 + 8 n_active) bytes <= 2 GiB, else MCSAS_EINVAL; capacity 0 clears. mcsas_hip_plan_launch_batch refuses a plan
+ *   with a trace (MCSAS_EINVAL, nothing is launched).
  * mcsas_hip_plan_fetch_trace: after the slot's result has been fetched.  MCSAS_EINVAL if the plan has no trace, if
  *   trace->capacity differs from the plan's, on a NULL array or a wrong struct_size, or if the slot's launch was not traced.
  * mcsas_hip_analyse_traced: the one-shot form; `start` as for the from-form above, or NULL for a cold run.  MCSAS_EXEC_AUTO means
- *   WAVE; WORKGROUP, PIPELINE, nq > 4096 and n_devices > 1 are refused, and so are a NULL trace, a NULL array in it, capacity < 1,
- *   a wrong struct_size and a non-finite start value — every refusal before a device is touched.  n_active == 0 is answered as
- *   mcsas_hip_analyse answers it, with count[0] = 0.
- * Out of scope (each refuses): batches, the q-split, workgroup-window and pipeline kernels, mcsas_hip_analyse_host_rows. */
+ *   WAVE, as it does for a start: with AUTO or WAVE nq > 4096 is refused, and the message names MCSAS_EXEC_WORKGROUP, which keeps
+ *   a trace for 1025...16384 q-points.  WORKGROUP up to 1024 q-points, PIPELINE and n_devices > 1 are refused, and so are a NULL
+ *   trace, a NULL array in it, capacity < 1, a wrong struct_size and a non-finite start value — every refusal before a device is
+ *   touched.  n_active == 0 is answered as mcsas_hip_analyse answers it, with count[0] = 0.
+ * Out of scope (each refuses): batches, device lists, the workgroup-window and pipeline kernels, mcsas_hip_analyse_host_rows. */
 typedef struct mcsas_trace {
     uint32_t struct_size;  /* sizeof(mcsas_trace) */
     int32_t  capacity;     /* records kept per repetition */

@@ -26,7 +26,7 @@
 //   CHAIN_STOP         expression: McSAS.stop has been asked for — one answer for all threads of the chain
 //   CHAIN_TRACE_START(c)          statement, or nothing: an attempt starts with reduced chi² c of its initial set (mcsas.py:343-344)
 //   CHAIN_TRACE_MOVE(i, s, c, k)  statement, or nothing: move i of the attempt was accepted at step s and left reduced chi² c; its
-//                      values are lane k of prow (mcsas.py:385-390).  Only the traced wave kernels (chain_wave.h) put anything here
+//                      values are lane k of prow (mcsas.py:385-390).  Only the traced kernels (chain_wave.h, chain_wide.h) put anything here
     double *rset = a.rset + (size_t)rep * N * P;
     double *cache = CACHE ? CHAIN_CACHE_PTR(a.cache + (size_t)rep * a.cache_rows * qpad) : nullptr;
     DrawSource src{a.replay ? a.replay + (size_t)rep * a.replay_len : nullptr, a.replay_len, a.seed,

@@ -12,7 +12,14 @@
 // partials in wave order — the same numbers in every wave, so the accept/reject decision is uniform over the workgroup
 // without a second exchange.  The partial slots alternate by step parity: a wave can only reach its write of step s + 2
 // through the barrier of step s + 1, which every wave passes after reading step s.
-#pragma once
+//
+// The file is read in passes.  The first one (no MCSAS_WIDE_PASS) declares what the kernels share and then includes this file once
+// per kernel, with the kernel's name, what it takes behind q3inv_glb and its two trace hooks as MCSAS_WIDE_* macros — the way
+// chain_wave_kernel.inc forwards MCSAS_WAVE_TRACE_*: chain_wide_kernel (hooks empty) and chain_wide_trace_kernel.  A kernel pass is
+// the text behind `#else` below: one kernel template, the only place of this family that includes chain_body.inc.
+#ifndef MCSAS_WIDE_PASS
+#ifndef MCSAS_CHAIN_WIDE_H
+#define MCSAS_CHAIN_WIDE_H
 #include "chain_common.h"
 
 namespace mcsas {
@@ -48,6 +55,53 @@ __device__ __forceinline__ bool wide_stop(const ChainArgs &a, int32_t *stop_word
     return *stop_word != 0;
 }
 
+}  // namespace mcsas
+
+#define MCSAS_WIDE_PASS
+// the chain and nothing else
+#define MCSAS_WIDE_KERNEL chain_wide_kernel
+#define MCSAS_WIDE_TRACE_PARAM
+#define MCSAS_WIDE_TRACE_START(c)
+#define MCSAS_WIDE_TRACE_MOVE(i, s, c, k)
+#include "chain_wide.h"
+#undef MCSAS_WIDE_KERNEL
+#undef MCSAS_WIDE_TRACE_PARAM
+#undef MCSAS_WIDE_TRACE_START
+#undef MCSAS_WIDE_TRACE_MOVE
+
+// The traced form (mcsas_hip_plan_set_trace on a q-split plan): the same chain, and thread 0 of the workgroup also records the accepted
+// moves of the last attempt in the repetition's part of `t` (TraceArgs, chain_common.h), with the semantics of chain_wave_trace_kernel
+// (chain_wave.h): an attempt's start writes the chi² of its initial set; move i of the attempt overwrites record i of the attempt
+// before, so what is left at the end are the records of the last attempt (its count is ChainOut::num_moves) and, behind them, stale
+// ones the host drops.  One writer is enough: prow, cur.chi2, num_iter and num_moves are the same numbers in every wave (the
+// proposals are, and the sums are added in wave order).  One bounds test and 2 + P stores per accepted move; nothing in a rejected
+// step.  Nothing the chain computes reads `t`.  The proposal's lane is read ahead of the predicate, with every lane active, as the
+// body reads it for rset: inside `if (keep)` lane k would be inactive, and a value reloaded from scratch there is lane 0's only.
+#define MCSAS_WIDE_KERNEL chain_wide_trace_kernel
+#define MCSAS_WIDE_TRACE_PARAM , const TraceArgs t
+#define MCSAS_WIDE_TRACE_START(c) if (tid == 0) t.chisq0[rep] = c;
+#define MCSAS_WIDE_TRACE_MOVE(i, s, c, k)                                                                              \
+    {                                                                                                                  \
+        const bool keep = tid == 0 && i < (int64_t)t.capacity;                                                         \
+        const size_t rec = (size_t)rep * (size_t)t.capacity + (size_t)i;                                               \
+        _Pragma("unroll") for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)                                                   \
+            if (p < P) {                                                                                               \
+                const double tv = readlane_f64(prow[p], k);                                                            \
+                if (keep) t.values[rec * P + p] = tv;                                                                  \
+            }                                                                                                          \
+        if (keep) { t.step[rec] = s; t.chisq[rec] = c; }                                                               \
+    }
+#include "chain_wide.h"
+#undef MCSAS_WIDE_KERNEL
+#undef MCSAS_WIDE_TRACE_PARAM
+#undef MCSAS_WIDE_TRACE_START
+#undef MCSAS_WIDE_TRACE_MOVE
+#undef MCSAS_WIDE_PASS
+
+#endif  // MCSAS_CHAIN_WIDE_H
+#else   // MCSAS_WIDE_PASS: one kernel of the family
+namespace mcsas {
+
 // GIVEN: the chain is started from a given set (mcsas_hip_plan_set_start): the host has copied the repetition's start into rset
 // ahead of the launch, and the first attempt takes it where the cold kernel generates one (chain_body.inc: GIVEN).  Here several waves
 // run that branch.  In the first attempt every wave reads rset[n * P + p] while wave 0 (CHAIN_FIRST) stores what it has just read back
@@ -57,7 +111,7 @@ __device__ __forceinline__ bool wide_stop(const ChainArgs &a, int32_t *stop_word
 // it only through the barriers of the attempt before (the sums of its initial and final fits), behind every wave's last read of the
 // start; nobody reads that set back.
 template <int M, int QPL, bool GIVEN>
-__global__ __launch_bounds__(WIDE_MAX_WAVES * 64) void chain_wide_kernel(const ChainArgs a, const double *q3inv_glb) {
+__global__ __launch_bounds__(WIDE_MAX_WAVES * 64) void MCSAS_WIDE_KERNEL(const ChainArgs a, const double *q3inv_glb MCSAS_WIDE_TRACE_PARAM) {
     extern __shared__ double lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NW = blockDim.x >> 6;
     const int rep = blockIdx.x;
@@ -97,8 +151,8 @@ __global__ __launch_bounds__(WIDE_MAX_WAVES * 64) void chain_wide_kernel(const C
 #define CHAIN_FIRST (wave == 0)
 #define CHAIN_LEADER (tid == 0)
 #define CHAIN_STOP wide_stop(a, stop_word, tid)
-#define CHAIN_TRACE_START(c)                                // (no trace in this family)
-#define CHAIN_TRACE_MOVE(i, s, c, k)
+#define CHAIN_TRACE_START(c) MCSAS_WIDE_TRACE_START(c)
+#define CHAIN_TRACE_MOVE(i, s, c, k) MCSAS_WIDE_TRACE_MOVE(i, s, c, k)
 #include "chain_body.inc"
 #undef CHAIN_STATE
 #undef CHAIN_CACHE_PTR
@@ -116,3 +170,4 @@ __global__ __launch_bounds__(WIDE_MAX_WAVES * 64) void chain_wide_kernel(const C
 }
 
 }  // namespace mcsas
+#endif  // MCSAS_WIDE_PASS

@@ -85,8 +85,9 @@ struct SmearDev {
 // attempt takes a given set (mcsas_hip_plan_set_start), the workgroup-window and pipeline families have none.  Every built-in model
 // has its instances in kern_*.hip (the started ones in kern_wave_start.hip and kern_wide_start.hip), a plug-in compiles its own on
 // first use.  KF_WAVE_TRACE: the wave kernel that also records its accepted moves (mcsas_hip_plan_set_trace; kern_wave_trace.hip),
-// cold and started; its second kernel argument is the launch's TraceArgs
-enum KernelFamily { KF_WAVE, KF_WAVE_BATCH, KF_WG, KF_WIDE, KF_PIPE_TICK, KF_WAVE_TRACE, KF_COUNT };
+// cold and started; its second kernel argument is the launch's TraceArgs.  KF_WIDE_TRACE: the same of the q-split kernel
+// (kern_wide_trace.hip); the TraceArgs are its third argument, behind q3inv
+enum KernelFamily { KF_WAVE, KF_WAVE_BATCH, KF_WG, KF_WIDE, KF_PIPE_TICK, KF_WAVE_TRACE, KF_WIDE_TRACE, KF_COUNT };
 enum PluginSmallKernel { PLUGIN_MODEL_ROWS, PLUGIN_OBSERVABILITY, PLUGIN_HIST_ROWS };
 
 inline bool is_plugin_model(int model_id) { return model_id >= MCSAS_MODEL_PLUGIN0 && model_id < MCSAS_MODEL_PLUGIN0 + MCSAS_MAX_PLUGINS; }

@@ -151,7 +151,8 @@ int plugin_chain_function(int model_id, KernelFamily family, int qpl, bool flag,
     // row queue), then whether the first attempt takes a given set
     static const struct { const char *kernel, *key; bool flagged, startable; } FAMILY[KF_COUNT] = {
         {"chain_wave_kernel", "wave", true, true}, {"chain_wave_batch_kernel", "wave batch", true, true}, {"chain_wg_kernel", "wg", false, false},
-        {"chain_wide_kernel", "wide", false, true}, {"pipe_tick_kernel", "pipe", true, false}, {"chain_wave_trace_kernel", "wave trace", true, true}};
+        {"chain_wide_kernel", "wide", false, true}, {"pipe_tick_kernel", "pipe", true, false}, {"chain_wave_trace_kernel", "wave trace", true, true},
+        {"chain_wide_trace_kernel", "wide trace", false, true}};
     const auto &f = FAMILY[family];
     if (given && !f.startable) return fail(MCSAS_EINVAL, "no %s start kernel for model %d qpl %d", f.key, model_id, qpl);
     // (started and cold kernels are programs of their own, each compiled when first asked for)

@@ -344,10 +344,10 @@ static int plan_activate_slot(mcsas_plan *pl, int k) {
 typedef void *KernelLookup(int qpl, bool flag);
 #define DECL_K(m) KernelLookup mcsas_wave_kernel_m##m, mcsas_wave_kernel_given_m##m, mcsas_wave_batch_kernel_m##m, mcsas_wave_batch_kernel_given_m##m, \
                                mcsas_wg_kernel_m##m, mcsas_wide_kernel_m##m, mcsas_wide_kernel_given_m##m, mcsas_pipe_tick_kernel_m##m, \
-                               mcsas_wave_trace_kernel_m##m, mcsas_wave_trace_kernel_given_m##m;
+                               mcsas_wave_trace_kernel_m##m, mcsas_wave_trace_kernel_given_m##m, mcsas_wide_trace_kernel_m##m, mcsas_wide_trace_kernel_given_m##m;
 #define ROW_K(m) {{mcsas_wave_kernel_m##m, mcsas_wave_kernel_given_m##m}, {mcsas_wave_batch_kernel_m##m, mcsas_wave_batch_kernel_given_m##m}, \
                   {mcsas_wg_kernel_m##m, nullptr}, {mcsas_wide_kernel_m##m, mcsas_wide_kernel_given_m##m}, {mcsas_pipe_tick_kernel_m##m, nullptr}, \
-                  {mcsas_wave_trace_kernel_m##m, mcsas_wave_trace_kernel_given_m##m}},
+                  {mcsas_wave_trace_kernel_m##m, mcsas_wave_trace_kernel_given_m##m}, {mcsas_wide_trace_kernel_m##m, mcsas_wide_trace_kernel_given_m##m}},
 MCSAS_FOR_MODELS(DECL_K)
 static KernelLookup *const BUILTIN[MCSAS_MODEL_COUNT][KF_COUNT][2] = {MCSAS_FOR_MODELS(ROW_K)};
 #undef DECL_K
@@ -355,31 +355,36 @@ static KernelLookup *const BUILTIN[MCSAS_MODEL_COUNT][KF_COUNT][2] = {MCSAS_FOR_
 void *mcsas_pipe_reset_kernel();
 
 // What a launch needs: the kernel (built-in models: the host handle of the __global__ function; plug-ins: the function of this
-// device's module), the block size, and which second kernel argument the family takes after its argument block.
+// device's module), the block size, and what the family takes after its argument block: its second argument, if any, and behind
+// that, in the traced families, the slot's TraceArgs.
 struct KernelRef {
     void *entry = nullptr;
     hipFunction_t plugin = nullptr;
     unsigned block = 0;
-    enum { ARG2_NONE, ARG2_WG, ARG2_Q3INV, ARG2_TRACE } arg2 = ARG2_NONE;
+    enum { ARG2_NONE, ARG2_WG, ARG2_Q3INV } arg2 = ARG2_NONE;
+    bool trace = false;
     const void *id() const { return plugin ? (const void *)plugin : entry; }
 };
 // the family of the plan's own launches; a batch (mcsas_hip_plan_launch_batch) runs the plan's chains in KF_WAVE_BATCH instead.  Either
 // way a launch takes the started kernel of its family while the plan holds a start (mcsas_hip_plan_set_start gives one to plans of
-// the wave and q-split families only), and a wave plan with a trace (mcsas_hip_plan_set_trace) the traced family.
+// the wave and q-split families only), and a plan of either with a trace (mcsas_hip_plan_set_trace) the traced family.
 static KernelFamily plan_family(const mcsas_plan *pl) {
     if (pl->mode == MCSAS_EXEC_WAVE) return pl->trace_capacity > 0 ? KF_WAVE_TRACE : KF_WAVE;
     if (pl->mode == MCSAS_EXEC_PIPELINE) return KF_PIPE_TICK;
-    return pl->wide ? KF_WIDE : KF_WG;
+    if (pl->wide) return pl->trace_capacity > 0 ? KF_WIDE_TRACE : KF_WIDE;
+    return KF_WG;
 }
 static int resolve_kernel(const mcsas_plan *pl, KernelFamily family, bool given, KernelRef *k) {
-    static const char *const name[KF_COUNT] = {"", "batch ", "", "q-split ", "pipeline ", "traced "};
+    static const char *const name[KF_COUNT] = {"", "batch ", "", "q-split ", "pipeline ", "traced ", "traced q-split "};
     const int model = pl->prob.model_id;
     const bool flag = family == KF_PIPE_TICK ? pl->pipe.g.rowq != 0 : pl->use_cache != 0;
     *k = KernelRef{};
-    k->block = family == KF_PIPE_TICK ? PIPE_BLOCK : (family == KF_WG || family == KF_WIDE ? WAVE * pl->waves : WAVE);
-    k->arg2 = family == KF_WG ? KernelRef::ARG2_WG : (family == KF_WIDE ? KernelRef::ARG2_Q3INV : (family == KF_WAVE_TRACE ? KernelRef::ARG2_TRACE : KernelRef::ARG2_NONE));
+    const bool q_split = family == KF_WIDE || family == KF_WIDE_TRACE;
+    k->block = family == KF_PIPE_TICK ? PIPE_BLOCK : (family == KF_WG || q_split ? WAVE * pl->waves : WAVE);
+    k->arg2 = family == KF_WG ? KernelRef::ARG2_WG : (q_split ? KernelRef::ARG2_Q3INV : KernelRef::ARG2_NONE);
+    k->trace = family == KF_WAVE_TRACE || family == KF_WIDE_TRACE;
     if (is_plugin_model(model)) {
-        if (pl->plugin_fn && family == plan_family(pl) && family != KF_WAVE_TRACE && !given) { k->plugin = pl->plugin_fn; return MCSAS_OK; }   // (looked up when the plan was made)
+        if (pl->plugin_fn && family == plan_family(pl) && !k->trace && !given) { k->plugin = pl->plugin_fn; return MCSAS_OK; }   // (looked up when the plan was made)
         return plugin_chain_function(model, family, pl->qpl, flag, given, &k->plugin);                           // (compiled on first use of this q count)
     }
     KernelLookup *const lookup = model >= 0 && model < MCSAS_MODEL_COUNT ? BUILTIN[model][family][given] : nullptr;
@@ -854,7 +859,7 @@ static int enqueue_start(mcsas_plan *pl, hipStream_t st) {
     return MCSAS_OK;
 }
 
-// ------------------------------------------------------------------------------ the trace of a wave plan (include/mcsas_hip.h)
+// ------------------------------------------------------------------------------ the trace of a wave or q-split plan (include/mcsas_hip.h)
 // bytes of one slot's trace block: step, chisq and values of `capacity` moves per repetition
 static size_t trace_record_bytes(size_t R, size_t capacity, size_t P) { return R * capacity * (16 + 8 * P); }
 static const size_t TRACE_MAX_BYTES = (size_t)2 << 30;
@@ -882,7 +887,7 @@ extern "C" int mcsas_hip_plan_set_trace(mcsas_plan *pl, int32_t capacity) {
     if (!pl) return fail(MCSAS_EINVAL, "set_trace: null plan");
     if (capacity < 0) return fail(MCSAS_EINVAL, "set_trace: capacity %d (>= 1, or 0 to clear the trace)", (int)capacity);
     if (capacity > 0) {
-        if (pl->mode != MCSAS_EXEC_WAVE || pl->wide)
+        if (pl->mode != MCSAS_EXEC_WAVE && !pl->wide)
             return fail(MCSAS_EINVAL, "set_trace: the plan runs in exec_mode %d (%s); a trace needs exec_mode = MCSAS_EXEC_WAVE (%d)", pl->mode, exec_mode_name(pl->mode), MCSAS_EXEC_WAVE);
         const size_t R = pl->prob.n_reps, P = pl->prob.n_active;
         if ((size_t)capacity > TRACE_MAX_BYTES / (R * (16 + 8 * P)))
@@ -900,7 +905,7 @@ extern "C" int mcsas_hip_plan_set_trace(mcsas_plan *pl, int32_t capacity) {
         const int32_t before = pl->trace_capacity;
         pl->trace_capacity = capacity;
         KernelRef k;
-        const int rc = is_plugin_model(pl->prob.model_id) ? MCSAS_OK : resolve_kernel(pl, KF_WAVE_TRACE, pl->has_start, &k);
+        const int rc = is_plugin_model(pl->prob.model_id) ? MCSAS_OK : resolve_kernel(pl, plan_family(pl), pl->has_start, &k);
         if (rc) { pl->trace_capacity = before; return rc; }
     }
     pl->trace_capacity = capacity;
@@ -1036,15 +1041,18 @@ extern "C" int mcsas_hip_plan_launch_slot(mcsas_plan *pl, void *hip_stream, int3
         if (int rc = pipeline_launch(pl, k, st)) return rc;
     } else {
         // the argument block by value, then what the family takes besides (a plug-in: the same arguments, through its code-object module)
-        if (k.arg2 == KernelRef::ARG2_TRACE) { if (int rc = make_slot_trace(pl, s)) return rc; }
-        void *kargs[] = {(void *)&pl->args, k.arg2 == KernelRef::ARG2_WG ? (void *)&pl->wg : (k.arg2 == KernelRef::ARG2_Q3INV ? (void *)&pl->d_q3inv
-                                            : (k.arg2 == KernelRef::ARG2_TRACE ? (void *)&s.trace : nullptr))};
+        if (k.trace) { if (int rc = make_slot_trace(pl, s)) return rc; }
+        void *kargs[3] = {(void *)&pl->args, nullptr, nullptr};
+        int nk = 1;
+        if (k.arg2 == KernelRef::ARG2_WG) kargs[nk++] = (void *)&pl->wg;
+        else if (k.arg2 == KernelRef::ARG2_Q3INV) kargs[nk++] = (void *)&pl->d_q3inv;
+        if (k.trace) kargs[nk++] = (void *)&s.trace;
         if (int rc = raise_lds_limit(k, pl->lds_bytes)) return rc;
         HIPCHK(hipEventRecord(s.ev0, st));
         if (pl->has_start) { if (int rc = enqueue_start(pl, st)) return rc; }
         if (int rc = launch_kernel(k, (unsigned)pl->prob.n_reps, kargs, pl->lds_bytes, st)) return rc;
         HIPCHK(hipEventRecord(s.ev1, st));
-        s.traced = k.arg2 == KernelRef::ARG2_TRACE;
+        s.traced = k.trace;
     }
     s.launched = true; guard.ok = true;
     return MCSAS_OK;
@@ -1449,7 +1457,8 @@ extern "C" int mcsas_hip_analyse_from(const mcsas_problem *p, const double *star
 }
 
 // mcsas_hip_analyse (MCSAS_EXEC_WAVE), or mcsas_hip_analyse_from when a start is given, with the accepted moves of every repetition's
-// last attempt (include/mcsas_hip.h); every refusal before a device is touched.
+// last attempt (include/mcsas_hip.h): one wavefront per chain, or, where MCSAS_EXEC_WORKGROUP is asked for more than 1024 q-points,
+// the q-split kernel; every refusal before a device is touched.
 extern "C" int mcsas_hip_analyse_traced(const mcsas_problem *p, const double *start, mcsas_result *res, mcsas_trace *tr) {
     if (!p || !res) return fail(MCSAS_EINVAL, "analyse_traced: null argument");
     if (p->struct_size != sizeof(mcsas_problem))
@@ -1460,9 +1469,13 @@ extern "C" int mcsas_hip_analyse_traced(const mcsas_problem *p, const double *st
         if (!rc) tr->count[0] = 0;
         return rc;
     }
-    if (p->exec_mode != MCSAS_EXEC_AUTO && p->exec_mode != MCSAS_EXEC_WAVE)
+    const bool q_split = p->exec_mode == MCSAS_EXEC_WORKGROUP && p->nq > 16 * WAVE;      // (decide_shape: the q-split kernel, whatever waves_per_chain says)
+    if (p->exec_mode != MCSAS_EXEC_AUTO && p->exec_mode != MCSAS_EXEC_WAVE && !q_split)
         return fail(MCSAS_EINVAL, "analyse_traced: exec_mode %d (%s) asked; a trace needs exec_mode = MCSAS_EXEC_WAVE (%d, or 0)", p->exec_mode, exec_mode_name(p->exec_mode), MCSAS_EXEC_WAVE);
-    if (p->nq > 64 * WAVE) return fail(MCSAS_EINVAL, "analyse_traced: nq %d > %d: one wavefront per chain does not take it, and only that kernel keeps a trace", p->nq, 64 * WAVE);
+    if (p->nq > WIDE_MAX_WAVES * WAVE * 32) return fail(MCSAS_EINVAL, "analyse_traced: nq %d > %d is not supported", p->nq, WIDE_MAX_WAVES * WAVE * 32);
+    if (!q_split && p->nq > 64 * WAVE)
+        return fail(MCSAS_EINVAL, "analyse_traced: nq %d > %d: one wavefront per chain does not take it, and with exec_mode %d a trace runs one wavefront per chain; "
+                    "MCSAS_EXEC_WORKGROUP (%d) keeps a trace for %d...%d q-points", p->nq, 64 * WAVE, p->exec_mode, MCSAS_EXEC_WORKGROUP, 16 * WAVE + 1, WIDE_MAX_WAVES * WAVE * 32);
     if (p->n_devices > 1) return fail(MCSAS_EINVAL, "analyse_traced: n_devices %d: a trace is kept on one device", p->n_devices);
     if (p->n_active < 0 || p->n_active > MCSAS_MAX_ACTIVE) return fail(MCSAS_EINVAL, "n_active %d out of range", p->n_active);
     if (p->n_contrib < 1 || p->n_reps < 1) return fail(MCSAS_EINVAL, "n_contrib and n_reps must be >= 1");
@@ -1470,7 +1483,7 @@ extern "C" int mcsas_hip_analyse_traced(const mcsas_problem *p, const double *st
         return fail(MCSAS_EINVAL, "analyse_traced: %d repetitions x capacity %d x %d bytes per move exceed 2 GiB", p->n_reps, (int)tr->capacity, 16 + 8 * p->n_active);
     if (start) { if (int rc = check_start_finite("analyse_traced", start, (size_t)p->n_contrib, (size_t)p->n_active, (size_t)p->n_reps, 0, (size_t)p->n_reps)) return rc; }
     mcsas_problem q = *p;
-    q.exec_mode = MCSAS_EXEC_WAVE;
+    q.exec_mode = q_split ? MCSAS_EXEC_WORKGROUP : MCSAS_EXEC_WAVE;
     q.n_devices = 0;
     mcsas_plan *pl = nullptr;
     int rc = mcsas_hip_plan_create(&q, &pl);

@@ -211,16 +211,20 @@ class ChainTrace:
 
 def _check_trace(trace, model: ModelSetup, st: Settings, nq, who="analyse"):
     """The capacity of a trace as an int; ValueError where no traced kernel exists for the analysis — before any library call: a trace
-    is kept by the wavefront-per-chain kernel, on one device."""
+    is kept by the wavefront-per-chain kernel and, where exec_mode asks for the workgroup mode with more than WG_MAX_Q q-points, by
+    the q-split workgroup kernel, on one device.  The trace never picks the mode."""
     k = int(trace)
     if k < 1:
         raise ValueError("%s: trace is the number of moves kept per repetition (>= 1), got %r" % (who, trace))
     if model.model_id == MODEL_HOST:
         raise ValueError("%s: a model that exists only as host code keeps no trace (a trace runs one wavefront per chain)" % who)
-    if st.exec_mode not in (EXEC_AUTO, EXEC_WAVE):
-        raise ValueError("%s: a trace runs one wavefront per chain; exec_mode %d was asked (0 or 1)" % (who, st.exec_mode))
-    if nq > WAVE_MAX_Q:
-        raise ValueError("%s: %d q-points; a trace runs one wavefront per chain, which takes up to %d" % (who, nq, WAVE_MAX_Q))
+    q_split = st.exec_mode == EXEC_WORKGROUP and nq > WG_MAX_Q
+    if st.exec_mode not in (EXEC_AUTO, EXEC_WAVE) and not q_split:
+        raise ValueError("%s: a trace runs one wavefront per chain, or a workgroup per chain with more than %d q-points; "
+                         "exec_mode %d was asked with %d q-points (0 or 1, or 2 beyond %d q-points)" % (who, WG_MAX_Q, st.exec_mode, nq, WG_MAX_Q))
+    if nq > WAVE_MAX_Q and not q_split:
+        raise ValueError("%s: %d q-points; with exec_mode %d a trace runs one wavefront per chain, which takes up to %d: "
+                         "set exec_mode to workgroup (%d)" % (who, nq, st.exec_mode, WAVE_MAX_Q, EXEC_WORKGROUP))
     if st.devices:
         raise ValueError("%s: a trace is kept on one device; a device list %r was given" % (who, tuple(st.devices)))
     return k
@@ -249,7 +253,8 @@ def analyse(model: ModelSetup, q, intensity, sigma, st: Settings, replay=None, s
     a random one (mcsas_hip_analyse_from, include/mcsas_hip.h) — one wavefront per chain, or with exec_mode 2 and more than
     WG_MAX_Q q-points the q-split workgroup kernel (the only one beyond WAVE_MAX_Q); exec_mode 2 below that and 3 are refused.
     `trace`: K >= 1 keeps the first K accepted moves of every repetition's last attempt in the result's .trace (a ChainTrace;
-    mcsas_hip_analyse_traced): one wavefront per chain, cold or from a start; every other array is what it is without a trace."""
+    mcsas_hip_analyse_traced): one wavefront per chain, or the q-split workgroup kernel under the same condition as for a start,
+    cold or from a start; every other array is what it is without a trace."""
     if trace is not None:
         trace = _check_trace(trace, model, st, int(np.size(q)))
     if start is not None and model.n_active > 0:
@@ -547,8 +552,8 @@ class Plan:
 
     def set_trace(self, capacity):
         """Every later launch of this plan keeps the first `capacity` accepted moves of every repetition's last attempt, per slot
-        (mcsas_hip_plan_set_trace); fetch() then fills ChainResults.trace.  0 or None clears it.  Plans in the wavefront mode; the
-        others refuse, and so does launch_batch for a plan with a trace."""
+        (mcsas_hip_plan_set_trace); fetch() then fills ChainResults.trace.  0 or None clears it.  Plans in the wavefront mode and
+        in the workgroup mode with more than WG_MAX_Q q-points (the q-split kernel); the others refuse, and so does launch_batch for a plan with a trace."""
         k = int(capacity or 0)
         check(self.lib.mcsas_hip_plan_set_trace(self.h, C.c_int32(k)), self.lib)
         self.trace_capacity = k

@@ -103,23 +103,29 @@ class McSAS(object):
 
     def _check_trace_mode(self, trace, data=None):
         """The execution mode a traced analysis of `data` (default: the current data) asks for, or None without a trace: one wavefront
-        per chain, the only kernel that keeps a trace (include/mcsas_hip.h: mcsas_hip_analyse_traced).  ValueError where execMode asks
-        for another, for more than engine.WAVE_MAX_Q points, for a model that exists only as host code and for a device list."""
+        per chain, or the q-split workgroup kernel where execMode asks for it with more than engine.WG_MAX_Q points
+        (include/mcsas_hip.h: mcsas_hip_analyse_traced).  The trace never picks the mode: ValueError where execMode asks for another,
+        for more than engine.WAVE_MAX_Q points without the workgroup mode, for a model that exists only as host code and for a device
+        list."""
         if trace is None:
             return None
         data = self.data if data is None else data
         nq = 0 if data is None else int(np.size(data.q))
         if int(trace) < 1:
             raise ValueError("McSAS: trace is the number of moves kept per repetition (>= 1), got %r" % (trace,))
-        if self.execMode not in (engine.EXEC_AUTO, engine.EXEC_WAVE):
-            raise ValueError("McSAS: a trace runs one wavefront per chain; execMode %d was asked (0 or 1)" % self.execMode)
-        if nq > engine.WAVE_MAX_Q:
-            raise ValueError("McSAS: %d points; a trace runs one wavefront per chain, which takes up to %d" % (nq, engine.WAVE_MAX_Q))
+        q_split = self.execMode == engine.EXEC_WORKGROUP and nq > engine.WG_MAX_Q
+        if self.execMode not in (engine.EXEC_AUTO, engine.EXEC_WAVE) and not q_split:
+            raise ValueError("McSAS: a trace runs one wavefront per chain, or a workgroup per chain with more than %d points; "
+                             "execMode %d was asked with %d points (0 or 1, or 2 beyond %d points)"
+                             % (engine.WG_MAX_Q, self.execMode, nq, engine.WG_MAX_Q))
+        if nq > engine.WAVE_MAX_Q and not q_split:
+            raise ValueError("McSAS: %d points; with execMode %d a trace runs one wavefront per chain, which takes up to %d: "
+                             "set execMode to workgroup (%d)" % (nq, self.execMode, engine.WAVE_MAX_Q, engine.EXEC_WORKGROUP))
         if self.devices:
             raise ValueError("McSAS: a trace is kept on one device; the device list %r was given" % (self.devices,))
         if self.model is not None and setup_from_model(self.model, data).model_id == engine.MODEL_HOST:
             raise ValueError("McSAS: a model that exists only as host code keeps no trace (it runs through host-evaluated rows)")
-        return engine.EXEC_WAVE
+        return engine.EXEC_WORKGROUP if q_split else engine.EXEC_WAVE
 
     def calc(self, **kwargs):                                # mcsas.py:149-179
         """`trace=K`: keeps the first K accepted moves of every repetition (step, chi-squared, new values: what the reference logs
@@ -160,8 +166,9 @@ class McSAS(object):
         for this call, or the q-split workgroup kernel (_check_start_mode; include/mcsas_hip.h: mcsas_hip_analyse_from); an explicit
         execMode of pipeline, or of workgroup with up to 1024 points, raises ValueError.
         `trace`: K >= 1 stores the first K accepted moves of every repetition's last attempt under result[0]['trace'] (count, chisq0,
-        step[K][R], chisq[K][R], values[K][P][R]: engine.ChainTrace); one wavefront per chain (_check_trace_mode)."""
-        self._check_trace_mode(trace)
+        step[K][R], chisq[K][R], values[K][P][R]: engine.ChainTrace); one wavefront per chain, or the q-split workgroup kernel where
+        execMode asks for it (_check_trace_mode)."""
+        trace_mode = self._check_trace_mode(trace)
         if self.result is None:
             self.result = []
         data, model = self.data, self.model
@@ -171,9 +178,7 @@ class McSAS(object):
             numContribs, numReps = self.numContribs(), self.numReps()
         pr = self._problem(numContribs, numReps, replay, start)
         if trace is not None:
-            if pr.get("start") is not None and pr["st"].exec_mode != engine.EXEC_WAVE:
-                raise ValueError("McSAS: this start runs the q-split workgroup kernel, which keeps no trace")
-            pr["st"].exec_mode = engine.EXEC_WAVE
+            pr["st"].exec_mode = trace_mode                  # (with a start: the mode _check_start_mode gave, wherever a trace is taken)
         if pr["model"].model_id == engine.MODEL_HOST:
             # a model with Python formfactor / volume only: its rows are evaluated here, by the model's own calcIntensity with the
             # set-value-and-restore semantics of ScatteringModel.calc (scatteringmodel.py:86-104); the device does the rest

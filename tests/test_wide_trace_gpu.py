@@ -1,0 +1,319 @@
+"""The accepted moves of q-split workgroup chains (csrc/chain_wide.h: chain_wide_trace_kernel<M, QPL, GIVEN>, more than 1024
+q-points, one workgroup per chain) behind mcsas_hip_plan_set_trace / _fetch_trace / mcsas_hip_analyse_traced with
+MCSAS_EXEC_WORKGROUP, engine.analyse(trace=), Plan.set_trace and McSAS(execMode=workgroup).calc(trace=) on the device.
+
+The machinery is tests/test_trace_gpu.py's, by import: the reference is the oracle's own mc_fit with generate_parameters and bgfit_calc
+wrapped to record every step's proposal and conval (_oracle_traced).  Counts, steps and VALUES are compared exactly (_check_exact
+below: a proposal is transform(u) * (hi - lo) + lo of the same uniform in the oracle and on the device, where no multiply-add is
+fused), chi² with that file's tolerance (_check_trace: 1e-7; _check_against_oracle for the result).
+Shapes and geometries are tests/test_wide_start_gpu.py's: 8 slots per lane at 1500 q (three waves) and at 1025 q (the third wave holds one real point), 16 slots at 4097 q, 32 slots at 8193 q
+(five waves, the last with one real point).  The criteria of the cold runs below were chosen with the oracle like those: chains end
+mid-run by convergence at different steps, each after an accepted move whose chi² lies 6 % or more under the criterion while the move
+before lies 8 % or more above it, so no chain's end sits on a numerically tied comparison."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+import mcsas_amd
+from mcsas_amd import engine, _lib
+from oracle import mcsas_oracle as O
+from helpers import make_models, plugin_twin, product_smearing
+from test_batch_gpu import RANGES, _synthetic, _same
+from test_start_gpu import R, REP_OFFSET, SEED, SHAPES, _check_against_oracle, _workload
+from test_trace_gpu import COLD_CRIT, K, _check_trace, _guarded_trace, _oracle_traced, _same_trace, _traced_workload
+from test_wide_start_gpu import GEOMETRY, _retry_workload
+
+WG = engine.EXEC_WORKGROUP
+MCSAS_EINVAL = -1
+# criterion of the COLD run of the shapes test_wide_start_gpu.py adds (sphere1500: test_trace_gpu.py's).  sphere8193: one chain of
+# the three runs to its budget
+COLD_CRIT.update({"sphere1025": 420.0, "sphere4097": 420.0, "sphere8193": 430.0})
+
+
+@functools.lru_cache(maxsize=None)
+def _run(name, started, replayed, trace, mode=WG):
+    wl = _traced_workload(name, started)
+    st = engine.Settings(**{**wl["st"].__dict__, "exec_mode": mode})
+    return engine.analyse(wl["setup"], wl["q"], wl["I"], wl["sig"], st, replay=wl["replay"] if replayed else None, start=wl["start"],
+                          trace=trace)
+
+
+def _check_exact(chains, tr, capacity):
+    """What _check_trace holds to 1e-12 holds bit for bit: the recorded values are the oracle's proposals."""
+    for r, c in enumerate(chains):
+        n = min(c["ref"].num_moves, capacity)
+        assert tr.count[r] == c["ref"].num_moves and np.array_equal(tr.step[:n, r], c["trace"]["step"][:n]), r
+        got, ref = tr.values[:n, :, r], c["trace"]["values"][:n]
+        print("chain %d: %d of %d recorded values differ from the oracle's" % (r, int((got != ref).sum()), got.size))
+        assert np.array_equal(got, ref), r
+
+
+ALL = [(name, started, replayed) for name in GEOMETRY for started in (False, True) for replayed in (False, True)]
+
+
+@pytest.mark.parametrize("name,started,replayed", ALL)
+def test_oracle_parity_of_the_trace(name, started, replayed):
+    wl = _traced_workload(name, started)
+    assert all(3 < c["ref"].num_moves < K for c in wl["chains"]), [c["ref"].num_moves for c in wl["chains"]]
+    pl = engine.Plan(wl["setup"], wl["q"], wl["I"], wl["sig"], engine.Settings(**{**wl["st"].__dict__, "exec_mode": WG}))
+    try:
+        info = pl.info
+    finally:
+        pl.close()
+    assert info["exec_mode"] == "workgroup" and (info["q_per_lane"], info["waves_per_chain"]) == GEOMETRY[name], info
+    res = _run(name, started, replayed, K)
+    _check_against_oracle(wl["chains"], res, wl["spec"].n_active)
+    _check_trace(wl["chains"], res.trace, K)
+    _check_exact(wl["chains"], res.trace, K)
+
+
+@pytest.mark.parametrize("name,started,replayed", ALL)
+def test_the_trace_only_observes(name, started, replayed):
+    """The same MCSAS_EXEC_WORKGROUP call without a trace: every result array but `seconds` bit for bit."""
+    traced, plain = _run(name, started, replayed, K), _run(name, started, replayed, None)
+    assert traced.trace is not None and plain.trace is None and int(plain.num_moves.sum()) > 0
+    _same(traced, plain, "traced against untraced")
+
+
+def _same_moves(wide, wave, what):
+    """Two kernels, one chain: the same decisions; the q-split kernel adds a chain's weighted sums per wave first, hence the bound
+    test_wide_start_gpu.py holds the two kernels' chi² to."""
+    assert (wave.trace.count > 0).all(), what
+    for name in ("num_iter", "num_moves", "attempts", "draws", "converged", "contribs"):
+        np.testing.assert_array_equal(getattr(wide, name), getattr(wave, name), err_msg=what + " " + name)
+    for f in ("count", "step", "values"):
+        assert np.array_equal(getattr(wide.trace, f), getattr(wave.trace, f), equal_nan=f == "values"), (what, f)
+    print("%s: largest relative difference of chisq %.3g, of chisq0 %.3g"
+          % (what, np.nanmax(np.abs(wide.trace.chisq / wave.trace.chisq - 1)), np.abs(wide.trace.chisq0 / wave.trace.chisq0 - 1).max()))
+    np.testing.assert_allclose(wide.trace.chisq, wave.trace.chisq, rtol=1e-10, err_msg=what)
+    np.testing.assert_allclose(wide.trace.chisq0, wave.trace.chisq0, rtol=1e-10, err_msg=what)
+
+
+@pytest.mark.parametrize("started", [False, True])
+def test_the_traced_wave_kernel_records_the_same_moves_at_1500_q(started):
+    _same_moves(_run("sphere1500", started, False, K), _run("sphere1500", started, False, K, engine.EXEC_WAVE), "sphere1500")
+
+
+@pytest.mark.parametrize("tag", ["cyl_aspect", "smeared_sphere"])
+def test_integral_and_smeared_rows_against_the_traced_wave_kernel(tag):
+    """Isotropic cylinders (intDiv 12) and a smeared sphere at 1500 q-points, cold and started."""
+    q, I, sig = _synthetic(1500)
+    smear = None
+    if tag == "cyl_aspect":
+        m, _ = make_models("cyl_aspect", *RANGES["cyl_aspect"], intDiv=12.)
+    else:
+        m, _ = make_models("sphere", *RANGES["sphere"])
+        _, smear = product_smearing("trapezoid", False, 9, q, I, sig, umbra=2e-3 * q.max(), penumbra=4e-3 * q.max())
+    setup = m.setup()
+    st = engine.Settings(n_contrib=12, n_reps=R, max_iter=40, conv_crit=1e-9, max_retries=0, seed=9, exec_mode=engine.EXEC_WAVE)
+    wide_st = engine.Settings(**{**st.__dict__, "exec_mode": WG})
+    start = engine.analyse(setup, q, I, sig, engine.Settings(**{**st.__dict__, "max_iter": 16, "seed": 8}), smear=smear).contribs
+    for given, what in ((None, "cold"), (start, "started")):
+        wave = engine.analyse(setup, q, I, sig, st, smear=smear, start=given, trace=K)
+        wide = engine.analyse(setup, q, I, sig, wide_st, smear=smear, start=given, trace=K)
+        assert (wave.trace.count < K).all()
+        _same_moves(wide, wave, "%s %s" % (tag, what))
+        _same(wide, engine.analyse(setup, q, I, sig, wide_st, smear=smear, start=given), "%s %s: traced against untraced" % (tag, what))
+
+
+@pytest.mark.parametrize("name", list(GEOMETRY))
+def test_the_records_rebuild_the_result(name):
+    """No oracle: the records written in order over the initial set, at row step % N, are the final parameter sets."""
+    N = SHAPES[name][2]
+    for started in (True, False):
+        wl, res = _traced_workload(name, started), _run(name, started, False, K)
+        for r in range(R):
+            if started:
+                rset = np.array(wl["start"][:, :, r])
+            else:                                       # the initial set of the chain: generateParameters(N) on its Philox stream
+                rset = O.generate_parameters(wl["spec"], O.PhiloxStream(SEED, REP_OFFSET + r, pos=0), N)
+            for i in range(int(res.trace.count[r])):
+                rset[res.trace.step[i, r] % N] = res.trace.values[i, :, r]
+            if started:
+                assert np.array_equal(rset, res.contribs[:, :, r]), r
+            else:
+                np.testing.assert_allclose(rset, res.contribs[:, :, r], rtol=1e-12)
+
+
+@pytest.mark.parametrize("capacity", [1, 3])
+@pytest.mark.parametrize("started", [False, True])
+def test_small_capacity_keeps_the_first_moves_and_writes_nothing_else(capacity, started):
+    name = "sphere1025"
+    wl, full = _traced_workload(name, started), _run(name, started, False, K)
+    P = wl["spec"].n_active
+    st = engine.Settings(**{**wl["st"].__dict__, "exec_mode": WG})
+    prob = engine.HipProblem(wl["setup"], wl["q"], wl["I"], wl["sig"], st)
+    res = engine.ChainResults(st.n_contrib, P, R, len(prob.q))
+    t, big, where = _guarded_trace(capacity, P, R)
+    lib = _lib.load()
+    given = np.ascontiguousarray(wl["start"]) if started else None
+    _lib.check(lib.mcsas_hip_analyse_traced(C.byref(prob.c), _lib.as_dp(given) if started else None, C.byref(res.c), C.byref(t)), lib)
+    _same(res, full, "small capacity")
+    got = {f: big[f][g:g + n] for f, (g, n) in where.items()}
+    assert np.array_equal(got["count"], full.num_moves) and np.array_equal(got["count"], full.trace.count) and (got["count"] > capacity).all()
+    assert np.array_equal(got["chisq0"], full.trace.chisq0)
+    assert np.array_equal(got["step"].reshape(capacity, R), full.trace.step[:capacity])
+    assert np.array_equal(got["chisq"].reshape(capacity, R), full.trace.chisq[:capacity])
+    assert np.array_equal(got["values"].reshape(capacity, P, R), full.trace.values[:capacity])
+    for f, (g, n) in where.items():                     # nothing on either side of the caller's arrays
+        assert (big[f][:g] == big[f][0]).all() and (big[f][g + n:] == big[f][0]).all() and big[f][0] in (-77, -77.5), f
+    # ... and through the Python front: the same records
+    small = engine.analyse(wl["setup"], wl["q"], wl["I"], wl["sig"], st, start=wl["start"], trace=capacity)
+    assert np.array_equal(small.trace.step, full.trace.step[:capacity]) and np.array_equal(small.trace.values, full.trace.values[:capacity])
+    _check_trace(wl["chains"], small.trace, capacity)
+    _check_exact(wl["chains"], small.trace, capacity)
+
+
+def test_retries_leave_the_trace_of_the_last_attempt():
+    """test_wide_start_gpu._retry_workload: 1025 q-points, a start no attempt brings to the criterion within 24 steps, two retries,
+    both taken by every chain.  The records of the earlier attempts are overwritten or dropped."""
+    wl = _retry_workload()
+    st, N = wl["st"], wl["st"].n_contrib
+    ost = O.Settings(n_contrib=N, n_reps=1, max_iter=st.max_iter, conv_crit=st.conv_crit, max_retries=2)
+    chains = [_oracle_traced(wl["spec"], wl["q"], wl["I"], wl["sig"], ost, O.PhiloxStream(st.seed, REP_OFFSET + r, pos=0),
+                             start=wl["start"][:, :, r], retries=2) for r in range(R)]
+    assert [c["attempts"] for c in chains] == [3, 3, 3] and [c["iters"] for c in chains] == [c["iters"] for c in wl["chains"]]
+    assert all(3 < c["ref"].num_moves < K for c in chains), [c["ref"].num_moves for c in chains]
+    res = engine.analyse(wl["setup"], wl["q"], wl["I"], wl["sig"], st, start=wl["start"], trace=K)
+    _check_against_oracle(chains, res, 1)
+    _check_trace(chains, res.trace, K)
+    _check_exact(chains, res.trace, K)
+    _same(res, engine.analyse(wl["setup"], wl["q"], wl["I"], wl["sig"], st, start=wl["start"]), "traced against untraced")
+
+
+def test_a_converged_start_leaves_an_empty_trace():
+    wl = _workload("sphere1025")
+    cold = engine.Settings(n_contrib=16, n_reps=R, max_iter=40, conv_crit=1e-9, max_retries=0, seed=21, exec_mode=WG)
+    first = engine.analyse(wl["setup"], wl["q"], wl["I"], wl["sig"], cold)
+    assert (first.num_moves > 0).all()
+    st = engine.Settings(n_contrib=16, n_reps=R, max_iter=40, conv_crit=1.5 * float(first.chisq.max()), max_retries=2, seed=22, exec_mode=WG)
+    res = engine.analyse(wl["setup"], wl["q"], wl["I"], wl["sig"], st, start=first.contribs, trace=5)
+    assert np.array_equal(res.contribs, first.contribs) and not res.num_iter.any() and (res.attempts == 1).all()
+    tr = res.trace
+    assert not tr.count.any()
+    np.testing.assert_allclose(tr.chisq0, res.chisq, rtol=1e-7)
+    assert (tr.step == -1).all() and np.isnan(tr.chisq).all() and np.isnan(tr.values).all()
+
+
+def test_plan_slots_reseed_clear_and_start_on_a_q_split_plan():
+    wl, wls = _traced_workload("sphere1025", False), _traced_workload("sphere1025", True)
+    st = engine.Settings(**{**wl["st"].__dict__, "exec_mode": WG})
+    one = _run("sphere1025", False, False, K)
+    # (the one-shot call from the start under the plan's criterion, the cold workload's; under its own: test_oracle_parity_of_the_trace)
+    one_started = engine.analyse(wl["setup"], wl["q"], wl["I"], wl["sig"], st, start=wls["start"], trace=K)
+    pl = engine.Plan(wl["setup"], wl["q"], wl["I"], wl["sig"], st)
+    other = engine.Plan(wl["setup"], wl["q"], wl["I"], wl["sig"], engine.Settings(**{**st.__dict__, "seed": SEED + 1}))
+    lib = pl.lib
+    try:
+        assert pl.info["exec_mode"] == "workgroup" and pl.info["q_per_lane"] == 8
+        pl.launch()
+        plain = pl.fetch()
+        with pytest.raises(_lib.McSASHipError, match="no trace") as e:       # no trace yet
+            pl.fetch_trace(capacity=K)
+        assert e.value.code == MCSAS_EINVAL
+        pl.set_trace(K)
+        assert pl.trace_capacity == K
+        with pytest.raises(_lib.McSASHipError, match="no traced launch"):     # slot 0 holds the untraced launch
+            pl.fetch_trace()
+        # two slots, two seeds: each slot keeps its own trace
+        pl.launch(slot=0)
+        pl.reseed(SEED + 1, REP_OFFSET)
+        pl.launch(slot=1)
+        b = pl.fetch(slot=1)
+        a = pl.fetch(slot=0)
+        _same(a, plain, "slot 0"); _same(a, one, "slot 0 against the one-shot call"); _same_trace(a.trace, one.trace, "slot 0")
+        assert not np.array_equal(b.trace.step, a.trace.step) and not np.array_equal(b.trace.values, a.trace.values)   # a reseed changes the trace
+        assert np.array_equal(b.trace.count, b.num_moves) and (b.num_moves > 3).all()
+        _same_trace(pl.fetch_trace(slot=0), a.trace, "slot 0 again, after slot 1 was fetched")
+        with pytest.raises(_lib.McSASHipError, match="capacity") as e:
+            pl.fetch_trace(capacity=K - 1)
+        assert e.value.code == MCSAS_EINVAL
+        other.launch()
+        _same(other.fetch(), b, "the untraced plan with the same seed")
+        # a batch takes no q-split plan, traced or not, and launches nothing
+        with pytest.raises(_lib.McSASHipError, match="launch_batch") as e:
+            engine.launch_batch([other, pl])
+        assert e.value.code == MCSAS_EINVAL
+        # a start set on the traced plan: the started form of the traced kernel; cleared: the cold form again
+        pl.reseed(SEED, REP_OFFSET)
+        pl.set_start(wls["start"])
+        pl.launch()
+        started = pl.fetch()
+        assert not np.array_equal(started.contribs, one.contribs) and (started.draws == started.num_iter).all()   # (no draws for the given set)
+        _same(started, one_started, "start set"); _same_trace(started.trace, one_started.trace, "start set")
+        pl.set_start(None)
+        pl.launch()
+        again = pl.fetch()
+        _same(again, one, "start cleared"); _same_trace(again.trace, one.trace, "start cleared")
+        # the trace cleared: nothing to fetch, the untraced kernel's results, with and without a start
+        pl.set_trace(0)
+        pl.launch()
+        cleared = pl.fetch()
+        assert cleared.trace is None
+        _same(cleared, plain, "trace cleared")
+        tr = engine.ChainTrace(K, 1, R)
+        assert lib.mcsas_hip_plan_fetch_trace(pl.h, 0, C.byref(tr.c)) == MCSAS_EINVAL
+        pl.set_start(wls["start"])
+        pl.launch()
+        untraced_started = pl.fetch()
+        assert untraced_started.trace is None
+        _same(untraced_started, started, "started, trace cleared")
+    finally:
+        pl.close(); other.close()
+
+
+def test_plugin_model_gives_the_trace_of_the_built_in_one():
+    q, I, sig = _synthetic(1025)
+    lo, hi = RANGES["gausschain"]
+    st = engine.Settings(n_contrib=16, n_reps=R, max_iter=48, conv_crit=1e-9, max_retries=0, seed=9, exec_mode=WG)
+    res = []
+    for as_plugin in (False, True):
+        m, _ = make_models("gausschain", lo, hi)
+        if as_plugin:
+            plugin_twin(m, "gausschain")
+        setup = m.setup()
+        assert (setup.model_id >= engine.MODEL_PLUGIN0) == as_plugin
+        if not res:
+            start = engine.analyse(setup, q, I, sig, engine.Settings(**{**st.__dict__, "max_iter": 16, "seed": 8})).contribs
+        res.append((engine.analyse(setup, q, I, sig, st, trace=K), engine.analyse(setup, q, I, sig, st, start=start, trace=K)))
+    for k, what in enumerate(("cold", "started")):
+        assert (res[0][k].trace.count > 0).all() and (res[0][k].trace.count < K).all()
+        _same(res[1][k], res[0][k], what); _same_trace(res[1][k].trace, res[0][k].trace, what)
+
+
+def test_calc_stores_the_trace_of_unbinned_data():
+    """McSAS(execMode=workgroup).calc(trace=K) on 4097 points (the settings of test_wide_start_gpu.py's front-end test)."""
+    q, I, sig = _synthetic(4097)
+    cap = 512
+    algo = mcsas_amd.McSAS.factory()(seed=17, device=0, execMode=WG)
+    algo.numContribs.setValue(16); algo.numReps.setValue(R); algo.maxIterations.setValue(300)
+    algo.convergenceCriterion.setValue(1500.0); algo.maxRetries.setValue(1)
+    algo.model, _ = make_models("sphere", *RANGES["sphere"])
+    algo.data = mcsas_amd.SASData(q, I, sig)
+    assert algo.data.count == 4097
+    algo.calc(trace=cap)
+    tr, d = algo.result[0]["trace"], algo.details
+    assert set(tr) == {"count", "chisq0", "step", "chisq", "values"}
+    assert tr["count"].shape == (R,) and tr["chisq0"].shape == (R,) and tr["step"].shape == (cap, R)
+    assert tr["chisq"].shape == (cap, R) and tr["values"].shape == (cap, 1, R)
+    assert np.array_equal(tr["count"], d.num_moves) and (d.converged == 1).all() and (d.num_moves > 0).all()
+    checked = 0
+    for r in range(R):
+        n = int(tr["count"][r])
+        if n <= cap:
+            np.testing.assert_allclose(tr["chisq"][n - 1, r], d.chisq[r], rtol=1e-7)
+            checked += 1
+    assert checked > 0
+    contribs = algo.result[0]["contribs"]
+    algo.calc()
+    assert "trace" not in algo.result[0] and np.array_equal(algo.result[0]["contribs"], contribs)
+    # ... and with a start: the tighter criterion, from the result
+    algo.convergenceCriterion.setValue(600.0)
+    algo.calc(start=contribs, trace=16)
+    tr2 = algo.result[0]["trace"]
+    assert tr2["step"].shape == (16, R) and np.array_equal(tr2["count"], algo.details.num_moves) and tr2["count"].any()
+    assert (tr2["chisq0"] <= d.chisq * (1 + 1e-7)).all()                     # the refined run starts where the first one ended
