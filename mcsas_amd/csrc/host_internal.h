@@ -1,10 +1,10 @@
-// host_internal.h — what the host translation units of libmcsas_hip.so share (mcsas_hip.hip: the analysis; host_plugin.hip: the
-// run-time compiler of model plug-ins; host_calls.hip: the small one-call entry points; host_hist.hip: McSAS.histogram()).  Host code
-// only: the run-time compiler never sees this file (it is not among the embedded headers).
+// host_internal.h — what the host units of libmcsas_hip.so share (mcsas_hip.hip: plans; host_analyse.hip: one-shot analyses; host_rows.hip:
+// rows evaluated by the caller; host_plugin.hip: run-time compiler of model plug-ins; host_calls.hip: small one-call entry points; host_hist.hip:
+// McSAS.histogram()).  Host code only: the run-time compiler never sees this file (it is not among the embedded headers).
 #pragma once
 #include <hip/hip_runtime.h>
-
 #include <string>
+#include <vector>
 
 #include "../../include/mcsas_hip.h"
 #include "chain_common.h"
@@ -110,4 +110,31 @@ static int plugin_small_launch(int model_id, PluginSmallKernel which, dim3 grid,
     return MCSAS_OK;
 }
 
+// ------------------------------------------------------------------------------ what a request is refused for, with and without a plan (mcsas_hip.hip)
+// plan_set_start / plan_set_trace / plan_fetch_trace and the one-shot entry points over them (host_analyse.hip) answer alike
+// the first non-finite value of the columns [first, first + R) of start[N][P][stride], or MCSAS_OK
+int check_start_finite(const char *who, const double *start, size_t N, size_t P, size_t stride, size_t first, size_t R);
+int check_trace_arrays(const char *who, const mcsas_trace *tr);
+const char *exec_mode_name(int mode);
+// a trace block (step, chisq and values of `capacity` moves per repetition) stays below this
+constexpr size_t TRACE_MAX_BYTES = (size_t)2 << 30;
+
 #pragma GCC visibility pop
+
+// ------------------------------------------------------------------------------ the data of a problem as the chains read them
+// the weights and weighted data, padded with zeros, and their sums in the argument block; sigma == 0 -> 1 (backgroundscalingfit.py:117).
+// Plan creation (mcsas_hip.hip) and the chains whose rows the caller evaluates (host_rows.hip) prepare them alike.  (Outside the hidden
+// region above: the library has always exported this constructor, and its list of symbols stays what it was.)
+struct WeighedData {
+    std::vector<double> w, wI, I;
+    WeighedData(const mcsas_problem *p, size_t qpad, mcsas::ChainArgs *a) : w(qpad, 0.), wI(qpad, 0.), I(qpad, 0.) {
+        double Sw = 0, SI = 0, SII = 0, Ss2 = 0;
+        for (int i = 0; i < p->nq; ++i) {
+            double e = p->sigma[i] == 0.0 ? 1.0 : p->sigma[i];
+            double wi = 1.0 / (e * e);
+            w[i] = wi; wI[i] = wi * p->intensity[i]; I[i] = p->intensity[i];
+            Sw += wi; SI += wi * p->intensity[i]; SII += wi * p->intensity[i] * p->intensity[i]; Ss2 += e * e;
+        }
+        a->nq = p->nq; a->qpad = (int)qpad; a->Sw = Sw; a->SI = SI; a->SII = SII; a->Ssig2 = Ss2;
+    }
+};

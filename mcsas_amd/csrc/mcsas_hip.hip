@@ -1,7 +1,8 @@
-// mcsas_hip.hip — libmcsas_hip.so: C ABI (include/mcsas_hip.h) over the gfx950 chain kernels.  This unit holds the analysis: plans,
-// launches, fetches, batches, sharding, rows evaluated by the caller, streams and the ABI queries; the run-time compiler of model
-// plug-ins is host_plugin.hip, the small one-call entry points (model.calc, input preparation) are host_calls.hip, McSAS.histogram()
-// is host_hist.hip, and what the four share is host_internal.h.
+// mcsas_hip.hip — libmcsas_hip.so: C ABI (include/mcsas_hip.h) over the gfx950 chain kernels.  This unit holds the plans: their
+// creation, start and trace, launches, fetches and batch launches, with the memory cache, the streams and the ABI queries.  The
+// one-shot analyses over plans are host_analyse.hip, the chains whose rows the caller evaluates host_rows.hip, the run-time compiler
+// of model plug-ins host_plugin.hip, the small one-call entry points (model.calc, input preparation) host_calls.hip,
+// McSAS.histogram() host_hist.hip; what they share is host_internal.h, and host_result.h writes every mcsas_result.
 // Built only for MI355X (gfx950); there is no CPU path in here.
 #include <hip/hip_runtime.h>
 
@@ -19,7 +20,7 @@
 #include <vector>
 
 #include "host_internal.h"
-#include "chain_feed.h"     // feed_rows_kernel: chains whose rows the caller evaluates (mcsas_hip_analyse_host_rows, _device_rows)
+#include "host_result.h"
 #include "chain_wg.h"   // WgGeom / wg_geometry only; the kernels are instantiated in kern_*.hip
 #include "pipe_layout.h" // the pipeline's argument blocks, constants and pipe_geometry (no kernel templates)
 #include "chain_wide.h" // WIDE_* constants only
@@ -455,7 +456,6 @@ static int auto_mode_light(int qpad, int n_contrib, double reps, bool pipe_ok, b
     return modes[best];
 }
 
-
 // ------------------------------------------------------------------------------ plan creation
 static int validate_problem(const mcsas_problem *p) {
     if (p->struct_size != sizeof(mcsas_problem))
@@ -606,20 +606,6 @@ static int decide_shape(const mcsas_problem *p, const ModelArgs &margs, int n_cu
     return MCSAS_OK;
 }
 
-// the weights and weighted data, padded with zeros, and their sums in the argument block; sigma == 0 -> 1 (backgroundscalingfit.py:117)
-struct WeighedData {
-    std::vector<double> w, wI, I;
-    WeighedData(const mcsas_problem *p, size_t qpad, ChainArgs *a) : w(qpad, 0.), wI(qpad, 0.), I(qpad, 0.) {
-        double Sw = 0, SI = 0, SII = 0, Ss2 = 0;
-        for (int i = 0; i < p->nq; ++i) {
-            double e = p->sigma[i] == 0.0 ? 1.0 : p->sigma[i];
-            double wi = 1.0 / (e * e);
-            w[i] = wi; wI[i] = wi * p->intensity[i]; I[i] = p->intensity[i];
-            Sw += wi; SI += wi * p->intensity[i]; SII += wi * p->intensity[i] * p->intensity[i]; Ss2 += e * e;
-        }
-        a->nq = p->nq; a->qpad = (int)qpad; a->Sw = Sw; a->SI = SI; a->SII = SII; a->Ssig2 = Ss2;
-    }
-};
 // the padded data vectors on the device
 static int upload_data(mcsas_plan *pl, const mcsas_problem *p, int qpad) {
     ChainArgs &a = pl->args;
@@ -813,7 +799,7 @@ extern "C" int mcsas_hip_plan_reseed(mcsas_plan *pl, uint64_t seed, int32_t rep_
 }
 
 // the first non-finite value of the columns [first, first + R) of start[N][P][stride], or MCSAS_OK
-static int check_start_finite(const char *who, const double *start, size_t N, size_t P, size_t stride, size_t first, size_t R) {
+int check_start_finite(const char *who, const double *start, size_t N, size_t P, size_t stride, size_t first, size_t R) {
     for (size_t i = 0; i < N * P; ++i)
         for (size_t r = 0; r < R; ++r)
             if (!std::isfinite(start[i * stride + first + r]))
@@ -821,7 +807,7 @@ static int check_start_finite(const char *who, const double *start, size_t N, si
     return MCSAS_OK;
 }
 
-static const char *exec_mode_name(int mode) {
+const char *exec_mode_name(int mode) {
     return mode == MCSAS_EXEC_WAVE ? "MCSAS_EXEC_WAVE" : mode == MCSAS_EXEC_WORKGROUP ? "MCSAS_EXEC_WORKGROUP" : mode == MCSAS_EXEC_PIPELINE ? "MCSAS_EXEC_PIPELINE" : "MCSAS_EXEC_AUTO";
 }
 
@@ -862,7 +848,6 @@ static int enqueue_start(mcsas_plan *pl, hipStream_t st) {
 // ------------------------------------------------------------------------------ the trace of a wave or q-split plan (include/mcsas_hip.h)
 // bytes of one slot's trace block: step, chisq and values of `capacity` moves per repetition
 static size_t trace_record_bytes(size_t R, size_t capacity, size_t P) { return R * capacity * (16 + 8 * P); }
-static const size_t TRACE_MAX_BYTES = (size_t)2 << 30;
 static void drop_slot_trace(mcsas_plan *pl, mcsas_plan::Slot &sl) {
     if (sl.d_trace) cached_dev_free(sl.d_trace, sl.trace_bytes, pl->dev);
     sl.d_trace = nullptr; sl.trace_bytes = 0; sl.trace = TraceArgs{}; sl.traced = false;
@@ -912,7 +897,7 @@ extern "C" int mcsas_hip_plan_set_trace(mcsas_plan *pl, int32_t capacity) {
     return MCSAS_OK;
 }
 
-static int check_trace_arrays(const char *who, const mcsas_trace *tr) {
+int check_trace_arrays(const char *who, const mcsas_trace *tr) {
     if (!tr) return fail(MCSAS_EINVAL, "%s: trace is NULL", who);
     if (tr->struct_size != sizeof(mcsas_trace)) return fail(MCSAS_EINVAL, "%s: mcsas_trace size %u, library expects %zu", who, tr->struct_size, sizeof(mcsas_trace));
     if (tr->capacity < 1) return fail(MCSAS_EINVAL, "%s: trace capacity %d (>= 1)", who, (int)tr->capacity);
@@ -1132,27 +1117,14 @@ extern "C" int mcsas_hip_plan_fetch_slot(mcsas_plan *pl, int32_t slot, mcsas_res
         if (res->contribs) {
             std::vector<double> hr(R * N * P);
             HIPCHK(d2h(hr.data(), s.d_rset, sizeof(double) * hr.size()));
-            for (size_t r = 0; r < R; ++r)
-                for (size_t n = 0; n < N; ++n)
-                    for (size_t p = 0; p < P; ++p) res->contribs[(n * P + p) * R + r] = hr[(r * N + n) * P + p];
+            result_put_sets(res, hr.data(), N, P, R, 0, R);
         }
         if (res->fit) {
             std::vector<double> hf(R * qpad);
             HIPCHK(d2h(hf.data(), s.d_fit, sizeof(double) * hf.size()));
-            for (size_t r = 0; r < R; ++r)
-                for (size_t k = 0; k < Q; ++k) res->fit[k * R + r] = hf[r * qpad + k];
+            result_put_fit(res, hf.data(), qpad, Q, R, 0, R);
         }
-        for (size_t r = 0; r < R; ++r) {
-            if (res->chisq) res->chisq[r] = ho[r].chisq;
-            if (res->scaling) res->scaling[r] = ho[r].scaling;
-            if (res->background) res->background[r] = ho[r].background;
-            if (res->num_iter) res->num_iter[r] = ho[r].num_iter;
-            if (res->num_moves) res->num_moves[r] = ho[r].num_moves;
-            if (res->attempts) res->attempts[r] = ho[r].attempts;
-            if (res->converged) res->converged[r] = ho[r].converged;
-            if (res->seconds) res->seconds[r] = ho[r].seconds;
-            if (res->draws) res->draws[r] = ho[r].draws;
-        }
+        for (size_t r = 0; r < R; ++r) result_put_row(res, r, ho[r]);
     }
     if (ovf) return fail(MCSAS_ESTREAM, "replay stream exhausted (replay_len=%lld)", (long long)pl->prob.replay_len);
     return MCSAS_OK;
@@ -1274,556 +1246,6 @@ extern "C" int mcsas_hip_plan_launch_batch(mcsas_plan *const *plans, int32_t n, 
     }
     guard.ok = true;
     return MCSAS_OK;
-}
-
-// One-shot form: plans in the wavefront-per-chain mode for every problem, one batch launch, results at their places.
-extern "C" int mcsas_hip_analyse_batch(const mcsas_problem *problems, int32_t n, mcsas_result *results) {
-    if (!problems || !results || n < 1) return fail(MCSAS_EINVAL, "analyse_batch: needs n >= 1 problems and results (n = %d)", (int)n);
-    for (int i = 0; i < n; ++i) {
-        const mcsas_problem *p = &problems[i];
-        if (p->struct_size != sizeof(mcsas_problem)) return fail(MCSAS_EINVAL, "analyse_batch: problem %d: mcsas_problem size %u, library expects %zu (ABI mismatch)", i, p->struct_size, sizeof(mcsas_problem));
-        if (results[i].struct_size != sizeof(mcsas_result)) return fail(MCSAS_EINVAL, "analyse_batch: result %d: mcsas_result size mismatch", i);
-        if (p->n_active == 0) continue;                                       // answered at its place below, as mcsas_hip_analyse does
-        if (p->exec_mode != MCSAS_EXEC_AUTO && p->exec_mode != MCSAS_EXEC_WAVE)
-            return fail(MCSAS_EINVAL, "analyse_batch: problem %d asks for exec_mode %d; a batch runs one wavefront per chain (exec_mode 0 or 1)", i, p->exec_mode);
-        if (p->n_devices > 1) return fail(MCSAS_EINVAL, "analyse_batch: problem %d spreads over %d devices; a batch runs on one", i, p->n_devices);
-        if (p->nq > 64 * WAVE) return fail(MCSAS_EINVAL, "analyse_batch: problem %d has nq %d > %d (one wavefront per chain)", i, p->nq, 64 * WAVE);
-    }
-    std::vector<mcsas_plan *> plans;
-    std::vector<int> index;
-    int rc = MCSAS_OK;
-    for (int i = 0; i < n && !rc; ++i) {
-        if (problems[i].n_active == 0) continue;
-        mcsas_problem p = problems[i];
-        p.exec_mode = MCSAS_EXEC_WAVE;
-        p.n_devices = 0;
-        mcsas_plan *pl = nullptr;
-        rc = mcsas_hip_plan_create(&p, &pl);
-        if (rc) { std::string e = g_err; rc = fail(rc, "analyse_batch: problem %d: %s", i, e.c_str()); break; }
-        plans.push_back(pl); index.push_back(i);
-    }
-    if (!rc && !plans.empty()) rc = mcsas_hip_plan_launch_batch(plans.data(), (int32_t)plans.size(), nullptr);
-    if (!rc) {
-        for (size_t k = 0; k < plans.size(); ++k) {
-            const int rk = mcsas_hip_plan_fetch(plans[k], &results[index[k]]);
-            if (rk && !rc) { std::string e = g_err; rc = fail(rk, "analyse_batch: problem %d: %s", index[k], e.c_str()); }
-        }
-    }
-    for (mcsas_plan *pl : plans) mcsas_hip_plan_destroy(pl);
-    if (rc) return rc;
-    for (int i = 0; i < n; ++i)
-        if (problems[i].n_active == 0) {
-            const int r0 = mcsas_hip_analyse(&problems[i], &results[i]);
-            if (r0) return r0;
-        }
-    return MCSAS_OK;
-}
-
-// `start` (or null): columns [rep_first, rep_first + n_reps) of start[n_contrib][n_active][rep_stride], mcsas_hip_plan_set_start
-static int analyse_one(const mcsas_problem *p, mcsas_result *res, const double *start = nullptr, int32_t rep_stride = 0, int32_t rep_first = 0) {
-    mcsas_plan *pl = nullptr;
-    int rc = mcsas_hip_plan_create(p, &pl);
-    if (rc) return rc;
-    if (start) rc = mcsas_hip_plan_set_start(pl, start, rep_stride, rep_first);
-    if (!rc) rc = mcsas_hip_plan_launch(pl, nullptr);
-    if (!rc) rc = mcsas_hip_plan_fetch(pl, res);
-    mcsas_hip_plan_destroy(pl);
-    return rc;
-}
-
-// repetitions [first, first + count) of device-list entry `index` (contiguous blocks, sizes differ by at most one)
-extern "C" int mcsas_hip_shard(int32_t n_reps, int32_t n_devices, int32_t index, int32_t *first, int32_t *count) {
-    if (n_reps < 0 || n_devices < 1 || index < 0 || index >= n_devices || !first || !count) return fail(MCSAS_EINVAL, "bad argument");
-    const int32_t base = n_reps / n_devices, extra = n_reps % n_devices;
-    *count = base + (index < extra ? 1 : 0);
-    *first = index * base + (index < extra ? index : extra);
-    return MCSAS_OK;
-}
-
-// McSAS.analyse's repetition loop (mcsas.py:214-262) over several GPUs: one host thread, one plan and one stream per
-// device, each running a contiguous block of repetitions under its global chain ids; every block lands in the caller's
-// (…, numReps) arrays at its place.  No data-path exchange between the devices: the blocks share read-only inputs only.
-static int analyse_sharded(const mcsas_problem *p, mcsas_result *res, const double *start = nullptr) {
-    if (res->struct_size != sizeof(mcsas_result)) return fail(MCSAS_EINVAL, "mcsas_result size mismatch");
-    const int G = p->n_devices;
-    if (G > MCSAS_MAX_DEVICES) return fail(MCSAS_EINVAL, "n_devices %d > %d", G, MCSAS_MAX_DEVICES);
-    if (p->n_reps < 1 || p->n_contrib < 1 || p->nq < 1) return fail(MCSAS_EINVAL, "n_reps, n_contrib and nq must be >= 1");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MCSAS_ENODEV, "no HIP device available");
-    for (int g = 0; g < G; ++g)
-        if (p->devices[g] < 0 || p->devices[g] >= ndev) return fail(MCSAS_ENODEV, "devices[%d] = %d, %d present", g, p->devices[g], ndev);
-    const size_t R = p->n_reps, N = p->n_contrib, P = p->n_active, Q = p->nq;
-    struct Shard {
-        mcsas_problem prob; mcsas_result out;
-        int32_t first = 0, count = 0; int rc = 0; std::string err;
-        std::vector<double> contribs, fit, chisq, scaling, background, seconds;
-        std::vector<int64_t> num_iter, num_moves, draws;
-        std::vector<int32_t> attempts, converged;
-    };
-    std::vector<Shard> sh(G);
-    std::vector<std::thread> th;
-    for (int g = 0; g < G; ++g) {
-        Shard &s = sh[g];
-        mcsas_hip_shard((int32_t)R, G, g, &s.first, &s.count);
-        if (s.count == 0) continue;
-        s.prob = *p;
-        s.prob.n_devices = 0; s.prob.device = p->devices[g];
-        s.prob.n_reps = s.count; s.prob.rep_offset = p->rep_offset + s.first;
-        if (p->replay_stream) s.prob.replay_stream = p->replay_stream + (size_t)s.first * p->replay_len;
-        const size_t Rg = s.count;
-        memset(&s.out, 0, sizeof s.out);
-        s.out.struct_size = sizeof(mcsas_result);
-#define SHBUF(f) do { if (res->f) { s.f.resize(Rg); s.out.f = s.f.data(); } } while (0)
-        if (res->contribs) { s.contribs.resize(N * P * Rg); s.out.contribs = s.contribs.data(); }
-        if (res->fit) { s.fit.resize(Q * Rg); s.out.fit = s.fit.data(); }
-        SHBUF(chisq); SHBUF(scaling); SHBUF(background); SHBUF(seconds); SHBUF(num_iter); SHBUF(num_moves); SHBUF(draws);
-        SHBUF(attempts); SHBUF(converged);
-#undef SHBUF
-        th.emplace_back([&s, start, R]() {
-            s.rc = analyse_one(&s.prob, &s.out, start, (int32_t)R, s.first);   // (every block reads its own columns of the one start)
-            if (s.rc) s.err = g_err;                          // (thread-local in the worker)
-        });
-    }
-    for (auto &t : th) t.join();
-    for (int g = 0; g < G; ++g)
-        if (sh[g].rc) return fail(sh[g].rc, "device %d (repetitions %d..%d): %s", p->devices[g], sh[g].first, sh[g].first + sh[g].count - 1, sh[g].err.c_str());
-    for (int g = 0; g < G; ++g) {
-        const Shard &s = sh[g];
-        const size_t Rg = s.count, f0 = s.first;
-        if (res->contribs) for (size_t i = 0; i < N * P; ++i) for (size_t r = 0; r < Rg; ++r) res->contribs[i * R + f0 + r] = s.contribs[i * Rg + r];
-        if (res->fit) for (size_t k = 0; k < Q; ++k) for (size_t r = 0; r < Rg; ++r) res->fit[k * R + f0 + r] = s.fit[k * Rg + r];
-        for (size_t r = 0; r < Rg; ++r) {
-#define SHCOPY(f) do { if (res->f) res->f[f0 + r] = s.f[r]; } while (0)
-            SHCOPY(chisq); SHCOPY(scaling); SHCOPY(background); SHCOPY(seconds); SHCOPY(num_iter); SHCOPY(num_moves); SHCOPY(draws);
-            SHCOPY(attempts); SHCOPY(converged);
-#undef SHCOPY
-        }
-    }
-    return MCSAS_OK;
-}
-
-extern "C" int mcsas_hip_analyse(const mcsas_problem *p, mcsas_result *res) {
-    if (!res) return fail(MCSAS_EINVAL, "null result");
-    if (p && p->n_active == 0) {
-        // No active fit parameter (mcsas.py:198-201, 238-239, 322-323): analyse() runs ONE repetition of ONE
-        // contribution, mcFit returns the model's intensity at its fixed parameter values with conval = -1,
-        // scaling 1, background 0, and the repetition loop leaves without retrying.  Result arrays are sized
-        // for n_contrib = n_reps = 1 whatever the problem says.
-        if (res->struct_size != sizeof(mcsas_result)) return fail(MCSAS_EINVAL, "mcsas_result size mismatch");
-        if (p->struct_size != sizeof(mcsas_problem)) return fail(MCSAS_EINVAL, "mcsas_problem size mismatch (ABI)");
-        if (p->nq < 1 || !p->q) return fail(MCSAS_EINVAL, "nq/q missing");
-        std::vector<double> cum(p->nq);
-        int rc0 = mcsas_hip_model_calc(p, nullptr, 1, cum.data(), nullptr, nullptr, nullptr, nullptr);
-        if (rc0) return rc0;
-        if (res->fit) for (int k = 0; k < p->nq; ++k) res->fit[k] = cum[k];
-        if (res->chisq) res->chisq[0] = -1.0;
-        if (res->scaling) res->scaling[0] = 1.0;
-        if (res->background) res->background[0] = 0.0;
-        if (res->num_iter) res->num_iter[0] = 0;
-        if (res->num_moves) res->num_moves[0] = 0;
-        if (res->attempts) res->attempts[0] = 1;
-        if (res->converged) res->converged[0] = 1;
-        if (res->seconds) res->seconds[0] = 0.0;
-        if (res->draws) res->draws[0] = 0;
-        return MCSAS_OK;
-    }
-    if (p && p->struct_size == sizeof(mcsas_problem) && p->n_devices > 1) return analyse_sharded(p, res);
-    return analyse_one(p, res);
-}
-
-// McSAS.analyse with the first attempt of every repetition started from a given set (include/mcsas_hip.h): one wavefront per chain,
-// or, where MCSAS_EXEC_WORKGROUP is asked for more than 1024 q-points, the q-split kernel; every refusal before a device is touched.
-extern "C" int mcsas_hip_analyse_from(const mcsas_problem *p, const double *start, mcsas_result *res) {
-    if (!p || !res) return fail(MCSAS_EINVAL, "analyse_from: null argument");
-    if (p->struct_size != sizeof(mcsas_problem))
-        return fail(MCSAS_EINVAL, "analyse_from: mcsas_problem size %u, library expects %zu (ABI mismatch)", p->struct_size, sizeof(mcsas_problem));
-    if (p->n_active == 0) return mcsas_hip_analyse(p, res);                     // nothing to start: one contribution at fixed values
-    if (!start) return fail(MCSAS_EINVAL, "analyse_from: start is NULL (mcsas_hip_analyse runs without one)");
-    const bool q_split = p->exec_mode == MCSAS_EXEC_WORKGROUP && p->nq > 16 * WAVE;      // (decide_shape: the q-split kernel, whatever waves_per_chain says)
-    if (p->exec_mode != MCSAS_EXEC_AUTO && p->exec_mode != MCSAS_EXEC_WAVE && !q_split)
-        return fail(MCSAS_EINVAL, "analyse_from: exec_mode %d (%s) asked with %d q-points; a start needs exec_mode = MCSAS_EXEC_WAVE (%d, or 0), or MCSAS_EXEC_WORKGROUP (%d) with more than %d q-points",
-                    p->exec_mode, exec_mode_name(p->exec_mode), p->nq, MCSAS_EXEC_WAVE, MCSAS_EXEC_WORKGROUP, 16 * WAVE);
-    if (p->nq > WIDE_MAX_WAVES * WAVE * 32) return fail(MCSAS_EINVAL, "analyse_from: nq %d > %d is not supported", p->nq, WIDE_MAX_WAVES * WAVE * 32);
-    if (!q_split && p->nq > 64 * WAVE)
-        return fail(MCSAS_EINVAL, "analyse_from: nq %d > %d: one wavefront per chain does not take it, and with exec_mode %d a start runs one wavefront per chain; "
-                    "MCSAS_EXEC_WORKGROUP (%d) takes a start for %d...%d q-points", p->nq, 64 * WAVE, p->exec_mode, MCSAS_EXEC_WORKGROUP, 16 * WAVE + 1, WIDE_MAX_WAVES * WAVE * 32);
-    if (p->n_active < 0 || p->n_active > MCSAS_MAX_ACTIVE) return fail(MCSAS_EINVAL, "n_active %d out of range", p->n_active);
-    if (p->n_contrib < 1 || p->n_reps < 1) return fail(MCSAS_EINVAL, "n_contrib and n_reps must be >= 1");
-    if (int rc = check_start_finite("analyse_from", start, (size_t)p->n_contrib, (size_t)p->n_active, (size_t)p->n_reps, 0, (size_t)p->n_reps)) return rc;
-    mcsas_problem q = *p;
-    q.exec_mode = q_split ? MCSAS_EXEC_WORKGROUP : MCSAS_EXEC_WAVE;
-    if (q.n_devices > 1) return analyse_sharded(&q, res, start);
-    return analyse_one(&q, res, start, q.n_reps, 0);
-}
-
-// mcsas_hip_analyse (MCSAS_EXEC_WAVE), or mcsas_hip_analyse_from when a start is given, with the accepted moves of every repetition's
-// last attempt (include/mcsas_hip.h): one wavefront per chain, or, where MCSAS_EXEC_WORKGROUP is asked for more than 1024 q-points,
-// the q-split kernel; every refusal before a device is touched.
-extern "C" int mcsas_hip_analyse_traced(const mcsas_problem *p, const double *start, mcsas_result *res, mcsas_trace *tr) {
-    if (!p || !res) return fail(MCSAS_EINVAL, "analyse_traced: null argument");
-    if (p->struct_size != sizeof(mcsas_problem))
-        return fail(MCSAS_EINVAL, "analyse_traced: mcsas_problem size %u, library expects %zu (ABI mismatch)", p->struct_size, sizeof(mcsas_problem));
-    if (int rc = check_trace_arrays("analyse_traced", tr)) return rc;
-    if (p->n_active == 0) {                                                    // one contribution at fixed values: no move is ever made
-        const int rc = mcsas_hip_analyse(p, res);
-        if (!rc) tr->count[0] = 0;
-        return rc;
-    }
-    const bool q_split = p->exec_mode == MCSAS_EXEC_WORKGROUP && p->nq > 16 * WAVE;      // (decide_shape: the q-split kernel, whatever waves_per_chain says)
-    if (p->exec_mode != MCSAS_EXEC_AUTO && p->exec_mode != MCSAS_EXEC_WAVE && !q_split)
-        return fail(MCSAS_EINVAL, "analyse_traced: exec_mode %d (%s) asked; a trace needs exec_mode = MCSAS_EXEC_WAVE (%d, or 0)", p->exec_mode, exec_mode_name(p->exec_mode), MCSAS_EXEC_WAVE);
-    if (p->nq > WIDE_MAX_WAVES * WAVE * 32) return fail(MCSAS_EINVAL, "analyse_traced: nq %d > %d is not supported", p->nq, WIDE_MAX_WAVES * WAVE * 32);
-    if (!q_split && p->nq > 64 * WAVE)
-        return fail(MCSAS_EINVAL, "analyse_traced: nq %d > %d: one wavefront per chain does not take it, and with exec_mode %d a trace runs one wavefront per chain; "
-                    "MCSAS_EXEC_WORKGROUP (%d) keeps a trace for %d...%d q-points", p->nq, 64 * WAVE, p->exec_mode, MCSAS_EXEC_WORKGROUP, 16 * WAVE + 1, WIDE_MAX_WAVES * WAVE * 32);
-    if (p->n_devices > 1) return fail(MCSAS_EINVAL, "analyse_traced: n_devices %d: a trace is kept on one device", p->n_devices);
-    if (p->n_active < 0 || p->n_active > MCSAS_MAX_ACTIVE) return fail(MCSAS_EINVAL, "n_active %d out of range", p->n_active);
-    if (p->n_contrib < 1 || p->n_reps < 1) return fail(MCSAS_EINVAL, "n_contrib and n_reps must be >= 1");
-    if ((size_t)tr->capacity > TRACE_MAX_BYTES / ((size_t)p->n_reps * (16 + 8 * (size_t)p->n_active)))
-        return fail(MCSAS_EINVAL, "analyse_traced: %d repetitions x capacity %d x %d bytes per move exceed 2 GiB", p->n_reps, (int)tr->capacity, 16 + 8 * p->n_active);
-    if (start) { if (int rc = check_start_finite("analyse_traced", start, (size_t)p->n_contrib, (size_t)p->n_active, (size_t)p->n_reps, 0, (size_t)p->n_reps)) return rc; }
-    mcsas_problem q = *p;
-    q.exec_mode = q_split ? MCSAS_EXEC_WORKGROUP : MCSAS_EXEC_WAVE;
-    q.n_devices = 0;
-    mcsas_plan *pl = nullptr;
-    int rc = mcsas_hip_plan_create(&q, &pl);
-    if (rc) return rc;
-    if (start) rc = mcsas_hip_plan_set_start(pl, start, q.n_reps, 0);
-    if (!rc) rc = mcsas_hip_plan_set_trace(pl, tr->capacity);
-    if (!rc) rc = mcsas_hip_plan_launch(pl, nullptr);
-    if (!rc) rc = mcsas_hip_plan_fetch(pl, res);
-    // (a replay stream that ran out is reported by the fetch; the trace of what ran is still the caller's)
-    if (!rc || rc == MCSAS_ESTREAM) {
-        const std::string e = g_err;
-        const int rt = mcsas_hip_plan_fetch_trace(pl, 0, tr);
-        if (rt) rc = rt; else g_err = e;
-    }
-    mcsas_hip_plan_destroy(pl);
-    return rc;
-}
-
-// ------------------------------------------------------------------------------ rows evaluated by the caller (ABI 4)
-// Philox4x32-10 on the host: the stream of device_util.h's philox_uniform (counter = (idx >> 1, chain, 0), key = seed; even draws
-// take words 0,1, odd draws words 2,3; 53 bits)
-static double philox_uniform_host(uint64_t seed, uint32_t chain, uint64_t idx) {
-    const uint64_t blk = idx >> 1;
-    uint32_t c0 = (uint32_t)blk, c1 = (uint32_t)(blk >> 32), c2 = chain, c3 = 0u;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    const uint32_t a = (idx & 1) ? c2 : c0, b = (idx & 1) ? c3 : c1;
-    return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) / 9007199254740992.0;
-}
-
-// what both entry points refuse of a problem, before a device is touched
-static int check_rows_problem(const mcsas_problem *p) {
-    if (p->struct_size != sizeof(mcsas_problem))
-        return fail(MCSAS_EINVAL, "mcsas_problem size %u, library expects %zu (ABI mismatch)", p->struct_size, sizeof(mcsas_problem));
-    if (p->nq < 1 || p->nq > 16384 || !p->q || !p->intensity || !p->sigma) return fail(MCSAS_EINVAL, "nq %d (1..16384) / data pointers", p->nq);
-    if (p->n_active < 1 || p->n_active > MCSAS_MAX_ACTIVE) return fail(MCSAS_EINVAL, "n_active %d (1..%d)", p->n_active, MCSAS_MAX_ACTIVE);
-    if (p->n_contrib < 1 || p->n_reps < 1 || p->max_iter < 0 || p->max_retries < 0) return fail(MCSAS_EINVAL, "n_contrib / n_reps / max_iter / max_retries");
-    if (p->reserved0) return fail(MCSAS_EINVAL, "reserved0 must be 0");
-    for (int c = 0; c < p->n_active; ++c)
-        if (p->gen_kind[c] < MCSAS_GEN_UNIFORM || p->gen_kind[c] > MCSAS_GEN_EXP3) return fail(MCSAS_EINVAL, "gen_kind[%d] = %d", c, p->gen_kind[c]);
-    return MCSAS_OK;
-}
-
-// rows per round: every chain's block is at most max(N, window) rows; as many chains per round as fit ~256 MB of rows
-static void rows_shape(const mcsas_problem *p, int32_t window, size_t *blk, size_t *round_rows, size_t *qpad) {
-    *qpad = ((size_t)p->nq + 63) / 64 * 64;
-    *blk = std::max((size_t)p->n_contrib, (size_t)(window < 1 ? 64 : window));
-    *round_rows = std::max(*blk, std::min((size_t)p->n_reps * *blk, (size_t)(256u << 20) / (*qpad * sizeof(double))));
-}
-
-// The chains of one such call, between the rounds: their state on the device (what feed_rows_kernel works on) and where the host
-// has each of them in its random stream and in the retry loop of McSAS.analyse (mcsas.py:220-246).  A round is plan_round (which
-// chains get rows, and where), the caller's rows, upload_meta and decide.  The device is selected by then.
-struct FeedRun {
-    struct HostChain { uint64_t draw_pos = 0; int64_t num_iter = 0, total = 0; int attempt = 0, phase = 0 /*0 init due, 1 running, 2 done*/, converged = 0, stopped = 0; double seconds = 0; };
-    const mcsas_problem *p;
-    const size_t R, N, P, Q, qpad;
-    const int64_t window;
-    const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
-    FeedArgs fa;
-    DevBuf<double> dw, dwI, dI, drset, dcache, dft, dfit;
-    DevBuf<FeedState> dstate;
-    DevBuf<int64_t> dmeta;
-    std::vector<HostChain> hc;
-    std::vector<FeedState> hs;
-    // the round's metadata, one upload: [2R] int64 (where each chain's attempt starts in its stream, the steps it has taken: what
-    // feed_draw_kernel reads), then [3R] int32 (first row, row count, FEED_* of each chain)
-    std::vector<int64_t> meta;
-    size_t done = 0;
-    bool stop_seen = false;
-
-    FeedRun(const mcsas_problem *p_, size_t qpad_, int32_t window_)
-        : p(p_), R(p_->n_reps), N(p_->n_contrib), P(p_->n_active), Q(p_->nq), qpad(qpad_), window(window_), hc(R), hs(R), meta(2 * R + (3 * R + 1) / 2) {}
-    int64_t *pos() { return meta.data(); }
-    int32_t *rows_of() { return reinterpret_cast<int32_t *>(meta.data() + 2 * R); }
-
-    // data vectors and their sums, as mcsas_hip_plan_create prepares them; the rows and parameter sets of a round at `rows`, `pvals`
-    int setup(const double *rows, const double *pvals) {
-        memset(&fa, 0, sizeof fa);
-        ChainArgs &a = fa.c;
-        const WeighedData h(p, qpad, &a);
-        HIPCHK(dw.alloc(qpad)); HIPCHK(dwI.alloc(qpad)); HIPCHK(dI.alloc(qpad));
-        HIPCHK(drset.alloc(R * N * P)); HIPCHK(dcache.alloc(R * N * qpad)); HIPCHK(dft.alloc(R * qpad)); HIPCHK(dfit.alloc(R * qpad));
-        HIPCHK(dstate.alloc(R)); HIPCHK(dmeta.alloc(meta.size()));
-        HIPCHK(hipMemcpy(dw.p, h.w.data(), sizeof(double) * qpad, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dwI.p, h.wI.data(), sizeof(double) * qpad, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dI.p, h.I.data(), sizeof(double) * qpad, hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(dstate.p, 0, sizeof(FeedState) * R));
-        HIPCHK(hipMemset(dfit.p, 0, sizeof(double) * R * qpad));
-
-        a.model.n_active = (int)P;
-        a.w = dw.p; a.wI = dwI.p; a.I = dI.p;
-        a.n_contrib = (int)N; a.n_reps = (int)R; a.find_bg = p->find_background; a.pos_bg = p->positive_background;
-        a.start_from_min = p->start_from_minimum; a.max_retries = p->max_retries; a.max_iter = p->max_iter; a.conv_crit = p->conv_crit;
-        a.rset = drset.p; a.cache = dcache.p; a.cache_rows = (int)N; a.fit = dfit.p;
-        fa.ft = dft.p; fa.state = dstate.p; fa.rows = rows; fa.pvals = pvals;
-        const int32_t *dm = reinterpret_cast<const int32_t *>(dmeta.p + 2 * R);
-        fa.first = dm; fa.count = dm + R; fa.kind = dm + 2 * R;
-        return MCSAS_OK;
-    }
-
-    // which chains get rows in the next round of at most `round_rows` rows; returns how many rows that is
-    size_t plan_round(size_t round_rows) {
-        if (p->stop && *p->stop) stop_seen = true;
-        size_t nrows = 0;
-        std::fill(meta.begin(), meta.end(), 0);
-        int32_t *m = rows_of();
-        for (size_t r = 0; r < R; ++r) {
-            HostChain &h = hc[r];
-            if (h.phase == 2) continue;
-            if (stop_seen) {                                                    // McSAS.stop (mcsas.py:357): end every chain where it is
-                if (h.phase == 1) { m[2 * R + r] = FEED_END; h.stopped = 1; }
-                else { h.phase = 2; h.stopped = 1; ++done; }
-                continue;
-            }
-            const size_t want = h.phase == 0 ? N : (size_t)std::min<int64_t>(window, p->max_iter - h.num_iter);
-            if (nrows + want > round_rows) continue;                            // next round
-            m[r] = (int32_t)nrows; m[R + r] = (int32_t)want; m[2 * R + r] = h.phase == 0 ? FEED_INIT : FEED_STEPS;
-            pos()[r] = (int64_t)h.draw_pos; pos()[R + r] = h.num_iter;
-            nrows += want;
-        }
-        return nrows;
-    }
-    int upload_meta() {
-        HIPCHK(hipMemcpy(dmeta.p, meta.data(), sizeof(int64_t) * meta.size(), hipMemcpyHostToDevice));
-        return MCSAS_OK;
-    }
-    // the decisions on the round's rows, and what they mean for the chains
-    int decide() {
-        hipLaunchKernelGGL(feed_rows_kernel, dim3((unsigned)R), dim3(64), 0, nullptr, fa);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpy(hs.data(), dstate.p, sizeof(FeedState) * R, hipMemcpyDeviceToHost));
-        const double now = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-        const int32_t *m = rows_of();
-        for (size_t r = 0; r < R; ++r) {
-            HostChain &h = hc[r];
-            const int kind = m[2 * R + r];
-            if (h.phase == 2 || (m[R + r] == 0 && kind != FEED_END)) continue;
-            if (kind == FEED_INIT) { h.phase = 1; h.num_iter = 0; if (!p->start_from_minimum) h.draw_pos += (uint64_t)N * P; }
-            h.num_iter = hs[r].num_iter;
-            if (hs[r].ended) {                                                  // the attempt is over (mcsas.py:424-439)
-                h.total += h.num_iter; h.draw_pos += (uint64_t)h.num_iter * P;
-                h.converged = hs[r].converged;
-                if (h.converged || h.stopped || h.attempt >= p->max_retries) { h.phase = 2; h.seconds = now; ++done; }
-                else { ++h.attempt; h.phase = 0; }                              // :220-246: the next attempt goes on in the stream
-            }
-        }
-        return MCSAS_OK;
-    }
-    int results(mcsas_result *res);
-};
-
-extern "C" int mcsas_hip_analyse_host_rows(const mcsas_problem *p, mcsas_rows_callback rows_cb, void *user, int32_t window,
-                                           mcsas_result *res) {
-    if (!p || !rows_cb || !res) return fail(MCSAS_EINVAL, "null argument");
-    if (int rc = check_rows_problem(p)) return rc;
-    if (window < 1) window = 64;
-    DeviceGuard guard;
-    { int rc = select_device(p->device); if (rc) return rc; }
-    size_t blk, round_rows, qpad;
-    rows_shape(p, window, &blk, &round_rows, &qpad);
-    FeedRun run(p, qpad, window);
-    const size_t R = run.R, N = run.N, P = run.P, Q = run.Q;
-    DevBuf<double> drows, dpv;
-    HIPCHK(drows.alloc(round_rows * qpad)); HIPCHK(dpv.alloc(round_rows * P));
-    if (int rc = run.setup(drows.p, dpv.p)) return rc;
-    std::vector<double> pset(round_rows * P), hrows(round_rows * Q), staged(round_rows * qpad, 0.);
-    // (a window is drawn ahead of the decisions: a draw behind the replay stream's end is no error here — the chain may end before
-    // the step that would need it; what was consumed is known when the chain is through, see below)
-    auto uniform = [&](size_t r, uint64_t idx) -> double {
-        if (p->replay_stream) {
-            if ((int64_t)idx < p->replay_len) return p->replay_stream[r * (size_t)p->replay_len + idx];
-            return 0.5;
-        }
-        return philox_uniform_host(p->seed, (uint32_t)(p->rep_offset + (int)r), idx);
-    };
-    auto generate = [&](int c, double u) -> double {                      // numbergenerator.py:28-31,168-191; parameter.py:66-84
-        if (p->gen_kind[c] != MCSAS_GEN_UNIFORM) {
-            const double up = (double)p->gen_kind[c];
-            u = (std::pow(10.0, 0.0 + (up - 0.0) * u) - 1.0) / (p->gen_kind[c] == 1 ? 10.0 : (p->gen_kind[c] == 2 ? 100.0 : 1000.0));
-        }
-        return u * (p->gen_hi[c] - p->gen_lo[c]) + p->gen_lo[c];
-    };
-    while (run.done < R) {
-        const size_t nrows = run.plan_round(round_rows);
-        const int32_t *first = run.rows_of(), *count = first + R, *kind = first + 2 * R;
-        for (size_t r = 0; r < R; ++r) {
-            const uint64_t draw_pos = (uint64_t)run.pos()[r];
-            const int64_t num_iter = run.pos()[R + r];
-            for (size_t k = 0; k < (size_t)count[r]; ++k)
-                for (size_t c = 0; c < P; ++c) {
-                    double v;
-                    if (kind[r] == FEED_INIT) v = p->start_from_minimum ? p->start_value[c]     // mcsas.py:310-317: N draws per parameter, parameter-major
-                                                                        : generate((int)c, uniform(r, draw_pos + c * N + k));
-                    else v = generate((int)c, uniform(r, draw_pos + (uint64_t)(num_iter + (int64_t)k) * P + c));   // :358
-                    pset[((size_t)first[r] + k) * P + c] = v;
-                }
-        }
-        if (nrows) {
-            // ScatteringModel.calc's loop body for every row (scatteringmodel.py:90-99): the caller's calcIntensity
-            const int rc = rows_cb(user, (int32_t)nrows, pset.data(), hrows.data());
-            if (rc) return fail(MCSAS_ECALLBACK, "rows callback returned %d", rc);
-            for (size_t i = 0; i < nrows; ++i) memcpy(&staged[i * qpad], &hrows[i * Q], sizeof(double) * Q);
-            HIPCHK(hipMemcpy(drows.p, staged.data(), sizeof(double) * nrows * qpad, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(dpv.p, pset.data(), sizeof(double) * nrows * P, hipMemcpyHostToDevice));
-        }
-        if (int rc = run.upload_meta()) return rc;
-        if (int rc = run.decide()) return rc;
-    }
-    return run.results(res);
-}
-
-// results in the layout of mcsas_result (mcsas.py:203-210,233-251)
-int FeedRun::results(mcsas_result *res) {
-    std::vector<double> hr(R * N * P), hf(R * qpad);
-    HIPCHK(hipMemcpy(hr.data(), drset.p, sizeof(double) * hr.size(), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hf.data(), dfit.p, sizeof(double) * hf.size(), hipMemcpyDeviceToHost));
-    int ovf = 0;
-    for (size_t r = 0; r < R; ++r) {
-        if (res->contribs) for (size_t n = 0; n < N; ++n) for (size_t c = 0; c < P; ++c) res->contribs[(n * P + c) * R + r] = hr[(r * N + n) * P + c];
-        if (res->fit) for (size_t k = 0; k < Q; ++k) res->fit[k * R + r] = hf[r * qpad + k];
-        if (res->chisq) res->chisq[r] = hs[r].chi2;
-        if (res->scaling) res->scaling[r] = hs[r].A;
-        if (res->background) res->background[r] = hs[r].b;
-        if (res->num_iter) res->num_iter[r] = hs[r].num_iter;
-        if (res->num_moves) res->num_moves[r] = hs[r].num_moves;
-        if (res->attempts) res->attempts[r] = hc[r].attempt + 1;
-        if (res->converged) res->converged[r] = hc[r].converged;
-        if (res->seconds) res->seconds[r] = hc[r].seconds;
-        if (res->draws) res->draws[r] = (int64_t)hc[r].draw_pos;
-        // exhausted: a step the chain TOOK needed a draw behind the end — draw_pos counts the initial sets of the attempts that
-        // were made and the steps that were decided, not what was drawn ahead for a window the chain left early
-        if (p->replay_stream && (int64_t)hc[r].draw_pos > p->replay_len) ovf = 1;
-    }
-    if (ovf) return fail(MCSAS_ESTREAM, "replay stream exhausted (replay_len=%lld)", (long long)p->replay_len);
-    return MCSAS_OK;
-}
-
-// ------------------------------------------------------------------------------ rows produced on the device by the caller
-// The same rounds with nothing of them on the host: feed_draw_kernel writes the round's parameter sets into the caller's d_pset,
-// the caller's device code fills d_rows, feed_rows_kernel decides on them where they lie.  Per round the metadata goes up and the
-// chains' FeedState comes down; a replay stream is uploaded once.
-// Measured once (one MI355X, 2026-10-19, tools/device_rows_ab.py -> profiles/device_rows_ab.md): a Sphere typed as a Python model,
-// 100 q x 200 contributions x 10 repetitions x 20 000 steps, window 64 — 8.81 us of wall time per step through
-// mcsas_hip_analyse_host_rows with a numpy model, 0.438 us through this entry point with the same model in torch: 20 times faster,
-// the same accepted moves.  The device run is bound by its 314 rounds of launches and synchronisations (0.28 ms each), not by arithmetic.
-extern "C" int mcsas_hip_device_rows_shape(const mcsas_problem *p, int32_t window, int64_t *min_rows, int64_t *useful_rows,
-                                           int32_t *row_stride) {
-    if (!p) return fail(MCSAS_EINVAL, "device_rows_shape: null problem");
-    if (p->struct_size != sizeof(mcsas_problem))
-        return fail(MCSAS_EINVAL, "mcsas_problem size %u, library expects %zu (ABI mismatch)", p->struct_size, sizeof(mcsas_problem));
-    if (p->nq < 1 || p->nq > 16384) return fail(MCSAS_EINVAL, "nq %d (1..16384)", p->nq);
-    if (p->n_contrib < 1 || p->n_reps < 1) return fail(MCSAS_EINVAL, "n_contrib / n_reps");
-    size_t blk, round_rows, qpad;
-    rows_shape(p, window, &blk, &round_rows, &qpad);
-    if (min_rows) *min_rows = (int64_t)blk;
-    if (useful_rows) *useful_rows = (int64_t)round_rows;
-    if (row_stride) *row_stride = (int32_t)qpad;
-    return MCSAS_OK;
-}
-
-// a buffer of the caller's must be device memory of the selected device before a kernel is launched on it
-static int check_device_buffer(const char *name, const void *ptr, int dev) {
-    hipPointerAttribute_t at;
-    memset(&at, 0, sizeof at);
-    const hipError_t e = hipPointerGetAttributes(&at, ptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();                                               // (an unknown pointer is the caller's mistake, not a state to keep)
-        return fail(MCSAS_EINVAL, "analyse_device_rows: %s is not device memory (%s)", name, hipGetErrorString(e));
-    }
-    if (at.type != hipMemoryTypeDevice || at.isManaged)
-        return fail(MCSAS_EINVAL, "analyse_device_rows: %s is not device memory (memory type %d)", name, (int)at.type);
-    if (at.device != dev) return fail(MCSAS_EINVAL, "analyse_device_rows: %s lies on device %d, the analysis runs on device %d", name, at.device, dev);
-    return MCSAS_OK;
-}
-
-static int device_rows_run(const mcsas_problem *p, double *d_pset, double *d_rows, size_t round_rows, size_t capacity, size_t qpad,
-                           mcsas_device_rows_callback rows_cb, void *user, int32_t window, mcsas_result *res) {
-    DeviceGuard guard;
-    { int rc = select_device(p->device); if (rc) return rc; }
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    if (int rc = check_device_buffer("d_pset", d_pset, dev)) return rc;
-    if (int rc = check_device_buffer("d_rows", d_rows, dev)) return rc;
-    FeedRun run(p, qpad, window);
-    if (int rc = run.setup(d_rows, d_pset)) return rc;
-    // what feed_draw_kernel reads of the problem beside the round's metadata
-    ChainArgs &a = run.fa.c;
-    for (size_t c = 0; c < run.P; ++c) {
-        a.gen_lo[c] = p->gen_lo[c]; a.gen_hi[c] = p->gen_hi[c]; a.start_value[c] = p->start_value[c];
-        a.gen_kind[c] = p->gen_kind[c];
-    }
-    a.seed = p->seed; a.rep_offset = p->rep_offset;
-    DevBuf<double> dreplay;
-    if (p->replay_stream) {
-        const size_t len = (size_t)std::max<int64_t>(p->replay_len, 0);
-        HIPCHK(dreplay.alloc(run.R * len));
-        HIPCHK(hipMemcpy(dreplay.p, p->replay_stream, sizeof(double) * run.R * len, hipMemcpyHostToDevice));
-        a.replay = dreplay.p; a.replay_len = (int64_t)len;
-    }
-    HIPCHK(hipMemset(d_rows, 0, sizeof(double) * capacity * qpad));            // the padding columns: the caller never writes them
-
-    while (run.done < run.R) {
-        const size_t nrows = run.plan_round(round_rows);
-        if (int rc = run.upload_meta()) return rc;
-        if (nrows) {
-            hipLaunchKernelGGL(feed_draw_kernel, dim3((unsigned)run.R), dim3(64), 0, nullptr, run.fa, d_pset, (const int64_t *)run.dmeta.p);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(nullptr));                             // the sets are complete before the caller reads them
-            const int rc = rows_cb(user, (int32_t)nrows);
-            if (rc) return fail(MCSAS_ECALLBACK, "rows callback returned %d", rc);
-        }
-        if (int rc = run.decide()) return rc;
-    }
-    return run.results(res);
-}
-
-extern "C" int mcsas_hip_analyse_device_rows(const mcsas_problem *p, double *d_pset, double *d_rows, int64_t capacity_rows,
-                                             mcsas_device_rows_callback rows_cb, void *user, int32_t window, mcsas_result *res) {
-    if (!p || !rows_cb || !res) return fail(MCSAS_EINVAL, "analyse_device_rows: null argument");
-    if (!d_pset) return fail(MCSAS_EINVAL, "analyse_device_rows: d_pset is NULL");
-    if (!d_rows) return fail(MCSAS_EINVAL, "analyse_device_rows: d_rows is NULL");
-    if (int rc = check_rows_problem(p)) return rc;
-    if (window < 1) window = 64;
-    size_t blk, useful, qpad;
-    rows_shape(p, window, &blk, &useful, &qpad);
-    if (capacity_rows < (int64_t)blk)
-        return fail(MCSAS_EINVAL, "analyse_device_rows: capacity_rows %lld < %lld = max(n_contrib, window), the rows of one chain's round (mcsas_hip_device_rows_shape)",
-                    (long long)capacity_rows, (long long)blk);
-    const size_t round_rows = std::min((size_t)capacity_rows, useful);
-    try {
-        return device_rows_run(p, d_pset, d_rows, round_rows, (size_t)capacity_rows, qpad, rows_cb, user, window, res);
-    } catch (const std::bad_alloc &) {
-        return fail(MCSAS_ENOMEM, "analyse_device_rows: out of host memory");
-    }
 }
 
 // streams for hosts without a HIP binding of their own (ctypes / cgo callers that want analyses on several streams)
