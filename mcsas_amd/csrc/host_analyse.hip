@@ -9,7 +9,6 @@
 
 #include "host_internal.h"
 #include "host_result.h"
-#include "chain_wide.h" // WIDE_MAX_WAVES only
 
 using namespace mcsas;
 
@@ -21,10 +20,11 @@ extern "C" int mcsas_hip_analyse_batch(const mcsas_problem *problems, int32_t n,
         if (p->struct_size != sizeof(mcsas_problem)) return fail(MCSAS_EINVAL, "analyse_batch: problem %d: mcsas_problem size %u, library expects %zu (ABI mismatch)", i, p->struct_size, sizeof(mcsas_problem));
         if (results[i].struct_size != sizeof(mcsas_result)) return fail(MCSAS_EINVAL, "analyse_batch: result %d: mcsas_result size mismatch", i);
         if (p->n_active == 0) continue;                                       // answered at its place below, as mcsas_hip_analyse does
-        if (p->exec_mode != MCSAS_EXEC_AUTO && p->exec_mode != MCSAS_EXEC_WAVE)
+        const WaveRequest wave = wave_request(p->exec_mode, p->nq);
+        if (wave == WAVE_NOT_ASKED)
             return fail(MCSAS_EINVAL, "analyse_batch: problem %d asks for exec_mode %d; a batch runs one wavefront per chain (exec_mode 0 or 1)", i, p->exec_mode);
         if (p->n_devices > 1) return fail(MCSAS_EINVAL, "analyse_batch: problem %d spreads over %d devices; a batch runs on one", i, p->n_devices);
-        if (p->nq > 64 * WAVE) return fail(MCSAS_EINVAL, "analyse_batch: problem %d has nq %d > %d (one wavefront per chain)", i, p->nq, 64 * WAVE);
+        if (wave == WAVE_TOO_MANY_Q) return fail(MCSAS_EINVAL, "analyse_batch: problem %d has nq %d > %d (one wavefront per chain)", i, p->nq, Q_MAX_WAVE);
     }
     std::vector<mcsas_plan *> plans;
     std::vector<int> index;
@@ -154,17 +154,19 @@ static int start_or_trace_request(const char *who, const mcsas_problem *p, const
     *fixed = p->n_active == 0;
     if (*fixed) return MCSAS_OK;
     if (!traced && !start) return fail(MCSAS_EINVAL, "%s: start is NULL (mcsas_hip_analyse runs without one)", who);
-    const bool q_split = p->exec_mode == MCSAS_EXEC_WORKGROUP && p->nq > 16 * WAVE;      // (decide_shape: the q-split kernel, whatever waves_per_chain says)
-    if (p->exec_mode != MCSAS_EXEC_AUTO && p->exec_mode != MCSAS_EXEC_WAVE && !q_split) {
+    // (a start or a trace never picks the mode: MCSAS_EXEC_AUTO is one wavefront per chain here, the q-split kernel has to be asked for)
+    const WaveRequest wave = wave_request(p->exec_mode, p->nq);
+    const bool q_split = p->exec_mode == MCSAS_EXEC_WORKGROUP && runs_q_split(p->exec_mode, p->waves_per_chain, p->nq);
+    if (wave == WAVE_NOT_ASKED && !q_split) {
         if (traced) return fail(MCSAS_EINVAL, "%s: exec_mode %d (%s) asked; a trace needs exec_mode = MCSAS_EXEC_WAVE (%d, or 0)", who, p->exec_mode, exec_mode_name(p->exec_mode), MCSAS_EXEC_WAVE);
         return fail(MCSAS_EINVAL, "%s: exec_mode %d (%s) asked with %d q-points; a start needs exec_mode = MCSAS_EXEC_WAVE (%d, or 0), or MCSAS_EXEC_WORKGROUP (%d) with more than %d q-points",
-                    who, p->exec_mode, exec_mode_name(p->exec_mode), p->nq, MCSAS_EXEC_WAVE, MCSAS_EXEC_WORKGROUP, 16 * WAVE);
+                    who, p->exec_mode, exec_mode_name(p->exec_mode), p->nq, MCSAS_EXEC_WAVE, MCSAS_EXEC_WORKGROUP, Q_MAX_WINDOW);
     }
-    if (p->nq > WIDE_MAX_WAVES * WAVE * 32) return fail(MCSAS_EINVAL, "%s: nq %d > %d is not supported", who, p->nq, WIDE_MAX_WAVES * WAVE * 32);
-    if (!q_split && p->nq > 64 * WAVE)
+    if (p->nq > Q_MAX_SPLIT) return fail(MCSAS_EINVAL, "%s: nq %d > %d is not supported", who, p->nq, Q_MAX_SPLIT);
+    if (wave == WAVE_TOO_MANY_Q)
         return fail(MCSAS_EINVAL, "%s: nq %d > %d: one wavefront per chain does not take it, and with exec_mode %d a %s runs one wavefront per chain; "
-                    "MCSAS_EXEC_WORKGROUP (%d) %s for %d...%d q-points", who, p->nq, 64 * WAVE, p->exec_mode, what, MCSAS_EXEC_WORKGROUP,
-                    traced ? "keeps a trace" : "takes a start", 16 * WAVE + 1, WIDE_MAX_WAVES * WAVE * 32);
+                    "MCSAS_EXEC_WORKGROUP (%d) %s for %d...%d q-points", who, p->nq, Q_MAX_WAVE, p->exec_mode, what, MCSAS_EXEC_WORKGROUP,
+                    traced ? "keeps a trace" : "takes a start", Q_MAX_WINDOW + 1, Q_MAX_SPLIT);
     if (traced && p->n_devices > 1) return fail(MCSAS_EINVAL, "%s: n_devices %d: a trace is kept on one device", who, p->n_devices);
     if (p->n_active < 0 || p->n_active > MCSAS_MAX_ACTIVE) return fail(MCSAS_EINVAL, "n_active %d out of range", p->n_active);
     if (p->n_contrib < 1 || p->n_reps < 1) return fail(MCSAS_EINVAL, "n_contrib and n_reps must be >= 1");

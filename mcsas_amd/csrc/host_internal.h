@@ -119,6 +119,25 @@ const char *exec_mode_name(int mode);
 // a trace block (step, chisq and values of `capacity` moves per repetition) stays below this
 constexpr size_t TRACE_MAX_BYTES = (size_t)2 << 30;
 
+// ------------------------------------------------------------------------------ which kernel takes how many q-points, a start, a trace
+// The q-points a kernel takes (mcsas_hip.hip ties them to WAVE and WIDE_MAX_WAVES): the workgroup-window kernel and the pipeline, one
+// wavefront per chain (32 / 64 q slots per lane beyond the first), the q-split kernel (8 waves of 32 slots per lane).
+constexpr int Q_MAX_WINDOW = 1024, Q_MAX_WAVE = 4096, Q_MAX_SPLIT = 16384;
+// Whether a problem runs the q-split kernel: more than Q_MAX_WINDOW q-points, unless one wavefront per chain is asked for — by
+// MCSAS_EXEC_WAVE, or by waves_per_chain = 1 where MCSAS_EXEC_AUTO leaves the choice.  (The pipeline has no kernel for such data, and
+// none takes more than Q_MAX_SPLIT: plan creation refuses both.)
+inline bool runs_q_split(int exec_mode, int waves_per_chain, int nq) {
+    const bool wave_asked = exec_mode == MCSAS_EXEC_WAVE || (exec_mode == MCSAS_EXEC_AUTO && waves_per_chain == 1);
+    return nq > Q_MAX_WINDOW && !wave_asked && exec_mode != MCSAS_EXEC_PIPELINE;
+}
+// A request that does not leave the mode to the plan — a start, a trace, a batch: MCSAS_EXEC_AUTO and MCSAS_EXEC_WAVE both mean one
+// wavefront per chain, which takes up to Q_MAX_WAVE q-points.  Each caller refuses the other two answers in its own order and words.
+enum WaveRequest { WAVE_RUNS, WAVE_NOT_ASKED, WAVE_TOO_MANY_Q };
+inline WaveRequest wave_request(int exec_mode, int nq) {
+    if (exec_mode != MCSAS_EXEC_AUTO && exec_mode != MCSAS_EXEC_WAVE) return WAVE_NOT_ASKED;
+    return nq > Q_MAX_WAVE ? WAVE_TOO_MANY_Q : WAVE_RUNS;
+}
+
 #pragma GCC visibility pop
 
 // ------------------------------------------------------------------------------ the data of a problem as the chains read them

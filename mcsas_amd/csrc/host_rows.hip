@@ -36,7 +36,7 @@ static double philox_uniform_host(uint64_t seed, uint32_t chain, uint64_t idx) {
 static int check_rows_problem(const mcsas_problem *p) {
     if (p->struct_size != sizeof(mcsas_problem))
         return fail(MCSAS_EINVAL, "mcsas_problem size %u, library expects %zu (ABI mismatch)", p->struct_size, sizeof(mcsas_problem));
-    if (p->nq < 1 || p->nq > 16384 || !p->q || !p->intensity || !p->sigma) return fail(MCSAS_EINVAL, "nq %d (1..16384) / data pointers", p->nq);
+    if (p->nq < 1 || p->nq > Q_MAX_SPLIT || !p->q || !p->intensity || !p->sigma) return fail(MCSAS_EINVAL, "nq %d (1..%d) / data pointers", p->nq, Q_MAX_SPLIT);
     if (p->n_active < 1 || p->n_active > MCSAS_MAX_ACTIVE) return fail(MCSAS_EINVAL, "n_active %d (1..%d)", p->n_active, MCSAS_MAX_ACTIVE);
     if (p->n_contrib < 1 || p->n_reps < 1 || p->max_iter < 0 || p->max_retries < 0) return fail(MCSAS_EINVAL, "n_contrib / n_reps / max_iter / max_retries");
     if (p->reserved0) return fail(MCSAS_EINVAL, "reserved0 must be 0");
@@ -246,7 +246,7 @@ extern "C" int mcsas_hip_device_rows_shape(const mcsas_problem *p, int32_t windo
     if (!p) return fail(MCSAS_EINVAL, "device_rows_shape: null problem");
     if (p->struct_size != sizeof(mcsas_problem))
         return fail(MCSAS_EINVAL, "mcsas_problem size %u, library expects %zu (ABI mismatch)", p->struct_size, sizeof(mcsas_problem));
-    if (p->nq < 1 || p->nq > 16384) return fail(MCSAS_EINVAL, "nq %d (1..16384)", p->nq);
+    if (p->nq < 1 || p->nq > Q_MAX_SPLIT) return fail(MCSAS_EINVAL, "nq %d (1..%d)", p->nq, Q_MAX_SPLIT);
     if (p->n_contrib < 1 || p->n_reps < 1) return fail(MCSAS_EINVAL, "n_contrib / n_reps");
     size_t blk, round_rows, qpad;
     rows_shape(p, window, &blk, &round_rows, &qpad);

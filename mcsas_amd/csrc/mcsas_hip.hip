@@ -29,6 +29,9 @@
 
 using namespace mcsas;
 
+// host_internal.h's q-point limits are the kernels': 16 q slots per lane, 64, and WIDE_MAX_WAVES waves of 32
+static_assert(Q_MAX_WINDOW == 16 * WAVE && Q_MAX_WAVE == 64 * WAVE && Q_MAX_SPLIT == WIDE_MAX_WAVES * WAVE * 32, "host_internal.h: Q_MAX_*");
+
 // ------------------------------------------------------------------------------ error plumbing
 thread_local std::string g_err;
 int fail(int code, const char *fmt, ...) {
@@ -366,14 +369,16 @@ struct KernelRef {
     bool trace = false;
     const void *id() const { return plugin ? (const void *)plugin : entry; }
 };
+// Whether the plan's family has started and traced kernels: the wavefront-per-chain and the q-split family have, the workgroup-window
+// kernel and the pipeline have none.  What mcsas_hip_plan_set_start and mcsas_hip_plan_set_trace refuse by, and a batch with `wide`.
+static bool takes_start_and_trace(const mcsas_plan *pl) { return pl->mode == MCSAS_EXEC_WAVE || pl->wide; }
 // the family of the plan's own launches; a batch (mcsas_hip_plan_launch_batch) runs the plan's chains in KF_WAVE_BATCH instead.  Either
 // way a launch takes the started kernel of its family while the plan holds a start (mcsas_hip_plan_set_start gives one to plans of
 // the wave and q-split families only), and a plan of either with a trace (mcsas_hip_plan_set_trace) the traced family.
 static KernelFamily plan_family(const mcsas_plan *pl) {
-    if (pl->mode == MCSAS_EXEC_WAVE) return pl->trace_capacity > 0 ? KF_WAVE_TRACE : KF_WAVE;
-    if (pl->mode == MCSAS_EXEC_PIPELINE) return KF_PIPE_TICK;
+    if (!takes_start_and_trace(pl)) return pl->mode == MCSAS_EXEC_PIPELINE ? KF_PIPE_TICK : KF_WG;
     if (pl->wide) return pl->trace_capacity > 0 ? KF_WIDE_TRACE : KF_WIDE;
-    return KF_WG;
+    return pl->trace_capacity > 0 ? KF_WAVE_TRACE : KF_WAVE;
 }
 static int resolve_kernel(const mcsas_plan *pl, KernelFamily family, bool given, KernelRef *k) {
     static const char *const name[KF_COUNT] = {"", "batch ", "", "q-split ", "pipeline ", "traced ", "traced q-split "};
@@ -512,17 +517,15 @@ static int decide_shape(const mcsas_problem *p, const ModelArgs &margs, int n_cu
     // one workgroup per chain with the q-points split over up to 8 waves (chain_wide.h; 8 / 16 / 32 slots per lane:
     // up to 4096 / 8192 / 16384 q-points) — MCSAS_EXEC_WORKGROUP, and what MCSAS_EXEC_AUTO picks; up to 4096 q-points
     // MCSAS_EXEC_WAVE still runs one wavefront per chain with 32 / 64 slots per lane
-    const bool wide_q = p->nq > 16 * WAVE;
-    bool wide = false;
+    const bool wide_q = p->nq > Q_MAX_WINDOW;
+    const bool wide = runs_q_split(p->exec_mode, p->waves_per_chain, p->nq);
     int wide_waves = 0;
     if (wide_q) {
-        const bool wave_asked = p->exec_mode == MCSAS_EXEC_WAVE || (p->exec_mode == MCSAS_EXEC_AUTO && p->waves_per_chain == 1);
-        if (p->exec_mode == MCSAS_EXEC_PIPELINE) return fail(MCSAS_EINVAL, "nq %d > 1024: the pipeline has no kernels for it (exec_mode 0, 1 or 2)", p->nq);
-        if (p->nq > WIDE_MAX_WAVES * WAVE * 32) return fail(MCSAS_EINVAL, "nq %d > 16384 is not supported", p->nq);
-        if (wave_asked && p->nq > 64 * WAVE) return fail(MCSAS_EINVAL, "nq %d > 4096 runs one workgroup per chain only (exec_mode 0 or 2)", p->nq);
-        if (!wave_asked) {
-            wide = true;
-            qpl = p->nq <= 8 * WAVE * WIDE_MAX_WAVES ? 8 : (p->nq <= 16 * WAVE * WIDE_MAX_WAVES ? 16 : 32);
+        if (p->exec_mode == MCSAS_EXEC_PIPELINE) return fail(MCSAS_EINVAL, "nq %d > %d: the pipeline has no kernels for it (exec_mode 0, 1 or 2)", p->nq, Q_MAX_WINDOW);
+        if (p->nq > Q_MAX_SPLIT) return fail(MCSAS_EINVAL, "nq %d > %d is not supported", p->nq, Q_MAX_SPLIT);
+        if (!wide && p->nq > Q_MAX_WAVE) return fail(MCSAS_EINVAL, "nq %d > %d runs one workgroup per chain only (exec_mode 0 or 2)", p->nq, Q_MAX_WAVE);
+        if (wide) {
+            for (qpl = 8; qpl * WAVE * WIDE_MAX_WAVES < p->nq;) qpl *= 2;               // 8 / 16 / 32 slots per lane
             wide_waves = (p->nq + qpl * WAVE - 1) / (qpl * WAVE);
         }
     }
@@ -632,7 +635,7 @@ static int upload_data(mcsas_plan *pl, const mcsas_problem *p, int qpad) {
 // the intensity cache (`cache_rows` rows per chain, plus the spare one) and the replay streams
 static int alloc_rows(mcsas_plan *pl, const mcsas_problem *p, int cache_rows) {
     const size_t R = p->n_reps;
-    const bool wide_q = p->nq > 16 * WAVE;
+    const bool wide_q = p->nq > Q_MAX_WINDOW;
     // The chains' row blocks must not all start at the same offset modulo the memory system's interleave: with N = 400 rows of
     // 4 KB a chain's block is 50 x 32 KB, every chain's row r sits at the same place in the channel pattern, and thousands of
     // chains walking their rows in step queue up on the same channels (measured: identical launches of 8192 chains at 3.7e8 or
@@ -818,9 +821,9 @@ const char *exec_mode_name(int mode) {
 extern "C" int mcsas_hip_plan_set_start(mcsas_plan *pl, const double *start, int32_t rep_stride, int32_t rep_first) {
     if (!pl) return fail(MCSAS_EINVAL, "set_start: null plan");
     if (!start) { pl->has_start = false; return MCSAS_OK; }
-    if (pl->mode != MCSAS_EXEC_WAVE && !pl->wide)
+    if (!takes_start_and_trace(pl))
         return fail(MCSAS_EINVAL, "set_start: the plan runs in exec_mode %d (%s) with %d q-points; a start needs exec_mode = MCSAS_EXEC_WAVE (%d), or MCSAS_EXEC_WORKGROUP (%d) with more than %d q-points",
-                    pl->mode, exec_mode_name(pl->mode), pl->prob.nq, MCSAS_EXEC_WAVE, MCSAS_EXEC_WORKGROUP, 16 * WAVE);
+                    pl->mode, exec_mode_name(pl->mode), pl->prob.nq, MCSAS_EXEC_WAVE, MCSAS_EXEC_WORKGROUP, Q_MAX_WINDOW);
     const size_t R = pl->prob.n_reps, N = pl->prob.n_contrib, P = pl->prob.n_active;
     if (rep_first < 0 || (int64_t)rep_first + (int64_t)R > (int64_t)rep_stride)
         return fail(MCSAS_EINVAL, "set_start: repetitions %d..%lld of a start with %d columns", rep_first, (long long)rep_first + (long long)R - 1, rep_stride);
@@ -872,7 +875,7 @@ extern "C" int mcsas_hip_plan_set_trace(mcsas_plan *pl, int32_t capacity) {
     if (!pl) return fail(MCSAS_EINVAL, "set_trace: null plan");
     if (capacity < 0) return fail(MCSAS_EINVAL, "set_trace: capacity %d (>= 1, or 0 to clear the trace)", (int)capacity);
     if (capacity > 0) {
-        if (pl->mode != MCSAS_EXEC_WAVE && !pl->wide)
+        if (!takes_start_and_trace(pl))
             return fail(MCSAS_EINVAL, "set_trace: the plan runs in exec_mode %d (%s); a trace needs exec_mode = MCSAS_EXEC_WAVE (%d)", pl->mode, exec_mode_name(pl->mode), MCSAS_EXEC_WAVE);
         const size_t R = pl->prob.n_reps, P = pl->prob.n_active;
         if ((size_t)capacity > TRACE_MAX_BYTES / (R * (16 + 8 * P)))
@@ -1162,7 +1165,7 @@ extern "C" int mcsas_hip_plan_launch_batch(mcsas_plan *const *plans, int32_t n, 
     for (int i = 0; i < n; ++i) {
         const mcsas_plan *pl = plans[i];
         if (!pl) return fail(MCSAS_EINVAL, "launch_batch: plan %d is null", i);
-        if (pl->mode != MCSAS_EXEC_WAVE || pl->wide)
+        if (!takes_start_and_trace(pl) || pl->wide)                          // (of the two such families, the wavefront-per-chain one)
             return fail(MCSAS_EINVAL, "launch_batch: plan %d runs in exec_mode %d; a batch takes wavefront-per-chain plans only (exec_mode %d)", i, pl->mode, MCSAS_EXEC_WAVE);
         if (pl->trace_capacity > 0)
             return fail(MCSAS_EINVAL, "launch_batch: plan %d has a trace (mcsas_hip_plan_set_trace, capacity %d); a batch records none: clear it, or launch the plan alone", i, (int)pl->trace_capacity);

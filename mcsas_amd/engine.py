@@ -45,6 +45,8 @@ def compile_plugin(source: str, tuning=False) -> int:
     return int(mid.value)
 EXEC_AUTO, EXEC_WAVE, EXEC_WORKGROUP, EXEC_PIPELINE = 0, 1, 2, 3
 GEN_UNIFORM, GEN_EXP1, GEN_EXP2, GEN_EXP3 = 0, 1, 2, 3
+WAVE_MAX_Q = 4096       # q-points one wavefront per chain takes (include/mcsas_hip.h: MCSAS_EXEC_WAVE)
+WG_MAX_Q = 1024         # ... and the workgroup-window kernel; beyond, MCSAS_EXEC_WORKGROUP is the q-split kernel, which takes a start
 INT64_MAX = (1 << 63) - 1
 
 
@@ -209,22 +211,46 @@ class ChainTrace:
         return dict(count=self.count, chisq0=self.chisq0, step=self.step, chisq=self.chisq, values=self.values)
 
 
+def kernel_mode(what, exec_mode, nq, who, auto_beyond_wave=False, mode_word="exec_mode", q_word="q-points"):
+    """The execution mode the library is asked for (EXEC_WAVE or EXEC_WORKGROUP) where an analysis of `nq` q-points under `exec_mode`
+    comes with a given start or a trace, or goes into a batch (`what`: "start", "trace", "batch"); ValueError where no kernel takes it.
+    This is the one place that says so in Python (the library: csrc/host_internal.h):
+    - EXEC_AUTO and EXEC_WAVE run one wavefront per chain, which takes up to WAVE_MAX_Q q-points;
+    - EXEC_WORKGROUP with more than WG_MAX_Q q-points runs the q-split kernel (up to 16384 q-points: the library's refusal), except
+      in a batch, which is one wavefront per chain throughout;
+    - the workgroup-window kernel (EXEC_WORKGROUP up to WG_MAX_Q q-points) and the pipeline take neither a start nor a trace.
+    Beyond WAVE_MAX_Q q-points without the q-split kernel the callers differ:
+    - a trace and a batch raise: neither ever picks the mode;
+    - a start returns EXEC_WAVE and leaves the refusal to the library (engine.analyse, analyse_many, and McSAS with execMode wave);
+    - a start with `auto_beyond_wave` (McSAS) returns EXEC_WORKGROUP where EXEC_AUTO left the choice open: no other kernel takes the data.
+    `who`, `mode_word` (exec_mode / execMode) and `q_word` (q-points / points) are the caller's wording of the messages."""
+    q_split = what != "batch" and exec_mode == EXEC_WORKGROUP and nq > WG_MAX_Q
+    if exec_mode not in (EXEC_AUTO, EXEC_WAVE) and not q_split:
+        if what == "batch":
+            raise ValueError("%s asks for %s %d; a batch runs one wavefront per chain" % (who, mode_word, exec_mode))
+        raise ValueError("%s: a %s runs one wavefront per chain, or a workgroup per chain with more than %d %s; "
+                         "%s %d was asked with %d %s (0 or 1, or 2 beyond %d %s)"
+                         % (who, what, WG_MAX_Q, q_word, mode_word, exec_mode, nq, q_word, WG_MAX_Q, q_word))
+    if nq > WAVE_MAX_Q and not q_split:
+        if what == "batch":
+            raise ValueError("%s has %d %s; one wavefront per chain takes up to %d" % (who, nq, q_word, WAVE_MAX_Q))
+        if what == "trace":
+            raise ValueError("%s: %d %s; with %s %d a trace runs one wavefront per chain, which takes up to %d: "
+                             "set %s to workgroup (%d)" % (who, nq, q_word, mode_word, exec_mode, WAVE_MAX_Q, mode_word, EXEC_WORKGROUP))
+        if auto_beyond_wave and exec_mode == EXEC_AUTO:
+            return EXEC_WORKGROUP
+    return EXEC_WORKGROUP if q_split else EXEC_WAVE
+
+
 def _check_trace(trace, model: ModelSetup, st: Settings, nq, who="analyse"):
-    """The capacity of a trace as an int; ValueError where no traced kernel exists for the analysis — before any library call: a trace
-    is kept by the wavefront-per-chain kernel and, where exec_mode asks for the workgroup mode with more than WG_MAX_Q q-points, by
-    the q-split workgroup kernel, on one device.  The trace never picks the mode."""
+    """The capacity of a trace as an int; ValueError where no traced kernel exists for the analysis (kernel_mode: the trace never
+    picks the mode), for a model that exists only as host code and for a device list — before any library call."""
     k = int(trace)
     if k < 1:
         raise ValueError("%s: trace is the number of moves kept per repetition (>= 1), got %r" % (who, trace))
     if model.model_id == MODEL_HOST:
         raise ValueError("%s: a model that exists only as host code keeps no trace (a trace runs one wavefront per chain)" % who)
-    q_split = st.exec_mode == EXEC_WORKGROUP and nq > WG_MAX_Q
-    if st.exec_mode not in (EXEC_AUTO, EXEC_WAVE) and not q_split:
-        raise ValueError("%s: a trace runs one wavefront per chain, or a workgroup per chain with more than %d q-points; "
-                         "exec_mode %d was asked with %d q-points (0 or 1, or 2 beyond %d q-points)" % (who, WG_MAX_Q, st.exec_mode, nq, WG_MAX_Q))
-    if nq > WAVE_MAX_Q and not q_split:
-        raise ValueError("%s: %d q-points; with exec_mode %d a trace runs one wavefront per chain, which takes up to %d: "
-                         "set exec_mode to workgroup (%d)" % (who, nq, st.exec_mode, WAVE_MAX_Q, EXEC_WORKGROUP))
+    kernel_mode("trace", st.exec_mode, nq, who)
     if st.devices:
         raise ValueError("%s: a trace is kept on one device; a device list %r was given" % (who, tuple(st.devices)))
     return k
@@ -413,13 +439,12 @@ def analyse_many(problems, streams=2):
             while len(pending) >= cap:
                 j, pl = pending.pop(0)
                 out[j] = pl.fetch(); pl.close()
-            if pr.get("start") is not None:                  # (a start runs one wavefront per chain or the q-split kernel: analyse)
-                q_split = st.exec_mode == EXEC_WORKGROUP and np.size(pr["q"]) > WG_MAX_Q
-                if st.exec_mode not in (EXEC_AUTO, EXEC_WAVE) and not q_split:
+            if pr.get("start") is not None:                  # (a start runs one wavefront per chain or the q-split kernel: kernel_mode)
+                try:
+                    st = replace(st, exec_mode=kernel_mode("start", st.exec_mode, np.size(pr["q"]), "analyse_many"))
+                except ValueError:
                     raise ValueError("analyse_many: problem %d asks for exec_mode %d with a start and %d q-points (0 or 1, or 2 with more than %d q-points)"
-                                     % (i, st.exec_mode, np.size(pr["q"]), WG_MAX_Q))
-                if not q_split:
-                    st = replace(st, exec_mode=EXEC_WAVE)
+                                     % (i, st.exec_mode, np.size(pr["q"]), WG_MAX_Q)) from None
             pl = Plan(pr["model"], pr["q"], pr["intensity"], pr["sigma"], st, pr.get("replay"), pr.get("stop"), pr.get("smear"))
             if pr.get("start") is not None:
                 try:
@@ -442,10 +467,6 @@ def analyse_many(problems, streams=2):
     return out
 
 
-WAVE_MAX_Q = 4096       # q-points one wavefront per chain takes (include/mcsas_hip.h: MCSAS_EXEC_WAVE)
-WG_MAX_Q = 1024         # ... and the workgroup-window kernel; beyond, MCSAS_EXEC_WORKGROUP is the q-split kernel, which takes a start
-
-
 def analyse_batch(problems):
     """Independent analyses — a series of data sets — in ONE wavefront-per-chain launch per kernel (mcsas_hip_analyse_batch,
     include/mcsas_hip.h): every repetition of every data set is one chain of the same launch, so a series of a few repetitions per
@@ -464,9 +485,7 @@ def analyse_batch(problems):
     for i, pr in enumerate(problems):
         if pr["model"].model_id == MODEL_HOST:
             raise ValueError("analyse_batch: problem %d: a model that exists only as host code has no device kernel to batch" % i)
-        if np.size(pr["q"]) > WAVE_MAX_Q:
-            raise ValueError("analyse_batch: problem %d has %d q-points; one wavefront per chain takes up to %d"
-                             % (i, np.size(pr["q"]), WAVE_MAX_Q))
+        kernel_mode("batch", EXEC_WAVE, np.size(pr["q"]), "analyse_batch: problem %d" % i)   # (the size; the mode a problem asks for: below)
     if not problems:
         return []
     out, batched = [None] * len(problems), []
@@ -478,9 +497,7 @@ def analyse_batch(problems):
         try:
             for i in batched:
                 pr = problems[i]
-                if pr["st"].exec_mode not in (EXEC_AUTO, EXEC_WAVE):
-                    raise ValueError("analyse_batch: problem %d asks for exec_mode %d; a batch runs one wavefront per chain" % (i, pr["st"].exec_mode))
-                st = replace(pr["st"], exec_mode=EXEC_WAVE)
+                st = replace(pr["st"], exec_mode=kernel_mode("batch", pr["st"].exec_mode, np.size(pr["q"]), "analyse_batch: problem %d" % i))
                 plans.append(Plan(pr["model"], pr["q"], pr["intensity"], pr["sigma"], st, pr.get("replay"), pr.get("stop"), pr.get("smear")))
                 if i in starts:
                     plans[-1].set_start(starts[i])

@@ -84,48 +84,31 @@ class McSAS(object):
         self._stop.value = 1 if flag else 0
 
     def _check_start_mode(self, start, data=None):
-        """The execution mode a started analysis of `data` (default: the current data) asks for, or None without a start: one wavefront per chain up
-        to engine.WAVE_MAX_Q points; the q-split workgroup kernel where execMode asks for it with more than engine.WG_MAX_Q points,
-        and beyond WAVE_MAX_Q also where execMode leaves the choice open (no other kernel takes such data).  ValueError otherwise."""
+        """The execution mode a started analysis of `data` (default: the current data) asks for, or None without a start
+        (engine.kernel_mode: here a start picks the workgroup mode where execMode leaves the choice open and no other kernel takes
+        the data).  ValueError where no kernel takes a start."""
         if start is None:
             return None
         data = self.data if data is None else data
         nq = 0 if data is None else int(np.size(data.q))
-        if self.execMode == engine.EXEC_WORKGROUP and nq > engine.WG_MAX_Q:
-            return engine.EXEC_WORKGROUP
-        if self.execMode not in (engine.EXEC_AUTO, engine.EXEC_WAVE):
-            raise ValueError("McSAS: a start runs one wavefront per chain, or a workgroup per chain with more than %d points; "
-                             "execMode %d was asked with %d points (0 or 1, or 2 beyond %d points)"
-                             % (engine.WG_MAX_Q, self.execMode, nq, engine.WG_MAX_Q))
-        if self.execMode == engine.EXEC_AUTO and nq > engine.WAVE_MAX_Q:
-            return engine.EXEC_WORKGROUP
-        return engine.EXEC_WAVE
+        return engine.kernel_mode("start", self.execMode, nq, "McSAS", auto_beyond_wave=True, mode_word="execMode", q_word="points")
 
     def _check_trace_mode(self, trace, data=None):
-        """The execution mode a traced analysis of `data` (default: the current data) asks for, or None without a trace: one wavefront
-        per chain, or the q-split workgroup kernel where execMode asks for it with more than engine.WG_MAX_Q points
-        (include/mcsas_hip.h: mcsas_hip_analyse_traced).  The trace never picks the mode: ValueError where execMode asks for another,
-        for more than engine.WAVE_MAX_Q points without the workgroup mode, for a model that exists only as host code and for a device
-        list."""
+        """The execution mode a traced analysis of `data` (default: the current data) asks for, or None without a trace
+        (engine.kernel_mode; include/mcsas_hip.h: mcsas_hip_analyse_traced).  The trace never picks the mode: ValueError where no
+        traced kernel runs under execMode, for a model that exists only as host code and for a device list."""
         if trace is None:
             return None
         data = self.data if data is None else data
         nq = 0 if data is None else int(np.size(data.q))
         if int(trace) < 1:
             raise ValueError("McSAS: trace is the number of moves kept per repetition (>= 1), got %r" % (trace,))
-        q_split = self.execMode == engine.EXEC_WORKGROUP and nq > engine.WG_MAX_Q
-        if self.execMode not in (engine.EXEC_AUTO, engine.EXEC_WAVE) and not q_split:
-            raise ValueError("McSAS: a trace runs one wavefront per chain, or a workgroup per chain with more than %d points; "
-                             "execMode %d was asked with %d points (0 or 1, or 2 beyond %d points)"
-                             % (engine.WG_MAX_Q, self.execMode, nq, engine.WG_MAX_Q))
-        if nq > engine.WAVE_MAX_Q and not q_split:
-            raise ValueError("McSAS: %d points; with execMode %d a trace runs one wavefront per chain, which takes up to %d: "
-                             "set execMode to workgroup (%d)" % (nq, self.execMode, engine.WAVE_MAX_Q, engine.EXEC_WORKGROUP))
+        mode = engine.kernel_mode("trace", self.execMode, nq, "McSAS", mode_word="execMode", q_word="points")
         if self.devices:
             raise ValueError("McSAS: a trace is kept on one device; the device list %r was given" % (self.devices,))
         if self.model is not None and setup_from_model(self.model, data).model_id == engine.MODEL_HOST:
             raise ValueError("McSAS: a model that exists only as host code keeps no trace (it runs through host-evaluated rows)")
-        return engine.EXEC_WORKGROUP if q_split else engine.EXEC_WAVE
+        return mode
 
     def calc(self, **kwargs):                                # mcsas.py:149-179
         """`trace=K`: keeps the first K accepted moves of every repetition (step, chi-squared, new values: what the reference logs

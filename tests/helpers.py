@@ -212,3 +212,65 @@ def plugin_twin(model, tag):
     """The same configured model instance, but as a user's own class: no built-in kernel id, its form factor as HIP text."""
     model.__class__ = type(type(model).__name__ + "AsPlugin", (type(model),), {"model_id": None, "hipSource": PLUGIN_SOURCES[tag]})
     return model
+
+
+# ---- models that exist only as Python, and the quickstart workload: shared by CPU and GPU test modules
+class PythonOnlySphere(mcsas_amd.SASModel):
+    """models/sphere.py:12-63 typed again the way a user of the reference writes a model: declarations + numpy formfactor / volume /
+    absVolume / surface — no kernel id, no HIP text."""
+    shortName = "Sphere (Python only)"
+    canSmear = True
+    parameters = mcsas_amd.Sphere.parameters
+
+    def __init__(self):
+        super().__init__()
+        self.radius.setActive(True)
+
+    def surface(self):
+        return 4. * np.pi * self.radius() * self.radius()
+
+    def volume(self):
+        return (np.pi * 4. / 3.) * self.radius()**3
+
+    def absVolume(self):
+        return self.volume() * self.sld()**2
+
+    def formfactor(self, dataset):
+        qr = self.getQ(dataset) * self.radius()
+        return 3. * (np.sin(qr) - qr * np.cos(qr)) / (qr**3.)
+
+
+class PythonOnlyCoreShell(mcsas_amd.SASModel):
+    """models/sphericalcoreshell.py:14-77 typed as a user would: numpy only; eleven parameters (more than the C ABI's eight: a model
+    whose rows the host evaluates keeps its parameter vector to itself), two of them active."""
+    shortName = "Core-shell sphere (Python only)"
+    parameters = mcsas_amd.SphericalCoreShell.parameters + tuple(
+        (lambda n: (lambda: mcsas_amd.Parameter(n, 1.0, displayName="unused " + n)))("extra%d" % i) for i in range(6))
+
+    def __init__(self):
+        super().__init__()
+        self.radius.setActive(True); self.t.setActive(True)
+
+    def volume(self):
+        return 4. / 3 * np.pi * (self.radius() + self.t())**3
+
+    def formfactor(self, dataset):
+        q = self.getQ(dataset)
+
+        def k(rr, d_eta):
+            qr = q * rr
+            return d_eta * 3 * (np.sin(qr) - qr * np.cos(qr)) / (qr)**3
+        vc = 4. / 3 * np.pi * self.radius()**3
+        vt = 4. / 3 * np.pi * (self.radius() + self.t())**3
+        return k(self.radius() + self.t(), self.eta_s() - self.eta_sol()) - (vc / vt) * k(self.radius(), self.eta_s() - self.eta_c())
+
+
+def _quickstart_algo(g, reps, seed):
+    lo, hi = float(g["lo"]), float(g["hi"])
+    m, _ = make_models("sphere", [lo], [hi])
+    m.radius.histograms().append(mcsas_amd.Histogram(m.radius, lo, hi, binCount=50, xscale='log', yweight='vol'))
+    algo = mcsas_amd.McSAS(seed=seed)
+    algo.numContribs.setValue(300); algo.numReps.setValue(reps); algo.convergenceCriterion.setValue(1.0)
+    algo.model = m
+    algo.data = mcsas_amd.SASData(g["data_q"], g["data_I"], g["data_sigma"], f_limit=g["data_f_limit"])
+    return algo, m

@@ -12,29 +12,9 @@ import mcsas_amd
 from mcsas_amd import engine, _lib
 from oracle import mcsas_oracle as O
 from helpers import load, make_models, product_smearing
+from chain_cases import RANGES, _alone, _same, _synthetic
 
-FIELDS = ("contribs", "fit", "chisq", "scaling", "background", "num_iter", "num_moves", "attempts", "converged", "draws")
-RANGES = {
-    "sphere": ([2e-9], [3e-7]), "cyl_aspect": ([1e-9, 0.5], [1e-7, 20.0]), "ellcs": ([1e-9, 2e-9, 2e-10], [1e-7, 2e-7, 1e-8]),
-    "kholodenko": ([1e-9, 1e-8, 1e-7], [5e-9, 5e-8, 1e-6]), "elliso": ([1e-9, 0.3], [1e-7, 8.0]), "sphcs": ([1e-9, 5e-10], [1e-7, 2e-8]),
-    "gausschain": ([1e-9, 1e-9], [1e-7, 1e-7]), "lmasphere": ([2e-9, 0.01], [2e-7, 0.4]),
-}
 HEAVY = {"cyl_aspect", "ellcs", "kholodenko", "elliso"}        # rows with an integral: fewer contributions and steps
-
-
-def _synthetic(nq):
-    from bench import synthetic_data
-    return synthetic_data(nq)
-
-
-def _same(got, one, what=""):
-    for name in FIELDS:
-        assert np.array_equal(getattr(got, name), getattr(one, name)), (what, name)
-
-
-def _alone(pr):
-    st = engine.Settings(**{**pr["st"].__dict__, "exec_mode": engine.EXEC_WAVE})
-    return engine.analyse(pr["model"], pr["q"], pr["intensity"], pr["sigma"], st, pr.get("replay"), pr.get("stop"), pr.get("smear"))
 
 
 def _problems(tag):

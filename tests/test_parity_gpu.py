@@ -16,6 +16,7 @@ from mcsas_amd import engine
 from mcsas_amd import _lib
 from oracle import mcsas_oracle as O
 from helpers import load, make_models, traj_setup, FakeData, SMEAR_CASES, product_smearing, oracle_smearing, traj_smearing
+from helpers import PythonOnlySphere, PythonOnlyCoreShell, _quickstart_algo    # noqa: F401 (other modules take them from here too)
 
 
 @pytest.mark.parametrize("tag", ["sphere", "cyl_aspect", "cyl_length", "ellcs", "kholodenko", "elliso", "sphcs",
@@ -252,17 +253,6 @@ def test_calc_converges_and_histogram_matches_reference():
         np.testing.assert_allclose(np.array(h.moments.fields)[0::2], g[p + "moments"][0::2], rtol=1e-6)
 
 
-def _quickstart_algo(g, reps, seed):
-    lo, hi = float(g["lo"]), float(g["hi"])
-    m, _ = make_models("sphere", [lo], [hi])
-    m.radius.histograms().append(mcsas_amd.Histogram(m.radius, lo, hi, binCount=50, xscale='log', yweight='vol'))
-    algo = mcsas_amd.McSAS(seed=seed)
-    algo.numContribs.setValue(300); algo.numReps.setValue(reps); algo.convergenceCriterion.setValue(1.0)
-    algo.model = m
-    algo.data = mcsas_amd.SASData(g["data_q"], g["data_I"], g["data_sigma"], f_limit=g["data_f_limit"])
-    return algo, m
-
-
 def test_quickstart_acceptance_free_running():
     """The reference's published workload, end to end and free-running (doc/source/quickstart.rst:66-107): Sphere on
     quickstartdemo1.csv, 300 contributions, criterion 1, one 50-bin log histogram — here 50 repetitions with the device's
@@ -442,31 +432,6 @@ def test_mcsas_front_end_device_list_with_an_integral_model_in_auto_mode():
         np.testing.assert_array_equal(a, b)
 
 
-class PythonOnlySphere(mcsas_amd.SASModel):
-    """models/sphere.py:12-63 typed again the way a user of the reference writes a model: declarations + numpy formfactor / volume /
-    absVolume / surface — no kernel id, no HIP text."""
-    shortName = "Sphere (Python only)"
-    canSmear = True
-    parameters = mcsas_amd.Sphere.parameters
-
-    def __init__(self):
-        super().__init__()
-        self.radius.setActive(True)
-
-    def surface(self):
-        return 4. * np.pi * self.radius() * self.radius()
-
-    def volume(self):
-        return (np.pi * 4. / 3.) * self.radius()**3
-
-    def absVolume(self):
-        return self.volume() * self.sld()**2
-
-    def formfactor(self, dataset):
-        qr = self.getQ(dataset) * self.radius()
-        return 3. * (np.sin(qr) - qr * np.cos(qr)) / (qr**3.)
-
-
 def test_python_only_model_replays_the_reference_through_host_rows():
     """A ScatteringModel that exists only as Python (the reference's plug-in contract as it stands: scatteringmodel.py:16-58,
     sasmodel.py:37-79) runs through McSAS.calc(): the library draws the proposals, calls back into the model's own calcIntensity
@@ -579,31 +544,6 @@ def test_python_only_model_flags_and_stream_end():
         engine.analyse_host_rows(m.setup(data), q, I, sig, engine.Settings(n_contrib=60, n_reps=1, max_iter=300, conv_crit=1e-9, max_retries=0),
                                  rows, replay=stream[None, :200], window=64)
     assert e.value.code == -5                                   # MCSAS_ESTREAM
-
-
-class PythonOnlyCoreShell(mcsas_amd.SASModel):
-    """models/sphericalcoreshell.py:14-77 typed as a user would: numpy only; eleven parameters (more than the C ABI's eight: a model
-    whose rows the host evaluates keeps its parameter vector to itself), two of them active."""
-    shortName = "Core-shell sphere (Python only)"
-    parameters = mcsas_amd.SphericalCoreShell.parameters + tuple(
-        (lambda n: (lambda: mcsas_amd.Parameter(n, 1.0, displayName="unused " + n)))("extra%d" % i) for i in range(6))
-
-    def __init__(self):
-        super().__init__()
-        self.radius.setActive(True); self.t.setActive(True)
-
-    def volume(self):
-        return 4. / 3 * np.pi * (self.radius() + self.t())**3
-
-    def formfactor(self, dataset):
-        q = self.getQ(dataset)
-
-        def k(rr, d_eta):
-            qr = q * rr
-            return d_eta * 3 * (np.sin(qr) - qr * np.cos(qr)) / (qr)**3
-        vc = 4. / 3 * np.pi * self.radius()**3
-        vt = 4. / 3 * np.pi * (self.radius() + self.t())**3
-        return k(self.radius() + self.t(), self.eta_s() - self.eta_sol()) - (vc / vt) * k(self.radius(), self.eta_s() - self.eta_c())
 
 
 def test_python_only_model_two_parameters_more_than_1024_q():

@@ -3,10 +3,8 @@ Plan.set_start, engine.analyse_batch "start" key, McSAS.calc(start=), run_series
 
 The reference of a started chain is the oracle's own mc_fit, unchanged: while it runs, generate_parameters is replaced so that its
 FIRST call returns a copy of the start set (the rset of mcsas.py:317) and every later call — the per-step draws, the fresh sets of
-retry attempts — goes to the real function.  That is the contract: the first attempt takes the given set and consumes no uniforms
+retry attempts — goes to the real function (chain_cases._oracle_from).  That is the contract: the first attempt takes the given set and consumes no uniforms
 for it; everything after is mcFit as it always was."""
-import functools
-
 import numpy as np
 import pytest
 
@@ -16,102 +14,13 @@ import mcsas_amd
 from mcsas_amd import engine, _lib
 from oracle import mcsas_oracle as O
 from helpers import make_models, plugin_twin
-from test_batch_gpu import FIELDS, RANGES, _synthetic, _same, _alone
-
-MCSAS_ESTREAM = -5
-SEED, REP_OFFSET, R = 5, 3, 3
-
-
-def _oracle_from(spec, q, I, sig, ost, start, stream, retries):
-    """The retry loop of tests/test_chain_end_gpu.py::_oracle_chain with the first initial set given."""
-    real, calls = O.generate_parameters, [0]
-
-    def given_first(spec_, stream_, count=1):
-        calls[0] += 1
-        if calls[0] == 1:
-            assert count == start.shape[0]
-            return np.array(start, dtype=float)
-        return real(spec_, stream_, count)
-
-    lim = ([I.min(), I.max()], [q.min(), q.max()])
-    iters, pos = [], []
-    O.generate_parameters = given_first
-    try:
-        while True:
-            ref = O.mc_fit(spec, q, I, sig, lim[0], lim[1], ost, stream, method="closed")
-            iters.append(ref.num_iter); pos.append(stream.pos)
-            if ref.conval <= ost.conv_crit or len(iters) > retries:
-                break
-    finally:
-        O.generate_parameters = real
-    assert calls[0] == 1 + sum(iters) + (len(iters) - 1)          # the start, one call per step, one per fresh set
-    return dict(attempts=len(iters), iters=iters, pos=pos, ref=ref, converged=int(ref.conval <= ost.conv_crit))
-
-
-# name: model, q-points, contributions, steps of the started run, steps of the cold run the start comes from, criterion (chosen with
-# the oracle so that chains end mid-run), fixed model parameters
-SHAPES = {
-    "sphere100": ("sphere", 100, 60, 700, 150, 50.0, {}),
-    "sphere200": ("sphere", 200, 60, 700, 150, 50.0, {}),
-    "cyl100": ("cyl_aspect", 100, 24, 120, 40, 7000.0, {"intDiv": 12.}),
-    "sphere1500": ("sphere", 1500, 16, 64, 20, 450.0, {}),          # 32 q slots per lane: a cache-only class
-}
-
-
-@functools.lru_cache(maxsize=None)
-def _workload(name):
-    """The start (a short cold run of the oracle: a realistic mid-fit state, one column per repetition, stored in columns 1..3 of
-    a five-column array) and the oracle's started chains on the Philox streams of chains REP_OFFSET + r — the same numbers serve
-    the replayed and the free-running run.  Computed once, shared, read-only."""
-    tag, nq, N, steps, steps0, crit, fixed = SHAPES[name]
-    q, I, sig = _synthetic(nq)
-    m, spec = make_models(tag, *RANGES[tag], **fixed)
-    lim = ([I.min(), I.max()], [q.min(), q.max()])
-    cold = O.Settings(n_contrib=N, n_reps=1, max_iter=steps0, conv_crit=1e-9, max_retries=0)
-    start = np.zeros((N, spec.n_active, 5))
-    start[:, :, 0] = start[:, :, 4] = np.nan                                 # (columns a correct rep_first never reads)
-    for r in range(R):
-        start[:, :, 1 + r] = O.mc_fit(spec, q, I, sig, lim[0], lim[1], cold, O.PhiloxStream(11, r), method="closed").rset
-    ost = O.Settings(n_contrib=N, n_reps=1, max_iter=steps, conv_crit=crit, max_retries=0)
-    chains = [_oracle_from(spec, q, I, sig, ost, start[:, :, 1 + r], O.PhiloxStream(SEED, REP_OFFSET + r, pos=0), 0) for r in range(R)]
-    P = spec.n_active
-    for c in chains:
-        assert c["attempts"] == 1 and c["pos"][-1] == P * c["iters"][0]         # no uniforms for the initial set
-        assert c["ref"].num_moves > 0
-    early = [c["iters"][0] for c in chains if c["iters"][0] < steps]
-    assert early and all(c["converged"] for c in chains if c["iters"][0] < steps)   # a mid-run end that is not the budget
-    assert len({c["iters"][0] for c in chains}) > 1
-    L = max(c["pos"][-1] for c in chains)
-    replay = np.stack([O.philox_uniform(SEED, REP_OFFSET + r, np.arange(L, dtype=np.uint64)) for r in range(R)])
-    for r, c in enumerate(chains):                                             # what a chain did not consume: OTHER uniforms
-        u = replay[r, c["pos"][-1]:]
-        replay[r, c["pos"][-1]:] = np.where(u < 0.5, u + 0.25, u - 0.25)
-    st = engine.Settings(n_contrib=N, n_reps=R, max_iter=steps, conv_crit=crit, max_retries=0, seed=SEED, rep_offset=REP_OFFSET)
-    for a in (start, replay):
-        a.setflags(write=False)
-    return dict(setup=m.setup(), spec=spec, q=q, I=I, sig=sig, st=st, start=start, chains=chains, replay=replay)
-
-
-def _check_against_oracle(chains, res, P):
-    """The comparison of tests/test_chain_end_gpu.py::_check_against_oracle, fit and scaling included."""
-    for r, c in enumerate(chains):
-        ref = c["ref"]
-        got = (res.num_iter[r], res.num_moves[r], res.attempts[r], res.converged[r], res.draws[r])
-        print("chain %d: iter, moves, attempts, converged, draws = %s; oracle %s"
-              % (r, got, (ref.num_iter, ref.num_moves, c["attempts"], c["converged"], c["pos"][-1])))
-        assert got == (ref.num_iter, ref.num_moves, c["attempts"], c["converged"], c["pos"][-1]), r
-        np.testing.assert_allclose(res.contribs[:, :, r], ref.rset, rtol=1e-12)
-        np.testing.assert_allclose(res.chisq[r], ref.conval, rtol=1e-7)
-        np.testing.assert_allclose(res.fit[:, r], ref.fit, rtol=1e-6, atol=1e-12 * np.abs(ref.fit).max())
-        np.testing.assert_allclose(res.scaling[r], ref.scaling, rtol=1e-6)
+from chain_cases import (CASES, MCSAS_ESTREAM, R, RANGES, REP_OFFSET, _alone, _check_against_oracle, _same, _synthetic, _wave_retry_workload,
+                         _workload)
 
 
 def _started(wl, replay=None, **over):
     st = engine.Settings(**{**wl["st"].__dict__, **over})
     return engine.analyse(wl["setup"], wl["q"], wl["I"], wl["sig"], st, replay=replay, start=wl["start"][:, :, 1:1 + R])
-
-
-CASES = [("sphere100", 1), ("sphere100", 0), ("sphere200", 1), ("sphere200", 0), ("cyl100", 1), ("sphere1500", -1)]
 
 
 @pytest.mark.parametrize("name,cache", CASES)
@@ -155,29 +64,9 @@ def test_plan_reads_its_own_columns_of_the_start():
 
 
 # ----------------------------------------------------------------------------- retries
-@functools.lru_cache(maxsize=None)
-def _retry_workload():
-    """A start the chain cannot bring to the criterion within its budget (every contribution at one small radius), two retries.
-    Seed and criterion chosen with the oracle: chains 0 and 2 converge in their second attempt, chain 1 in none of its three."""
-    nq, N, steps, crit, seed = 100, 40, 300, 90.0, 3
-    q, I, sig = _synthetic(nq)
-    m, spec = make_models("sphere", *RANGES["sphere"])
-    start = np.full((N, 1, R), 2e-9) * np.array([1.0, 1.5, 2.0])[None, None, :]
-    ost = O.Settings(n_contrib=N, n_reps=1, max_iter=steps, conv_crit=crit, max_retries=2)
-    chains = [_oracle_from(spec, q, I, sig, ost, start[:, :, r], O.PhiloxStream(seed, REP_OFFSET + r, pos=0), 2) for r in range(R)]
-    assert [c["attempts"] for c in chains] == [2, 3, 2] and [c["converged"] for c in chains] == [1, 0, 1]
-    for c in chains:                                                            # the started attempt ran to its budget, a retry WAS taken
-        assert c["iters"][0] == steps and c["pos"][0] == steps                  # ... and the start cost no draws
-        assert c["pos"][-1] == sum(c["iters"]) + N * (c["attempts"] - 1)        # N * P for each later initial set
-    assert chains[0]["iters"][1] < steps and chains[2]["iters"][1] < steps      # converged mid-run in the later attempt
-    st = engine.Settings(n_contrib=N, n_reps=R, max_iter=steps, conv_crit=crit, max_retries=2, seed=seed, rep_offset=REP_OFFSET)
-    start.setflags(write=False)
-    return dict(setup=m.setup(), spec=spec, q=q, I=I, sig=sig, st=st, start=start, chains=chains)
-
-
 @pytest.mark.parametrize("cache", [1, 0])
 def test_retries_after_a_started_attempt_draw_fresh_sets(cache):
-    wl = _retry_workload()
+    wl = _wave_retry_workload()
     st = engine.Settings(**{**wl["st"].__dict__, "cache_intensities": cache})
     res = engine.analyse(wl["setup"], wl["q"], wl["I"], wl["sig"], st, start=wl["start"])
     _check_against_oracle(wl["chains"], res, 1)

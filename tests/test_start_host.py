@@ -11,34 +11,13 @@ import pytest
 
 import mcsas_amd
 from mcsas_amd import _lib, engine
-from helpers import make_models
+from helpers import PythonOnlySphere, make_models
+from chain_cases import MCSAS_EINVAL, _NoLibrary, _algo_40q, _data, _from, _problem
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mcsas_hip.h")
-MCSAS_EINVAL = -1
 # sizeof(mcsas_problem), sizeof(mcsas_result) of ABI 5 before the start entry points existed (x86-64)
 PROBLEM_BYTES, RESULT_BYTES = 512, 96
-
-
-def _data(nq=40):
-    q = np.linspace(1e8, 2e9, nq)
-    I = 1.0 / (1.0 + (q * 2e-9) ** 4)
-    return q, I, 0.02 * I
-
-
-def _problem(nq=40, N=8, R=2, **over):
-    q, I, sig = _data(nq)
-    m, _ = make_models("sphere", [2e-9], [3e-7])
-    st = engine.Settings(**{**dict(n_contrib=N, n_reps=R, max_iter=10, conv_crit=1e-9, max_retries=0), **over})
-    prob = engine.HipProblem(m.setup(), q, I, sig, st)
-    res = engine.ChainResults(N, 1, R, nq)
-    return prob, res
-
-
-def _from(prob, start, res):
-    lib = _lib.load()
-    rc = lib.mcsas_hip_analyse_from(C.byref(prob.c), None if start is None else _lib.as_dp(start), C.byref(res.c))
-    return rc, lib.mcsas_hip_last_error().decode()
 
 
 def test_the_abi_is_extended_not_changed(tmp_path):
@@ -88,14 +67,6 @@ def test_set_start_on_a_null_plan():
     assert lib.mcsas_hip_plan_set_start(None, None, 0, 0) == MCSAS_EINVAL
 
 
-class _NoLibrary(object):
-    """_lib.load replaced for the duration: a refusal made in Python must come before the library is needed."""
-    def __init__(self, monkeypatch):
-        def load(*a, **k):
-            raise AssertionError("the library was asked for before the argument check")
-        monkeypatch.setattr(_lib, "load", load)
-
-
 def test_engine_shape_errors_come_before_any_library_call(monkeypatch):
     _NoLibrary(monkeypatch)
     q, I, sig = _data()
@@ -112,26 +83,17 @@ def test_engine_shape_errors_come_before_any_library_call(monkeypatch):
         engine.analyse(host, q, I, sig, st, start=np.full((8, 1, 3), 5e-8))
 
 
-def _algo(**kw):
-    q, I, sig = _data()
-    algo = mcsas_amd.McSAS.factory()(seed=1, **kw)
-    algo.numContribs.setValue(8); algo.numReps.setValue(3); algo.maxIterations.setValue(10)
-    algo.model, _ = make_models("sphere", [2e-9], [3e-7])
-    algo.data = mcsas_amd.SASData(q, I, sig)
-    return algo
-
-
 def test_front_end_refusals(monkeypatch):
     _NoLibrary(monkeypatch)
     good = np.full((8, 1, 3), 5e-8)
     for mode in (engine.EXEC_PIPELINE, engine.EXEC_WORKGROUP):
         with pytest.raises(ValueError, match="execMode"):
-            _algo(execMode=mode).calc(start=good)
+            _algo_40q(execMode=mode).calc(start=good)
     with pytest.raises(ValueError):
-        _algo().calc(start=np.full((8, 1, 2), 5e-8))                  # fewer start repetitions than numReps
+        _algo_40q().calc(start=np.full((8, 1, 2), 5e-8))                  # fewer start repetitions than numReps
     with pytest.raises(ValueError):
-        _algo().calc(start=np.full((9, 1, 3), 5e-8))
-    algo = _algo()
+        _algo_40q().calc(start=np.full((9, 1, 3), 5e-8))
+    algo = _algo_40q()
     with pytest.raises(ValueError, match="previous"):
         mcsas_amd.run_series(algo, [algo.data], start="previous", batch=True)
     with pytest.raises(ValueError, match="previous"):
@@ -141,9 +103,8 @@ def test_front_end_refusals(monkeypatch):
 
 
 def test_python_only_model_takes_no_start(monkeypatch):
-    from test_parity_gpu import PythonOnlySphere
     _NoLibrary(monkeypatch)
-    algo = _algo()
+    algo = _algo_40q()
     hm = PythonOnlySphere()
     hm.radius.setActiveRange((2e-9, 3e-7))
     algo.model = hm

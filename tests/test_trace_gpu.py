@@ -2,10 +2,10 @@
 engine.analyse(trace=), Plan.set_trace, McSAS.calc(trace=)) on the device.
 
 The reference is the oracle's own mc_fit, unchanged.  While it runs, two of the functions it calls are wrapped: generate_parameters
-(as tests/test_start_gpu.py::_oracle_from wraps it: the first call may return a given start) records the proposal of every step,
+(as chain_cases._oracle_from wraps it: the first call may return a given start) records the proposal of every step,
 and bgfit_calc records its conval call by call — the second call of an attempt is the chi² of the initial set (mcsas.py:343),
 call 2 + s belongs to step s (mcsas.py:376).  ref.accepted names the steps of the moves; together: step, chi², values of every move.
-Tolerances are those of test_start_gpu._check_against_oracle: steps and counts exact, values rtol 1e-12, chi² rtol 1e-7."""
+(chain_cases._oracle_traced).  Tolerances are those of chain_cases._check_against_oracle: steps and counts exact, values rtol 1e-12, chi² rtol 1e-7."""
 import ctypes as C
 import functools
 
@@ -16,84 +16,9 @@ pytestmark = pytest.mark.gpu
 
 from mcsas_amd import engine, _lib
 from oracle import mcsas_oracle as O
-from helpers import load, make_models, plugin_twin
-from test_batch_gpu import RANGES, _synthetic, _same
-from test_start_gpu import CASES, R, REP_OFFSET, SEED, SHAPES, _check_against_oracle, _retry_workload, _workload
-from test_parity_gpu import _quickstart_algo
-
-MCSAS_EINVAL = -1
-K = 200           # above the moves of every chain below (asserted)
-# criterion of the COLD run of each shape, chosen with the oracle so that chains end mid-run, at different steps
-COLD_CRIT = {"sphere100": 60.0, "sphere200": 70.0, "cyl100": 7000.0, "sphere1500": 500.0}
-
-
-def _oracle_traced(spec, q, I, sig, ost, stream, start=None, retries=0):
-    """The retry loop of test_start_gpu._oracle_from (start: the first initial set given, or None for a cold chain) with every
-    attempt's proposals and convals recorded; the trace is the last attempt's."""
-    real_gen, real_fit = O.generate_parameters, O.bgfit_calc
-    calls, props, convals = [0], [], []
-
-    def gen(spec_, stream_, count=1):
-        calls[0] += 1
-        if calls[0] == 1 and start is not None:
-            assert count == start.shape[0]
-            return np.array(start, dtype=float)
-        out = real_gen(spec_, stream_, count)
-        if count == 1:
-            props.append(out[0].copy())
-        return out
-
-    def fit(*a, **k):
-        out = real_fit(*a, **k)
-        convals.append(float(out[1]))
-        return out
-
-    lim = ([I.min(), I.max()], [q.min(), q.max()])
-    iters, pos = [], []
-    O.generate_parameters, O.bgfit_calc = gen, fit
-    try:
-        while True:
-            del props[:], convals[:]
-            ref = O.mc_fit(spec, q, I, sig, lim[0], lim[1], ost, stream, method="closed")
-            iters.append(ref.num_iter); pos.append(stream.pos)
-            if ref.conval <= ost.conv_crit or len(iters) > retries:
-                break
-    finally:
-        O.generate_parameters, O.bgfit_calc = real_gen, real_fit
-    assert len(props) == ref.num_iter and len(convals) == 3 + ref.num_iter and len(ref.accepted) == ref.num_moves
-    trace = dict(chisq0=convals[1], step=np.array(ref.accepted, dtype=np.int64),
-                 chisq=np.array([convals[2 + s] for s in ref.accepted]),
-                 values=np.array([props[s] for s in ref.accepted]).reshape(ref.num_moves, spec.n_active))
-    return dict(attempts=len(iters), iters=iters, pos=pos, ref=ref, converged=int(ref.conval <= ost.conv_crit), trace=trace)
-
-
-def _assert_chains_are_worth_tracing(chains, steps):
-    assert all(3 < c["ref"].num_moves < K for c in chains), [c["ref"].num_moves for c in chains]
-    assert len({c["iters"][-1] for c in chains}) > 1                            # chains end at different steps
-    assert any(c["iters"][-1] < steps and c["converged"] for c in chains)       # ... one of them mid-run, by convergence
-
-
-@functools.lru_cache(maxsize=None)
-def _traced_workload(name, started):
-    """The workload of test_start_gpu._workload(name) with the oracle's traces: started from its start, or cold (the chain's own
-    initial set, a criterion of its own).  The chains run on the Philox streams of chains REP_OFFSET + r; `replay` holds the same
-    numbers.  Computed once, shared, read-only."""
-    wl = _workload(name)
-    tag, nq, N, steps, steps0, crit, fixed = SHAPES[name]
-    spec, q, I, sig = wl["spec"], wl["q"], wl["I"], wl["sig"]
-    if not started:
-        crit = COLD_CRIT[name]
-    ost = O.Settings(n_contrib=N, n_reps=1, max_iter=steps, conv_crit=crit, max_retries=0)
-    chains = [_oracle_traced(spec, q, I, sig, ost, O.PhiloxStream(SEED, REP_OFFSET + r, pos=0),
-                             start=wl["start"][:, :, 1 + r] if started else None) for r in range(R)]
-    _assert_chains_are_worth_tracing(chains, steps)
-    if started:
-        assert [c["iters"] for c in chains] == [c["iters"] for c in wl["chains"]]
-    L = max(c["pos"][-1] for c in chains)
-    replay = np.stack([O.philox_uniform(SEED, REP_OFFSET + r, np.arange(L, dtype=np.uint64)) for r in range(R)])
-    replay.setflags(write=False)
-    st = engine.Settings(**{**wl["st"].__dict__, "conv_crit": crit})
-    return dict(wl, st=st, chains=chains, replay=replay, start=wl["start"][:, :, 1:1 + R] if started else None)
+from helpers import _quickstart_algo, load, make_models, plugin_twin
+from chain_cases import (CASES, K, MCSAS_EINVAL, R, RANGES, REP_OFFSET, SEED, SHAPES, _check_against_oracle, _check_trace, _guarded_trace,
+                         _oracle_traced, _same, _same_trace, _synthetic, _traced_workload, _wave_retry_workload, _workload)
 
 
 @functools.lru_cache(maxsize=None)
@@ -102,23 +27,6 @@ def _run(name, cache, started, replayed, trace):
     st = engine.Settings(**{**wl["st"].__dict__, "cache_intensities": cache, "exec_mode": engine.EXEC_WAVE})
     return engine.analyse(wl["setup"], wl["q"], wl["I"], wl["sig"], st, replay=wl["replay"] if replayed else None, start=wl["start"],
                           trace=trace)
-
-
-def _check_trace(chains, tr, capacity):
-    """The trace against the oracle's, and what holds of any trace: steps rise, chi² falls from chisq0 on, sentinels behind."""
-    assert tr.step.shape == (capacity, len(chains)) and tr.chisq.shape == tr.step.shape and tr.values.shape[::2] == tr.step.shape
-    for r, c in enumerate(chains):
-        ref, t = c["ref"], c["trace"]
-        n = min(ref.num_moves, capacity)
-        print("chain %d: count %d (oracle %d), chisq0 %.17g (oracle %.17g), last kept chisq %.17g (oracle %.17g)"
-              % (r, tr.count[r], ref.num_moves, tr.chisq0[r], t["chisq0"], tr.chisq[n - 1, r], t["chisq"][n - 1]))
-        assert tr.count[r] == ref.num_moves
-        assert np.array_equal(tr.step[:n, r], t["step"][:n])
-        np.testing.assert_allclose(tr.values[:n, :, r], t["values"][:n], rtol=1e-12)
-        np.testing.assert_allclose(tr.chisq[:n, r], t["chisq"][:n], rtol=1e-7)
-        np.testing.assert_allclose(tr.chisq0[r], t["chisq0"], rtol=1e-7)
-        assert (np.diff(tr.step[:n, r]) > 0).all() and (np.diff(tr.chisq[:n, r]) < 0).all() and tr.chisq[0, r] < tr.chisq0[r]
-        assert (tr.step[n:, r] == -1).all() and np.isnan(tr.chisq[n:, r]).all() and np.isnan(tr.values[n:, :, r]).all()
 
 
 ALL = [(name, cache, started, replayed) for name, cache in CASES for started in (False, True) for replayed in (False, True)]
@@ -159,17 +67,6 @@ def test_the_records_rebuild_the_result(name, cache):
                 np.testing.assert_allclose(rset, res.contribs[:, :, r], rtol=1e-12)
 
 
-def _guarded_trace(capacity, P, n_reps, guard=64):
-    """A mcsas_trace whose arrays sit inside larger ones filled with sentinels: (the block, the larger arrays by field)."""
-    sizes = dict(count=n_reps, chisq0=n_reps, step=capacity * n_reps, chisq=capacity * n_reps, values=capacity * P * n_reps)
-    big = {f: (np.full(n + 2 * guard, -77, dtype=np.int64) if f in ("count", "step") else np.full(n + 2 * guard, -77.5)) for f, n in sizes.items()}
-    t = _lib.Trace()
-    t.struct_size, t.capacity = C.sizeof(_lib.Trace), capacity
-    for f, a in big.items():
-        setattr(t, f, a[guard:].ctypes.data_as(C.POINTER(C.c_int64 if a.dtype == np.int64 else C.c_double)))
-    return t, big, {f: (guard, n) for f, n in sizes.items()}
-
-
 @pytest.mark.parametrize("capacity", [1, 3])
 @pytest.mark.parametrize("started", [False, True])
 def test_small_capacity_keeps_the_first_moves_and_writes_nothing_else(capacity, started):
@@ -200,9 +97,9 @@ def test_small_capacity_keeps_the_first_moves_and_writes_nothing_else(capacity, 
 
 @pytest.mark.parametrize("cache", [1, 0])
 def test_retries_leave_the_trace_of_the_last_attempt(cache):
-    """test_start_gpu._retry_workload: a start the chain cannot bring to the criterion within its budget, two retries — chains 0 and
+    """chain_cases._wave_retry_workload: a start the chain cannot bring to the criterion within its budget, two retries — chains 0 and
     2 converge in their second attempt, chain 1 in none of its three.  The first attempt's records are overwritten or dropped."""
-    wl = _retry_workload()
+    wl = _wave_retry_workload()
     st, N = wl["st"], wl["st"].n_contrib
     ost = O.Settings(n_contrib=N, n_reps=1, max_iter=st.max_iter, conv_crit=st.conv_crit, max_retries=2)
     chains = [_oracle_traced(wl["spec"], wl["q"], wl["I"], wl["sig"], ost, O.PhiloxStream(st.seed, REP_OFFSET + r, pos=0),
@@ -227,11 +124,6 @@ def test_a_converged_start_leaves_an_empty_trace():
     assert not tr.count.any()
     np.testing.assert_allclose(tr.chisq0, res.chisq, rtol=1e-7)
     assert (tr.step == -1).all() and np.isnan(tr.chisq).all() and np.isnan(tr.values).all()
-
-
-def _same_trace(a, b, what=""):
-    for f in ("count", "chisq0", "step", "chisq", "values"):
-        assert np.array_equal(getattr(a, f), getattr(b, f), equal_nan=f != "count" and f != "step"), (what, f)
 
 
 def test_plan_slots_reseed_clear_and_batch():

@@ -11,12 +11,11 @@ import pytest
 
 import mcsas_amd
 from mcsas_amd import _lib, engine
-from helpers import make_models
-from test_start_host import _NoLibrary, _algo, _data, _problem
+from helpers import PythonOnlySphere, make_models
+from chain_cases import MCSAS_EINVAL, _NoLibrary, _algo_40q, _data, _problem, _traced
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mcsas_hip.h")
-MCSAS_EINVAL = -1
 NEW = {"mcsas_hip_plan_set_trace", "mcsas_hip_plan_fetch_trace", "mcsas_hip_analyse_traced"}
 FIELDS = ("struct_size", "capacity", "count", "chisq0", "step", "chisq", "values")
 
@@ -37,13 +36,6 @@ def test_trace_layout_matches_the_header(tmp_path):
     out = [int(x) for x in subprocess.check_output([str(tmp_path / "tr")]).split()]
     assert [name for name, _ in _lib.Trace._fields_] == list(FIELDS)
     assert out == [C.sizeof(_lib.Trace)] + [getattr(_lib.Trace, f).offset for f in FIELDS]
-
-
-def _traced(prob, res, tr, start=None):
-    lib = _lib.load()
-    rc = lib.mcsas_hip_analyse_traced(C.byref(prob.c), None if start is None else _lib.as_dp(start), C.byref(res.c),
-                                      None if tr is None else C.byref(tr.c))
-    return rc, lib.mcsas_hip_last_error().decode()
 
 
 def test_analyse_traced_refuses_before_a_device_is_touched():
@@ -127,24 +119,23 @@ def test_engine_refusals_come_before_any_library_call(monkeypatch):
 
 
 def test_front_end_refusals(monkeypatch):
-    from test_parity_gpu import PythonOnlySphere
     _NoLibrary(monkeypatch)
     for mode in (engine.EXEC_PIPELINE, engine.EXEC_WORKGROUP):
         for call in ("calc", "analyse"):
             with pytest.raises(ValueError, match="execMode %d" % mode):
-                getattr(_algo(execMode=mode), call)(trace=16)
+                getattr(_algo_40q(execMode=mode), call)(trace=16)
     with pytest.raises(ValueError, match="device list"):
-        _algo(device=[0, 0]).calc(trace=16)
-    algo = _algo()
+        _algo_40q(device=[0, 0]).calc(trace=16)
+    algo = _algo_40q()
     qq, II, ss = _data(engine.WAVE_MAX_Q + 1)
     algo.data = mcsas_amd.SASData(qq, II, ss)
     with pytest.raises(ValueError, match=str(engine.WAVE_MAX_Q)):
         algo.calc(trace=16)
-    algo = _algo()
+    algo = _algo_40q()
     hm = PythonOnlySphere()
     hm.radius.setActiveRange((2e-9, 3e-7))
     algo.model = hm
     with pytest.raises(ValueError, match="host code"):
         algo.calc(trace=16)
     with pytest.raises(ValueError, match=">= 1"):
-        _algo().calc(trace=0)
+        _algo_40q().calc(trace=0)

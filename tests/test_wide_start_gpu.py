@@ -2,7 +2,7 @@
 contributions: chain_wide_kernel<M, QPL, true> behind mcsas_hip_analyse_from / mcsas_hip_plan_set_start with MCSAS_EXEC_WORKGROUP, and
 behind McSAS.calc(start=) on un-binned data.
 
-The machinery is tests/test_start_gpu.py's, by import: the reference of a started chain is the oracle's own mc_fit with its first
+The machinery is tests/test_start_gpu.py's (chain_cases.py): the reference of a started chain is the oracle's own mc_fit with its first
 generate_parameters call answered by the start (_oracle_from), compared with that file's tolerances (_check_against_oracle: counts
 exact, contribs 1e-12, chi-squared 1e-7, fit and scaling 1e-6).
 
@@ -11,8 +11,6 @@ test_start_gpu.py) and at 1025 q (the third wave holds one real point), 16 slots
 with one real point).  Steps and criteria were chosen with the oracle so that chains end mid-run by convergence, at different steps,
 each after an accepted move (_workload asserts it), and with a margin: a criterion 10 lower ends every chain at the same step, so no
 chain's end sits on a numerically tied comparison.  Should a free-running chain ever do, the seed is what changes, not a tolerance."""
-import functools
-
 import numpy as np
 import pytest
 
@@ -22,19 +20,8 @@ import mcsas_amd
 from mcsas_amd import engine, _lib
 from oracle import mcsas_oracle as O
 from helpers import make_models, plugin_twin, product_smearing
-from test_batch_gpu import RANGES, _synthetic, _same
-from test_start_gpu import MCSAS_ESTREAM, R, REP_OFFSET, SHAPES, _check_against_oracle, _oracle_from, _workload
-
-WG = engine.EXEC_WORKGROUP
-# further rows of test_start_gpu.py's table (its _workload builds and keeps a workload by name): model, q-points, contributions,
-# steps, steps of the cold oracle run the start comes from, criterion, fixed parameters
-SHAPES.update({
-    "sphere1025": ("sphere", 1025, 16, 64, 20, 440.0, {}),
-    "sphere4097": ("sphere", 4097, 16, 64, 20, 440.0, {}),
-    "sphere8193": ("sphere", 8193, 12, 64, 20, 460.0, {}),          # one chain of the three runs to its budget
-})
-# name: q slots per lane, waves per chain
-GEOMETRY = {"sphere1500": (8, 3), "sphere1025": (8, 3), "sphere4097": (16, 5), "sphere8193": (32, 5)}
+from chain_cases import (GEOMETRY, MCSAS_ESTREAM, R, RANGES, REP_OFFSET, WG, _check_against_oracle, _same, _synthetic, _wide_retry_workload,
+                         _workload)
 
 
 def _settings(wl, **over):
@@ -100,29 +87,8 @@ def test_plan_slots_read_their_columns_and_a_cleared_start_runs_cold():
     _same(again, cold, "start cleared")
 
 
-@functools.lru_cache(maxsize=None)
-def _retry_workload():
-    """1025 q-points, every contribution of a start at one large radius, a budget of 24 steps: no started attempt reaches the
-    criterion, two retries.  Seed and criterion chosen with the oracle: chains 0 and 1 converge mid-run in their third attempt
-    (at 0.99 and 0.96 of the criterion), chain 2 in none."""
-    nq, N, steps, crit, seed = 1025, 16, 24, 1000.0, 4
-    q, I, sig = _synthetic(nq)
-    m, spec = make_models("sphere", *RANGES["sphere"])
-    start = np.full((N, 1, R), 1.5e-7) * np.array([1.0, 1.5, 2.0])[None, None, :]
-    ost = O.Settings(n_contrib=N, n_reps=1, max_iter=steps, conv_crit=crit, max_retries=2)
-    chains = [_oracle_from(spec, q, I, sig, ost, start[:, :, r], O.PhiloxStream(seed, REP_OFFSET + r, pos=0), 2) for r in range(R)]
-    assert [c["attempts"] for c in chains] == [3, 3, 3] and [c["converged"] for c in chains] == [1, 1, 0]
-    for c in chains:                                                            # the started attempt ran to its budget, retries WERE taken
-        assert c["iters"][0] == steps and c["pos"][0] == steps                  # ... and the start cost no draws
-        assert c["pos"][-1] == sum(c["iters"]) + N * (c["attempts"] - 1)        # N * P for each later initial set
-    assert chains[0]["iters"][2] < steps and chains[1]["iters"][2] < steps
-    st = engine.Settings(n_contrib=N, n_reps=R, max_iter=steps, conv_crit=crit, max_retries=2, seed=seed, rep_offset=REP_OFFSET, exec_mode=WG)
-    start.setflags(write=False)
-    return dict(setup=m.setup(), spec=spec, q=q, I=I, sig=sig, st=st, start=start, chains=chains)
-
-
 def test_retries_after_a_started_attempt_draw_fresh_sets():
-    wl = _retry_workload()
+    wl = _wide_retry_workload()
     res = engine.analyse(wl["setup"], wl["q"], wl["I"], wl["sig"], wl["st"], start=wl["start"])
     _check_against_oracle(wl["chains"], res, 1)
     L = max(c["pos"][-1] for c in wl["chains"])

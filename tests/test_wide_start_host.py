@@ -10,54 +10,31 @@ import pytest
 import mcsas_amd
 from mcsas_amd import _lib, engine
 from helpers import make_models
-from test_start_host import MCSAS_EINVAL, _data, _from, _problem
-
-MCSAS_OK, MCSAS_ENODEV = 0, -2
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mcsas_amd", "csrc")
-
-
-class _LibraryReached(Exception):
-    pass
-
-
-def _stub_library(monkeypatch):
-    """_lib.load replaced for the duration: reaching it means every check made in Python has passed."""
-    def load(*a, **k):
-        raise _LibraryReached()
-    monkeypatch.setattr(_lib, "load", load)
-
-
-def _algo(nq, **kw):
-    q, I, sig = _data(nq)
-    algo = mcsas_amd.McSAS.factory()(seed=1, **kw)
-    algo.numContribs.setValue(8); algo.numReps.setValue(3); algo.maxIterations.setValue(10)
-    algo.model, _ = make_models("sphere", [2e-9], [3e-7])
-    algo.data = mcsas_amd.SASData(q, I, sig)
-    return algo
+from chain_cases import CSRC, MCSAS_EINVAL, MCSAS_ENODEV, MCSAS_OK, _LibraryReached, _algo_nq, _code, _data, _from, _problem, _stub_library
 
 
 def test_front_end_takes_the_workgroup_mode_beyond_1024_points(monkeypatch):
     _stub_library(monkeypatch)
     good = np.full((8, 1, 3), 5e-8)
     with pytest.raises(_LibraryReached):
-        _algo(1500, execMode=engine.EXEC_WORKGROUP).calc(start=good)
+        _algo_nq(1500, execMode=engine.EXEC_WORKGROUP).calc(start=good)
     with pytest.raises(ValueError, match="execMode"):
-        _algo(40, execMode=engine.EXEC_WORKGROUP).calc(start=good)
+        _algo_nq(40, execMode=engine.EXEC_WORKGROUP).calc(start=good)
     with pytest.raises(ValueError, match="execMode"):
-        _algo(1024, execMode=engine.EXEC_WORKGROUP).calc(start=good)
+        _algo_nq(1024, execMode=engine.EXEC_WORKGROUP).calc(start=good)
     with pytest.raises(ValueError, match="execMode"):
-        _algo(1500, execMode=engine.EXEC_PIPELINE).calc(start=good)
+        _algo_nq(1500, execMode=engine.EXEC_PIPELINE).calc(start=good)
     # the mode a started problem asks for: one wavefront per chain while it takes the data, the workgroup mode where nothing else does
     for nq, mode, asked in ((1500, engine.EXEC_AUTO, engine.EXEC_WAVE), (1500, engine.EXEC_WORKGROUP, engine.EXEC_WORKGROUP),
                             (4096, engine.EXEC_AUTO, engine.EXEC_WAVE), (4097, engine.EXEC_AUTO, engine.EXEC_WORKGROUP),
                             (4097, engine.EXEC_WAVE, engine.EXEC_WAVE), (40, engine.EXEC_AUTO, engine.EXEC_WAVE)):
-        algo = _algo(nq, execMode=mode)
+        algo = _algo_nq(nq, execMode=mode)
         assert algo._problem(start=good)["st"].exec_mode == asked, (nq, mode)
         assert algo._problem()["st"].exec_mode == mode, (nq, mode)              # (without a start: what was set)
     # a series checks each data set against its own size
-    algo = _algo(40, execMode=engine.EXEC_WORKGROUP)
+    algo = _algo_nq(40, execMode=engine.EXEC_WORKGROUP)
     with pytest.raises(ValueError, match="execMode"):
-        mcsas_amd.run_series(algo, [_algo(1500).data, _algo(40).data], start=good)
+        mcsas_amd.run_series(algo, [_algo_nq(1500).data, _algo_nq(40).data], start=good)
 
 
 def test_analyse_many_with_a_start_and_the_workgroup_mode(monkeypatch):
@@ -92,10 +69,6 @@ def test_analyse_from_takes_the_workgroup_mode_beyond_1024_q():
     prob, res = _problem(nq=1500, exec_mode=engine.EXEC_WORKGROUP)
     rc, msg = _from(prob, bad, res)
     assert rc == MCSAS_EINVAL and "not finite" in msg, msg
-
-
-def _code(name):
-    return re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, name)).read())
 
 
 def test_the_new_family_is_entered_in_every_table():

@@ -2,7 +2,7 @@
 q-points, one workgroup per chain) behind mcsas_hip_plan_set_trace / _fetch_trace / mcsas_hip_analyse_traced with
 MCSAS_EXEC_WORKGROUP, engine.analyse(trace=), Plan.set_trace and McSAS(execMode=workgroup).calc(trace=) on the device.
 
-The machinery is tests/test_trace_gpu.py's, by import: the reference is the oracle's own mc_fit with generate_parameters and bgfit_calc
+The machinery is tests/test_trace_gpu.py's (chain_cases.py): the reference is the oracle's own mc_fit with generate_parameters and bgfit_calc
 wrapped to record every step's proposal and conval (_oracle_traced).  Counts, steps and VALUES are compared exactly (_check_exact
 below: a proposal is transform(u) * (hi - lo) + lo of the same uniform in the oracle and on the device, where no multiply-add is
 fused), chi² with that file's tolerance (_check_trace: 1e-7; _check_against_oracle for the result).
@@ -22,16 +22,8 @@ import mcsas_amd
 from mcsas_amd import engine, _lib
 from oracle import mcsas_oracle as O
 from helpers import make_models, plugin_twin, product_smearing
-from test_batch_gpu import RANGES, _synthetic, _same
-from test_start_gpu import R, REP_OFFSET, SEED, SHAPES, _check_against_oracle, _workload
-from test_trace_gpu import COLD_CRIT, K, _check_trace, _guarded_trace, _oracle_traced, _same_trace, _traced_workload
-from test_wide_start_gpu import GEOMETRY, _retry_workload
-
-WG = engine.EXEC_WORKGROUP
-MCSAS_EINVAL = -1
-# criterion of the COLD run of the shapes test_wide_start_gpu.py adds (sphere1500: test_trace_gpu.py's).  sphere8193: one chain of
-# the three runs to its budget
-COLD_CRIT.update({"sphere1025": 420.0, "sphere4097": 420.0, "sphere8193": 430.0})
+from chain_cases import (GEOMETRY, K, MCSAS_EINVAL, R, RANGES, REP_OFFSET, SEED, SHAPES, WG, _check_against_oracle, _check_trace, _guarded_trace,
+                         _oracle_traced, _same, _same_trace, _synthetic, _traced_workload, _wide_retry_workload, _workload)
 
 
 @functools.lru_cache(maxsize=None)
@@ -169,9 +161,9 @@ def test_small_capacity_keeps_the_first_moves_and_writes_nothing_else(capacity, 
 
 
 def test_retries_leave_the_trace_of_the_last_attempt():
-    """test_wide_start_gpu._retry_workload: 1025 q-points, a start no attempt brings to the criterion within 24 steps, two retries,
+    """chain_cases._wide_retry_workload: 1025 q-points, a start no attempt brings to the criterion within 24 steps, two retries,
     both taken by every chain.  The records of the earlier attempts are overwritten or dropped."""
-    wl = _retry_workload()
+    wl = _wide_retry_workload()
     st, N = wl["st"], wl["st"].n_contrib
     ost = O.Settings(n_contrib=N, n_reps=1, max_iter=st.max_iter, conv_crit=st.conv_crit, max_retries=2)
     chains = [_oracle_traced(wl["spec"], wl["q"], wl["I"], wl["sig"], ost, O.PhiloxStream(st.seed, REP_OFFSET + r, pos=0),

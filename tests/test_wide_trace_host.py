@@ -12,11 +12,7 @@ import pytest
 import mcsas_amd
 from mcsas_amd import _lib, engine
 from helpers import make_models
-from test_start_host import MCSAS_EINVAL, _data, _problem
-from test_trace_host import _traced
-from test_wide_start_host import CSRC, MCSAS_ENODEV, MCSAS_OK, _LibraryReached, _algo, _code, _stub_library
-
-WG = engine.EXEC_WORKGROUP
+from chain_cases import CSRC, MCSAS_EINVAL, MCSAS_ENODEV, MCSAS_OK, WG, _LibraryReached, _algo_nq, _code, _data, _problem, _stub_library, _traced
 
 
 def test_the_traced_q_split_family_is_entered_in_every_table():
@@ -110,18 +106,18 @@ def test_python_checks_let_the_workgroup_mode_through_beyond_1024_points(monkeyp
     good = np.full((8, 1, 3), 5e-8)
     for kw in ({}, {"start": good}):
         with pytest.raises(_LibraryReached):
-            _algo(4097, execMode=WG).calc(trace=16, **kw)
+            _algo_nq(4097, execMode=WG).calc(trace=16, **kw)
         with pytest.raises(_LibraryReached):
-            _algo(1025, execMode=WG).analyse(trace=16, **kw)
-    assert _algo(4097, execMode=WG)._check_trace_mode(16) == WG and _algo(1025, execMode=WG)._check_trace_mode(16) == WG
-    assert _algo(1500)._check_trace_mode(16) == engine.EXEC_WAVE and _algo(1500, execMode=engine.EXEC_WAVE)._check_trace_mode(16) == engine.EXEC_WAVE
+            _algo_nq(1025, execMode=WG).analyse(trace=16, **kw)
+    assert _algo_nq(4097, execMode=WG)._check_trace_mode(16) == WG and _algo_nq(1025, execMode=WG)._check_trace_mode(16) == WG
+    assert _algo_nq(1500)._check_trace_mode(16) == engine.EXEC_WAVE and _algo_nq(1500, execMode=engine.EXEC_WAVE)._check_trace_mode(16) == engine.EXEC_WAVE
     for nq in (40, 1024):
         with pytest.raises(ValueError, match="execMode 2"):
-            _algo(nq, execMode=WG).calc(trace=16)
+            _algo_nq(nq, execMode=WG).calc(trace=16)
     with pytest.raises(ValueError, match="execMode 3"):
-        _algo(4097, execMode=engine.EXEC_PIPELINE).calc(trace=16)
+        _algo_nq(4097, execMode=engine.EXEC_PIPELINE).calc(trace=16)
     with pytest.raises(ValueError, match="device list"):
-        _algo(4097, execMode=WG, device=[0, 0]).calc(trace=16)
+        _algo_nq(4097, execMode=WG, device=[0, 0]).calc(trace=16)
 
 
 def test_the_trace_never_picks_the_mode(monkeypatch):
@@ -134,4 +130,4 @@ def test_the_trace_never_picks_the_mode(monkeypatch):
             engine.analyse(m.setup(), q, I, sig, engine.Settings(n_contrib=8, n_reps=3, max_iter=10, exec_mode=mode), trace=16)
         for kw in ({}, {"start": np.full((8, 1, 3), 5e-8)}):
             with pytest.raises(ValueError, match=r"4096.*set execMode to workgroup"):
-                _algo(engine.WAVE_MAX_Q + 1, execMode=mode).calc(trace=16, **kw)
+                _algo_nq(engine.WAVE_MAX_Q + 1, execMode=mode).calc(trace=16, **kw)
