@@ -170,8 +170,8 @@ static int start_or_trace_request(const char *who, const mcsas_problem *p, const
     if (traced && p->n_devices > 1) return fail(MCSAS_EINVAL, "%s: n_devices %d: a trace is kept on one device", who, p->n_devices);
     if (p->n_active < 0 || p->n_active > MCSAS_MAX_ACTIVE) return fail(MCSAS_EINVAL, "n_active %d out of range", p->n_active);
     if (p->n_contrib < 1 || p->n_reps < 1) return fail(MCSAS_EINVAL, "n_contrib and n_reps must be >= 1");
-    if (traced && (size_t)tr->capacity > TRACE_MAX_BYTES / ((size_t)p->n_reps * (16 + 8 * (size_t)p->n_active)))
-        return fail(MCSAS_EINVAL, "%s: %d repetitions x capacity %d x %d bytes per move exceed 2 GiB", who, p->n_reps, (int)tr->capacity, 16 + 8 * p->n_active);
+    if (traced && TraceLayout::too_large((size_t)p->n_reps, (size_t)tr->capacity, (size_t)p->n_active))
+        return fail(MCSAS_EINVAL, "%s: %d repetitions x capacity %d x %d bytes per move exceed 2 GiB", who, p->n_reps, (int)tr->capacity, (int)TraceLayout(1, 0, (size_t)p->n_active).move_bytes);
     if (start) { if (int rc = check_start_finite(who, start, (size_t)p->n_contrib, (size_t)p->n_active, (size_t)p->n_reps, 0, (size_t)p->n_reps)) return rc; }
     *q = *p;
     q->exec_mode = q_split ? MCSAS_EXEC_WORKGROUP : MCSAS_EXEC_WAVE;

@@ -1,5 +1,5 @@
-// host_internal.h — what the host units of libmcsas_hip.so share (mcsas_hip.hip: plans; host_analyse.hip: one-shot analyses; host_rows.hip:
-// rows evaluated by the caller; host_plugin.hip: run-time compiler of model plug-ins; host_calls.hip: small one-call entry points; host_hist.hip:
+// host_internal.h — what the host units of libmcsas_hip.so share (mcsas_hip.hip: plans; host_decide.hip: what is decided without a device; host_analyse.hip:
+// one-shot analyses; host_rows.hip: rows evaluated by the caller; host_plugin.hip: run-time compiler of model plug-ins; host_calls.hip: small one-call entry points; host_hist.hip:
 // McSAS.histogram()).  Host code only: the run-time compiler never sees this file (it is not among the embedded headers).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -11,7 +11,7 @@
 
 #pragma GCC visibility push(hidden)
 
-// ------------------------------------------------------------------------------ error plumbing (mcsas_hip.hip)
+// ------------------------------------------------------------------------------ error plumbing (host_decide.hip)
 extern thread_local std::string g_err;
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 #define HIPCHK(expr)                                                                         \
@@ -59,35 +59,35 @@ template <typename T> struct DevBuf {
     }
 };
 
-// ------------------------------------------------------------------------------ models (mcsas_hip.hip)
-// what the host needs to know about a model, read off its Contrib<M> (models.h) — no per-model code outside this table
-struct ModelTraits { int int_div_param, rowtab, row_class; bool can_smear; int (*table_doubles)(int); int contrib_doubles; };
-ModelTraits model_traits(int model_id);
-inline int table_doubles_host(int model_id, int K) { return model_traits(model_id).table_doubles(K); }
-// per-wave scratch for the per-row orientation table (Contrib<M>::ROWTAB * K doubles, models.h); beyond
-// K = 256 the chain kernels evaluate the integrand directly
-inline int rowtab_doubles_host(int model_id, int K) { return K > 256 ? 0 : model_traits(model_id).rowtab * K; }
-int fill_model_args(const mcsas_problem *p, mcsas::ModelArgs *m);
+// ------------------------------------------------------------------------------ the chain kernel families
+// A kernel is (family, given): the wave, wave-batch and q-split families have a second form whose first attempt takes a given set
+// (mcsas_hip_plan_set_start), the workgroup-window and pipeline families have none.  Every built-in model has its instances in
+// kern_*.hip (the started ones in kern_wave_start.hip and kern_wide_start.hip), a plug-in compiles its own on first use.  The traced
+// families (kern_wave_trace.hip, kern_wide_trace.hip) also record their accepted moves (mcsas_hip_plan_set_trace), cold and started.
+enum KernelFamily { KF_WAVE, KF_WAVE_BATCH, KF_WG, KF_WIDE, KF_PIPE_TICK, KF_WAVE_TRACE, KF_WIDE_TRACE, KF_COUNT };
 
-// Device copy of the smearing tables of a problem: locs transposed to [K][stride] (pad columns repeat
-// column 0, like the padded q) and cw[m] = 2 * trapezoid coefficient(q_offset)[m] * weights[m], so that
-// sum_m cw[m] y[m] = 2 trapz(y * weights, x = q_offset) (sasmodel.py:72-73).
-struct SmearDev {
-    double *locs_t = nullptr, *cw = nullptr;
-    ~SmearDev() { if (locs_t) hipFree(locs_t); if (cw) hipFree(cw); }
-    static bool active(const mcsas_problem *p);            // smearing asked for and the model can be smeared (canSmear)
-    static int check(const mcsas_problem *p);              // the refusal of upload(), without a HIP call
-    int upload(const mcsas_problem *p, int stride, mcsas::ModelArgs *m);
+// One row per family, the one place that says what a family is: the word for it in messages; the kernel template's name (namespace
+// mcsas) and the key of a plug-in's program; whether the template has, behind <model, qpl>, a flag (the row cache of the wave families,
+// rows pulled from a queue by the pipeline tick) and GIVEN; whether the kernel's last argument is the launch's TraceArgs; what it takes
+// between its argument block and those (nothing, the WgGeom, q3inv); its block: one wave, the plan's waves per chain, PIPE_BLOCK threads.
+struct FamilyInfo {
+    const char *word, *kernel, *key;
+    bool flagged, startable, trace;
+    enum Arg2 { ARG2_NONE, ARG2_WG, ARG2_Q3INV } arg2;
+    enum Block { BLOCK_WAVE, BLOCK_WAVES, BLOCK_PIPE } block;
+};
+
+constexpr FamilyInfo KERNEL_FAMILY[KF_COUNT] = {
+    {"", "chain_wave_kernel", "wave", true, true, false, FamilyInfo::ARG2_NONE, FamilyInfo::BLOCK_WAVE},
+    {"batch ", "chain_wave_batch_kernel", "wave batch", true, true, false, FamilyInfo::ARG2_NONE, FamilyInfo::BLOCK_WAVE},
+    {"", "chain_wg_kernel", "wg", false, false, false, FamilyInfo::ARG2_WG, FamilyInfo::BLOCK_WAVES},
+    {"q-split ", "chain_wide_kernel", "wide", false, true, false, FamilyInfo::ARG2_Q3INV, FamilyInfo::BLOCK_WAVES},
+    {"pipeline ", "pipe_tick_kernel", "pipe", true, false, false, FamilyInfo::ARG2_NONE, FamilyInfo::BLOCK_PIPE},
+    {"traced ", "chain_wave_trace_kernel", "wave trace", true, true, true, FamilyInfo::ARG2_NONE, FamilyInfo::BLOCK_WAVE},
+    {"traced q-split ", "chain_wide_trace_kernel", "wide trace", false, true, true, FamilyInfo::ARG2_Q3INV, FamilyInfo::BLOCK_WAVES},
 };
 
 // ------------------------------------------------------------------------------ run-time model plug-ins (host_plugin.hip)
-// the chain kernel families.  A kernel is (family, given): the wave, wave-batch and q-split families have a second form whose first
-// attempt takes a given set (mcsas_hip_plan_set_start), the workgroup-window and pipeline families have none.  Every built-in model
-// has its instances in kern_*.hip (the started ones in kern_wave_start.hip and kern_wide_start.hip), a plug-in compiles its own on
-// first use.  KF_WAVE_TRACE: the wave kernel that also records its accepted moves (mcsas_hip_plan_set_trace; kern_wave_trace.hip),
-// cold and started; its second kernel argument is the launch's TraceArgs.  KF_WIDE_TRACE: the same of the q-split kernel
-// (kern_wide_trace.hip); the TraceArgs are its third argument, behind q3inv
-enum KernelFamily { KF_WAVE, KF_WAVE_BATCH, KF_WG, KF_WIDE, KF_PIPE_TICK, KF_WAVE_TRACE, KF_WIDE_TRACE, KF_COUNT };
 enum PluginSmallKernel { PLUGIN_MODEL_ROWS, PLUGIN_OBSERVABILITY, PLUGIN_HIST_ROWS };
 
 inline bool is_plugin_model(int model_id) { return model_id >= MCSAS_MODEL_PLUGIN0 && model_id < MCSAS_MODEL_PLUGIN0 + MCSAS_MAX_PLUGINS; }
@@ -110,17 +110,46 @@ static int plugin_small_launch(int model_id, PluginSmallKernel which, dim3 grid,
     return MCSAS_OK;
 }
 
-// ------------------------------------------------------------------------------ what a request is refused for, with and without a plan (mcsas_hip.hip)
+// ------------------------------------------------------------------------------ models (host_decide.hip)
+// what the host needs to know about a model, read off its Contrib<M> (models.h) — no per-model code outside this table
+struct ModelTraits { int int_div_param, rowtab, row_class; bool can_smear; int (*table_doubles)(int); int contrib_doubles; };
+ModelTraits model_traits(int model_id);
+inline int table_doubles_host(int model_id, int K) { return model_traits(model_id).table_doubles(K); }
+// per-wave scratch for the per-row orientation table (Contrib<M>::ROWTAB * K doubles, models.h); beyond
+// K = 256 the chain kernels evaluate the integrand directly
+inline int rowtab_doubles_host(int model_id, int K) { return K > 256 ? 0 : model_traits(model_id).rowtab * K; }
+int fill_model_args(const mcsas_problem *p, mcsas::ModelArgs *m);
+
+// Device copy of the smearing tables of a problem: locs transposed to [K][stride] (pad columns repeat
+// column 0, like the padded q) and cw[m] = 2 * trapezoid coefficient(q_offset)[m] * weights[m], so that
+// sum_m cw[m] y[m] = 2 trapz(y * weights, x = q_offset) (sasmodel.py:72-73).
+struct SmearDev {
+    double *locs_t = nullptr, *cw = nullptr;
+    ~SmearDev() { if (locs_t) hipFree(locs_t); if (cw) hipFree(cw); }
+    static bool active(const mcsas_problem *p);            // smearing asked for and the model can be smeared (canSmear)
+    static int check(const mcsas_problem *p);              // the refusal of upload(), without a HIP call
+    int upload(const mcsas_problem *p, int stride, mcsas::ModelArgs *m);
+};
+
+// ------------------------------------------------------------------------------ what a request is refused for, with and without a plan (host_decide.hip)
 // plan_set_start / plan_set_trace / plan_fetch_trace and the one-shot entry points over them (host_analyse.hip) answer alike
 // the first non-finite value of the columns [first, first + R) of start[N][P][stride], or MCSAS_OK
 int check_start_finite(const char *who, const double *start, size_t N, size_t P, size_t stride, size_t first, size_t R);
 int check_trace_arrays(const char *who, const mcsas_trace *tr);
 const char *exec_mode_name(int mode);
-// a trace block (step, chisq and values of `capacity` moves per repetition) stays below this
+// A slot's trace block: [step | chisq | values | chisq0] of R repetitions with room for K moves of P values each, on the host as
+// fetched and in its 256-byte-aligned device block.  Step, chisq and values together stay below TRACE_MAX_BYTES.
 constexpr size_t TRACE_MAX_BYTES = (size_t)2 << 30;
+struct TraceLayout {
+    size_t move_bytes, step, chisq, values, chisq0, host_bytes, dev_bytes;
+    constexpr TraceLayout(size_t R, size_t K, size_t P)
+        : move_bytes(16 + 8 * P), step(0), chisq(8 * R * K), values(16 * R * K), chisq0(move_bytes * R * K),
+          host_bytes(chisq0 + 8 * R), dev_bytes((host_bytes + 255) / 256 * 256) {}
+    static constexpr bool too_large(size_t R, size_t K, size_t P) { return K > TRACE_MAX_BYTES / (R * TraceLayout(R, 0, P).move_bytes); }
+};
 
 // ------------------------------------------------------------------------------ which kernel takes how many q-points, a start, a trace
-// The q-points a kernel takes (mcsas_hip.hip ties them to WAVE and WIDE_MAX_WAVES): the workgroup-window kernel and the pipeline, one
+// The q-points a kernel takes (host_decide.hip ties them to WAVE and WIDE_MAX_WAVES): the workgroup-window kernel and the pipeline, one
 // wavefront per chain (32 / 64 q slots per lane beyond the first), the q-split kernel (8 waves of 32 slots per lane).
 constexpr int Q_MAX_WINDOW = 1024, Q_MAX_WAVE = 4096, Q_MAX_SPLIT = 16384;
 // Whether a problem runs the q-split kernel: more than Q_MAX_WINDOW q-points, unless one wavefront per chain is asked for — by

@@ -15,7 +15,7 @@
 #include <string>
 #include <vector>
 
-#include "host_internal.h"
+#include "host_decide.h"
 #include "embedded_headers.inc"
 
 struct Plugin {
@@ -147,18 +147,8 @@ int plugin_small_function(int model_id, PluginSmallKernel which, hipFunction_t *
     return plugin_function(model_id, "small", exprs, exprs[which], fn);
 }
 int plugin_chain_function(int model_id, KernelFamily family, int qpl, bool flag, bool given, hipFunction_t *fn) {
-    // the kernel template, the program key, and which template arguments the family has behind <model, qpl>: its flag (row cache /
-    // row queue), then whether the first attempt takes a given set
-    static const struct { const char *kernel, *key; bool flagged, startable; } FAMILY[KF_COUNT] = {
-        {"chain_wave_kernel", "wave", true, true}, {"chain_wave_batch_kernel", "wave batch", true, true}, {"chain_wg_kernel", "wg", false, false},
-        {"chain_wide_kernel", "wide", false, true}, {"pipe_tick_kernel", "pipe", true, false}, {"chain_wave_trace_kernel", "wave trace", true, true},
-        {"chain_wide_trace_kernel", "wide trace", false, true}};
-    const auto &f = FAMILY[family];
-    if (given && !f.startable) return fail(MCSAS_EINVAL, "no %s start kernel for model %d qpl %d", f.key, model_id, qpl);
-    // (started and cold kernels are programs of their own, each compiled when first asked for)
-    const std::string e = std::string("mcsas::") + f.kernel + "<MCSAS_MODEL_PLUGIN, " + std::to_string(qpl) + (f.flagged ? (flag ? ", true" : ", false") : "")
-                          + (f.startable ? (given ? ", true" : ", false") : "") + ">";
-    const std::string k = std::string(f.key) + (given ? " start " : " ") + std::to_string(qpl) + (f.flagged ? (flag ? " 1" : " 0") : "");
+    std::string e, k;                                     // (KERNEL_FAMILY, host_internal.h: the template's name and arguments, the program key)
+    if (int rc = plugin_kernel_name(model_id, family, qpl, flag, given, &e, &k)) return rc;
     return plugin_function(model_id, k, {e}, e, fn);
 }
 

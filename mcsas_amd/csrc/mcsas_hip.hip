@@ -1,15 +1,14 @@
 // mcsas_hip.hip — libmcsas_hip.so: C ABI (include/mcsas_hip.h) over the gfx950 chain kernels.  This unit holds the plans: their
-// creation, start and trace, launches, fetches and batch launches, with the memory cache, the streams and the ABI queries.  The
-// one-shot analyses over plans are host_analyse.hip, the chains whose rows the caller evaluates host_rows.hip, the run-time compiler
-// of model plug-ins host_plugin.hip, the small one-call entry points (model.calc, input preparation) host_calls.hip,
-// McSAS.histogram() host_hist.hip; what they share is host_internal.h, and host_result.h writes every mcsas_result.
+// creation, start and trace, launches, fetches and batch launches, with the memory cache, the streams and the ABI queries.  What
+// it decides without a device is host_decide.hip, the one-shot analyses over plans are host_analyse.hip, the chains whose rows the
+// caller evaluates host_rows.hip, the run-time compiler of model plug-ins host_plugin.hip, the small one-call entry points (model.calc,
+// input preparation) host_calls.hip, McSAS.histogram() host_hist.hip; what they share is host_internal.h, and host_result.h writes every mcsas_result.
 // Built only for MI355X (gfx950); there is no CPU path in here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -19,75 +18,14 @@
 #include <thread>
 #include <vector>
 
-#include "host_internal.h"
+#include "host_decide.h" // host_internal.h, and of the kernel headers chain_wg.h and pipe_layout.h: geometry and argument blocks
 #include "host_result.h"
-#include "chain_wg.h"   // WgGeom / wg_geometry only; the kernels are instantiated in kern_*.hip
-#include "pipe_layout.h" // the pipeline's argument blocks, constants and pipe_geometry (no kernel templates)
 #include "chain_wide.h" // WIDE_* constants only
-#include "auto_table.h" // measured rates of the execution modes (tools/make_auto_table.py)
 #include "model_list.h" // MCSAS_FOR_MODELS: the built-in models
 
 using namespace mcsas;
 
-// host_internal.h's q-point limits are the kernels': 16 q slots per lane, 64, and WIDE_MAX_WAVES waves of 32
-static_assert(Q_MAX_WINDOW == 16 * WAVE && Q_MAX_WAVE == 64 * WAVE && Q_MAX_SPLIT == WIDE_MAX_WAVES * WAVE * 32, "host_internal.h: Q_MAX_*");
-
-// ------------------------------------------------------------------------------ error plumbing
-thread_local std::string g_err;
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    g_err = buf;
-    return code;
-}
-
 // ------------------------------------------------------------------------------ host helpers
-ModelTraits model_traits(int model_id) {
-#define TRAITS_OF(m) {Contrib<m>::INT_DIV_PARAM, Contrib<m>::ROWTAB, Contrib<m>::ROW_CLASS, Contrib<m>::CAN_SMEAR, &Contrib<m>::table_doubles, (int)(sizeof(Contrib<m>) / 8)},
-    static const ModelTraits builtin[] = {MCSAS_FOR_MODELS(TRAITS_OF)};
-#undef TRAITS_OF
-    static_assert(sizeof builtin / sizeof builtin[0] == MCSAS_MODEL_COUNT, "model_list.h and include/mcsas_hip.h disagree");
-    if (model_id >= 0 && model_id < MCSAS_MODEL_COUNT) return builtin[model_id];
-    int row_class = 0;
-    bool can_smear = false;
-    (void)plugin_declares(model_id, &row_class, &can_smear);                          // plugin_model.h
-    // (Contrib<MCSAS_MODEL_PLUGIN>, plugin_model.h: the full parameter vector and three doubles)
-    return ModelTraits{-1, 0, row_class, can_smear, [](int) { return 0; }, MCSAS_MAX_PARAMS + 3};
-}
-static int model_int_div(const mcsas_problem *p) {
-    const int i = model_traits(p->model_id).int_div_param;
-    return i < 0 ? 1 : (int)p->params[i];
-}
-
-int fill_model_args(const mcsas_problem *p, ModelArgs *m) {
-    if ((p->model_id < 0 || p->model_id >= MCSAS_MODEL_COUNT) && !(is_plugin_model(p->model_id) && plugin_declares(p->model_id, nullptr, nullptr)))
-        return fail(MCSAS_EINVAL, "unknown model_id %d", p->model_id);
-    if (p->n_active < 0 || p->n_active > MCSAS_MAX_ACTIVE) return fail(MCSAS_EINVAL, "n_active %d out of range", p->n_active);
-    memset(m, 0, sizeof *m);
-    m->model_id = p->model_id; m->n_active = p->n_active; m->comp_exp = p->comp_exp;
-    for (int i = 0; i < MCSAS_MAX_PARAMS; ++i) m->params[i] = p->params[i];
-    for (int c = 0; c < MCSAS_MAX_ACTIVE; ++c) {
-        m->active_index[c] = c < p->n_active ? p->active_index[c] : -1;
-        m->clip_lo[c] = p->clip_lo[c]; m->clip_hi[c] = p->clip_hi[c];
-        if (c < p->n_active && (p->active_index[c] < 0 || p->active_index[c] >= MCSAS_MAX_PARAMS))
-            return fail(MCSAS_EINVAL, "active_index[%d]=%d out of range", c, p->active_index[c]);
-    }
-    m->int_div = model_int_div(p);
-    m->use_rowtab = rowtab_doubles_host(p->model_id, m->int_div) > 0;
-    m->qmax = 0.;
-    if (p->q) for (int i = 0; i < p->nq; ++i) m->qmax = std::max(m->qmax, std::fabs(p->q[i]));
-    if (model_traits(p->model_id).int_div_param >= 0 && (m->int_div < 2 || m->int_div > 4096))
-        return fail(MCSAS_EINVAL, "intDiv %d unsupported (2..4096)", m->int_div);
-    return MCSAS_OK;
-}
-
-bool SmearDev::active(const mcsas_problem *p) { return p->smear_nk > 0 && model_traits(p->model_id).can_smear; }   // canSmear = False: not smeared
-int SmearDev::check(const mcsas_problem *p) {
-    const int K = p->smear_nk;
-    if (active(p) && (K < 2 || K > 4096 || !p->smear_locs || !p->smear_q_offset || !p->smear_weights))
-        return fail(MCSAS_EINVAL, "smearing: smear_nk %d (2..4096) needs locs, q_offset and weights", K);
-    return MCSAS_OK;
-}
 int SmearDev::upload(const mcsas_problem *p, int stride, ModelArgs *m) {
     m->smear_nk = 0; m->smear_stride = 0; m->smear_locs_t = nullptr; m->smear_cw = nullptr;
     if (!active(p)) return MCSAS_OK;
@@ -353,9 +291,10 @@ typedef void *KernelLookup(int qpl, bool flag);
                   {mcsas_wg_kernel_m##m, nullptr}, {mcsas_wide_kernel_m##m, mcsas_wide_kernel_given_m##m}, {mcsas_pipe_tick_kernel_m##m, nullptr}, \
                   {mcsas_wave_trace_kernel_m##m, mcsas_wave_trace_kernel_given_m##m}, {mcsas_wide_trace_kernel_m##m, mcsas_wide_trace_kernel_given_m##m}},
 MCSAS_FOR_MODELS(DECL_K)
-static KernelLookup *const BUILTIN[MCSAS_MODEL_COUNT][KF_COUNT][2] = {MCSAS_FOR_MODELS(ROW_K)};
+static constexpr KernelLookup *const BUILTIN[MCSAS_MODEL_COUNT][KF_COUNT][2] = {MCSAS_FOR_MODELS(ROW_K)};
 #undef DECL_K
 #undef ROW_K
+static_assert(BUILTIN[MCSAS_MODEL_COUNT - 1][KF_COUNT - 1][0] != nullptr, "ROW_K: a pair of lookups per family of KernelFamily (too few leave the last one null)");
 void *mcsas_pipe_reset_kernel();
 
 // What a launch needs: the kernel (built-in models: the host handle of the __global__ function; plug-ins: the function of this
@@ -365,7 +304,7 @@ struct KernelRef {
     void *entry = nullptr;
     hipFunction_t plugin = nullptr;
     unsigned block = 0;
-    enum { ARG2_NONE, ARG2_WG, ARG2_Q3INV } arg2 = ARG2_NONE;
+    FamilyInfo::Arg2 arg2 = FamilyInfo::ARG2_NONE;
     bool trace = false;
     const void *id() const { return plugin ? (const void *)plugin : entry; }
 };
@@ -375,27 +314,25 @@ static bool takes_start_and_trace(const mcsas_plan *pl) { return pl->mode == MCS
 // the family of the plan's own launches; a batch (mcsas_hip_plan_launch_batch) runs the plan's chains in KF_WAVE_BATCH instead.  Either
 // way a launch takes the started kernel of its family while the plan holds a start (mcsas_hip_plan_set_start gives one to plans of
 // the wave and q-split families only), and a plan of either with a trace (mcsas_hip_plan_set_trace) the traced family.
-static KernelFamily plan_family(const mcsas_plan *pl) {
+static KernelFamily plan_family(const mcsas_plan *pl, bool traced) {
     if (!takes_start_and_trace(pl)) return pl->mode == MCSAS_EXEC_PIPELINE ? KF_PIPE_TICK : KF_WG;
-    if (pl->wide) return pl->trace_capacity > 0 ? KF_WIDE_TRACE : KF_WIDE;
-    return pl->trace_capacity > 0 ? KF_WAVE_TRACE : KF_WAVE;
+    if (pl->wide) return traced ? KF_WIDE_TRACE : KF_WIDE;
+    return traced ? KF_WAVE_TRACE : KF_WAVE;
 }
+static KernelFamily plan_family(const mcsas_plan *pl) { return plan_family(pl, pl->trace_capacity > 0); }
 static int resolve_kernel(const mcsas_plan *pl, KernelFamily family, bool given, KernelRef *k) {
-    static const char *const name[KF_COUNT] = {"", "batch ", "", "q-split ", "pipeline ", "traced ", "traced q-split "};
+    const FamilyInfo &f = KERNEL_FAMILY[family];
     const int model = pl->prob.model_id;
     const bool flag = family == KF_PIPE_TICK ? pl->pipe.g.rowq != 0 : pl->use_cache != 0;
     *k = KernelRef{};
-    const bool q_split = family == KF_WIDE || family == KF_WIDE_TRACE;
-    k->block = family == KF_PIPE_TICK ? PIPE_BLOCK : (family == KF_WG || q_split ? WAVE * pl->waves : WAVE);
-    k->arg2 = family == KF_WG ? KernelRef::ARG2_WG : (q_split ? KernelRef::ARG2_Q3INV : KernelRef::ARG2_NONE);
-    k->trace = family == KF_WAVE_TRACE || family == KF_WIDE_TRACE;
+    k->block = family_block(family, pl->waves); k->arg2 = f.arg2; k->trace = f.trace;
     if (is_plugin_model(model)) {
         if (pl->plugin_fn && family == plan_family(pl) && !k->trace && !given) { k->plugin = pl->plugin_fn; return MCSAS_OK; }   // (looked up when the plan was made)
         return plugin_chain_function(model, family, pl->qpl, flag, given, &k->plugin);                           // (compiled on first use of this q count)
     }
     KernelLookup *const lookup = model >= 0 && model < MCSAS_MODEL_COUNT ? BUILTIN[model][family][given] : nullptr;
     k->entry = lookup ? lookup(pl->qpl, flag) : nullptr;
-    if (!k->entry) return fail(MCSAS_EINVAL, "%sno %s%skernel for model %d qpl %d", family == KF_WAVE_BATCH ? "launch_batch: " : "", name[family], given ? "start " : "", model, pl->qpl);
+    if (!k->entry) return fail(MCSAS_EINVAL, "%sno %s%skernel for model %d qpl %d", family == KF_WAVE_BATCH ? "launch_batch: " : "", f.word, given ? "start " : "", model, pl->qpl);
     return MCSAS_OK;
 }
 // the kernel a launch of the plan takes now
@@ -413,6 +350,14 @@ static int raise_lds_limit(const KernelRef &k, size_t lds) {
     return MCSAS_OK;
 }
 
+// waits for every launch of the plan still in flight, slot by slot; the first error, after every slot was waited for
+static hipError_t wait_for_slots(mcsas_plan *pl) {
+    hipError_t first = hipSuccess;
+    for (mcsas_plan::Slot &sl : pl->slots)
+        if (sl.launched && sl.ev1) { const hipError_t e = hipEventSynchronize(sl.ev1); if (first == hipSuccess) first = e; }
+    return first;
+}
+
 extern "C" void mcsas_hip_plan_destroy(mcsas_plan *pl) {
     if (!pl) return;
     // (nothing of this plan may still be running when its memory goes back to the cache: hipFree used to wait, the cache does not)
@@ -422,8 +367,7 @@ extern "C" void mcsas_hip_plan_destroy(mcsas_plan *pl) {
         (void)hipDeviceSynchronize();
         (void)hipGetLastError();
     }
-    for (mcsas_plan::Slot &sl : pl->slots)
-        if (sl.launched && sl.ev1) (void)hipEventSynchronize(sl.ev1);
+    (void)wait_for_slots(pl);
     pl->pool.release();                 // every device array of the plan
     cached_host_free(pl->h_stop, sizeof(int32_t), hipHostMallocMapped);
     for (int i = 0; i < mcsas_plan::RING; ++i)
@@ -438,177 +382,7 @@ extern "C" void mcsas_hip_plan_destroy(mcsas_plan *pl) {
     delete pl;
 }
 
-// MCSAS_EXEC_AUTO, rows without an integral: nearest swept shape in (log q slots, log contributions), rates interpolated
-// linearly in the repetition count, modes that cannot run the shape left out
-static int auto_mode_light(int qpad, int n_contrib, double reps, bool pipe_ok, bool wg_ok) {
-    if (reps < (double)auto_reps[0]) return pipe_ok ? MCSAS_EXEC_PIPELINE : (wg_ok ? MCSAS_EXEC_WORKGROUP : MCSAS_EXEC_WAVE);
-    int iq = 0, in = 0;
-    for (int i = 1; i < AUTO_NQ; ++i) if (std::fabs(std::log((double)qpad / auto_qpad[i])) < std::fabs(std::log((double)qpad / auto_qpad[iq]))) iq = i;
-    for (int i = 1; i < AUTO_NN; ++i) if (std::fabs(std::log((double)n_contrib / auto_ncontrib[i])) < std::fabs(std::log((double)n_contrib / auto_ncontrib[in]))) in = i;
-    int ir = 0;
-    while (ir + 2 < AUTO_NR && reps >= (double)auto_reps[ir + 1]) ++ir;
-    double f = (reps - auto_reps[ir]) / (double)(auto_reps[ir + 1] - auto_reps[ir]);
-    f = f < 0. ? 0. : (f > 1. ? 1. : f);
-    const float (&a)[3] = auto_rate[iq][in][ir], (&b)[3] = auto_rate[iq][in][ir + 1];
-    const bool ok[3] = {true, wg_ok, pipe_ok};
-    static const int modes[3] = {MCSAS_EXEC_WAVE, MCSAS_EXEC_WORKGROUP, MCSAS_EXEC_PIPELINE};
-    int best = 0; double best_rate = -1.;
-    for (int m = 0; m < 3; ++m) {
-        if (!ok[m] || a[m] <= 0.f || b[m] <= 0.f) continue;
-        const double r = a[m] + f * (b[m] - a[m]);
-        if (r > best_rate) { best_rate = r; best = m; }
-    }
-    return modes[best];
-}
-
 // ------------------------------------------------------------------------------ plan creation
-static int validate_problem(const mcsas_problem *p) {
-    if (p->struct_size != sizeof(mcsas_problem))
-        return fail(MCSAS_EINVAL, "mcsas_problem size %u, library expects %zu (ABI mismatch)", p->struct_size, sizeof(mcsas_problem));
-#ifndef MCSAS_TUNING
-    if (p->reserved0 != 0) return fail(MCSAS_EINVAL, "mcsas_problem.reserved0 must be 0 (it is %d)", p->reserved0);
-#endif
-    if (p->nq < 1 || !p->q || !p->intensity || !p->sigma) return fail(MCSAS_EINVAL, "nq/q/intensity/sigma missing");
-    if (p->n_contrib < 1 || p->n_reps < 1) return fail(MCSAS_EINVAL, "n_contrib and n_reps must be >= 1");
-    if (p->n_active < 1) return fail(MCSAS_EINVAL, "a plan needs an active parameter (mcsas_hip_analyse answers the no-active-parameter case itself)");
-    if (p->max_iter < 0 || p->max_retries < 0) return fail(MCSAS_EINVAL, "max_iter/max_retries negative");
-    if (p->replay_stream && p->replay_len < 1) return fail(MCSAS_EINVAL, "replay_len must be >= 1");
-    return MCSAS_OK;
-}
-
-// what the pipeline's tuning word asks for; all zero (automatic) in the release library
-struct TuneWord { int rpw = 0, sub = 0, gram_global = 0, eager = 0; };
-static TuneWord tune_word(const mcsas_problem *p) {
-    TuneWord t;
-#ifdef MCSAS_TUNING
-    // measurement build (make tuning): mcsas_problem.reserved0 is the tuning / ablation word of the pipeline mode —
-    // bits 8-11 rows per producer wave (0 = automatic), 12-15 cap on the scan sub-window in units of 8 steps, 16 every
-    // proposal's `new` row stored and row slots swapped on acceptance (no lazy re-evaluation of stale rows), 18 the overlapped
-    // producer (Gram MFMAs of sub-window s between the rows of s + 1, operands from HBM/L2), 19-20 row shares of a SIMD's two
-    // producer waves, 7 XCD-aware block map; bits 0-6 switch stages OFF and give invalid results
-    t.rpw = (p->reserved0 >> 8) & 15; t.sub = (p->reserved0 >> 12) & 15; t.gram_global = (p->reserved0 >> 18) & 1; t.eager = (p->reserved0 >> 16) & 1;
-#else
-    (void)p;
-#endif
-    return t;
-}
-
-// doubles of model tables a block of `waves_per_block` waves keeps in LDS: the shared table and one row scratch per wave
-static int table_doubles_block(int model_id, int int_div, int waves_per_block) {
-    return table_doubles_host(model_id, int_div) + waves_per_block * rowtab_doubles_host(model_id, int_div);
-}
-
-// How a problem runs: q slots per lane, execution mode, waves per chain, the geometry of the speculative modes and the rows of
-// the intensity cache (before the spare row of alloc_rows).  A pure function of its arguments — the caller asks the device for its
-// CU count and, where MCSAS_EXEC_AUTO decides, for its free memory (SIZE_MAX: not known, nothing is ruled out by it).
-struct PlanShape {
-    int qpl = 1, qpad = 0;
-    bool wide = false;
-    int waves = 1, mode = MCSAS_EXEC_WAVE, cache_rows = 0;
-    WgGeom wg{};
-    PipeGeom pipe{};
-};
-static int decide_shape(const mcsas_problem *p, const ModelArgs &margs, int n_cus, size_t free_bytes, const TuneWord &tw, PlanShape *s) {
-    *s = PlanShape{};
-    // q slots per lane: power of two so the kernels are fully unrolled
-    int qpl = 1;
-    while (qpl * WAVE < p->nq && qpl < 64) qpl *= 2;
-    // up to 1024 q-points every execution mode has kernels (q slots per lane 1..16).  More (un-binned data, nBin = 0):
-    // one workgroup per chain with the q-points split over up to 8 waves (chain_wide.h; 8 / 16 / 32 slots per lane:
-    // up to 4096 / 8192 / 16384 q-points) — MCSAS_EXEC_WORKGROUP, and what MCSAS_EXEC_AUTO picks; up to 4096 q-points
-    // MCSAS_EXEC_WAVE still runs one wavefront per chain with 32 / 64 slots per lane
-    const bool wide_q = p->nq > Q_MAX_WINDOW;
-    const bool wide = runs_q_split(p->exec_mode, p->waves_per_chain, p->nq);
-    int wide_waves = 0;
-    if (wide_q) {
-        if (p->exec_mode == MCSAS_EXEC_PIPELINE) return fail(MCSAS_EINVAL, "nq %d > %d: the pipeline has no kernels for it (exec_mode 0, 1 or 2)", p->nq, Q_MAX_WINDOW);
-        if (p->nq > Q_MAX_SPLIT) return fail(MCSAS_EINVAL, "nq %d > %d is not supported", p->nq, Q_MAX_SPLIT);
-        if (!wide && p->nq > Q_MAX_WAVE) return fail(MCSAS_EINVAL, "nq %d > %d runs one workgroup per chain only (exec_mode 0 or 2)", p->nq, Q_MAX_WAVE);
-        if (wide) {
-            for (qpl = 8; qpl * WAVE * WIDE_MAX_WAVES < p->nq;) qpl *= 2;               // 8 / 16 / 32 slots per lane
-            wide_waves = (p->nq + qpl * WAVE - 1) / (qpl * WAVE);
-        }
-    }
-    const int qpad = wide ? qpl * WAVE * wide_waves : qpl * WAVE;
-    if (int rc = SmearDev::check(p)) return rc;
-    // rows that cost a numerical integration each (2: and whose cost varies with the parameter set — pipe_layout.h, pipe_geometry)
-    const int heavy_rows = std::max(model_traits(p->model_id).row_class, SmearDev::active(p) ? 1 : 0);
-    const int contrib_doubles = model_traits(p->model_id).contrib_doubles;
-    auto tabd = [&](int waves_per_block) { return table_doubles_block(p->model_id, margs.int_div, waves_per_block); };
-    const int N = p->n_contrib;
-    // execution mode (results do not depend on it)
-    int mode = p->exec_mode;
-    int waves = p->waves_per_chain;
-    if (is_plugin_model(p->model_id) && wide_q && !wide)
-        return fail(MCSAS_EINVAL, "model plug-ins: more than 1024 q-points run one workgroup per chain only (exec_mode 0 or 2; nq %d, exec_mode %d asked)", p->nq, p->exec_mode);
-    if (mode == MCSAS_EXEC_AUTO) {
-        if (waves == 1) mode = MCSAS_EXEC_WAVE;
-        else if (waves > 1) mode = MCSAS_EXEC_WORKGROUP;
-        else {
-            PipeGeom pg; WgGeom wgm;
-            bool pipe_ok = pipe_geometry(p->nq, N, tabd(PIPE_BLOCK / 64), heavy_rows, tw.rpw, tw.sub, tw.gram_global, tw.eager, p->n_reps, n_cus, &pg, contrib_doubles) == 0;
-            bool wg_ok = !wide_q && wg_geometry(p->nq, N, tabd(WG_MAX_WAVES), WG_MAX_WAVES, &wgm) == 0;
-            // MCSAS_EXEC_AUTO never picks a mode whose working set does not fit the device: the speculative modes
-            // NEED their row cache (N + 2 windows of rows per chain) and the pipeline its window buffers on top (d rows, Gram blocks,
-            // scalars, proposals: 2 Kb (qpad + W + 4 + P) doubles per chain) — against half of what is free, the same rule the
-            // allocation (alloc_rows) applies; one wavefront per chain runs without a cache when it must.  An explicitly requested
-            // mode still fails with MCSAS_ENOMEM.
-            if (free_bytes != SIZE_MAX) {
-                const double Rd = (double)p->n_reps, row = 8.0 * (double)qpad, fr = (double)free_bytes;
-                if (pipe_ok) {
-                    const double need = Rd * (((double)N + 2.0 * pg.kb + 1.0) * row
-                                              + 2.0 * pg.kb * (row + 8.0 * (pg.w + 4 + MCSAS_MAX_ACTIVE) + 4.0));
-                    if (need >= 0.5 * fr) pipe_ok = false;
-                }
-                if (wg_ok && Rd * ((double)N + 2.0 * wgm.window + 1.0) * row >= 0.5 * fr) wg_ok = false;
-            }
-            if (!heavy_rows) {
-                // rows without an integral: the mode with the highest MEASURED rate at the nearest swept shape
-                // (auto_table.h: 128..1024 q slots x 200..1000 contributions x 64..3000 repetitions on a 256-CU MI355X;
-                // profiles/r03_mode_sweep*.jsonl).  Fewer than 64 chains: the pipeline wins at every swept shape (1, 10, 50
-                // repetitions).  A device with another CU count is asked at the repetition count that loads it the same.
-                mode = auto_mode_light(qpad, N, (double)p->n_reps * 256.0 / (double)n_cus, pipe_ok, wg_ok);
-            } else {
-                // Rows that cost an integral each: the pipeline at every chain count, since its producer waves pull the rows from a
-                // queue (round 4, tools/sweep_heavy_modes2.sh, profiles/r04_heavy_modes.txt; steps/s pipeline | one wavefront per chain:
-                // cylinders 5.2e6 | 1.3e6 at 300 chains, 6.0e6 | 3.6e6 at 2048, 5.7e6 | 4.4e6 at 4096; Kholodenko 4.4e6 | 0.9e6 at 300,
-                // 5.2e6 | 4.8e6 at 2048, 4.7e6 | 4.5e6 at 4096; core-shell ellipsoids 2.5e6 | 0.7e6 at 300 chains x 1000 steps,
-                // 3.8e6 | 3.6e6 at 2048 x 3000; the workgroup mode in between at best).  Where the pipeline's geometry does not fit
-                // (fewer than 16 contributions), the older rule: one wavefront per chain from where the chains alone fill the
-                // SIMDs, a workgroup per chain below.  Units of a 256-CU device.
-                const double r_eff = (double)p->n_reps * 256.0 / (double)n_cus;
-                if (pipe_ok) mode = MCSAS_EXEC_PIPELINE;
-                else if (r_eff >= 1024.) mode = MCSAS_EXEC_WAVE;
-                else if (wg_ok) mode = MCSAS_EXEC_WORKGROUP;
-                else mode = MCSAS_EXEC_WAVE;
-            }
-        }
-    }
-    if (wide) { mode = MCSAS_EXEC_WORKGROUP; waves = wide_waves; }
-    else if (wide_q) mode = MCSAS_EXEC_WAVE;
-    if (mode == MCSAS_EXEC_WORKGROUP && waves < 2) waves = WG_MAX_WAVES;
-    if (mode != MCSAS_EXEC_WORKGROUP) waves = 1;
-    if (mode < MCSAS_EXEC_WAVE || mode > MCSAS_EXEC_PIPELINE) return fail(MCSAS_EINVAL, "exec_mode %d", mode);
-
-    // per-contribution intensity rows: the speculative kernels add two windows of spare row slots
-    int cache_rows = N;
-    if (wide) {
-        // q-split workgroup: no speculation, rows [N][qpad] like the wave kernel
-    } else if (mode == MCSAS_EXEC_WORKGROUP) {
-        if (wg_geometry(p->nq, N, tabd(waves), waves, &s->wg))
-            return fail(MCSAS_EINVAL, "workgroup kernel: needs 2*window <= n_contrib and the window in LDS (nq=%d, n_contrib=%d, waves=%d)", p->nq, N, waves);
-        cache_rows = N + 2 * s->wg.window;
-    } else if (mode == MCSAS_EXEC_PIPELINE) {
-        if (const int rcg = pipe_geometry(p->nq, N, tabd(PIPE_BLOCK / 64), heavy_rows, tw.rpw, tw.sub, tw.gram_global, tw.eager, p->n_reps, n_cus, &s->pipe, contrib_doubles)) {
-            if (rcg == 2) return fail(MCSAS_EINVAL, "pipeline: the window's row buffers / proposal records do not fit the 160 KB of LDS (nq=%d, n_contrib=%d)", p->nq, N);
-            return fail(MCSAS_EINVAL, "pipeline: needs n_contrib >= 16 and nq <= 1024 (nq=%d, n_contrib=%d)", p->nq, N);
-        }
-        cache_rows = N + 2 * s->pipe.kb;
-    }
-    s->qpl = qpl; s->qpad = qpad; s->wide = wide; s->waves = waves; s->mode = mode; s->cache_rows = cache_rows;
-    return MCSAS_OK;
-}
-
 // the padded data vectors on the device
 static int upload_data(mcsas_plan *pl, const mcsas_problem *p, int qpad) {
     ChainArgs &a = pl->args;
@@ -801,19 +575,6 @@ extern "C" int mcsas_hip_plan_reseed(mcsas_plan *pl, uint64_t seed, int32_t rep_
     return MCSAS_OK;
 }
 
-// the first non-finite value of the columns [first, first + R) of start[N][P][stride], or MCSAS_OK
-int check_start_finite(const char *who, const double *start, size_t N, size_t P, size_t stride, size_t first, size_t R) {
-    for (size_t i = 0; i < N * P; ++i)
-        for (size_t r = 0; r < R; ++r)
-            if (!std::isfinite(start[i * stride + first + r]))
-                return fail(MCSAS_EINVAL, "%s: start[%zu][%zu][%zu] (index %zu) is not finite", who, i / P, i % P, first + r, i * stride + first + r);
-    return MCSAS_OK;
-}
-
-const char *exec_mode_name(int mode) {
-    return mode == MCSAS_EXEC_WAVE ? "MCSAS_EXEC_WAVE" : mode == MCSAS_EXEC_WORKGROUP ? "MCSAS_EXEC_WORKGROUP" : mode == MCSAS_EXEC_PIPELINE ? "MCSAS_EXEC_PIPELINE" : "MCSAS_EXEC_AUTO";
-}
-
 // The set every later launch of the plan starts its repetitions from (include/mcsas_hip.h), kept on the device in the layout of rset;
 // a launch copies it into its slot's rset on the launch stream and runs the started form of the plan's kernel, whose first attempt reads
 // it where the cold one generates a set (chain_body.inc: GIVEN).  The wavefront-per-chain and the q-split kernels have such a form; the
@@ -833,9 +594,7 @@ extern "C" int mcsas_hip_plan_set_start(mcsas_plan *pl, const double *start, int
         for (size_t i = 0; i < N * P; ++i) hr[r * N * P + i] = start[i * (size_t)rep_stride + (size_t)rep_first + r];
     DeviceGuard dev_guard;
     HIPCHK(hipSetDevice(pl->dev));
-    // (a launch still in flight may not have made its copy of the previous start yet)
-    for (mcsas_plan::Slot &sl : pl->slots)
-        if (sl.launched && sl.ev1) HIPCHK(hipEventSynchronize(sl.ev1));
+    HIPCHK(wait_for_slots(pl));                           // (a launch still in flight may not have made its copy of the previous start yet)
     if (!pl->d_start) HIPCHK(pl->pool.get(&pl->d_start, sizeof(double) * hr.size()));
     HIPCHK(hipMemcpy(pl->d_start, hr.data(), sizeof(double) * hr.size(), hipMemcpyHostToDevice));
     pl->has_start = true;
@@ -849,8 +608,6 @@ static int enqueue_start(mcsas_plan *pl, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------ the trace of a wave or q-split plan (include/mcsas_hip.h)
-// bytes of one slot's trace block: step, chisq and values of `capacity` moves per repetition
-static size_t trace_record_bytes(size_t R, size_t capacity, size_t P) { return R * capacity * (16 + 8 * P); }
 static void drop_slot_trace(mcsas_plan *pl, mcsas_plan::Slot &sl) {
     if (sl.d_trace) cached_dev_free(sl.d_trace, sl.trace_bytes, pl->dev);
     sl.d_trace = nullptr; sl.trace_bytes = 0; sl.trace = TraceArgs{}; sl.traced = false;
@@ -859,14 +616,13 @@ static void drop_slot_trace(mcsas_plan *pl, mcsas_plan::Slot &sl) {
 static int make_slot_trace(mcsas_plan *pl, mcsas_plan::Slot &sl) {
     if (sl.d_trace && sl.trace.capacity == pl->trace_capacity) return MCSAS_OK;
     drop_slot_trace(pl, sl);
-    const size_t R = pl->prob.n_reps, K = (size_t)pl->trace_capacity, P = pl->prob.n_active;
-    const size_t bytes = (trace_record_bytes(R, K, P) + 8 * R + 255) / 256 * 256;
-    HIPCHK(cached_dev_malloc((void **)&sl.d_trace, bytes));
-    sl.trace_bytes = bytes;
-    sl.trace.step = (int64_t *)sl.d_trace;
-    sl.trace.chisq = (double *)(sl.d_trace + 8 * R * K);
-    sl.trace.values = (double *)(sl.d_trace + 16 * R * K);
-    sl.trace.chisq0 = (double *)(sl.d_trace + (16 + 8 * P) * R * K);
+    const TraceLayout at(pl->prob.n_reps, (size_t)pl->trace_capacity, pl->prob.n_active);
+    HIPCHK(cached_dev_malloc((void **)&sl.d_trace, at.dev_bytes));
+    sl.trace_bytes = at.dev_bytes;
+    sl.trace.step = (int64_t *)(sl.d_trace + at.step);
+    sl.trace.chisq = (double *)(sl.d_trace + at.chisq);
+    sl.trace.values = (double *)(sl.d_trace + at.values);
+    sl.trace.chisq0 = (double *)(sl.d_trace + at.chisq0);
     sl.trace.capacity = pl->trace_capacity; sl.trace.pad = 0;
     return MCSAS_OK;
 }
@@ -878,34 +634,20 @@ extern "C" int mcsas_hip_plan_set_trace(mcsas_plan *pl, int32_t capacity) {
         if (!takes_start_and_trace(pl))
             return fail(MCSAS_EINVAL, "set_trace: the plan runs in exec_mode %d (%s); a trace needs exec_mode = MCSAS_EXEC_WAVE (%d)", pl->mode, exec_mode_name(pl->mode), MCSAS_EXEC_WAVE);
         const size_t R = pl->prob.n_reps, P = pl->prob.n_active;
-        if ((size_t)capacity > TRACE_MAX_BYTES / (R * (16 + 8 * P)))
-            return fail(MCSAS_EINVAL, "set_trace: %d repetitions x capacity %d x %zu bytes per move exceed 2 GiB", pl->prob.n_reps, (int)capacity, 16 + 8 * P);
+        if (TraceLayout::too_large(R, (size_t)capacity, P))
+            return fail(MCSAS_EINVAL, "set_trace: %d repetitions x capacity %d x %zu bytes per move exceed 2 GiB", pl->prob.n_reps, (int)capacity, TraceLayout(R, 0, P).move_bytes);
     }
     DeviceGuard dev_guard;
     HIPCHK(hipSetDevice(pl->dev));
     if (capacity != pl->trace_capacity) {
-        // (a launch still in flight writes the blocks that go back to the cache here)
-        for (mcsas_plan::Slot &sl : pl->slots)
-            if (sl.launched && sl.ev1) HIPCHK(hipEventSynchronize(sl.ev1));
+        HIPCHK(wait_for_slots(pl));                       // (a launch still in flight writes the blocks that go back to the cache here)
         for (mcsas_plan::Slot &sl : pl->slots) drop_slot_trace(pl, sl);
     }
-    if (capacity > 0) {                                   // a shape without a traced kernel is refused here, as the plan's own is at its creation
-        const int32_t before = pl->trace_capacity;
-        pl->trace_capacity = capacity;
+    if (capacity > 0 && !is_plugin_model(pl->prob.model_id)) {   // a shape without a traced kernel is refused here, as the plan's own is at its creation
         KernelRef k;
-        const int rc = is_plugin_model(pl->prob.model_id) ? MCSAS_OK : resolve_kernel(pl, plan_family(pl), pl->has_start, &k);
-        if (rc) { pl->trace_capacity = before; return rc; }
+        if (int rc = resolve_kernel(pl, plan_family(pl, true), pl->has_start, &k)) return rc;
     }
     pl->trace_capacity = capacity;
-    return MCSAS_OK;
-}
-
-int check_trace_arrays(const char *who, const mcsas_trace *tr) {
-    if (!tr) return fail(MCSAS_EINVAL, "%s: trace is NULL", who);
-    if (tr->struct_size != sizeof(mcsas_trace)) return fail(MCSAS_EINVAL, "%s: mcsas_trace size %u, library expects %zu", who, tr->struct_size, sizeof(mcsas_trace));
-    if (tr->capacity < 1) return fail(MCSAS_EINVAL, "%s: trace capacity %d (>= 1)", who, (int)tr->capacity);
-    if (!tr->count || !tr->chisq0 || !tr->step || !tr->chisq || !tr->values)
-        return fail(MCSAS_EINVAL, "%s: trace array %s is NULL", who, !tr->count ? "count" : !tr->chisq0 ? "chisq0" : !tr->step ? "step" : !tr->chisq ? "chisq" : "values");
     return MCSAS_OK;
 }
 
@@ -923,23 +665,9 @@ extern "C" int mcsas_hip_plan_fetch_trace(mcsas_plan *pl, int32_t slot, mcsas_tr
     const size_t R = pl->prob.n_reps, K = (size_t)pl->trace_capacity, P = pl->prob.n_active;
     std::vector<ChainOut> ho(R);
     HIPCHK(hipMemcpy(ho.data(), s.d_out, sizeof(ChainOut) * R, hipMemcpyDeviceToHost));
-    std::vector<char> h(trace_record_bytes(R, K, P) + 8 * R);
+    std::vector<char> h(TraceLayout(R, K, P).host_bytes);
     HIPCHK(hipMemcpy(h.data(), s.d_trace, h.size(), hipMemcpyDeviceToHost));
-    const int64_t *hstep = (const int64_t *)h.data();
-    const double *hchi = (const double *)(h.data() + 8 * R * K), *hval = (const double *)(h.data() + 16 * R * K);
-    const double *hchi0 = (const double *)(h.data() + (16 + 8 * P) * R * K);
-    const double nan = std::nan("");
-    // [rep][capacity] -> the caller's [capacity][n_reps]; what lies behind the last attempt's moves is an earlier attempt's or nothing
-    for (size_t r = 0; r < R; ++r) {
-        const int64_t moves = ho[r].num_moves;
-        tr->count[r] = moves; tr->chisq0[r] = hchi0[r];
-        for (size_t i = 0; i < K; ++i) {
-            const bool kept = (int64_t)i < moves;
-            tr->step[i * R + r] = kept ? hstep[r * K + i] : -1;
-            tr->chisq[i * R + r] = kept ? hchi[r * K + i] : nan;
-            for (size_t p = 0; p < P; ++p) tr->values[(i * P + p) * R + r] = kept ? hval[(r * K + i) * P + p] : nan;
-        }
-    }
+    trace_transpose(h.data(), R, K, P, ho.data(), tr);
     return MCSAS_OK;
 }
 
@@ -969,16 +697,7 @@ static int pipeline_launch(mcsas_plan *pl, const KernelRef &tick, hipStream_t st
         void *ka[] = {(void *)&pl->d_pipeargs};
         HIPCHK(hipLaunchKernel(reset, dim3((R + 63) / 64), dim3(64), ka, 0, st));
     }
-    // worst case: every attempt runs to max_iter
-    // (saturating: max_iter may be 2^62 and a product of two such numbers must not wrap to a negative budget)
-    const long long TICK_CAP = 2000000000LL;
-    const long long win_per_attempt = (long long)(pl->prob.max_iter / Kb) + 4;
-    const long long attempts = (long long)pl->prob.max_retries + 1;
-    // one attempt: its last window (index ceil(max_iter / Kb) - 1) is scanned at tick ceil(max_iter / Kb), exactly; with
-    // retries the schedule depends on when attempts end, so the bound is generous and the host leaves when all chains are done
-    const long long one_attempt = std::min((long long)((pl->prob.max_iter + Kb - 1) / Kb) + 1, TICK_CAP);
-    const long long max_ticks = attempts == 1 ? one_attempt
-                              : ((win_per_attempt >= TICK_CAP / attempts) ? TICK_CAP : std::min(attempts * win_per_attempt + 4, TICK_CAP));
+    const long long max_ticks = pipeline_tick_budget(pl->prob.max_iter, pl->prob.max_retries, Kb);     // worst case: every attempt runs to max_iter
     // scan blocks + producer blocks (chain-major; 8 XCD classes of ceil(R/8) chains each with diagnostic bit 128)
     const dim3 grid((MCSAS_TUNE_BITS(pl->args) & 128) ? R + 8 * ((R + 7) / 8) * pa.g.prod_blocks_y : R + R * pa.g.prod_blocks_y);
     PipeHot hot{};
@@ -1032,8 +751,8 @@ extern "C" int mcsas_hip_plan_launch_slot(mcsas_plan *pl, void *hip_stream, int3
         if (k.trace) { if (int rc = make_slot_trace(pl, s)) return rc; }
         void *kargs[3] = {(void *)&pl->args, nullptr, nullptr};
         int nk = 1;
-        if (k.arg2 == KernelRef::ARG2_WG) kargs[nk++] = (void *)&pl->wg;
-        else if (k.arg2 == KernelRef::ARG2_Q3INV) kargs[nk++] = (void *)&pl->d_q3inv;
+        if (k.arg2 == FamilyInfo::ARG2_WG) kargs[nk++] = (void *)&pl->wg;
+        else if (k.arg2 == FamilyInfo::ARG2_Q3INV) kargs[nk++] = (void *)&pl->d_q3inv;
         if (k.trace) kargs[nk++] = (void *)&s.trace;
         if (int rc = raise_lds_limit(k, pl->lds_bytes)) return rc;
         HIPCHK(hipEventRecord(s.ev0, st));

@@ -274,3 +274,50 @@ def _quickstart_algo(g, reps, seed):
     algo.model = m
     algo.data = mcsas_amd.SASData(g["data_q"], g["data_I"], g["data_sigma"], f_limit=g["data_f_limit"])
     return algo, m
+
+
+# ---- what plan creation decides (csrc/host_decide.hip: decide_shape), replayed on the GPU through engine.Plan (test_plan_lifecycle_gpu.py)
+# and without one through the stand-alone check (test_plan_decisions_host.py), against tests/golden/plan_shapes_mi355x.json
+PLAN_SHAPES_GOLDEN = os.path.join(G, "plan_shapes_mi355x.json")
+PLAN_SHAPE_RANGES = {"sphere": ([2e-9], [3e-7]), "cyl_aspect": ([1e-9, 0.5], [1e-7, 20.0]), "gausschain": ([1e-9, 1e-9], [1e-7, 1e-7])}
+_A, _W, _G, _P = engine.EXEC_AUTO, engine.EXEC_WAVE, engine.EXEC_WORKGROUP, engine.EXEC_PIPELINE
+# (id, model tag, nq, contributions, repetitions, exec mode, waves_per_chain, cache_intensities, variant) — every branch of the
+# shape and mode decision, then its refusals.  All working sets stay under 1 GB: the free-memory gate decides no row.
+PLAN_SHAPE_CASES = (
+    [("auto_r%d" % r, "sphere", 100, 200, r, _A, 0, -1, None) for r in (1, 64, 300, 3000)]
+    + [("wave_cache%+d" % c, "sphere", 100, 200, 6, _W, 0, c, None) for c in (-1, 0, 1)]
+    + [("wg_waves%d" % w, "sphere", 100, 200, 6, _G, w, -1, None) for w in (0, 2, 4)]
+    + [("pipeline", "sphere", 100, 200, 6, _P, 0, -1, None)]
+    + [("auto_q%d" % nq, "sphere", nq, 200, 6, _A, 0, -1, None) for nq in (1000, 1500, 5000)]
+    + [("wave_q1500", "sphere", 1500, 200, 6, _W, 0, -1, None),
+       ("cyl_48x4", "cyl_aspect", 64, 48, 4, _A, 0, -1, None),
+       ("cyl_8x4", "cyl_aspect", 64, 8, 4, _A, 0, -1, None),
+       ("cyl_8x2000", "cyl_aspect", 64, 8, 2000, _A, 0, -1, None),
+       ("smeared_auto", "sphere", 100, 200, 6, _A, 0, -1, "smear"),
+       ("plugin_auto", "gausschain", 100, 200, 6, _A, 0, -1, "plugin"),
+       ("plugin_wave", "gausschain", 100, 200, 6, _W, 0, -1, "plugin"),
+       # refusals
+       ("no_pipeline_n8", "sphere", 100, 8, 6, _P, 0, -1, None),
+       ("no_pipeline_q1500", "sphere", 1500, 200, 6, _P, 0, -1, None),
+       ("no_wave_q5000", "sphere", 5000, 200, 6, _W, 0, -1, None),
+       ("no_q20000", "sphere", 20000, 200, 6, _A, 0, -1, None),
+       ("no_wg_n2", "sphere", 100, 2, 6, _G, 0, -1, None),
+       ("no_plugin_wave_q1500", "gausschain", 1500, 200, 6, _W, 0, -1, "plugin")])
+
+
+def plan_shape_problem(case):
+    """The case as what engine.Plan and engine.HipProblem take: (model, q, I, sigma, settings, smear)."""
+    from bench import synthetic_data
+    _, tag, nq, n, reps, mode, waves, cache, variant = case
+    q, I, sig = synthetic_data(nq)
+    lo, hi = PLAN_SHAPE_RANGES[tag]
+    m, _ = make_models(tag, lo, hi, **({"intDiv": 20.} if tag == "cyl_aspect" else {}))
+    smear = None
+    if variant == "plugin":
+        plugin_twin(m, tag)
+    if variant == "smear":
+        d, _ = product_smearing("trapezoid", False, 15, q, I, sig, umbra=2e-3 * q.max(), penumbra=4e-3 * q.max())
+        smear = d.smearArgs(m)
+    st = engine.Settings(n_contrib=n, n_reps=reps, max_iter=100, max_retries=0, seed=1, exec_mode=mode, waves_per_chain=waves,
+                         cache_intensities=cache)
+    return m, q, I, sig, st, smear

@@ -1,0 +1,96 @@
+"""What the library decides without a device (csrc/host_decide.hip) as a stand-alone host program under AddressSanitizer and
+UndefinedBehaviorSanitizer: tests/plan_decisions_check.hip, compiled here together with that unit and run as a child process.
+No GPU, nothing loaded into this process.  The recorded plan shapes (tests/golden/plan_shapes_mi355x.json) are replayed through
+decide_shape with the recording's CU count; the free-memory gate of MCSAS_EXEC_AUTO, which no device of the library's own kind
+exercises, is checked at its threshold; the family table, the trace block's layout and the tick budget against values worked
+out by hand."""
+import json
+import os
+import shutil
+import subprocess
+
+import pytest
+
+from mcsas_amd import engine
+from helpers import PLAN_SHAPE_CASES, PLAN_SHAPES_GOLDEN, make_models, plan_shape_problem
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+CSRC = os.path.join(HERE, "..", "mcsas_amd", "csrc")
+# the rows that need the run-time compiler: they stay with tests/test_plan_lifecycle_gpu.py
+PLUGIN_ROWS = {"plugin_auto", "plugin_wave", "no_plugin_wave_q1500"}
+MODE_NAMES = {1: "wave", 2: "workgroup", 3: "pipeline"}
+
+
+def build_check(tmp_path):
+    """The check program, built; a function that runs it with arguments and standard input and returns what it printed."""
+    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    exe = str(tmp_path / "plan_decisions_check")
+    # the Makefile's language flags; the sanitizers on the host side only, their runtimes inside the program (clang's default)
+    build = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror",
+                            "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",
+                            "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-I" + CSRC,
+                            "-o", exe, os.path.join(HERE, "plan_decisions_check.hip"), os.path.join(CSRC, "host_decide.hip")],
+                           capture_output=True, text=True)
+    if build.returncode and ("cannot find" in build.stderr or "unsupported" in build.stderr) and "san" in build.stderr:
+        pytest.skip("the compiler has no sanitizer runtimes: " + build.stderr.strip().splitlines()[-1])
+    assert build.returncode == 0, build.stderr
+
+    def run(*args, text=""):
+        r = subprocess.run([exe] + list(args), input=text, capture_output=True, text=True)
+        assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+        return r.stdout
+    return run
+
+
+def problem_line(name, m, q, I, sig, st, smear=None):
+    """The fields of the mcsas_problem that engine.HipProblem fills, as the line of text the check program reads."""
+    p = engine.HipProblem(m.setup(), q, I, sig, st, smear=smear).c
+    fields = [name, p.model_id, p.nq, p.n_contrib, p.n_reps, p.exec_mode, p.waves_per_chain, p.smear_nk, p.n_active]
+    fields += [p.active_index[c] for c in range(p.n_active)] + [repr(float(x)) for x in p.params]
+    return " ".join(str(f) for f in fields) + "\n"
+
+
+def recorded_plan_shapes(check):
+    """Every row of the recording but the three plug-in rows: mode, waves per chain, q slots per lane and window, or the refusal's
+    code and message.  (`launches` and `cached_rows` come from the device.)"""
+    rec = json.load(open(PLAN_SHAPES_GOLDEN))
+    assert rec["cu_count"] == 256                                             # (what the check program hands decide_shape)
+    cases = [c for c in PLAN_SHAPE_CASES if c[0] not in PLUGIN_ROWS]
+    assert set(c[0] for c in cases) == set(rec["rows"]) - PLUGIN_ROWS and all(c[8] == "plugin" for c in PLAN_SHAPE_CASES if c[0] in PLUGIN_ROWS)
+    out = check("shapes", text="".join(problem_line(c[0], *plan_shape_problem(c)) for c in cases))
+    got = {}
+    for line in out.splitlines():
+        name, kind, rest = line.split(" ", 2)
+        if kind == "shape":
+            mode, waves, qpl, window = (int(x) for x in rest.split())
+            got[name] = dict(exec_mode=MODE_NAMES[mode], waves_per_chain=waves, q_per_lane=qpl, window=window)
+        else:
+            code, msg = rest.split(" ", 1)
+            got[name] = dict(error_code=int(code), error="libmcsas_hip error %d: %s" % (int(code), msg))
+    assert set(got) == set(c[0] for c in cases)
+    for name, row in got.items():
+        want = {k: v for k, v in rec["rows"][name].items() if k not in ("launches", "cached_rows")}
+        assert row == want, name
+
+
+def free_memory_gate(check):
+    """The case of test_auto_mode_never_picks_a_mode_whose_working_set_does_not_fit (9000 chains of 1000 core-shell ellipsoids on
+    1024 q-points), which an MI355X with more than 290e9 bytes free skips: the pipeline just above twice its need, not at or below
+    it, one wavefront per chain at 288 GiB, the pipeline when the free memory is not known."""
+    from bench import synthetic_data
+    q, I, sig = synthetic_data(1024)
+    m, _ = make_models("ellcs", [1e-9, 2e-9, 2e-10], [1e-7, 2e-7, 1e-8])
+    st = engine.Settings(n_contrib=1000, n_reps=9000, max_iter=10, conv_crit=0.0, max_retries=0, seed=1)
+    out = check("gate", text=problem_line("gate", m, q, I, sig, st)).split()
+    assert out[0] == "ok", out
+    # twice the need lies above 288 GiB: at the card's own memory size the gate decides, as the GPU test's docstring says
+    assert 2 * int(out[2]) > 288 * 2 ** 30, out
+
+
+def test_plan_decisions_without_a_device(tmp_path):
+    check = build_check(tmp_path)
+    assert check().strip() == "ok"                      # the family table, the trace block's layout and transposition, the tick budget
+    recorded_plan_shapes(check)
+    free_memory_gate(check)

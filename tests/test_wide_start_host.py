@@ -72,14 +72,15 @@ def test_analyse_from_takes_the_workgroup_mode_beyond_1024_q():
 
 
 def test_the_new_family_is_entered_in_every_table():
-    """A kernel is (family, given): five families, one row each in the plug-in compiler's table, the started q-split kernels compiled
-    by a unit of their own, and no copy of a kernel template for the start."""
+    """A kernel is (family, given): one row per family in the table beside the enum, the started q-split kernels compiled by a unit
+    of their own, and no copy of a kernel template for the start."""
     families = re.search(r"enum\s+KernelFamily\s*\{([^}]*)\}", _code("host_internal.h")).group(1).replace(" ", "").split(",")
     assert families[-1] == "KF_COUNT" and "KF_WIDE" in families[:-1] and len(set(families)) == len(families)
     n = len(families) - 1
-    table = re.search(r"FAMILY\[KF_COUNT\]\s*=\s*\{(.*?)\};", _code("host_plugin.hip"), re.S).group(1)
-    rows = re.findall(r'\{\s*"(\w+)"\s*,\s*"([\w ]+)"\s*(?:,\s*(?:true|false)\s*)+\}', table)
+    table = re.search(r"KERNEL_FAMILY\[KF_COUNT\]\s*=\s*\{(.*?)\};", _code("host_internal.h"), re.S).group(1)
+    rows = re.findall(r'\{\s*"[\w -]*"\s*,\s*"(\w+)"\s*,\s*"([\w ]+)"\s*(?:,\s*(?:true|false)\s*)+(?:,\s*FamilyInfo::\w+\s*)+\}', table)
     assert len(rows) == n and rows[families.index("KF_WIDE")][0] == "chain_wide_kernel", rows
+    assert "FAMILY[" not in _code("host_plugin.hip") and "plugin_kernel_name(" in _code("host_plugin.hip")       # (no table of its own)
     assert len(re.findall(r"\{[^{}]*\}", table)) == n, table                    # (no row of another shape)
     assert len({key for _, key in rows}) == n                                    # (the program keys tell the families apart)
     # the built-in models: one row of lookups per family, cold and started, for every model of the list

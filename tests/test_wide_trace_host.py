@@ -16,13 +16,13 @@ from chain_cases import CSRC, MCSAS_EINVAL, MCSAS_ENODEV, MCSAS_OK, WG, _Library
 
 
 def test_the_traced_q_split_family_is_entered_in_every_table():
-    """Seven families; KF_WIDE_TRACE has its row in the plug-in compiler's table (the q-split family's shape: no flag, startable), its
+    """Seven families; KF_WIDE_TRACE has its row in the table beside the enum (the q-split family's shape: no flag, startable), its
     pair of lookups in ROW_K, a unit per model through the shared q-split table, and its Makefile rule."""
     families = re.search(r"enum\s+KernelFamily\s*\{([^}]*)\}", _code("host_internal.h")).group(1).replace(" ", "").split(",")
     assert len(families) == 8 and families[-1] == "KF_COUNT" and len(set(families)) == 8, families
     k = families.index("KF_WIDE_TRACE")
-    table = re.search(r"FAMILY\[KF_COUNT\]\s*=\s*\{(.*?)\};", _code("host_plugin.hip"), re.S).group(1)
-    rows = re.findall(r'\{\s*"(\w+)"\s*,\s*"([\w ]+)"\s*,\s*(true|false)\s*,\s*(true|false)\s*\}', table)
+    table = re.search(r"KERNEL_FAMILY\[KF_COUNT\]\s*=\s*\{(.*?)\};", _code("host_internal.h"), re.S).group(1)
+    rows = re.findall(r'\{\s*"[\w -]*"\s*,\s*"(\w+)"\s*,\s*"([\w ]+)"\s*,\s*(true|false)\s*,\s*(true|false)\s*,\s*(?:true|false)\s*(?:,\s*FamilyInfo::\w+\s*)+\}', table)
     assert len(rows) == 7 and len({key for _, key, _, _ in rows}) == 7, rows
     assert rows[k][0] == "chain_wide_trace_kernel" and rows[k][2:] == ("false", "true"), rows[k]
     assert rows[k][2:] == rows[families.index("KF_WIDE")][2:]                   # (the arguments behind <model, qpl> of its untraced twin)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: [MODELS="0 1"] tools/build_variant.sh <name> [extra hipcc flags]  -> mcsas_amd/lib/libmcsas_<name>.so from the CURRENT sources of the host
-# translation units (mcsas_hip.hip, host_plugin.hip, host_calls.hip, host_hist.hip, host_analyse.hip, host_rows.hip) and the pipeline kernels (kern_pipe.hip: chain_pipe.h and the pipe_*.h under it) of the models in MODELS (default: the sphere; the other objects are taken from build/csrc:
+# translation units (mcsas_hip.hip, host_decide.hip, host_plugin.hip, host_calls.hip, host_hist.hip, host_analyse.hip, host_rows.hip) and the pipeline kernels (kern_pipe.hip: chain_pipe.h and the pipe_*.h under it) of the models in MODELS (default: the sphere; the other objects are taken from build/csrc:
 # run `make release` first)
 set -e
 cd $(dirname $0)/../mcsas_amd/csrc
@@ -8,7 +8,7 @@ name=$1; shift
 B=../../build/csrc; V=../../build/variant_$name; mkdir -p $V
 F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -Wno-unused-value -I$B $*"
 make --no-print-directory $B/embedded_headers.inc
-HOST="mcsas_hip host_plugin host_calls host_hist host_analyse host_rows"
+HOST="mcsas_hip host_decide host_plugin host_calls host_hist host_analyse host_rows"
 for u in $HOST; do /opt/rocm/bin/hipcc $F -c -o $V/$u.o $u.hip & done
 MODELS=${MODELS:-0}
 for m in $MODELS; do /opt/rocm/bin/hipcc $F -DMCSAS_M=$m -c -o $V/kern_pipe_m$m.o kern_pipe.hip & done

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """MC steps/s of the three execution modes over (q points) x (contributions) x (repetitions), sphere model: the table
-behind MCSAS_EXEC_AUTO (mcsas_hip.hip, mode selection).  Fixed budget, convergenceCriterion 0, HIP-event time of the second
+behind MCSAS_EXEC_AUTO (host_decide.hip, mode selection).  Fixed budget, convergenceCriterion 0, HIP-event time of the second
 launch of a plan (chain initialisation included, as a user pays it).  One JSON line per point on stdout; `auto` = what
 MCSAS_EXEC_AUTO picked and delivered.  The reference's default shape (mcsasparameters.json: 300 contributions, 10
 repetitions; 100 q after the default rebinning) is in the grid."""
