@@ -4,7 +4,7 @@ The reference's models evaluate closed formulas (and, for the orientation- or co
 doubles; the kernels evaluate the same expressions in another order with fastmath.h.  Here both are held to the EXACT value of
 that discrete operation — the formula at the doubles the reference feeds it (q r rounded, the quadrature nodes numpy.linspace
 makes), evaluated in 40-digit mpmath — and each device row must lie within a bound DERIVED from the kernel's operation order by
-a running error analysis (class R): every value carries the exact (mpmath) result and a bound on what a double evaluation in the
+a running error analysis (class R of tests/exact.py): every value carries the exact (mpmath) result and a bound on what a double evaluation in the
 kernel's order may be off by,
 
     a +- b: e_a + e_b + u|a +- b|            a b: |a| e_b + |b| e_a + e_a e_b + u|a b|         u = 2^-53 (one rounding)
@@ -17,8 +17,6 @@ so a bound is the stated fastmath error plus one rounding per operation, propaga
 sphere's sin x - x cos x, for one, carries an absolute error of order u |x cos x|, not u |sin x - x cos x|.  The kernel is not
 asked to beat the reference's formula (the replays depend on evaluating the same expression), only to stay inside what that
 formula allows.  The intensities are taken at compensation exponent 0 (w = volume^0 = 1), so a row is F^2 itself."""
-import math
-
 import mpmath as mp
 import numpy as np
 import pytest
@@ -26,117 +24,17 @@ import pytest
 import mcsas_amd
 from mcsas_amd import engine
 from helpers import FakeData
+from exact import R, U, check, div_fast, fma, j1, libm1, sincos
 from test_fastmath import tan_x_zeros
 
 pytestmark = pytest.mark.gpu
 
 mp.mp.dps = 40
-U = 2.0**-53
-ULP_SINCOS, ABS_SINCOS, ULP_LIBM, ABS_J1 = 1.6, 2e-26, 2.0, 5e-16
-
-
-class R:
-    """An exact value (mpmath) and a bound on the error of its double evaluation in the kernel's order (module docstring)."""
-    __slots__ = ("v", "e")
-
-    def __init__(self, v, e=0.0):
-        self.v, self.e = mp.mpf(v), float(e)
-
-    @staticmethod
-    def _r(v):
-        return U * abs(float(v))
-
-    def __add__(self, o):
-        o = o if isinstance(o, R) else R(o)
-        v = self.v + o.v
-        return R(v, self.e + o.e + self._r(v))
-
-    def __radd__(self, o):
-        return self + o
-
-    def __sub__(self, o):
-        o = o if isinstance(o, R) else R(o)
-        v = self.v - o.v
-        return R(v, self.e + o.e + self._r(v))
-
-    def __rsub__(self, o):
-        return R(o) - self
-
-    def __neg__(self):
-        return R(-self.v, self.e)
-
-    def __mul__(self, o):
-        o = o if isinstance(o, R) else R(o)
-        v = self.v * o.v
-        return R(v, abs(float(self.v)) * o.e + abs(float(o.v)) * self.e + self.e * o.e + self._r(v))
-
-    def __rmul__(self, o):
-        return R(o) * self
-
-    def div(self, o, ulps=0.5):
-        o = o if isinstance(o, R) else R(o)
-        v = self.v / o.v
-        room = abs(float(o.v)) - o.e
-        e = (self.e + abs(float(v)) * o.e) / room if room > 0 else math.inf
-        return R(v, e + 2 * ulps * self._r(v))
-
-    def __truediv__(self, o):
-        return self.div(o)
-
-    def __rtruediv__(self, o):
-        return R(o).div(self)
-
-    def sqrt(self):
-        v = mp.sqrt(self.v)
-        lo = max(float(self.v) - self.e, 0.0)
-        return R(v, self.e / (float(v) + math.sqrt(lo)) + self._r(v) if float(v) > 0 else math.sqrt(self.e))
-
-
-def fma(a, b, c):
-    a, b, c = (x if isinstance(x, R) else R(x) for x in (a, b, c))
-    v = a.v * b.v + c.v
-    return R(v, abs(float(a.v)) * b.e + abs(float(b.v)) * a.e + a.e * b.e + c.e + R._r(v))
-
-
-def div_fast(a, b):
-    return (a if isinstance(a, R) else R(a)).div(b, ulps=1.0)
-
-
-def sincos(x, libm=None):
-    """sincos_fast (|x| < 2^20; its libm branch above) or, libm=True, the device libm's sin / cos."""
-    s, c = mp.sin(x.v), mp.cos(x.v)
-    if libm is None:
-        libm = abs(float(x.v)) >= 2.0**20
-    k, a = (ULP_LIBM, 0.0) if libm else (ULP_SINCOS, ABS_SINCOS)
-    d2 = x.e * x.e / 2
-    return (R(s, abs(float(c)) * x.e + d2 + 2 * k * R._r(s) + a), R(c, abs(float(s)) * x.e + d2 + 2 * k * R._r(c) + a))
-
-
-def j1(x):
-    v = mp.besselj(1, x.v)
-    return R(v, x.e + ABS_J1 + R._r(v))
-
-
-def libm1(f, x):
-    """a device libm function of one argument (expm1): 2 ulp, propagated through its derivative (numerically, in mpmath)."""
-    v = f(x.v)
-    return R(v, abs(float(mp.diff(f, x.v))) * x.e + 2 * 2 * R._r(v))
 
 
 def rows_of(model, q, pset):
     q = np.ascontiguousarray(q, dtype=float)
     return engine.model_calc(model.setup(FakeData(q)), q, np.ascontiguousarray(pset, dtype=float), 0.0, want_rows=True)[4]
-
-
-def check(got, ref, what):
-    """got[i] within ref[i].e of ref[i].v; returns the worst error / bound."""
-    worst = 0.0
-    for i, (g, r) in enumerate(zip(np.ravel(got), np.ravel(ref))):
-        err = abs(mp.mpf(float(g)) - r.v)
-        assert float(err) <= r.e, "%s [%d]: got %r, exact %s, error %.3g > bound %.3g" % (what, i, g, mp.nstr(r.v, 20), float(err), r.e)
-        if r.e > 0 and math.isfinite(r.e):
-            worst = max(worst, float(err) / r.e)
-    return worst
 
 
 # ------------------------------------------------------------------------------------------------- the closed-form models
