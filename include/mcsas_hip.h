@@ -429,6 +429,35 @@ int mcsas_hip_histogram_batch(int32_t n_sets, const mcsas_problem *problems, con
                               const int32_t *n_hist, const mcsas_histogram_spec *const *specs,
                               double *const *scaling, double *const *fractions, double *const *out);
 
+/* ---- McSAS.histogram() of a model whose rows the caller computes ON THE DEVICE (additive to ABI 5) ------------------------------
+ * mcsas_hip_histogram for the models of mcsas_hip_analyse_device_rows: contribs, n_hist, specs, scaling, fractions, out and the limit
+ * n_contrib <= 4096 mean what they mean there, the layouts are the same; only the rows and the per-row volume / weight / surface come
+ * from the caller's device code, a round at a time, and never cross the bus: one packed upload, per round the kernels, one packed
+ * download.  A round is a block of whole repetitions [r0, r0 + k), k = min(n_reps - r0, capacity_rows / n_contrib) (65535 at the most);
+ * row rl * n_contrib + c of the round is contribution c of repetition r0 + rl.
+ *   d_pset [capacity_rows][n_active], d_rows [capacity_rows][row_stride], d_vws [3][capacity_rows]: the CALLER's device memory on
+ *     problem->device; row_stride = nq (dense: ask mcsas_hip_histogram_rows_shape, never hard-code it).
+ *   rows_cb(user, n): d_pset[0..n) holds the round's parameter sets (activeParams() order, NOT clipped, taken from contribs[c][p][r]),
+ *     complete on the device when the callback is entered; the callback fills columns 0..nq of rows 0..n of d_rows and entries 0..n
+ *     of each third of d_vws (volume, weight, surface of each row, the order calcIntensity returns them), complete on the device when
+ *     it returns; return 0, anything else aborts with MCSAS_ECALLBACK.  Calling thread only, between the library's launches.
+ *   mcsas_hip_histogram_rows_shape (touches no device): *min_rows = n_contrib is the least capacity_rows (one repetition per round);
+ *     *useful_rows = n_contrib * n_reps, capped by 256 MiB / (row_stride * 8) rounded down to whole repetitions, never below
+ *     min_rows; *row_stride as above.  Any of the three may be NULL.
+ * Uses problem->{nq, q, intensity, sigma, n_active, n_contrib, n_reps, find_background, positive_background, device}; model_id,
+ * params, clip_*, comp_exp are the callback's business.  Smearing is not: a problem that carries a smearing table is refused.
+ * Refused with MCSAS_EINVAL before a device is touched: NULL problem / contribs / d_pset / d_rows / d_vws / rows_cb / out, a wrong
+ * struct_size, capacity_rows < n_contrib, a smearing table, and whatever mcsas_hip_histogram refuses of sizes and histogram records
+ * (the same sentences behind "histogram_device_rows: "); after the device is selected, before anything is launched: a buffer that is
+ * not device memory of that device (MCSAS_EINVAL).  A failed allocation of the staging blocks: MCSAS_ENOMEM.
+ * Fed the rows of a built-in model, every array is mcsas_hip_histogram's bit for bit, whatever the rounds (tests/test_hist_rows_gpu.py). */
+int mcsas_hip_histogram_rows_shape(const mcsas_problem *problem, int64_t *min_rows, int64_t *useful_rows, int32_t *row_stride);
+int mcsas_hip_histogram_device_rows(const mcsas_problem *problem, const double *contribs,
+                                    double *d_pset, double *d_rows, double *d_vws, int64_t capacity_rows,
+                                    mcsas_device_rows_callback rows_cb, void *user,
+                                    int32_t n_hist, const mcsas_histogram_spec *specs,
+                                    double *scaling, double *fractions, double *out);
+
 /* ---- input preparation ----------------------------------------------------------
  * DataObj._prepareUncertainty (dataobj/dataobj.py:204-227): sigma_out = max(sigma_raw, fu_min * I),
  * fu_min * I when sigma_raw is NULL (no uncertainty column), +inf where that is not finite. */

@@ -1,5 +1,5 @@
 // host_hist.hip — McSAS.histogram() on the device: the hist_* kernels, their batch forms and the entry points mcsas_hip_histogram_prep,
-// mcsas_hip_histogram and mcsas_hip_histogram_batch.  What makes a set acceptable (check_hist_set), how a set lies in the staging
+// mcsas_hip_histogram, mcsas_hip_histogram_batch and mcsas_hip_histogram_device_rows (the rows filled by the caller).  What makes a set acceptable (check_hist_set), how a set lies in the staging
 // blocks (HistSizes, pack_hist_set, unpack_hist_set) and how many repetitions share a block of rows (hist_rep_chunk) are each said
 // once here, for the single call and the batch alike.  Nothing here knows about plans.
 #include <hip/hip_runtime.h>
@@ -192,6 +192,24 @@ __global__ __launch_bounds__(64) void hist_bins_kernel(int N, int P, int R, cons
     hist_bins_body(N, P, R, blockIdx.y, specs[blockIdx.x], contribs, frac8, edges_all, out, hl);
 }
 
+// ---- a round of mcsas_hip_histogram_device_rows: n_rows = k N rows of the caller's, row rl N + c = contribution c of repetition r0 + rl.
+// Plain loads and stores, one thread per element; the host reads neither buffer.
+// the round's parameter sets, unclipped, in activeParams() order: pset[row][p] = contribs[c][p][r0 + rl]
+__global__ void hist_pset_kernel(int N, int P, int R, int r0, size_t n_rows, const double *__restrict__ contribs, double *__restrict__ pset) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rows * P) return;
+    const size_t row = i / P, rl = row / N, c = row % N, p = i % P;
+    pset[i] = contribs[(c * P + p) * R + r0 + rl];
+}
+// the round's volumes, weights and surfaces, vws[3][capacity] as the caller filled them, into the [c R + r] arrays of the kernels above
+__global__ void hist_take_vws_kernel(int N, int R, int r0, size_t n_rows, size_t capacity, const double *__restrict__ vws,
+                                     double *__restrict__ vset, double *__restrict__ wset, double *__restrict__ sset) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rows) return;
+    const size_t j = (i % N) * R + r0 + i / N;
+    vset[j] = vws[i]; wset[j] = vws[capacity + i]; sset[j] = vws[2 * capacity + i];
+}
+
 // ---- the same for a batch of data sets (mcsas_hip_histogram_batch): one launch each over the (set, repetition) blocks of a chunk.
 // A set's record (HistSetDev, small_kernels.h) says where its arrays lie in the packed upload `in`, the packed download `back` and
 // the scratch blocks; blockIdx.x picks the (set, repetition), blockIdx.y runs to the chunk's largest extent (contributions, q blocks,
@@ -260,15 +278,18 @@ struct HistSizes {
 // a histogram's outputs: bins, observability and cumulative distribution [n_bin][R] each, then the moments [5][R] (hist_bins_body)
 static size_t hist_out_doubles(int n_bin, size_t R) { return (size_t)3 * n_bin * R + 5 * R; }
 
-// Every check of a set that needs no device; fills the model arguments and the sizes.
+// Every check of a set that needs no device; fills the model arguments and the sizes.  m == NULL: the rows are the caller's
+// (mcsas_hip_histogram_device_rows), the model and its smearing are not looked at.
 static int check_hist_set(const mcsas_problem *p, const double *contribs, int n_hist, const mcsas_histogram_spec *specs, double *scaling, double *out,
                           ModelArgs *m, HistSizes *sz) {
     if (!p || !contribs || !scaling || !p->q || !p->intensity || !p->sigma || p->nq < 1 || p->n_contrib < 1 || p->n_reps < 1 || n_hist < 0 ||
         (n_hist > 0 && (!specs || !out)))
         return fail(MCSAS_EINVAL, "bad argument");
     if (p->n_contrib > 4096) return fail(MCSAS_EINVAL, "mcsas_hip_histogram stages a repetition's contributions in LDS: n_contrib %d > 4096 (use mcsas_hip_histogram_prep)", p->n_contrib);
-    if (int rc = fill_model_args(p, m)) return rc;
-    if (int rc = SmearDev::check(p)) return rc;
+    if (m) {
+        if (int rc = fill_model_args(p, m)) return rc;
+        if (int rc = SmearDev::check(p)) return rc;
+    }
     const size_t Q = p->nq, P = p->n_active, N = p->n_contrib, R = p->n_reps;
     *sz = HistSizes{};
     for (int h = 0; h < n_hist; ++h) {
@@ -413,6 +434,104 @@ extern "C" int mcsas_hip_histogram(const mcsas_problem *p, const double *contrib
     SmearDev smear;
     if (int rc = smear.upload(p, p->nq, &m)) return rc;
     if (int rc = launch_hist_reps(p, m, chunk, dq, dI, dsg, dc, drows.p, dcum.p, dsc, dv, dw, ds, dm)) return rc;
+    hist_fractions_kernel<<<(unsigned)R, WAVE>>>((int)N, (int)R, dsc, dv, dw, ds, dm, dfrac);
+    HIPCHK(hipGetLastError());
+    if (n_hist > 0) {
+        if (sizeof(double) * 3 * N > 64 * 1024)
+            HIPCHK(hipFuncSetAttribute((const void *)hist_bins_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * 3 * N)));
+        hist_bins_kernel<<<dim3((unsigned)n_hist, (unsigned)R), WAVE, sizeof(double) * 3 * N>>>((int)N, (int)P, (int)R, dc, dfrac, dedges, dspecs, dout);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(hback.p, dback.p, hback.bytes, hipMemcpyDeviceToHost, nullptr));
+    HIPCHK(hipStreamSynchronize(nullptr));
+    sync_guard.armed = false;
+    unpack_hist_set(hback.p, sz, scaling, fractions, out);
+    return MCSAS_OK;
+}
+
+// ------------------------------------------------------------------------------ one set, the rows filled by the caller: mcsas_hip_histogram_device_rows
+// rows of 256 MiB at the most make a useful round, never less than one repetition's; the row pitch is nq: hist_colsum_body walks a
+// repetition's rows densely
+static size_t hist_rows_useful(size_t N, size_t Q, size_t R) {
+    const size_t cap = ((size_t)256 << 20) / (Q * sizeof(double)) / N * N;
+    return std::max(N, std::min(N * R, cap));
+}
+// what the shape query and the entry point refuse of a problem alike, ahead of check_hist_set
+static int check_hist_rows_problem(const char *who, const mcsas_problem *p) {
+    if (!p) return fail(MCSAS_EINVAL, "%s: problem is NULL", who);
+    if (p->struct_size != sizeof(mcsas_problem))
+        return fail(MCSAS_EINVAL, "%s: mcsas_problem size %u, library expects %zu (ABI mismatch)", who, p->struct_size, sizeof(mcsas_problem));
+    if (p->nq < 1 || p->n_contrib < 1 || p->n_reps < 1)
+        return fail(MCSAS_EINVAL, "%s: nq %d, n_contrib %d, n_reps %d (each >= 1)", who, p->nq, p->n_contrib, p->n_reps);
+    return MCSAS_OK;
+}
+extern "C" int mcsas_hip_histogram_rows_shape(const mcsas_problem *p, int64_t *min_rows, int64_t *useful_rows, int32_t *row_stride) {
+    if (int rc = check_hist_rows_problem("histogram_rows_shape", p)) return rc;
+    if (min_rows) *min_rows = p->n_contrib;
+    if (useful_rows) *useful_rows = (int64_t)hist_rows_useful(p->n_contrib, p->nq, p->n_reps);
+    if (row_stride) *row_stride = p->nq;
+    return MCSAS_OK;
+}
+
+// The second half of mcsas_hip_histogram with the first half's rows handed over by the caller, a round of whole repetitions at a
+// time (include/mcsas_hip.h): hist_pset_kernel lays the round's parameter sets out for the callback, the callback fills d_rows and
+// d_vws, hist_take_vws_kernel files the three per-row values, and hist_colsum / hist_fit_cum / hist_obs read the rows where they lie.
+// After the last round the call is mcsas_hip_histogram again.  Every refusal of the arguments comes before a device is touched, the
+// buffers are looked at before anything is queued, and from the upload on sync_guard waits on every way out, a failing callback's too.
+extern "C" int mcsas_hip_histogram_device_rows(const mcsas_problem *p, const double *contribs, double *d_pset, double *d_rows, double *d_vws,
+                                               int64_t capacity_rows, mcsas_device_rows_callback rows_cb, void *user, int32_t n_hist,
+                                               const mcsas_histogram_spec *specs, double *scaling, double *fractions, double *out) {
+    static const char who[] = "histogram_device_rows";
+    const struct { const char *name; const void *ptr; } needed[] = {{"problem", p}, {"contribs", contribs}, {"d_pset", d_pset}, {"d_rows", d_rows},
+                                                                    {"d_vws", d_vws}, {"rows_cb", (const void *)rows_cb}, {"out", out}};
+    for (const auto &a : needed)
+        if (!a.ptr) return fail(MCSAS_EINVAL, "%s: %s is NULL", who, a.name);
+    if (int rc = check_hist_rows_problem(who, p)) return rc;
+    HistSizes sz;
+    if (const int rc = check_hist_set(p, contribs, n_hist, specs, scaling, out, nullptr, &sz)) { const std::string why = g_err; return fail(rc, "%s: %s", who, why.c_str()); }
+    if (p->n_active < 1 || p->n_active > MCSAS_MAX_ACTIVE) return fail(MCSAS_EINVAL, "%s: n_active %d (1..%d)", who, p->n_active, MCSAS_MAX_ACTIVE);
+    if (capacity_rows < p->n_contrib)
+        return fail(MCSAS_EINVAL, "%s: capacity_rows %lld < %d = n_contrib, the rows of one repetition (mcsas_hip_histogram_rows_shape)", who,
+                    (long long)capacity_rows, p->n_contrib);
+    if (p->smear_nk != 0 || p->smear_locs || p->smear_q_offset || p->smear_weights)
+        return fail(MCSAS_EINVAL, "%s: a smearing table (smear_nk %d) is given, but the rows are the caller's: nothing here would apply it", who, p->smear_nk);
+    DeviceGuard dev_guard;
+    if (int rc = select_device(p->device)) return rc;
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    if (int rc = check_device_buffer(who, "d_pset", d_pset, dev)) return rc;
+    if (int rc = check_device_buffer(who, "d_rows", d_rows, dev)) return rc;
+    if (int rc = check_device_buffer(who, "d_vws", d_vws, dev)) return rc;
+    const size_t Q = p->nq, P = p->n_active, N = p->n_contrib, R = p->n_reps, NR = N * R, cap = (size_t)capacity_rows;
+    const size_t per_round = std::min<size_t>({R, cap / N, 65535});            // (whole repetitions; a grid's y extent ends at 65535)
+    DevBuf<double> din, dback, dcum, dvws;
+    HIPCHK(din.alloc(sz.n_in)); HIPCHK(dback.alloc(sz.n_back)); HIPCHK(dcum.alloc(per_round * Q)); HIPCHK(dvws.alloc(4 * NR));
+    Pinned hin, hback;
+    HIPCHK(hin.alloc(sz.n_in)); HIPCHK(hback.alloc(sz.n_back));
+    SyncGuard sync_guard;
+    pack_hist_set(hin.p, p, contribs, n_hist, specs, sz);
+    HIPCHK(hipMemcpyAsync(din.p, hin.p, hin.bytes, hipMemcpyHostToDevice, nullptr));
+    const double *dI = din.p + sz.I_off, *dsg = din.p + sz.sg_off, *dc = din.p + sz.c_off, *dedges = din.p + sz.edge_off;
+    const HistSpecDev *dspecs = reinterpret_cast<const HistSpecDev *>(din.p + sz.spec_off);
+    double *dsc = dback.p, *dfrac = dback.p + sz.frac_off, *dout = dback.p + sz.out_off;
+    double *dv = dvws.p, *dw = dvws.p + NR, *ds = dvws.p + 2 * NR, *dm = dvws.p + 3 * NR;
+    for (size_t r0 = 0; r0 < R; r0 += per_round) {
+        const unsigned nr = (unsigned)std::min(per_round, R - r0);
+        const size_t n_rows = nr * N;
+        hist_pset_kernel<<<(unsigned)((n_rows * P + 255) / 256), 256>>>((int)N, (int)P, (int)R, (int)r0, n_rows, dc, d_pset);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(nullptr));                                 // the sets are complete before the caller reads them
+        const int rc = rows_cb(user, (int32_t)n_rows);
+        if (rc) return fail(MCSAS_ECALLBACK, "%s: rows callback returned %d", who, rc);
+        hist_take_vws_kernel<<<(unsigned)((n_rows + 255) / 256), 256>>>((int)N, (int)R, (int)r0, n_rows, cap, d_vws, dv, dw, ds);
+        HIPCHK(hipGetLastError());
+        hist_colsum_kernel<<<dim3((unsigned)((Q + 255) / 256), nr), 256>>>(p->nq, (int)N, d_rows, dcum.p);
+        HIPCHK(hipGetLastError());
+        hist_fit_cum_kernel<<<nr, WAVE>>>(p->nq, dI, dsg, (int)R, (int)r0, dcum.p, p->find_background != 0, p->positive_background != 0, dsc);
+        HIPCHK(hipGetLastError());
+        hist_obs_kernel<<<dim3((unsigned)N, nr), WAVE>>>(p->nq, dsg, (int)N, (int)R, (int)r0, d_rows, dsc, dv, dw, dm);
+        HIPCHK(hipGetLastError());
+    }
     hist_fractions_kernel<<<(unsigned)R, WAVE>>>((int)N, (int)R, dsc, dv, dw, ds, dm, dfrac);
     HIPCHK(hipGetLastError());
     if (n_hist > 0) {

@@ -23,6 +23,9 @@ int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
     } while (0)
 
 int select_device(int device);
+// A buffer the caller hands over as device memory (host_rows.hip; mcsas_hip_analyse_device_rows, mcsas_hip_histogram_device_rows):
+// MCSAS_EINVAL in `who`'s name unless `ptr` is unmanaged device memory of device `dev`.  Asked before a kernel is launched on it.
+int check_device_buffer(const char *who, const char *name, const void *ptr, int dev);
 
 // Every entry point that selects a device puts the calling thread's current device back on the way out: a
 // host that shares the HIP runtime (torch with RCCL in bench.py, the hosts of INTEGRATION.md) keeps its own.

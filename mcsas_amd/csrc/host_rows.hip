@@ -256,18 +256,18 @@ extern "C" int mcsas_hip_device_rows_shape(const mcsas_problem *p, int32_t windo
     return MCSAS_OK;
 }
 
-// a buffer of the caller's must be device memory of the selected device before a kernel is launched on it
-static int check_device_buffer(const char *name, const void *ptr, int dev) {
+// a buffer of the caller's must be device memory of the selected device before a kernel is launched on it (host_internal.h)
+int check_device_buffer(const char *who, const char *name, const void *ptr, int dev) {
     hipPointerAttribute_t at;
     memset(&at, 0, sizeof at);
     const hipError_t e = hipPointerGetAttributes(&at, ptr);
     if (e != hipSuccess) {
         (void)hipGetLastError();                                               // (an unknown pointer is the caller's mistake, not a state to keep)
-        return fail(MCSAS_EINVAL, "analyse_device_rows: %s is not device memory (%s)", name, hipGetErrorString(e));
+        return fail(MCSAS_EINVAL, "%s: %s is not device memory (%s)", who, name, hipGetErrorString(e));
     }
     if (at.type != hipMemoryTypeDevice || at.isManaged)
-        return fail(MCSAS_EINVAL, "analyse_device_rows: %s is not device memory (memory type %d)", name, (int)at.type);
-    if (at.device != dev) return fail(MCSAS_EINVAL, "analyse_device_rows: %s lies on device %d, the analysis runs on device %d", name, at.device, dev);
+        return fail(MCSAS_EINVAL, "%s: %s is not device memory (memory type %d)", who, name, (int)at.type);
+    if (at.device != dev) return fail(MCSAS_EINVAL, "%s: %s lies on device %d, the call runs on device %d", who, name, at.device, dev);
     return MCSAS_OK;
 }
 
@@ -277,8 +277,8 @@ static int device_rows_run(const mcsas_problem *p, double *d_pset, double *d_row
     { int rc = select_device(p->device); if (rc) return rc; }
     int dev = 0;
     HIPCHK(hipGetDevice(&dev));
-    if (int rc = check_device_buffer("d_pset", d_pset, dev)) return rc;
-    if (int rc = check_device_buffer("d_rows", d_rows, dev)) return rc;
+    if (int rc = check_device_buffer("analyse_device_rows", "d_pset", d_pset, dev)) return rc;
+    if (int rc = check_device_buffer("analyse_device_rows", "d_rows", d_rows, dev)) return rc;
     FeedRun run(p, qpad, window);
     if (int rc = run.setup(d_rows, d_pset)) return rc;
     // what feed_draw_kernel reads of the problem beside the round's metadata

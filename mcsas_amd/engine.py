@@ -17,7 +17,7 @@ from ._lib import MAX_ACTIVE, MAX_DEVICES, MAX_PARAMS, Problem, Result, as_dp, c
 MODEL_SPHERE, MODEL_CYL_ISO, MODEL_ELL_CS, MODEL_KHOLODENKO = 0, 1, 2, 3
 MODEL_ELL_ISO, MODEL_SPH_CS, MODEL_GAUSS_CHAIN, MODEL_LMA_SPHERE = 4, 5, 6, 7
 MODEL_PLUGIN0 = 64      # first id of a run-time model plug-in (include/mcsas_hip.h: MCSAS_MODEL_PLUGIN0)
-MODEL_HOST = -1         # a model that exists only as host code (Python formfactor / volume: rows through analyse_host_rows; torch calcIntensityBatch: analyse_device_rows)
+MODEL_HOST = -1         # a model that exists only as host code (Python formfactor / volume: rows through analyse_host_rows; torch calcIntensityBatch: analyse_device_rows, histogram_device_rows)
 
 
 class PluginCompileError(ValueError):
@@ -753,6 +753,79 @@ def histogram_device_batch(items):
         check(lib.mcsas_hip_histogram_batch(n, probs, dpp(*[as_dp(c.contribs) for c in calls]), n_hist, specs, dpp(*[as_dp(c.sc) for c in calls]),
                                             dpp(*[as_dp(c.frac) for c in calls]), dpp(*[as_dp(c.out) for c in calls])), lib)
     return [c.unpack() for c in calls]
+
+
+def histogram_rows_shape(model: ModelSetup, q, st_or_sizes):
+    """(min_rows, useful_rows, row_stride) of histogram_device_rows (mcsas_hip_histogram_rows_shape; no device is touched): the
+    least and the most rows of a round, and the row pitch of the rows buffer (the q count, dense).  `st_or_sizes`: a Settings, or
+    (n_contrib, n_reps)."""
+    if isinstance(st_or_sizes, Settings):
+        st = st_or_sizes
+    else:
+        n_contrib, n_reps = st_or_sizes
+        st = Settings(n_contrib=int(n_contrib), n_reps=int(n_reps))
+    q = f64(q).ravel()
+    return _histogram_rows_shape(_lib.load(), HipProblem(model, q, np.ones_like(q), np.ones_like(q), st))
+
+
+def _histogram_rows_shape(lib, prob):
+    lo, hi, stride = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    check(lib.mcsas_hip_histogram_rows_shape(C.byref(prob.c), C.byref(lo), C.byref(hi), C.byref(stride)), lib)
+    return lo.value, hi.value, stride.value
+
+
+def histogram_device_rows(model: ModelSetup, q, intensity, sigma, contribs, specs, row_fn, find_background=True,
+                          positive_background=False, device=-1, capacity=None):
+    """histogram_device for a model whose rows the caller computes ON THE DEVICE with torch (mcsas_hip_histogram_device_rows,
+    include/mcsas_hip.h): a round of whole repetitions at a time the library lays the parameter sets out in a torch tensor,
+    `row_fn(pset[n][n_active]) -> (it[n][nq], v[n], w[n], s[n])` — calcIntensityBatch's return; pset is not yet clipped — gives the
+    rows and each row's volume, weight and surface, which are copied into the library's views, and the scale / background fit, the
+    visibility limits, fractions, bins and moments are taken on the device from the rows where they lie.  `capacity`: rows of the
+    tensors (default: the most a round uses, histogram_rows_shape; at least n_contrib).  Returns histogram_device's triple.
+    torch is imported here, not with the package."""
+    import torch                                 # (ahead of the library's first load: see _one_hip_runtime)
+    lib = _lib.load()
+    c3 = f64(contribs)
+    if c3.ndim != 3 or c3.shape[1] != model.n_active or model.n_active < 1:
+        raise ValueError("histogram_device_rows: contribs must be (n_contrib, n_active, n_reps) with n_active = %d >= 1, got %r"
+                         % (model.n_active, c3.shape))
+    call = _HistogramCall(model, q, intensity, sigma, c3, 0.0, specs, find_background, positive_background, device, None)
+    call.prob.c.model_id = MODEL_HOST
+    N, P, R = call.contribs.shape
+    nq = len(call.prob.q)
+    min_rows, useful_rows, stride = _histogram_rows_shape(lib, call.prob)
+    capacity = int(useful_rows if capacity is None else capacity)
+    if capacity < min_rows:
+        raise ValueError("histogram_device_rows: capacity %d < %d rows, what one repetition takes (n_contrib)" % (capacity, min_rows))
+    _one_hip_runtime()
+    dev = torch.device("cuda", torch.cuda.current_device() if int(device) < 0 else int(device))
+    pset = torch.empty((capacity, P), dtype=torch.float64, device=dev)
+    rows = torch.empty((capacity, stride), dtype=torch.float64, device=dev)
+    vws = torch.empty((3, capacity), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize(dev)                  # (the library works on the null stream of its own)
+    failure = []
+
+    def cb(user, n):
+        try:
+            with torch.cuda.device(dev):
+                it, v, w, s = row_fn(pset[:n])
+                rows[:n, :nq].copy_(torch.as_tensor(it, dtype=torch.float64, device=dev).reshape(n, nq))
+                for k, x in enumerate((v, w, s)):
+                    vws[k, :n].copy_(torch.as_tensor(x, dtype=torch.float64, device=dev))
+                torch.cuda.current_stream(dev).synchronize()
+            return 0
+        except BaseException as e:           # (an exception must not cross the C frame: hand it over and re-raise below)
+            failure.append(e)
+            return 1
+
+    rc = lib.mcsas_hip_histogram_device_rows(C.byref(call.prob.c), as_dp(call.contribs), C.c_void_p(pset.data_ptr()),
+                                             C.c_void_p(rows.data_ptr()), C.c_void_p(vws.data_ptr()), capacity,
+                                             _lib.DeviceRowsCallback(cb), None, len(call.specs), call.arr, as_dp(call.sc),
+                                             as_dp(call.frac), as_dp(call.out))
+    if failure:
+        raise failure[0]
+    check(rc, lib)
+    return call.unpack()
 
 
 def prepare_uncertainty(intensity, sigma_raw, fu_min, device=-1):

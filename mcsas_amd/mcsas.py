@@ -20,6 +20,11 @@ from .scatteringmodels import (setup_from_model, host_model_calc, is_batch_model
                                refuse_batch_smearing)
 
 
+# what McSAS.histogram() does for a calcIntensityBatch model where McSAS.deviceRowsHistogram is None: the rows stay on the device
+# (engine.histogram_device_rows); False: the rows are downloaded and the limits taken in numpy (the measurement behind it)
+DEVICE_ROWS_HISTOGRAM_DEFAULT = True
+
+
 class _Setting(object):
     """Algorithm parameter with the reference's accessors (`p()`, `p.value()`, `p.setValue(v)`)."""
 
@@ -72,6 +77,7 @@ class McSAS(object):
         self._stop = C.c_int32(0)
         self.details = None
         self.hostRowWindow = 64          # proposals evaluated ahead per chain for models that exist only as Python (mcsas_hip.h)
+        self.deviceRowsHistogram = None  # histogram() of a calcIntensityBatch model on the device: None = DEVICE_ROWS_HISTOGRAM_DEFAULT
 
     # McSAS.stop is polled once per step in the reference (mcsas.py:357); here the word is
     # forwarded to the running kernel by the library
@@ -255,6 +261,22 @@ class McSAS(object):
         c = self.compensationExponent()
         sig = np.array(data.f.binnedDataU, dtype=float)
         if setup.model_id == engine.MODEL_HOST:
+            on_device = DEVICE_ROWS_HISTOGRAM_DEFAULT if self.deviceRowsHistogram is None else self.deviceRowsHistogram
+            if is_batch_model(model) and numContribs <= engine.HISTOGRAM_MAX_CONTRIBS and on_device:
+                # calcIntensityBatch in torch: the rows of a round of repetitions in one call on the device, where the library laid
+                # the sets out and takes the fit, the limits, the fractions and the histograms from them (mcsas_hip_histogram_device_rows)
+                refuse_batch_smearing(model, data)
+                qdev = []
+
+                def rows_on_device(pset):
+                    if not qdev:
+                        import torch
+                        qdev.append(torch.as_tensor(np.ascontiguousarray(data.q, dtype=np.float64), device=pset.device).reshape(-1))
+                    return model.calcIntensityBatch(qdev[0], batch_clip(model, pset), c)
+                item = self._histogram_item(setup, None, contribs)
+                del item["comp_exp"], item["smear"]
+                self._histogram_from_device(engine.histogram_device_rows(row_fn=rows_on_device, **item))
+                return
             # rows by the model's own calcIntensity (:552, :577-578), the fit on the device (:559), the visibility limits in numpy (:575-590)
             scalingFactors = np.zeros((2, numReps))
             vsets = np.zeros((numContribs, numReps)); wsets = np.zeros((numContribs, numReps)); ssets = np.zeros((numContribs, numReps))
