@@ -44,7 +44,7 @@ struct PipeGeom {
                                   // nothing a chain decides then depends on the window, which follows the chain count for rows with an integral
     int32_t rowq;                 // rows with an integral (round 4): the producer waves of a chain PULL the window's rows from a queue, most expensive
                                   // first (no static deal), and the scan block works out the 8-step Gram blocks itself from the rows in its LDS
-    int32_t rec_off;              // rowq: producer LDS offset (doubles) of the window's proposal records
+    int32_t rec_off;              // producer LDS offset (doubles) of the proposal records: the window's (rowq), the block's (gram_lds: PIPE_PROP_DOUBLES each)
     int32_t help;                 // rowq: a producer block whose chain's queue is empty joins another chain's (pipe_prod_rowq)
     uint64_t prod_lds, scan_lds;
 };
@@ -84,7 +84,8 @@ constexpr int PIPE_BLOCK = 512;      // threads per workgroup of the tick kernel
 constexpr int PIPE_WAVES = PIPE_BLOCK / 64;
 constexpr int PIPE_GRAM_TILES_PER_ROUND = 2;   // producer: 16x16 Gram tiles summed across the 8 waves per LDS round (32 KB), one thread per tile element
 constexpr int PIPE_DROW_PAD = 8;         // LDS d rows: stride qpad + 8 doubles, so that the 64 16-byte operands of one Gram load hit 64 different bank groups
-constexpr int PIPE_GRAM_NT_MAX = 3;          // overlapped producer: tiles per sub-window — W <= 32 (two 16-row groups: 3 tiles) or 24 packed (2)
+constexpr int PIPE_PROP_DOUBLES = 12;    // producer: doubles per Contrib record in LDS (a stale row's; a proposal's, whose last double holds its two row slots)
+constexpr int PIPE_GRAM_NT_MAX = 3;         // overlapped producer: tiles per sub-window — W <= 32 (two 16-row groups: 3 tiles) or 24 packed (2)
 constexpr int PIPE_RESUM_STEPS = 64;        // rows with an integral: the running sums are re-derived from ft every 64 steps of an attempt (a multiple of the 8-step sub-window)
 constexpr int PIPE_MAX_ROW_DOUBLES = 32;   // scan block: doubles per lane held in row registers (rows per wave and sub-window x q per lane)
 #define PIPE_TL_WORDS 30                 /* timeline record of a wave: start, end, HW_ID, XCC_ID, then 26 marks */
@@ -226,16 +227,18 @@ static inline int pipe_geometry(int nq, int n_contrib, int tab_doubles, int heav
         g->overlap = overlap ? 1 : 0;
         // Rows without an integral: the Gram phase is a third of the producer's tick; with the sub-window's d rows parked
         // in LDS on their way to HBM it is MFMA-bound instead of waiting for an L2 round trip per sub-window.
+        // Behind the rows the block's proposal records (its waves claim rows one by one and read a row's proposal from there).
         g->gram_lds = 0; g->drow_off = 0;
-        const size_t with_rows = g->prod_lds + sizeof(double) * (size_t)g->w * (qpad + PIPE_DROW_PAD);
+        const size_t drows = (size_t)g->w * (qpad + PIPE_DROW_PAD);
+        const size_t with_rows = g->prod_lds + sizeof(double) * (drows + (size_t)8 * rpw * PIPE_PROP_DOUBLES);
         if (!overlap && with_rows <= 160 * 1024) {
-            g->gram_lds = 1; g->drow_off = g->gram_off + 16 + (int)red; g->prod_lds = with_rows;
+            g->gram_lds = 1; g->drow_off = g->gram_off + 16 + (int)red; g->rec_off = g->drow_off + (int)drows; g->prod_lds = with_rows;
         }
         // ... and no `new` rows go to HBM either (4 KB per step at Q = 512, a fifth of the tick's memory traffic): see lazy_rows
         g->lazy_rows = ((g->gram_lds || overlap) && !eager_req) ? 1 : 0;
         // pipe_prod_block has these two paths and no third: with neither, no window row would be written and the scan would
-        // decide on stale buffers.  (With tables of up to 1840 doubles the row buffer fits for every W pick_w allows; the
-        // built-in models without an integral have none.)  The overlapped producer exists in a tuning build only.
+        // decide on stale buffers.  (With tables of up to 1264 doubles the row buffer and the records fit for every W pick_w
+        // allows — the tightest is 512 q, W = 24, six rows per wave —; the built-in models without an integral have none.)  The overlapped producer exists in a tuning build only.
         if (!g->gram_lds && !g->overlap) return 2;
 #ifndef MCSAS_TUNING
         if (g->overlap) return 2;

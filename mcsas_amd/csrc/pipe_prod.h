@@ -94,7 +94,10 @@ __device__ __forceinline__ void pipe_prod_block(const PipeArgs &pa, const PipeHo
     }
     PIPE_TL_CLOCK(c_tab);
     Contrib<M>::fill_table(a.model, tab, tid, PIPE_BLOCK);
-    if (tid == 0) *reinterpret_cast<int32_t *>(lds + pa.g.gram_off + 16) = 0;   // lazy rows: the block's stale-row count
+    if (tid == 0) {
+        *reinterpret_cast<int32_t *>(lds + pa.g.gram_off + 16) = 0;   // lazy rows: the block's stale-row count
+        *reinterpret_cast<int32_t *>(lds + pa.g.gram_off) = 0;        // the next row of the block to hand out (row claims below)
+    }
     __syncthreads();
     PIPE_TL_CLOCK(c_bar);
     PIPE_TL_PUT(pa, t, 22, c_entry); PIPE_TL_PUT(pa, t, 23, c_snap); PIPE_TL_PUT(pa, t, 24, c_tab); PIPE_TL_PUT(pa, t, 25, c_bar);
@@ -151,27 +154,9 @@ __device__ __forceinline__ void pipe_prod_block(const PipeArgs &pa, const PipeHo
 
     if (MCSAS_TUNE_BITS(a) & 16) return;                                  // diagnostic: no window rows
     if constexpr (pipe_light_model_v<M>) if (pa.g.overlap || pa.g.gram_lds) {   // (rows with an integral never take this path: not instantiated for them)
-        // ---- overlapped producer.  The block's rows are nsb sub-windows of W; phase ss = the rows of sub-window ss, every
-        // wave its share, d = new - old straight to the window buffer.  The Gram block of sub-window ss - 1 is worked off
-        // in units BETWEEN the rows of phase ss (matrix pipe beside the vector pipe: while one wave of a SIMD is inside a run
-        // of MFMAs its partner has the vector issue slots to itself), its operands read back from the window buffer.
-        // One barrier per phase, and it waits for no memory: a wave passes B(ss - 1) — "the rows of ss - 1 are visible to the
-        // workgroup" — behind its FIRST row of phase ss, after a counted wait that covers exactly its stores of phase
-        // ss - 1 (the counter is in order: everything older than that row's own stores has completed by then).  The partial
-        // tiles of a block are parked in LDS when a wave has done its last unit and summed by all threads behind the next
-        // barrier (two reduction buffers, by parity).  Only the last sub-window's Gram block runs with nothing beside it.
+        // ---- the block's rows: nsb sub-windows of W, d = new - old straight to the window buffer, and the Gram block of
+        // every sub-window (pipe_gram.h).
         const int W = pa.g.w, nsb = pa.g.sub_per_block, BR = nsb * W;
-        // Rows per wave and sub-window: W / 8 on average; tuning bits 19-20 shift rows from the four waves that share
-        // their SIMDs with an older wave (4-7) to the older ones (0-3): 0 = equal shares, 1 / 2 = one / two rows.
-        // (the LDS variant's default is one row: the SIMD arbitrates oldest-first, so with equal shares the older wave is done
-        // early and the younger one finishes the phase alone, latency-bound — measured 4 + 2 rows 3.92 ms, 3 + 3 4.03, 5 + 1 4.2;
-        // bits 19-20 = 3 there: equal shares)
-        const int rw_even = W >> 3, skew_bits = (MCSAS_TUNE_BITS(a) >> 19) & 3;
-        const int skew_req = pa.g.gram_lds ? (skew_bits == 0 ? 1 : (skew_bits == 3 ? 0 : skew_bits)) : skew_bits;
-        const int skew = skew_req < rw_even ? skew_req : rw_even - 1;
-        const int wv = __builtin_amdgcn_readfirstlane(wave);
-        const int RW = wv < 4 ? rw_even + skew : rw_even - skew;                        // my rows per sub-window
-        const int rbase = wv < 4 ? wv * (rw_even + skew) : 4 * (rw_even + skew) + (wv - 4) * (rw_even - skew);   // my first row in a sub-window
         const int buf = t & 1;
         const int64_t w = (int64_t)t - sn.t_init - 1;
         const int64_t sb0 = w * Kb + (int64_t)by * BR;                                 // global step of the block's first row
@@ -181,67 +166,31 @@ __device__ __forceinline__ void pipe_prod_block(const PipeArgs &pa, const PipeHo
         auto povf = glb(pa.povf) + ((size_t)rep * 2 + buf) * Kb;
         auto gwin = glb(pa.gwin) + ((size_t)rep * 2 + buf) * Kb * W;
         double *gred = lds + pa.g.gram_off + 16;                                       // [2][8 waves][PIPE_GRAM_NT_MAX][256]
-        constexpr size_t GRED = (size_t)PIPE_WAVES * PIPE_GRAM_NT_MAX * 256;
-        const int nmine = nsb * RW;                                                    // my rows (<= 8), lane l <-> my l-th row
         const bool no_gram = MCSAS_TUNE_BITS(a) & 64;                                              // diagnostic: no Gram blocks (uniform)
-        const int lrow = (lane / RW) * W + rbase + (lane % RW);                        // its offset in the block
         const bool lazy = pa.g.lazy_rows;
         PIPE_TLX_MARK(pa, t, 0);
         // ---- lazy rows: the block's stale `old` rows (their last proposal, N steps ago, was accepted: ~6 % of them) are
         // evaluated again from the parameter set, one q per thread and row — an eighth of a wave's row time for the whole
-        // block, and no wave ends up with more rows than the others — and written back to the row cache.  Lanes 32 + l of
-        // a wave mirror its lanes l: the same rows, their `old` side — validity flag and parameter set in one round trip
-        // (under way while the proposals are drawn), and ONE prepare() call serves the proposals and the old sets.
-        constexpr int CON = 12;                                   // doubles per Contrib record in LDS
-        static_assert(sizeof(Contrib<M>) <= 8 * CON && sizeof(Contrib<M>) % 8 == 0, "Contrib record");
+        // block, and no wave ends up with more rows than the others — and written back to the row cache.  The threads that
+        // prepare the proposals are mirrored by threads that take the same rows' `old` side — validity flag and parameter set
+        // in one round trip (under way while the proposals are drawn) — and ONE prepare() call serves the proposals and the
+        // old sets.  A thread that finds its row stale puts it on the block's list (stale_push); stale_refresh, called by
+        // every thread, works the list off.
+        constexpr int CON = PIPE_PROP_DOUBLES;                    // doubles per Contrib record in LDS
+        static_assert(sizeof(Contrib<M>) <= 8 * (CON - 1) && sizeof(Contrib<M>) % 8 == 0, "Contrib record");
         int32_t *stl = reinterpret_cast<int32_t *>(gred);         // [0] count (zeroed before the tables' barrier), then the stale contributions
         double *scon = gred + 64;                                 // their Contrib records
-        double prow[MCSAS_MAX_ACTIVE] = {0., 0., 0., 0.};
-        const int l2 = lane - 32;
-        const bool old_lane = lazy && l2 >= 0 && l2 < nmine;
-        int stale_r = -1;
-        if (old_lane) {
-            const int lrow_o = (l2 / RW) * W + rbase + (l2 % RW);
-            if (sb0 + lrow_o < max_iter) {
-                const int r = (int)((sb0 + lrow_o) % N);
-                const int v = row_valid[r];
+        auto stale_push = [&](int r, const Contrib<M> &c) {
+            const int e = atomicAdd(&stl[0], 1);
+            stl[1 + e] = r;
+            double tmp[CON] = {};
+            __builtin_memcpy(tmp, &c, sizeof(Contrib<M>));
 #pragma unroll
-                for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p) if (p < P) prow[p] = rset[(size_t)r * P + p];
-                if (!v) stale_r = r;
-            }
-        }
-        int pov = 0, my_oslot = 0, my_sslot = 0;
-        {
-            const int r = (int)((sb0 + lrow) % N);
-            if (lane < nmine) {
-                if (lazy) my_oslot = r;
-                else { my_oslot = slot_of[r]; my_sslot = stage[buf * Kb + by * BR + lrow]; }
-            }
-            const int64_t sl = sb0 + lrow;
-#pragma unroll
-            for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)
-                if (p < P) {
-                    double u = 0.5;
-                    if (lane < nmine && sl < max_iter) u = src.at(sn.step_base + (uint64_t)sl * P + p, pov);
-                    const double pv = gen_transform(a.gen_kind[p], u) * (a.gen_hi[p] - a.gen_lo[p]) + a.gen_lo[p];
-                    if (!(old_lane && sb0 + ((l2 / RW) * W + rbase + (l2 % RW)) < max_iter)) prow[p] = pv;
-                }
-        }
-        Contrib<M> prop;
-        prop.prepare(a.model, prow);
-        PIPE_TLX_MARK(pa, t, 1);
-        int nst = 0;
-        if (lazy) {
-            if (stale_r >= 0) {
-                const int e = atomicAdd(&stl[0], 1);
-                stl[1 + e] = stale_r;
-                double tmp[CON] = {};
-                __builtin_memcpy(tmp, &prop, sizeof(Contrib<M>));
-#pragma unroll
-                for (int i = 0; i < (int)(sizeof(Contrib<M>) / 8); ++i) scon[e * CON + i] = tmp[i];
-            }
+            for (int i = 0; i < (int)(sizeof(Contrib<M>) / 8); ++i) scon[e * CON + i] = tmp[i];
+        };
+        auto stale_refresh = [&]() {
             PIPE_LDS_BARRIER();
-            nst = stl[0];
+            const int nst = stl[0];
             for (int i = 0; i < nst; ++i) {                       // (list order varies from run to run, the rows do not depend on it)
                 const int r = stl[1 + i];
                 Contrib<M> c;
@@ -260,54 +209,122 @@ __device__ __forceinline__ void pipe_prod_block(const PipeArgs &pa, const PipeHo
             }
             if (nst) __syncthreads();                             // the refreshed rows have landed before the row loop loads them (uniform)
             else PIPE_LDS_BARRIER();                              // (the stale list shares the reduction buffer: read by all before it is reused)
-        }
-        PIPE_TLX_MARK(pa, t, 2);
-        PIPE_TLX_MARK(pa, t, 3);
-        // proposals and replay-overflow flags of all my rows: one store per wave (lane l <-> my l-th row)
-        if (lane < nmine) {
-            const int k = by * BR + lrow;
-#pragma unroll
-            for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p) if (p < P) pval[k * MCSAS_MAX_ACTIVE + p] = prow[p];
-            povf[k] = pov;
-        }
+        };
         auto nvalid_of = [&](int ss) {
             const int64_t left = max_iter - (w * Kb + (int64_t)(by * nsb + ss) * W);
             return left >= W ? W : (left > 0 ? (int)left : 0);
         };
         if (pa.g.gram_lds) {
-            // ---- default: sub-window by sub-window — every wave evaluates its rows of the sub-window (d also into the LDS row
+            // ---- default: sub-window by sub-window — the waves evaluate the sub-window's rows (d also into the LDS row
             // buffer), barrier, the eight waves take the Gram block from LDS, next sub-window.  Only the LDS traffic is waited
             // for at the barriers: the rows' global stores drain behind the MFMAs.
+            // No wave has rows of its own: a wave CLAIMS the block's rows one by one from a counter in LDS (one returning add
+            // by lane 0), always the next row before it evaluates the current one, so that the next `old` row is under way a
+            // row ahead.  The SIMD arbitrates oldest-first, so of two waves that share one the younger (4-7) is the slower; with a
+            // fixed deal one of the two finished a sub-window alone, latency-bound (2.1 us a row against 1.15 per row and SIMD for
+            // two waves), whatever the deal — the first sub-window starts with every wave waiting for an `old` row, the later ones
+            // do not.  A row's values, its sums and its place in the row buffer do not depend on the wave that evaluates it.
+            // A claim behind the sub-window is kept across the Gram phase (its `old` row stays in flight), one behind the block
+            // ends the wave's rows.
             const int dstr = qpad + PIPE_DROW_PAD;
             double *dbuf = lds + pa.g.drow_off;
+            double *prec = lds + pa.g.rec_off;                    // [BR][CON] the block's proposals; a record's last double: `old` row slot, spare slot (eager rows)
+            int32_t *claim = reinterpret_cast<int32_t *>(lds + pa.g.gram_off);   // (zeroed before the tables' barrier)
+            auto take = [&]() {
+                int v = 0;
+                if (lane == 0) v = __hip_atomic_fetch_add(claim, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                return __builtin_amdgcn_readfirstlane(v);
+            };
+            int kc = take();                                      // my first row (the round trip runs beside the proposals)
+            // the block's proposals, each worked out once: thread k < BR row k, thread 64 + k the `old` side of row k
+            const int kk = tid & 63;
+            const int64_t sl = sb0 + kk;
+            const bool prop_thr = tid < BR, old_thr = lazy && tid >= 64 && tid - 64 < BR && sl < max_iter;
+            const int rk = (int)(sl % N);
+            double prow[MCSAS_MAX_ACTIVE] = {0., 0., 0., 0.};
+            int stale_r = -1, pov = 0;
+            if (old_thr) {
+                const int v = row_valid[rk];
+#pragma unroll
+                for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p) if (p < P) prow[p] = rset[(size_t)rk * P + p];
+                if (!v) stale_r = rk;
+            }
+#pragma unroll
+            for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)
+                if (p < P) {
+                    double u = 0.5;
+                    if (prop_thr && sl < max_iter) u = src.at(sn.step_base + (uint64_t)sl * P + p, pov);
+                    const double pv = gen_transform(a.gen_kind[p], u) * (a.gen_hi[p] - a.gen_lo[p]) + a.gen_lo[p];
+                    if (!old_thr) prow[p] = pv;
+                }
+            Contrib<M> prop;
+            prop.prepare(a.model, prow);
+            PIPE_TLX_MARK(pa, t, 1);
+            if (prop_thr) {
+                double tmp[CON] = {};
+                __builtin_memcpy(tmp, &prop, sizeof(Contrib<M>));
+#pragma unroll
+                for (int i = 0; i < (int)(sizeof(Contrib<M>) / 8); ++i) prec[kk * CON + i] = tmp[i];
+                if (!lazy) {
+                    int32_t *slots = reinterpret_cast<int32_t *>(prec + kk * CON + CON - 1);
+                    slots[0] = slot_of[rk]; slots[1] = stage[buf * Kb + by * BR + kk];
+                }
+                // proposals and replay-overflow flags of the block's rows: one store (long done when the first `old` row is waited for)
+                const int k = by * BR + kk;
+#pragma unroll
+                for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p) if (p < P) pval[k * MCSAS_MAX_ACTIVE + p] = prow[p];
+                povf[k] = pov;
+            }
+            if (stale_r >= 0) stale_push(stale_r, prop);
+            if (lazy) stale_refresh();
+            else PIPE_LDS_BARRIER();                              // the records are in LDS
+            PIPE_TLX_MARK(pa, t, 2);
+            PIPE_TLX_MARK(pa, t, 3);
+            // the `old` row of row k of the block: lazy rows keep contribution r in slot r, r = (sb0 + k) % N (BR <= N / 2: one wrap)
+            const int r0 = (int)(sb0 % N);
+            auto oslot_of = [&](int k) {
+                if (lazy) return r0 + k < N ? r0 + k : r0 + k - N;
+                return __builtin_amdgcn_readfirstlane(reinterpret_cast<const int32_t *>(prec + k * CON + CON - 1)[0]);
+            };
             double ocur[QPL], onext[QPL];
             {
-                const auto orow0 = cache + (size_t)__builtin_amdgcn_readlane(my_oslot, 0) * qpad + lane;
+                const auto orow0 = cache + (size_t)oslot_of(kc < BR ? kc : BR - 1) * qpad + lane;
 #pragma unroll
                 for (int j = 0; j < QPL; ++j) ocur[j] = orow0[WAVE * j];
             }
             PIPE_PIN_ROW(ocur);                                   // (a pending load carried into the loop would be waited for at its head, every iteration)
+#ifdef MCSAS_STAMPS
+            int nmine = 0;                                        // rows this wave has evaluated
+#endif
             for (int ss = 0; ss < nsb; ++ss) {
-                for (int jr = 0; jr < RW; ++jr) {
-                    const int l = ss * RW + jr, bl = __builtin_amdgcn_readfirstlane(l);
-                    const int kl = ss * W + rbase + jr, k = by * BR + kl;
-                    const Contrib<M> cnew = prop.bcast(bl);
-                    const int sslot = __builtin_amdgcn_readlane(my_sslot, bl);
+                while (kc < (ss + 1) * W) {
+                    const int kn = take();
+                    const int k = by * BR + kc;
+                    Contrib<M> cnew;
+                    int sslot = 0;
+                    {
+                        Contrib<M> cl;
+                        double tmp[CON];
+#pragma unroll
+                        for (int i = 0; i < (int)(sizeof(Contrib<M>) / 8); ++i) tmp[i] = prec[kc * CON + i];   // one address for the wave
+                        __builtin_memcpy(&cl, tmp, sizeof(Contrib<M>));
+                        cnew = cl.bcast(0);
+                        if (!lazy) sslot = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int32_t *>(prec + kc * CON + CON - 1)[1]);
+                    }
                     double d[QPL], nwv[QPL];
                     {
-                        const int bn = __builtin_amdgcn_readfirstlane(l + 1 < nmine ? l + 1 : l);
-                        const auto orow = cache + (size_t)__builtin_amdgcn_readlane(my_oslot, bn) * qpad + lane;
+                        const auto orow = cache + (size_t)oslot_of(kn < BR ? kn : kc) * qpad + lane;
 #pragma unroll
                         for (int j = 0; j < QPL; ++j) onext[j] = orow[WAVE * j];
                     }
-                    // (a row behind max_iter — the last window of a run only — is evaluated like any other: its proposal is the
-                    // generators' midpoint, its stores land in slots nobody reads, the Gram block masks it)
+                    // (a row behind max_iter — the last window of a run only — is claimed and evaluated like any other: its proposal
+                    // is the generators' midpoint, its stores land in slots nobody reads, the Gram block masks it)
                     const auto nrow = cache + (size_t)sslot * qpad + lane;
                     const auto dr = dwin + (size_t)k * qpad + lane;
-                    double *dl = dbuf + (size_t)(rbase + jr) * dstr + lane;
+                    double *dl = dbuf + (size_t)(kc - ss * W) * dstr + lane;
                     RowEval<M, QPL>::run(cnew, qt, lane, nwv);
-#ifdef MCSAS_STAMPS                                               /* marks 4..11: my first four rows — evaluated / `old` rows there and stores out */
-                    if (l < 4) { PIPE_PIN_ROW(nwv); PIPE_TL_MARK(pa, t, 4 + 2 * l); }
+#ifdef MCSAS_STAMPS                                               /* marks 4..11: the first four rows I claimed — evaluated / `old` rows there and stores out */
+                    if (nmine < 4) { PIPE_PIN_ROW(nwv); PIPE_TL_MARK(pa, t, 4 + 2 * nmine); }
 #endif
                     PIPE_PIN_ROW(ocur); PIPE_PIN_ROW(onext); PIPE_PIN_ROW(nwv);   // both `old` rows have landed before the first store is issued
                     double s1 = 0., s2 = 0.;
@@ -326,8 +343,10 @@ __device__ __forceinline__ void pipe_prod_block(const PipeArgs &pa, const PipeHo
 #pragma unroll
                     for (int j = 0; j < QPL; ++j) ocur[j] = onext[j];
 #ifdef MCSAS_STAMPS
-                    if (l < 4) PIPE_TL_MARK(pa, t, 5 + 2 * l);
+                    if (nmine < 4) PIPE_TL_MARK(pa, t, 5 + 2 * nmine);
+                    ++nmine;
 #endif
+                    kc = kn;
                 }
                 PIPE_TL_MARK(pa, t, 2 * (ss < 4 ? ss : 3));
                 if (!no_gram) PIPE_LDS_BARRIER();                 // the sub-window's rows are in LDS

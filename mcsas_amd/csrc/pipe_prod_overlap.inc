@@ -1,6 +1,70 @@
 // pipe_prod_overlap.inc — the overlapped variant of the producer's row loop (tuning word bit 18; pipe_geometry: overlap), a
 // measurement build's.  Included once, inside pipe_prod_block (pipe_prod.h), whose locals it uses; kept as text because a
 // function of its own would change the generated code.
+        // Phase ss = the rows of sub-window ss, every wave its share.  The Gram block of sub-window ss - 1 is worked off
+        // in units BETWEEN the rows of phase ss (matrix pipe beside the vector pipe: while one wave of a SIMD is inside a run
+        // of MFMAs its partner has the vector issue slots to itself), its operands read back from the window buffer.
+        // One barrier per phase, and it waits for no memory: a wave passes B(ss - 1) — "the rows of ss - 1 are visible to the
+        // workgroup" — behind its FIRST row of phase ss, after a counted wait that covers exactly its stores of phase
+        // ss - 1 (the counter is in order: everything older than that row's own stores has completed by then).  The partial
+        // tiles of a block are parked in LDS when a wave has done its last unit and summed by all threads behind the next
+        // barrier (two reduction buffers, by parity).  Only the last sub-window's Gram block runs with nothing beside it.
+        // Rows per wave and sub-window, a fixed deal: W / 8 on average; tuning bits 19-20 shift rows from the four waves that
+        // share their SIMDs with an older wave (4-7) to the older ones (0-3): 0 = equal shares, 1 / 2 = one / two rows.
+        const int wv = __builtin_amdgcn_readfirstlane(wave);
+        const int rw_even = W >> 3, skew_req = (MCSAS_TUNE_BITS(a) >> 19) & 3;
+        const int skew = skew_req < rw_even ? skew_req : rw_even - 1;
+        const int RW = wv < 4 ? rw_even + skew : rw_even - skew;                        // my rows per sub-window
+        const int rbase = wv < 4 ? wv * (rw_even + skew) : 4 * (rw_even + skew) + (wv - 4) * (rw_even - skew);   // my first row in a sub-window
+        constexpr size_t GRED = (size_t)PIPE_WAVES * PIPE_GRAM_NT_MAX * 256;
+        const int nmine = nsb * RW;                                                    // my rows (<= 8), lane l <-> my l-th row
+        const int lrow = (lane / RW) * W + rbase + (lane % RW);                        // its offset in the block
+        // Lanes 32 + l of a wave mirror its lanes l: the same rows, their `old` side (see the stale rows in pipe_prod.h).
+        double prow[MCSAS_MAX_ACTIVE] = {0., 0., 0., 0.};
+        const int l2 = lane - 32;
+        const bool old_lane = lazy && l2 >= 0 && l2 < nmine;
+        int stale_r = -1;
+        if (old_lane) {
+            const int lrow_o = (l2 / RW) * W + rbase + (l2 % RW);
+            if (sb0 + lrow_o < max_iter) {
+                const int r = (int)((sb0 + lrow_o) % N);
+                const int v = row_valid[r];
+#pragma unroll
+                for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p) if (p < P) prow[p] = rset[(size_t)r * P + p];
+                if (!v) stale_r = r;
+            }
+        }
+        int pov = 0, my_oslot = 0, my_sslot = 0;
+        {
+            const int r = (int)((sb0 + lrow) % N);
+            if (lane < nmine) {
+                if (lazy) my_oslot = r;
+                else { my_oslot = slot_of[r]; my_sslot = stage[buf * Kb + by * BR + lrow]; }
+            }
+            const int64_t sl = sb0 + lrow;
+#pragma unroll
+            for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)
+                if (p < P) {
+                    double u = 0.5;
+                    if (lane < nmine && sl < max_iter) u = src.at(sn.step_base + (uint64_t)sl * P + p, pov);
+                    const double pv = gen_transform(a.gen_kind[p], u) * (a.gen_hi[p] - a.gen_lo[p]) + a.gen_lo[p];
+                    if (!(old_lane && sb0 + ((l2 / RW) * W + rbase + (l2 % RW)) < max_iter)) prow[p] = pv;
+                }
+        }
+        Contrib<M> prop;
+        prop.prepare(a.model, prow);
+        PIPE_TLX_MARK(pa, t, 1);
+        if (stale_r >= 0) stale_push(stale_r, prop);
+        if (lazy) stale_refresh();
+        PIPE_TLX_MARK(pa, t, 2);
+        PIPE_TLX_MARK(pa, t, 3);
+        // proposals and replay-overflow flags of all my rows: one store per wave (lane l <-> my l-th row)
+        if (lane < nmine) {
+            const int k = by * BR + lrow;
+#pragma unroll
+            for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p) if (p < P) pval[k * MCSAS_MAX_ACTIVE + p] = prow[p];
+            povf[k] = pov;
+        }
         const int ntiles = pipe_gram_tiles(W);
         constexpr int UN = QPL;                                   // Gram units (8 q each) of my q slice
         // the tile scheme is uniform for the launch; everything below is compiled once per scheme
