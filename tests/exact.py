@@ -1,6 +1,7 @@
 """Exact values with derived error bounds: shared by the modules that hold device arithmetic to the EXACT value of the discrete
-operation it performs (test_formfactor_exact.py, test_fit_exact_host.py, test_fit_exact_gpu.py).  A plain module like helpers.py:
-nothing in here is collected.
+operation it performs (test_formfactor_exact.py; test_fit_exact_host.py, test_fit_exact_gpu.py through fit_exact.py;
+test_hist_exact_host.py, test_hist_exact_gpu.py through hist_exact.py).  A plain module like helpers.py: nothing in here is
+collected.
 
 A value of class R carries the exact (mpmath) result and a bound on what a double evaluation in the kernel's order may be off by
 (a running error analysis):
