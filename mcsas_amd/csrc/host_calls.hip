@@ -1,14 +1,13 @@
 // host_calls.hip — the small one-call entry points of libmcsas_hip.so and their kernels: model.calc, the background / scaling fit,
-// observability and the input preparation (uncertainty floor, re-binning); McSAS.histogram() is host_hist.hip.  Nothing here knows
-// about plans.
+// observability and the input preparation (uncertainty floor, re-binning); McSAS.histogram() is host_hist.hip.  The two kernels that
+// evaluate a model (model_rows_kernel, observability_kernel: small_kernels.h) are launched by model id through small_launch.h.
+// Nothing here knows about plans.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <vector>
 
-#include "host_internal.h"
-#include "small_kernels.h"   // model_rows_kernel, observability_kernel
-#include "model_list.h"      // MCSAS_FOR_MODELS: the built-in models
+#include "small_launch.h"    // model_rows_kernel, observability_kernel: from a model id to the instance
 
 using namespace mcsas;
 
@@ -113,16 +112,8 @@ extern "C" int mcsas_hip_model_calc(const mcsas_problem *p, const double *pset, 
     rc = smear.upload(p, p->nq, &m);
     if (rc) return rc;
     size_t lds = sizeof(double) * table_doubles_host(p->model_id, m.int_div);
-    switch (p->model_id) {
-#define CASE_K(mm) case mm: model_rows_kernel<mm><<<n, WAVE, lds>>>(m, p->nq, dq.p, dp.p, n, dr.p, dv.p, dw.p, ds.p); break;
-        MCSAS_FOR_MODELS(CASE_K)
-#undef CASE_K
-        default:
-            if (!is_plugin_model(p->model_id)) return fail(MCSAS_EINVAL, "model %d", p->model_id);
-            rc = plugin_small_launch(p->model_id, PLUGIN_MODEL_ROWS, dim3(n), lds, m, (int)p->nq, (const double *)dq.p, (const double *)dp.p, (int)n, dr.p, dv.p, dw.p, ds.p);
-            if (rc) return rc;
-    }
-    HIPCHK(hipGetLastError());
+    rc = launch_small_kernel<ModelRowsFamily>(p->model_id, dim3(n), lds, m, p->nq, dq.p, dp.p, n, dr.p, dv.p, dw.p, ds.p);
+    if (rc) return rc;
     rows_cumsum_kernel<<<(p->nq + 255) / 256, 256>>>(p->nq, n, dr.p, dc.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
@@ -174,18 +165,8 @@ extern "C" int mcsas_hip_observability(const mcsas_problem *p, const double *con
     if (rc) return rc;
     size_t lds = sizeof(double) * table_doubles_host(p->model_id, m.int_div);
     dim3 grid((unsigned)N, (unsigned)R);
-    switch (p->model_id) {
-#define CASE_K(mm) case mm: observability_kernel<mm><<<grid, WAVE, lds>>>(m, p->nq, dq.p, dsg.p, (int)N, (int)R, dc.p, dsc.p, dvf.p, dm.p); break;
-        MCSAS_FOR_MODELS(CASE_K)
-#undef CASE_K
-        default: {
-            if (!is_plugin_model(p->model_id)) return fail(MCSAS_EINVAL, "model %d", p->model_id);
-            int rcp = plugin_small_launch(p->model_id, PLUGIN_OBSERVABILITY, grid, lds, m, (int)p->nq, (const double *)dq.p, (const double *)dsg.p, (int)N, (int)R,
-                                          (const double *)dc.p, (const double *)dsc.p, (const double *)dvf.p, dm.p);
-            if (rcp) return rcp;
-        }
-    }
-    HIPCHK(hipGetLastError());
+    rc = launch_small_kernel<ObservabilityFamily>(p->model_id, grid, lds, m, p->nq, dq.p, dsg.p, N, R, dc.p, dsc.p, dvf.p, dm.p);
+    if (rc) return rc;
     HIPCHK(hipMemcpy(min_req_vol, dm.p, sizeof(double) * N * R, hipMemcpyDeviceToHost));
     return MCSAS_OK;
 }

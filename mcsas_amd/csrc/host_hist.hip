@@ -1,7 +1,9 @@
 // host_hist.hip — McSAS.histogram() on the device: the hist_* kernels, their batch forms and the entry points mcsas_hip_histogram_prep,
-// mcsas_hip_histogram, mcsas_hip_histogram_batch and mcsas_hip_histogram_device_rows (the rows filled by the caller).  What makes a set acceptable (check_hist_set), how a set lies in the staging
-// blocks (HistSizes, pack_hist_set, unpack_hist_set) and how many repetitions share a block of rows (hist_rep_chunk) are each said
-// once here, for the single call and the batch alike.  Nothing here knows about plans.
+// mcsas_hip_histogram, mcsas_hip_histogram_batch and mcsas_hip_histogram_device_rows (the rows filled by the caller).  What makes a
+// set acceptable (check_hist_set), how a set lies in the staging blocks (HistSizes, pack_hist_set, unpack_hist_set) and how many
+// repetitions share a block of rows (hist_rep_chunk) are each said once here, for the single call and the batch alike; how one set
+// is held on the device and finished (HistOnDevice), what follows a block of rows (launch_hist_fit_obs) and how a bins kernel is
+// launched (launch_hist_bins) once for the entry points that differ only in who fills the rows.  Nothing here knows about plans.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -10,28 +12,26 @@
 #include <cstring>
 #include <vector>
 
-#include "host_internal.h"
-#include "small_kernels.h"   // hist_rows_kernel, hist_rows_batch_kernel, HistSetDev
-#include "model_list.h"      // MCSAS_FOR_MODELS: the built-in models
+#include "small_launch.h"    // hist_rows_kernel, hist_rows_batch_kernel (from a model id to the instance), HistSetDev, visibility_limit
 
 using namespace mcsas;
+
+// mcsas_hip_histogram stages a repetition's contributions in LDS (hist_bins_body: 3 N doubles); engine.HISTOGRAM_MAX_CONTRIBS
+constexpr int HIST_MAX_CONTRIBS = 4096;
+// what a kernel may ask of dynamic LDS without its limit being raised first, and where a grid's y extent ends
+constexpr size_t LDS_UNRAISED_MAX = 64 * 1024, GRID_Y_MAX = 65535;
 
 // ------------------------------------------------------------------------------ kernels
 // The arithmetic of each kernel is a device function of one (data set, repetition): the single call's kernel hands it its own
 // arguments, the batch kernel (further down) what its set's record says.
 
-// min over q of sigma*vf / (A*I_c(q)), I_c != 0 (mcsas.py:582-590) from the stored row of contribution c of repetition r
+// the visibility limit (visibility_limit, small_kernels.h) of contribution c of repetition r from its stored row, at the volume
+// fraction its fitted scale gives it
 __device__ __forceinline__ void hist_obs_body(int nq, const double *sigma, int R, int c, int r, const double *row, const double *scaling,
                                               const double *vset, const double *wset, double *min_req) {
     const double A = scaling[r];
     const double vf = wset[(size_t)c * R + r] * A / vset[(size_t)c * R + r];      // modeldata.py:57-61
-    double best = INFINITY;
-    for (int k = threadIdx.x; k < nq; k += WAVE) {
-        const double scaled = A * row[k];
-        if (scaled != 0.) best = fmin(best, (sigma[k] * vf) / scaled);
-    }
-    best = wave_min(best);
-    if (threadIdx.x == 0) min_req[(size_t)c * R + r] = best;
+    visibility_limit(nq, sigma, vf, A, [&](int k) { return row[k]; }, min_req + (size_t)c * R + r);
 }
 __global__ __launch_bounds__(64) void hist_obs_kernel(int nq, const double *sigma, int N, int R, int r0, const double *rows,
                                                       const double *scaling, const double *vset, const double *wset, double *min_req) {
@@ -285,7 +285,8 @@ static int check_hist_set(const mcsas_problem *p, const double *contribs, int n_
     if (!p || !contribs || !scaling || !p->q || !p->intensity || !p->sigma || p->nq < 1 || p->n_contrib < 1 || p->n_reps < 1 || n_hist < 0 ||
         (n_hist > 0 && (!specs || !out)))
         return fail(MCSAS_EINVAL, "bad argument");
-    if (p->n_contrib > 4096) return fail(MCSAS_EINVAL, "mcsas_hip_histogram stages a repetition's contributions in LDS: n_contrib %d > 4096 (use mcsas_hip_histogram_prep)", p->n_contrib);
+    if (p->n_contrib > HIST_MAX_CONTRIBS)
+        return fail(MCSAS_EINVAL, "mcsas_hip_histogram stages a repetition's contributions in LDS: n_contrib %d > %d (use mcsas_hip_histogram_prep)", p->n_contrib, HIST_MAX_CONTRIBS);
     if (m) {
         if (int rc = fill_model_args(p, m)) return rc;
         if (int rc = SmearDev::check(p)) return rc;
@@ -344,41 +345,98 @@ struct SyncGuard { bool armed = true; ~SyncGuard() { if (armed) (void)hipStreamS
 // The rows of a block of repetitions stay in HBM between the kernels: how many repetitions share a block of at most ~8 GB.
 static size_t hist_rep_chunk(size_t N, size_t Q, size_t R) { return std::max<size_t>(1, std::min<size_t>(R, ((size_t)8 << 30) / (N * Q * sizeof(double)))); }
 
-// ------------------------------------------------------------------------------ one set: mcsas_hip_histogram_prep, mcsas_hip_histogram
-// hist_rows_kernel of the problem's model for repetitions [r0, r0 + grid.y) on the null stream
-static int launch_hist_rows(const mcsas_problem *p, const ModelArgs &m, dim3 grid, size_t lds, const double *dq, int N, int R, int r0,
-                            const double *dc, double *drows, double *dv, double *dw, double *ds) {
-    switch (p->model_id) {
-#define CASE_K(mm) case mm: hist_rows_kernel<mm><<<grid, WAVE, lds>>>(m, p->nq, dq, N, R, r0, dc, drows, dv, dw, ds); break;
-        MCSAS_FOR_MODELS(CASE_K)
-#undef CASE_K
-        default:
-            if (!is_plugin_model(p->model_id)) return fail(MCSAS_EINVAL, "model %d", p->model_id);
-            if (int rc = plugin_small_launch(p->model_id, PLUGIN_HIST_ROWS, grid, lds, m, (int)p->nq, dq, N, R, r0, dc, drows, dv, dw, ds)) return rc;
-    }
+// ------------------------------------------------------------------------------ one set on the null stream: what its entry points share
+// Where a set's arrays lie on the device: the data vectors and the parameter sets [N][P][R]; the summed rows of a block of
+// repetitions, Q doubles each; scaling [2][R]; volumes, weights, surfaces and visibility limits, [N][R] each.
+struct HistArrays { const double *q, *I, *sg, *c; double *cum, *sc, *v, *w, *s, *m; };
+
+// Of repetitions [r0, r0 + nr), whose rows begin at `rows` (row rl N + c = contribution c of repetition r0 + rl): cumInt = the sum
+// of the rows in contribution order (scatteringmodel.py:101), the closed-form scale / background fit (mcsas.py:559) and the
+// visibility limits.  Whoever filled the rows has filed their volumes and weights.
+static int launch_hist_fit_obs(const mcsas_problem *p, const HistArrays &a, size_t r0, unsigned nr, const double *rows) {
+    const int nq = p->nq, N = p->n_contrib, R = p->n_reps;
+    hist_colsum_kernel<<<dim3((unsigned)(((size_t)nq + 255) / 256), nr), 256>>>(nq, N, rows, a.cum);
+    HIPCHK(hipGetLastError());
+    hist_fit_cum_kernel<<<nr, WAVE>>>(nq, a.I, a.sg, R, (int)r0, a.cum, p->find_background != 0, p->positive_background != 0, a.sc);
+    HIPCHK(hipGetLastError());
+    hist_obs_kernel<<<dim3((unsigned)N, nr), WAVE>>>(nq, a.sg, N, R, (int)r0, rows, a.sc, a.v, a.w, a.m);
     HIPCHK(hipGetLastError());
     return MCSAS_OK;
 }
-// The first half of histogram() for all repetitions, a chunk of them at a time: per repetition the rows with their volumes, weights
-// and surfaces, cumInt = the sum of the rows in contribution order (scatteringmodel.py:101), the closed-form scale / background fit
-// (mcsas.py:559) and the visibility limits.  drows holds chunk * N * Q doubles, dcum chunk * Q; dsc is [2][R], the others [N][R].
-static int launch_hist_reps(const mcsas_problem *p, const ModelArgs &m, size_t chunk, const double *dq, const double *dI, const double *dsg,
-                            const double *dc, double *drows, double *dcum, double *dsc, double *dv, double *dw, double *ds, double *dm) {
-    const size_t Q = p->nq, N = p->n_contrib, R = p->n_reps;
+// The first half of histogram() for all repetitions, a chunk of them at a time: per repetition the rows of the problem's model with
+// their volumes, weights and surfaces, then launch_hist_fit_obs.  drows holds chunk * N * Q doubles, a.cum chunk * Q.
+static int launch_hist_reps(const mcsas_problem *p, const ModelArgs &m, size_t chunk, const HistArrays &a, double *drows) {
+    const size_t R = p->n_reps;
     const size_t lds = sizeof(double) * table_doubles_host(p->model_id, m.int_div);
     for (size_t r0 = 0; r0 < R; r0 += chunk) {
         const unsigned nr = (unsigned)std::min(chunk, R - r0);
-        const dim3 grid((unsigned)N, nr);
-        if (int rc = launch_hist_rows(p, m, grid, lds, dq, (int)N, (int)R, (int)r0, dc, drows, dv, dw, ds)) return rc;
-        hist_colsum_kernel<<<dim3((unsigned)((Q + 255) / 256), nr), 256>>>(p->nq, (int)N, drows, dcum);
-        HIPCHK(hipGetLastError());
-        hist_fit_cum_kernel<<<nr, WAVE>>>(p->nq, dI, dsg, (int)R, (int)r0, dcum, p->find_background != 0, p->positive_background != 0, dsc);
-        HIPCHK(hipGetLastError());
-        hist_obs_kernel<<<grid, WAVE>>>(p->nq, dsg, (int)N, (int)R, (int)r0, drows, dsc, dv, dw, dm);
-        HIPCHK(hipGetLastError());
+        if (int rc = launch_small_kernel<HistRowsFamily>(p->model_id, dim3((unsigned)p->n_contrib, nr), lds, m, p->nq, a.q, p->n_contrib, p->n_reps, r0,
+                                                         a.c, drows, a.v, a.w, a.s))
+            return rc;
+        if (int rc = launch_hist_fit_obs(p, a, r0, nr, drows)) return rc;
     }
     return MCSAS_OK;
 }
+// A bins kernel — hist_bins_kernel or its batch form — over `grid`: its dynamic LDS is 3 N doubles (hist_bins_body), and the limit of
+// that is raised first where N asks for more than a kernel gets unasked
+template <class... P>
+static int launch_hist_bins(void (*kernel)(P...), dim3 grid, size_t N, typename as_declared<P>::type... args) {
+    const size_t lds = sizeof(double) * 3 * N;
+    if (lds > LDS_UNRAISED_MAX) HIPCHK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kernel<<<grid, WAVE, lds>>>(args...);
+    HIPCHK(hipGetLastError());
+    return MCSAS_OK;
+}
+
+// A checked set on the device, as mcsas_hip_histogram and mcsas_hip_histogram_device_rows hold it: ONE packed upload (data vectors,
+// parameter sets, bin edges, histogram records) from a pinned staging block, the kernels back to back on the null stream, ONE packed
+// download — a call costs two transfers and no allocation once its block sizes have been seen (MemCache).  Between upload() and
+// finish() the entry point fills the rows its own way and calls launch_hist_fit_obs on them.
+// The members go in the reverse of this order: first the guard waits for what is queued, on every way out; only then the smearing
+// tables the kernels read, the staging blocks the copies read and write, and the device blocks go back to where the next call
+// would take them from.  (In an unnamed namespace: the library's list of symbols stays what it was.)
+namespace {
+struct HistOnDevice {
+    const mcsas_problem *p = nullptr;
+    int n_hist = 0;
+    HistSizes sz;
+    DevBuf<double> din, dback, dcum, dvws;
+    Pinned hin, hback;
+    SmearDev smear;                                            // (the built-in rows' tables; none where the rows are the caller's)
+    SyncGuard sync_guard;
+    HistArrays a{};
+
+    // `block_reps`: how many repetitions' summed rows a.cum holds
+    int upload(const mcsas_problem *p_, const double *contribs, int n_hist_, const mcsas_histogram_spec *specs, const HistSizes &sz_, size_t block_reps) {
+        p = p_; n_hist = n_hist_; sz = sz_;
+        const size_t NR = (size_t)p->n_contrib * p->n_reps;
+        HIPCHK(din.alloc(sz.n_in)); HIPCHK(dback.alloc(sz.n_back)); HIPCHK(dcum.alloc(block_reps * p->nq)); HIPCHK(dvws.alloc(4 * NR));
+        HIPCHK(hin.alloc(sz.n_in)); HIPCHK(hback.alloc(sz.n_back));
+        pack_hist_set(hin.p, p, contribs, n_hist, specs, sz);
+        HIPCHK(hipMemcpyAsync(din.p, hin.p, hin.bytes, hipMemcpyHostToDevice, nullptr));
+        a = HistArrays{din.p, din.p + sz.I_off, din.p + sz.sg_off, din.p + sz.c_off, dcum.p, dback.p, dvws.p, dvws.p + NR, dvws.p + 2 * NR, dvws.p + 3 * NR};
+        return MCSAS_OK;
+    }
+    // the second half of histogram() once every repetition has its scale and limits: fractions, bins, the download, the results
+    int finish(double *scaling, double *fractions, double *out) {
+        const int N = p->n_contrib, R = p->n_reps;
+        double *dfrac = dback.p + sz.frac_off;
+        hist_fractions_kernel<<<(unsigned)R, WAVE>>>(N, R, a.sc, a.v, a.w, a.s, a.m, dfrac);
+        HIPCHK(hipGetLastError());
+        if (n_hist > 0)
+            if (int rc = launch_hist_bins(hist_bins_kernel, dim3((unsigned)n_hist, (unsigned)R), N, N, p->n_active, R, a.c, dfrac, din.p + sz.edge_off,
+                                          reinterpret_cast<const HistSpecDev *>(din.p + sz.spec_off), dback.p + sz.out_off))
+                return rc;
+        HIPCHK(hipMemcpyAsync(hback.p, dback.p, hback.bytes, hipMemcpyDeviceToHost, nullptr));
+        HIPCHK(hipStreamSynchronize(nullptr));
+        sync_guard.armed = false;
+        unpack_hist_set(hback.p, sz, scaling, fractions, out);
+        return MCSAS_OK;
+    }
+};
+}  // namespace
+
+// ------------------------------------------------------------------------------ one set: mcsas_hip_histogram_prep, mcsas_hip_histogram
 
 extern "C" int mcsas_hip_histogram_prep(const mcsas_problem *p, const double *contribs, double *scaling, double *vset,
                                         double *wset, double *sset, double *min_req_vol) {
@@ -400,7 +458,7 @@ extern "C" int mcsas_hip_histogram_prep(const mcsas_problem *p, const double *co
     HIPCHK(hipMemcpy(dc.p, contribs, sizeof(double) * N * P * R, hipMemcpyHostToDevice));
     SmearDev smear;
     if (int rc = smear.upload(p, p->nq, &m)) return rc;
-    if (int rc = launch_hist_reps(p, m, chunk, dq.p, dI.p, dsg.p, dc.p, drows.p, dcum.p, dsc.p, dv.p, dw.p, ds.p, dm.p)) return rc;
+    if (int rc = launch_hist_reps(p, m, chunk, HistArrays{dq.p, dI.p, dsg.p, dc.p, dcum.p, dsc.p, dv.p, dw.p, ds.p, dm.p}, drows.p)) return rc;
     HIPCHK(hipMemcpy(scaling, dsc.p, sizeof(double) * 2 * R, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(vset, dv.p, sizeof(double) * N * R, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(wset, dw.p, sizeof(double) * N * R, hipMemcpyDeviceToHost));
@@ -409,44 +467,22 @@ extern "C" int mcsas_hip_histogram_prep(const mcsas_problem *p, const double *co
     return MCSAS_OK;
 }
 
-// McSAS.histogram() complete (include/mcsas_hip.h): ONE packed upload (data vectors, parameter sets, bin edges, histogram records) from
-// a pinned staging block, the kernels back to back on the null stream, ONE packed download — a call costs two transfers and no
-// allocation once its block sizes have been seen (MemCache).  Every refusal of the set itself comes before a device is touched.
+// McSAS.histogram() complete (include/mcsas_hip.h): the set on the device (HistOnDevice), its rows by the model's kernel a chunk of
+// repetitions at a time.  Every refusal of the set itself comes before a device is touched.
 extern "C" int mcsas_hip_histogram(const mcsas_problem *p, const double *contribs, int32_t n_hist, const mcsas_histogram_spec *specs,
                                    double *scaling, double *fractions, double *out) {
     ModelArgs m; HistSizes sz;
     if (int rc = check_hist_set(p, contribs, n_hist, specs, scaling, out, &m, &sz)) return rc;
     DeviceGuard dev_guard;
     if (int rc = select_device(p->device)) return rc;
-    const size_t Q = p->nq, P = p->n_active, N = p->n_contrib, R = p->n_reps, NR = N * R;
-    const size_t chunk = hist_rep_chunk(N, Q, R);
-    DevBuf<double> din, dback, drows, dcum, dvws;
-    HIPCHK(din.alloc(sz.n_in)); HIPCHK(dback.alloc(sz.n_back)); HIPCHK(drows.alloc(chunk * N * Q)); HIPCHK(dcum.alloc(chunk * Q)); HIPCHK(dvws.alloc(4 * NR));
-    Pinned hin, hback;
-    HIPCHK(hin.alloc(sz.n_in)); HIPCHK(hback.alloc(sz.n_back));
-    SyncGuard sync_guard;
-    pack_hist_set(hin.p, p, contribs, n_hist, specs, sz);
-    HIPCHK(hipMemcpyAsync(din.p, hin.p, hin.bytes, hipMemcpyHostToDevice, nullptr));
-    const double *dq = din.p, *dI = din.p + sz.I_off, *dsg = din.p + sz.sg_off, *dc = din.p + sz.c_off, *dedges = din.p + sz.edge_off;
-    const HistSpecDev *dspecs = reinterpret_cast<const HistSpecDev *>(din.p + sz.spec_off);
-    double *dsc = dback.p, *dfrac = dback.p + sz.frac_off, *dout = dback.p + sz.out_off;
-    double *dv = dvws.p, *dw = dvws.p + NR, *ds = dvws.p + 2 * NR, *dm = dvws.p + 3 * NR;
-    SmearDev smear;
-    if (int rc = smear.upload(p, p->nq, &m)) return rc;
-    if (int rc = launch_hist_reps(p, m, chunk, dq, dI, dsg, dc, drows.p, dcum.p, dsc, dv, dw, ds, dm)) return rc;
-    hist_fractions_kernel<<<(unsigned)R, WAVE>>>((int)N, (int)R, dsc, dv, dw, ds, dm, dfrac);
-    HIPCHK(hipGetLastError());
-    if (n_hist > 0) {
-        if (sizeof(double) * 3 * N > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void *)hist_bins_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * 3 * N)));
-        hist_bins_kernel<<<dim3((unsigned)n_hist, (unsigned)R), WAVE, sizeof(double) * 3 * N>>>((int)N, (int)P, (int)R, dc, dfrac, dedges, dspecs, dout);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipMemcpyAsync(hback.p, dback.p, hback.bytes, hipMemcpyDeviceToHost, nullptr));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    sync_guard.armed = false;
-    unpack_hist_set(hback.p, sz, scaling, fractions, out);
-    return MCSAS_OK;
+    const size_t Q = p->nq, N = p->n_contrib, chunk = hist_rep_chunk(N, Q, p->n_reps);
+    DevBuf<double> drows;                                      // (ahead of the set: it goes back after the set's guard has waited)
+    HistOnDevice d;
+    HIPCHK(drows.alloc(chunk * N * Q));
+    if (int rc = d.upload(p, contribs, n_hist, specs, sz, chunk)) return rc;
+    if (int rc = d.smear.upload(p, p->nq, &m)) return rc;
+    if (int rc = launch_hist_reps(p, m, chunk, d.a, drows.p)) return rc;
+    return d.finish(scaling, fractions, out);
 }
 
 // ------------------------------------------------------------------------------ one set, the rows filled by the caller: mcsas_hip_histogram_device_rows
@@ -475,9 +511,9 @@ extern "C" int mcsas_hip_histogram_rows_shape(const mcsas_problem *p, int64_t *m
 
 // The second half of mcsas_hip_histogram with the first half's rows handed over by the caller, a round of whole repetitions at a
 // time (include/mcsas_hip.h): hist_pset_kernel lays the round's parameter sets out for the callback, the callback fills d_rows and
-// d_vws, hist_take_vws_kernel files the three per-row values, and hist_colsum / hist_fit_cum / hist_obs read the rows where they lie.
+// d_vws, hist_take_vws_kernel files the three per-row values, and launch_hist_fit_obs reads the rows where they lie.
 // After the last round the call is mcsas_hip_histogram again.  Every refusal of the arguments comes before a device is touched, the
-// buffers are looked at before anything is queued, and from the upload on sync_guard waits on every way out, a failing callback's too.
+// buffers are looked at before anything is queued, and from the upload on the set's guard waits on every way out, a failing callback's too.
 extern "C" int mcsas_hip_histogram_device_rows(const mcsas_problem *p, const double *contribs, double *d_pset, double *d_rows, double *d_vws,
                                                int64_t capacity_rows, mcsas_device_rows_callback rows_cb, void *user, int32_t n_hist,
                                                const mcsas_histogram_spec *specs, double *scaling, double *fractions, double *out) {
@@ -502,65 +538,26 @@ extern "C" int mcsas_hip_histogram_device_rows(const mcsas_problem *p, const dou
     if (int rc = check_device_buffer(who, "d_pset", d_pset, dev)) return rc;
     if (int rc = check_device_buffer(who, "d_rows", d_rows, dev)) return rc;
     if (int rc = check_device_buffer(who, "d_vws", d_vws, dev)) return rc;
-    const size_t Q = p->nq, P = p->n_active, N = p->n_contrib, R = p->n_reps, NR = N * R, cap = (size_t)capacity_rows;
-    const size_t per_round = std::min<size_t>({R, cap / N, 65535});            // (whole repetitions; a grid's y extent ends at 65535)
-    DevBuf<double> din, dback, dcum, dvws;
-    HIPCHK(din.alloc(sz.n_in)); HIPCHK(dback.alloc(sz.n_back)); HIPCHK(dcum.alloc(per_round * Q)); HIPCHK(dvws.alloc(4 * NR));
-    Pinned hin, hback;
-    HIPCHK(hin.alloc(sz.n_in)); HIPCHK(hback.alloc(sz.n_back));
-    SyncGuard sync_guard;
-    pack_hist_set(hin.p, p, contribs, n_hist, specs, sz);
-    HIPCHK(hipMemcpyAsync(din.p, hin.p, hin.bytes, hipMemcpyHostToDevice, nullptr));
-    const double *dI = din.p + sz.I_off, *dsg = din.p + sz.sg_off, *dc = din.p + sz.c_off, *dedges = din.p + sz.edge_off;
-    const HistSpecDev *dspecs = reinterpret_cast<const HistSpecDev *>(din.p + sz.spec_off);
-    double *dsc = dback.p, *dfrac = dback.p + sz.frac_off, *dout = dback.p + sz.out_off;
-    double *dv = dvws.p, *dw = dvws.p + NR, *ds = dvws.p + 2 * NR, *dm = dvws.p + 3 * NR;
+    const size_t P = p->n_active, N = p->n_contrib, R = p->n_reps, cap = (size_t)capacity_rows;
+    const size_t per_round = std::min<size_t>({R, cap / N, GRID_Y_MAX});       // (whole repetitions)
+    HistOnDevice d;
+    if (int rc = d.upload(p, contribs, n_hist, specs, sz, per_round)) return rc;
     for (size_t r0 = 0; r0 < R; r0 += per_round) {
         const unsigned nr = (unsigned)std::min(per_round, R - r0);
         const size_t n_rows = nr * N;
-        hist_pset_kernel<<<(unsigned)((n_rows * P + 255) / 256), 256>>>((int)N, (int)P, (int)R, (int)r0, n_rows, dc, d_pset);
+        hist_pset_kernel<<<(unsigned)((n_rows * P + 255) / 256), 256>>>((int)N, (int)P, (int)R, (int)r0, n_rows, d.a.c, d_pset);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(nullptr));                                 // the sets are complete before the caller reads them
         const int rc = rows_cb(user, (int32_t)n_rows);
         if (rc) return fail(MCSAS_ECALLBACK, "%s: rows callback returned %d", who, rc);
-        hist_take_vws_kernel<<<(unsigned)((n_rows + 255) / 256), 256>>>((int)N, (int)R, (int)r0, n_rows, cap, d_vws, dv, dw, ds);
+        hist_take_vws_kernel<<<(unsigned)((n_rows + 255) / 256), 256>>>((int)N, (int)R, (int)r0, n_rows, cap, d_vws, d.a.v, d.a.w, d.a.s);
         HIPCHK(hipGetLastError());
-        hist_colsum_kernel<<<dim3((unsigned)((Q + 255) / 256), nr), 256>>>(p->nq, (int)N, d_rows, dcum.p);
-        HIPCHK(hipGetLastError());
-        hist_fit_cum_kernel<<<nr, WAVE>>>(p->nq, dI, dsg, (int)R, (int)r0, dcum.p, p->find_background != 0, p->positive_background != 0, dsc);
-        HIPCHK(hipGetLastError());
-        hist_obs_kernel<<<dim3((unsigned)N, nr), WAVE>>>(p->nq, dsg, (int)N, (int)R, (int)r0, d_rows, dsc, dv, dw, dm);
-        HIPCHK(hipGetLastError());
+        if (int rc2 = launch_hist_fit_obs(p, d.a, r0, nr, d_rows)) return rc2;
     }
-    hist_fractions_kernel<<<(unsigned)R, WAVE>>>((int)N, (int)R, dsc, dv, dw, ds, dm, dfrac);
-    HIPCHK(hipGetLastError());
-    if (n_hist > 0) {
-        if (sizeof(double) * 3 * N > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void *)hist_bins_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * 3 * N)));
-        hist_bins_kernel<<<dim3((unsigned)n_hist, (unsigned)R), WAVE, sizeof(double) * 3 * N>>>((int)N, (int)P, (int)R, dc, dfrac, dedges, dspecs, dout);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipMemcpyAsync(hback.p, dback.p, hback.bytes, hipMemcpyDeviceToHost, nullptr));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    sync_guard.armed = false;
-    unpack_hist_set(hback.p, sz, scaling, fractions, out);
-    return MCSAS_OK;
+    return d.finish(scaling, fractions, out);
 }
 
 // ------------------------------------------------------------------------------ a batch of sets: mcsas_hip_histogram_batch
-// hist_rows_batch_kernel of built-in model `model_id` over the grid.x blocks that `dblocks` begins with
-static int launch_hist_rows_batch(int model_id, dim3 grid, size_t lds, const HistSetDev *dsets, const ChainRef *dblocks, const double *din,
-                                  double *drows, double *dvws) {
-    switch (model_id) {
-#define CASE_K(mm) case mm: hist_rows_batch_kernel<mm><<<grid, WAVE, lds>>>(dsets, dblocks, din, drows, dvws); break;
-        MCSAS_FOR_MODELS(CASE_K)
-#undef CASE_K
-        default: return fail(MCSAS_EINVAL, "model %d has no batch kernel", model_id);
-    }
-    HIPCHK(hipGetLastError());
-    return MCSAS_OK;
-}
-
 // the rows budget of a batch chunk: 2 GiB, or MCSAS_HIP_HIST_BATCH_MB (a number of MiB, fractions allowed) — read at every call
 static size_t hist_batch_budget() {
     double mb = 2048.;
@@ -651,7 +648,8 @@ static int launch_hist_chunk(const std::vector<HistBatchSet> &sets, const HistCh
                 lds = std::max(lds, sizeof(double) * table_doubles_host(mid, sets[t].m.int_div));
             }
         if (!g_blk) continue;
-        if (int rc = launch_hist_rows_batch(mid, dim3((unsigned)g_blk, (unsigned)g_N), lds, d.sets, cb + g_first, d.in, d.rows, d.vws)) return rc;
+        // (hist_rows_batch_kernel of built-in model `mid` over the g_blk blocks of its sets)
+        if (int rc = launch_small_kernel<HistRowsBatchFamily>(mid, dim3((unsigned)g_blk, (unsigned)g_N), lds, d.sets, cb + g_first, d.in, d.rows, d.vws)) return rc;
         g_first += g_blk;
     }
     const unsigned nb = (unsigned)c.n_blk;
@@ -663,14 +661,8 @@ static int launch_hist_chunk(const std::vector<HistBatchSet> &sets, const HistCh
     HIPCHK(hipGetLastError());
     hist_fractions_batch_kernel<<<nb, WAVE>>>(d.sets, cb, d.vws, d.back);
     HIPCHK(hipGetLastError());
-    if (c.maxH > 0) {
-        const size_t lds = sizeof(double) * 3 * c.maxN;
-        if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)hist_bins_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        for (size_t h0 = 0; h0 < c.maxH; h0 += 65535) {      // (a grid's y extent ends at 65535)
-            hist_bins_batch_kernel<<<dim3(nb, (unsigned)std::min<size_t>(65535, c.maxH - h0)), WAVE, lds>>>(d.sets, cb, (int)h0, d.in, d.back);
-            HIPCHK(hipGetLastError());
-        }
-    }
+    for (size_t h0 = 0; h0 < c.maxH; h0 += GRID_Y_MAX)
+        if (int rc = launch_hist_bins(hist_bins_batch_kernel, dim3(nb, (unsigned)std::min(GRID_Y_MAX, c.maxH - h0)), c.maxN, d.sets, cb, h0, d.in, d.back)) return rc;
     return MCSAS_OK;
 }
 

@@ -1,6 +1,6 @@
 // host_internal.h — what the host units of libmcsas_hip.so share (mcsas_hip.hip: plans; host_decide.hip: what is decided without a device; host_analyse.hip:
 // one-shot analyses; host_rows.hip: rows evaluated by the caller; host_plugin.hip: run-time compiler of model plug-ins; host_calls.hip: small one-call entry points; host_hist.hip:
-// McSAS.histogram()).  Host code only: the run-time compiler never sees this file (it is not among the embedded headers).
+// McSAS.histogram(); small_launch.h: from a model id to a small kernel's instance, for the last two).  Host code only: the run-time compiler never sees this file (it is not among the embedded headers).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
@@ -101,8 +101,8 @@ bool plugin_declares(int model_id, int *row_class, bool *can_smear);
 int plugin_chain_function(int model_id, KernelFamily family, int qpl, bool flag, bool given, hipFunction_t *fn);
 int plugin_small_function(int model_id, PluginSmallKernel which, hipFunction_t *fn);
 
-// launch of a small kernel of a plug-in on the null stream; the arguments are passed by address,
-// so their types must be the kernel's parameter types exactly
+// launch of a small kernel of a plug-in on the null stream; the arguments are passed by address, so their types must be the
+// kernel's parameter types exactly — launch_small_kernel (small_launch.h) makes them so and is the only caller
 template <class... A>
 static int plugin_small_launch(int model_id, PluginSmallKernel which, dim3 grid, size_t lds, A... args) {
     hipFunction_t fn = nullptr;

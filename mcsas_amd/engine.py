@@ -311,36 +311,65 @@ def analyse_host_rows(model: ModelSetup, q, intensity, sigma, st: Settings, row_
     prob.c.model_id = MODEL_HOST
     nq, P = len(prob.q), model.n_active
     res = ChainResults(st.n_contrib, P, st.n_reps, nq)
-    failure = []
 
-    def cb(user, n, pset_p, rows_p):
-        try:
-            pset = np.ctypeslib.as_array(pset_p, shape=(n, P))
-            out = np.ctypeslib.as_array(rows_p, shape=(n, nq))
-            out[:, :] = np.asarray(row_fn(pset), dtype=np.float64).reshape(n, nq)
-            return 0
-        except BaseException as e:           # (an exception must not cross the C frame: hand it over and re-raise below)
-            failure.append(e)
-            return 1
+    def fill(n, pset_p, rows_p):
+        pset = np.ctypeslib.as_array(pset_p, shape=(n, P))
+        out = np.ctypeslib.as_array(rows_p, shape=(n, nq))
+        out[:, :] = np.asarray(row_fn(pset), dtype=np.float64).reshape(n, nq)
 
-    rc = lib.mcsas_hip_analyse_host_rows(C.byref(prob.c), _lib.RowsCallback(cb), None, int(window), C.byref(res.c))
+    cb, failure = _rows_callback(_lib.RowsCallback, fill)
+    rc = lib.mcsas_hip_analyse_host_rows(C.byref(prob.c), cb, None, int(window), C.byref(res.c))
     if failure:
         raise failure[0]
     check(rc, lib)
     return res
 
 
+def _rows_callback(ctype, fill):
+    """(callback, failure): `fill(n, ...)`, a rows callback's arguments after `user`, wrapped for ctypes.  An exception must not
+    cross the C frame: the callback hands it over in `failure` and returns 1, and the caller re-raises failure[0] after the call."""
+    failure = []
+
+    def cb(user, *args):
+        try:
+            fill(*args)
+            return 0
+        except BaseException as e:
+            failure.append(e)
+            return 1
+    return ctype(cb), failure
+
+
 def device_rows_shape(model: ModelSetup, q, st: Settings, window=64):
     """(min_rows, useful_rows, row_stride) of analyse_device_rows for this problem (mcsas_hip_device_rows_shape; no device is touched):
     the least and the most rows of a round, and the row pitch of the rows buffer (the q count rounded up to 64)."""
     q = f64(q).ravel()
-    return _rows_shape(_lib.load(), HipProblem(model, q, np.ones_like(q), np.ones_like(q), st), window)
+    prob = HipProblem(model, q, np.ones_like(q), np.ones_like(q), st)
+    return _shape_triple(_lib.load().mcsas_hip_device_rows_shape, prob, int(window))
 
 
-def _rows_shape(lib, prob, window):
+def _shape_triple(query, prob, *args):
+    """(min_rows, useful_rows, row_stride) as a shape query of the library answers for `prob`"""
     lo, hi, stride = C.c_int64(0), C.c_int64(0), C.c_int32(0)
-    check(lib.mcsas_hip_device_rows_shape(C.byref(prob.c), int(window), C.byref(lo), C.byref(hi), C.byref(stride)), lib)
+    check(query(C.byref(prob.c), *args, C.byref(lo), C.byref(hi), C.byref(stride)))
     return lo.value, hi.value, stride.value
+
+
+def _device_rows_tensors(who, shape, capacity, takes, device, n_active, vws=False):
+    """The torch side of a device-rows call: `capacity` (default: the most a round uses) checked against the shape query's answer,
+    then (capacity, device, pset[capacity][n_active], rows[capacity][stride], and with `vws` a third tensor [3][capacity]) on
+    `device` (< 0: torch's current one), complete before the library — which works on the null stream of its own — sees them."""
+    import torch
+    min_rows, useful_rows, stride = shape
+    capacity = int(useful_rows if capacity is None else capacity)
+    if capacity < min_rows:
+        raise ValueError("%s: capacity %d < %d rows, what %s" % (who, capacity, min_rows, takes))
+    _one_hip_runtime()
+    dev = torch.device("cuda", torch.cuda.current_device() if int(device) < 0 else int(device))
+    sizes = [(capacity, n_active), (capacity, stride)] + ([(3, capacity)] if vws else [])
+    tensors = [torch.empty(s, dtype=torch.float64, device=dev) for s in sizes]
+    torch.cuda.synchronize(dev)
+    return (capacity, dev, *tensors)
 
 
 def _one_hip_runtime():
@@ -366,40 +395,41 @@ def analyse_device_rows(model: ModelSetup, q, intensity, sigma, st: Settings, ro
     uses, device_rows_shape).  torch is imported here, not with the package."""
     import torch                                 # (ahead of the library's first load: see _one_hip_runtime)
     lib = _lib.load()
-    _one_hip_runtime()
+    _one_hip_runtime()                           # (this call's first refusal; _device_rows_tensors asks again, to no effect)
     prob = HipProblem(model, q, intensity, sigma, st, replay, stop, None)
     prob.c.model_id = MODEL_HOST
     nq, P = len(prob.q), model.n_active
-    min_rows, useful_rows, stride = _rows_shape(lib, prob, window)
-    capacity = int(useful_rows if capacity is None else capacity)
-    if capacity < min_rows:
-        raise ValueError("analyse_device_rows: capacity %d < %d rows, what one chain's round takes (max(n_contrib, window))" % (capacity, min_rows))
+    capacity, device, pset, rows = _device_rows_tensors(
+        "analyse_device_rows", _shape_triple(lib.mcsas_hip_device_rows_shape, prob, int(window)), capacity,
+        "one chain's round takes (max(n_contrib, window))", st.device, P)
     res = ChainResults(st.n_contrib, P, st.n_reps, nq)
-    device = torch.device("cuda", torch.cuda.current_device() if st.device < 0 else int(st.device))
-    pset = torch.empty((capacity, P), dtype=torch.float64, device=device)
-    rows = torch.empty((capacity, stride), dtype=torch.float64, device=device)
-    torch.cuda.synchronize(device)               # (the library works on the null stream of its own)
-    failure = []
 
-    def cb(user, n):
-        try:
-            with torch.cuda.device(device):
-                view = rows[:n, :nq]
-                out = row_fn(pset[:n], view)
-                if out is not None and out is not view:
-                    view.copy_(torch.as_tensor(out, dtype=torch.float64, device=device).reshape(n, nq))
-                torch.cuda.current_stream(device).synchronize()
-            return 0
-        except BaseException as e:           # (an exception must not cross the C frame: hand it over and re-raise below)
-            failure.append(e)
-            return 1
+    def fill(n):
+        with torch.cuda.device(device):
+            view = rows[:n, :nq]
+            out = row_fn(pset[:n], view)
+            if out is not None and out is not view:
+                view.copy_(torch.as_tensor(out, dtype=torch.float64, device=device).reshape(n, nq))
+            torch.cuda.current_stream(device).synchronize()
 
+    cb, failure = _rows_callback(_lib.DeviceRowsCallback, fill)
     rc = lib.mcsas_hip_analyse_device_rows(C.byref(prob.c), C.c_void_p(pset.data_ptr()), C.c_void_p(rows.data_ptr()), capacity,
-                                           _lib.DeviceRowsCallback(cb), None, int(window), C.byref(res.c))
+                                           cb, None, int(window), C.byref(res.c))
     if failure:
         raise failure[0]
     check(rc, lib)
     return res
+
+
+def _as_problem(p):
+    """A problem of analyse_many / analyse_batch as a dict: given as one, or as (model, q, intensity, sigma, settings)"""
+    return p if isinstance(p, dict) else dict(model=p[0], q=p[1], intensity=p[2], sigma=p[3], st=p[4])
+
+
+def _analyse_problem(pr):
+    """analyse() of such a dict, for what runs at its place in the sequence instead of with the others"""
+    return analyse(pr["model"], pr["q"], pr["intensity"], pr["sigma"], pr["st"], pr.get("replay"), pr.get("stop"), pr.get("smear"),
+                   start=pr.get("start"))
 
 
 def analyse_many(problems, streams=2):
@@ -408,7 +438,7 @@ def analyse_many(problems, streams=2):
     HIP streams, two per stream in flight, so the chip always has one analysis' scan-bound ticks beside another's producer-bound
     ones.  `problems`: sequence of (model: ModelSetup, q, intensity, sigma, settings) or of dicts with those keys
     plus optional replay / stop / smear.  Returns the ChainResults in order — each identical to analyse() of that problem."""
-    problems = [p if isinstance(p, dict) else dict(model=p[0], q=p[1], intensity=p[2], sigma=p[3], st=p[4]) for p in problems]
+    problems = [_as_problem(p) for p in problems]
     if not problems:
         return []
     lib = _lib.load(tuning=bool(problems[0]["st"].debug_flags))
@@ -422,10 +452,6 @@ def analyse_many(problems, streams=2):
             hs.append(h)
         return hs[k % len(hs)]
 
-    def direct(pr):
-        return analyse(pr["model"], pr["q"], pr["intensity"], pr["sigma"], pr["st"], pr.get("replay"), pr.get("stop"), pr.get("smear"),
-                       start=pr.get("start"))
-
     out, pending, launched = [None] * len(problems), [], {}
     try:
         for i, pr in enumerate(problems):
@@ -433,7 +459,7 @@ def analyse_many(problems, streams=2):
             # what a plan cannot do goes through mcsas_hip_analyse at its place in the sequence: a model with no active parameter
             # (one contribution, nothing to fit: mcsas.py:198-199) and a device list (the library shards the repetitions itself)
             if pr["model"].n_active == 0 or st.devices:
-                out[i] = direct(pr)
+                out[i] = _analyse_problem(pr)
                 continue
             cap = 2 * max(1, streams)
             while len(pending) >= cap:
@@ -476,7 +502,7 @@ def analyse_batch(problems):
     more than WAVE_MAX_Q q-points raises ValueError before anything is launched.  A problem may carry a "start" key (see analyse);
     a batch with one runs through resident plans (Plan.set_start, launch_batch, fetch), the problems without a start included, and
     each result is then identical to analyse(..., start=...) of that problem."""
-    problems = [p if isinstance(p, dict) else dict(model=p[0], q=p[1], intensity=p[2], sigma=p[3], st=p[4]) for p in problems]
+    problems = [_as_problem(p) for p in problems]
     starts = {}
     for i, pr in enumerate(problems):
         if pr.get("start") is not None and pr["model"].n_active > 0:
@@ -528,8 +554,7 @@ def analyse_batch(problems):
             out[i] = r
     for i, pr in enumerate(problems):
         if out[i] is None:
-            out[i] = analyse(pr["model"], pr["q"], pr["intensity"], pr["sigma"], pr["st"], pr.get("replay"), pr.get("stop"), pr.get("smear"),
-                             start=pr.get("start"))
+            out[i] = _analyse_problem(pr)
     return out
 
 
@@ -765,13 +790,7 @@ def histogram_rows_shape(model: ModelSetup, q, st_or_sizes):
         n_contrib, n_reps = st_or_sizes
         st = Settings(n_contrib=int(n_contrib), n_reps=int(n_reps))
     q = f64(q).ravel()
-    return _histogram_rows_shape(_lib.load(), HipProblem(model, q, np.ones_like(q), np.ones_like(q), st))
-
-
-def _histogram_rows_shape(lib, prob):
-    lo, hi, stride = C.c_int64(0), C.c_int64(0), C.c_int32(0)
-    check(lib.mcsas_hip_histogram_rows_shape(C.byref(prob.c), C.byref(lo), C.byref(hi), C.byref(stride)), lib)
-    return lo.value, hi.value, stride.value
+    return _shape_triple(_lib.load().mcsas_hip_histogram_rows_shape, HipProblem(model, q, np.ones_like(q), np.ones_like(q), st))
 
 
 def histogram_device_rows(model: ModelSetup, q, intensity, sigma, contribs, specs, row_fn, find_background=True,
@@ -791,37 +810,23 @@ def histogram_device_rows(model: ModelSetup, q, intensity, sigma, contribs, spec
                          % (model.n_active, c3.shape))
     call = _HistogramCall(model, q, intensity, sigma, c3, 0.0, specs, find_background, positive_background, device, None)
     call.prob.c.model_id = MODEL_HOST
-    N, P, R = call.contribs.shape
     nq = len(call.prob.q)
-    min_rows, useful_rows, stride = _histogram_rows_shape(lib, call.prob)
-    capacity = int(useful_rows if capacity is None else capacity)
-    if capacity < min_rows:
-        raise ValueError("histogram_device_rows: capacity %d < %d rows, what one repetition takes (n_contrib)" % (capacity, min_rows))
-    _one_hip_runtime()
-    dev = torch.device("cuda", torch.cuda.current_device() if int(device) < 0 else int(device))
-    pset = torch.empty((capacity, P), dtype=torch.float64, device=dev)
-    rows = torch.empty((capacity, stride), dtype=torch.float64, device=dev)
-    vws = torch.empty((3, capacity), dtype=torch.float64, device=dev)
-    torch.cuda.synchronize(dev)                  # (the library works on the null stream of its own)
-    failure = []
+    capacity, dev, pset, rows, vws = _device_rows_tensors(
+        "histogram_device_rows", _shape_triple(lib.mcsas_hip_histogram_rows_shape, call.prob), capacity,
+        "one repetition takes (n_contrib)", device, model.n_active, vws=True)
 
-    def cb(user, n):
-        try:
-            with torch.cuda.device(dev):
-                it, v, w, s = row_fn(pset[:n])
-                rows[:n, :nq].copy_(torch.as_tensor(it, dtype=torch.float64, device=dev).reshape(n, nq))
-                for k, x in enumerate((v, w, s)):
-                    vws[k, :n].copy_(torch.as_tensor(x, dtype=torch.float64, device=dev))
-                torch.cuda.current_stream(dev).synchronize()
-            return 0
-        except BaseException as e:           # (an exception must not cross the C frame: hand it over and re-raise below)
-            failure.append(e)
-            return 1
+    def fill(n):
+        with torch.cuda.device(dev):
+            it, v, w, s = row_fn(pset[:n])
+            rows[:n, :nq].copy_(torch.as_tensor(it, dtype=torch.float64, device=dev).reshape(n, nq))
+            for k, x in enumerate((v, w, s)):
+                vws[k, :n].copy_(torch.as_tensor(x, dtype=torch.float64, device=dev))
+            torch.cuda.current_stream(dev).synchronize()
 
+    cb, failure = _rows_callback(_lib.DeviceRowsCallback, fill)
     rc = lib.mcsas_hip_histogram_device_rows(C.byref(call.prob.c), as_dp(call.contribs), C.c_void_p(pset.data_ptr()),
                                              C.c_void_p(rows.data_ptr()), C.c_void_p(vws.data_ptr()), capacity,
-                                             _lib.DeviceRowsCallback(cb), None, len(call.specs), call.arr, as_dp(call.sc),
-                                             as_dp(call.frac), as_dp(call.out))
+                                             cb, None, len(call.specs), call.arr, as_dp(call.sc), as_dp(call.frac), as_dp(call.out))
     if failure:
         raise failure[0]
     check(rc, lib)

@@ -25,6 +25,19 @@ from .scatteringmodels import (setup_from_model, host_model_calc, is_batch_model
 DEVICE_ROWS_HISTOGRAM_DEFAULT = True
 
 
+def _q_on_device(q):
+    """`at(pset)`: q as a flat torch tensor on the device of `pset`, made at the first call and kept (torch is imported there, not
+    with the package): what a calcIntensityBatch model is handed beside the parameter sets of every round"""
+    kept = []
+
+    def at(pset):
+        if not kept:
+            import torch
+            kept.append(torch.as_tensor(np.ascontiguousarray(q, dtype=np.float64), device=pset.device).reshape(-1))
+        return kept[0]
+    return at
+
+
 class _Setting(object):
     """Algorithm parameter with the reference's accessors (`p()`, `p.value()`, `p.setValue(v)`)."""
 
@@ -176,13 +189,10 @@ class McSAS(object):
                 # ... or with calcIntensityBatch in torch: the rows of a whole round in one call on the device, where the library
                 # generated the proposals and decides on them (mcsas_hip_analyse_device_rows); the clipping of setValue on a copy
                 refuse_batch_smearing(model, data)
-                qdev = []
+                qdev = _q_on_device(pr["q"])
 
                 def rows_on_device(pset, out):
-                    if not qdev:
-                        import torch
-                        qdev.append(torch.as_tensor(np.ascontiguousarray(pr["q"], dtype=np.float64), device=pset.device).reshape(-1))
-                    return model.calcIntensityBatch(qdev[0], batch_clip(model, pset), c)[0]
+                    return model.calcIntensityBatch(qdev(pset), batch_clip(model, pset), c)[0]
                 res = engine.analyse_device_rows(pr["model"], pr["q"], pr["intensity"], pr["sigma"], pr["st"], rows_on_device,
                                                  replay=pr["replay"], stop=pr["stop"], window=self.hostRowWindow)
             else:
@@ -266,13 +276,10 @@ class McSAS(object):
                 # calcIntensityBatch in torch: the rows of a round of repetitions in one call on the device, where the library laid
                 # the sets out and takes the fit, the limits, the fractions and the histograms from them (mcsas_hip_histogram_device_rows)
                 refuse_batch_smearing(model, data)
-                qdev = []
+                qdev = _q_on_device(data.q)
 
                 def rows_on_device(pset):
-                    if not qdev:
-                        import torch
-                        qdev.append(torch.as_tensor(np.ascontiguousarray(data.q, dtype=np.float64), device=pset.device).reshape(-1))
-                    return model.calcIntensityBatch(qdev[0], batch_clip(model, pset), c)
+                    return model.calcIntensityBatch(qdev(pset), batch_clip(model, pset), c)
                 item = self._histogram_item(setup, None, contribs)
                 del item["comp_exp"], item["smear"]
                 self._histogram_from_device(engine.histogram_device_rows(row_fn=rows_on_device, **item))

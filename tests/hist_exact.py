@@ -1,7 +1,7 @@
 """Shared by test_hist_exact_host.py and test_hist_exact_gpu.py: what McSAS.histogram() reads off a set of contributions (visibility
 limits, fractions, bins, observability, cumulative distribution, moments: csrc/host_hist.hip hist_obs_body, hist_fractions_body,
-hist_bins_body), engine.observability (csrc/small_kernels.h observability_kernel) and the re-binning of raw data (csrc/host_calls.hip
-rebin_kernel) as
+hist_bins_body), engine.observability (csrc/small_kernels.h observability_kernel; both limits are its visibility_limit) and the
+re-binning of raw data (csrc/host_calls.hip rebin_kernel) as
   - the cases,
   - exact values (fractions.Fraction and mpmath, 60 digits) of the discrete operation at the doubles the kernel is given,
   - bounds derived from the kernels' operation order (tests/exact.py: R, V, gamma, reduced_sum), the line a count was read from next
@@ -116,10 +116,11 @@ def min_within(exact_candidates, delta):
 
 # ------------------------------------------------------------------------------------------------- exact values and bounds: histogram
 LIMIT_ROUNDINGS = 5
-# hist_obs_body: `vf = wset * A / vset` (two roundings), per q `scaled = A * row[k]` (one), `(sigma[k] * vf) / scaled` (two): a
-# quotient of products, five factors (1 + d) in all, within gamma(5) of sigma vf / (A row) = sigma w / (v row): A cancels.
+# hist_obs_body: `vf = wset * A / vset` (two roundings), then visibility_limit (small_kernels.h) with intensity(k) = row[k]: per q
+# `scaled = A * intensity(k)` (one), `(sigma[k] * vf) / scaled` (two): a quotient of products, five factors (1 + d) in all, within
+# gamma(5) of sigma vf / (A row) = sigma w / (v row): A cancels.
 OBS_ROUNDINGS = 3
-# observability_kernel: vf is the caller's double: `scaled = A * it`, `(sigma[k] * vf) / scaled`: three
+# observability_kernel: vf is the caller's double, intensity(k) the model's row: `scaled = A * intensity(k)`, `(sigma[k] * vf) / scaled`: three
 
 
 def scaled_classes(A, row):

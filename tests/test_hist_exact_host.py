@@ -146,7 +146,7 @@ def test_products_with_the_scale_are_the_class_the_case_says():
     assert set(cls(2)[0::2]) == {"zero"} and set(cls(2)[1::2]) == {"normal"}
     assert set(cls(3)[:32]) == {"underflow"} and set(cls(3)[32:]) == {"normal"}
     assert all(set(cls(i)) == {"normal"} for i in range(4, c["N"]))
-    assert fr["mv"][0, 0] == math.inf and fr["mv"][1, 0] == math.inf              # an empty minimum: +inf (hist_obs_body's `best = INFINITY`)
+    assert fr["mv"][0, 0] == math.inf and fr["mv"][1, 0] == math.inf              # an empty minimum: +inf (visibility_limit's `best = __builtin_inf()`)
     assert all(not H.special(fr["mv"][i, 0]) for i in range(2, c["N"]))
     c, A, _ = case("n64")
     i = c["claims"]["min_at_last_q"]

@@ -1429,7 +1429,8 @@ def test_pipeline_geometry_follows_the_chain_count():
 def test_plugin_model_replays_the_reference_and_equals_its_built_in_twin(tag, name):
     """A model that reaches the library as HIP source text (mcsas_hip_plugin_compile) runs the same kernels as the built-in
     ones, in every execution mode: written operation for operation like its built-in twin it replays the reference's trajectory
-    and is bit-identical to the twin — chain results, ScatteringModel.calc and the histogram preparation alike."""
+    and is bit-identical to the twin — chain results, ScatteringModel.calc, the histogram preparation and the visibility limits
+    alike."""
     from helpers import plugin_twin
     g, m, spec, st, ost = traj_setup(name)
     q, I, sig = g["data_q"], g["data_I"], g["data_sigma"]
@@ -1442,6 +1443,9 @@ def test_plugin_model_replays_the_reference_and_equals_its_built_in_twin(tag, na
     pset = np.array(ref.contribs[:, :, 0])
     calc_ref = engine.model_calc(m.setup(), q, pset, st.comp_exp, want_rows=True)
     prep_ref = engine.histogram_prep(m.setup(), q, I, sig, ref.contribs, st.comp_exp, st.find_background, st.positive_background)
+    sc, v, w = prep_ref[0], prep_ref[1], prep_ref[2]
+    vf = w * sc[0][None, :] / v
+    obs_ref = engine.observability(m.setup(), q, sig, ref.contribs, sc[0], vf, st.comp_exp)
     plugin_twin(m, tag)
     setup = m.setup(FakeData(q))
     assert setup.model_id >= engine.MODEL_PLUGIN0
@@ -1456,6 +1460,7 @@ def test_plugin_model_replays_the_reference_and_equals_its_built_in_twin(tag, na
         assert np.array_equal(a, b)
     for a, b in zip(engine.histogram_prep(setup, q, I, sig, ref.contribs, st.comp_exp, st.find_background, st.positive_background), prep_ref):
         assert np.array_equal(a, b)
+    assert np.array_equal(engine.observability(setup, q, sig, ref.contribs, sc[0], vf, st.comp_exp), obs_ref)
     # more than 1024 q-points: the q-split workgroup kernel, compiled for the plug-in like the others (what auto picks); one
     # wavefront per chain is refused for a plug-in there, not silently replaced
     qw, Iw, sw = _synthetic(1500)
