@@ -21,10 +21,10 @@ typedef double v2f64 __attribute__((ext_vector_type(2)));
 // with v_mfma_f64_16x16x4_f64: D(16x16) += A(16x4) B(4x16), lane l supplies A[l % 16][l / 16] and
 // B[l / 16][l % 16], result register r holds D[4 r + l / 16][l % 16].  With A = d rows and B = (w d) rows both
 // operands of lane l are the SAME element (row l % 16, q-slot l / 16) — one load, one multiply, one MFMA.
-// Wave v takes the q slice [v 8 QPL, (v + 1) 8 QPL) for ALL tiles (every row element is loaded exactly once
-// per block); one operand load covers 8 consecutive q of the slice, two per lane slot kk = l / 16 (any
-// assignment of q to MFMA k-slots is fine, the sum runs over all of them).
-// The eight partial tiles are then summed in wave order through LDS (deterministic) and written to
+// The q range is cut into eight slices, slice v = [v 8 QPL, (v + 1) 8 QPL), each summed for ALL tiles into a partial of
+// its own (which waves take them: pipe_prod_gram_lds_t); one operand load covers 8 consecutive q of the slice, two per
+// lane slot kk = l / 16 (any assignment of q to MFMA k-slots is fine, the sum runs over all of them).
+// The eight partial tiles are then summed in slice order through LDS (deterministic) and written to
 // gout[a][k], a, k < W.
 
 // tile number -> (row group, column group) of the upper triangle, and the store of one summed element
@@ -48,18 +48,26 @@ __device__ __forceinline__ void pipe_gram_store(int tsel, int idx, double sum, i
 // PACK (W = 24, three 8-row groups g0 g1 g2): the six upper-triangular 8x8 blocks fit TWO 16x16 tiles instead of the
 // three of the 16-row grouping — tile 0 = rows [g0 g1] x columns [g1 g2] (blocks 01 02 11 12), tile 1 = rows and
 // columns [g0 g2] (blocks 00 22; its 02 is a duplicate and not stored): a third fewer MFMAs.
-template <int QPL, int T, bool PACK>
-__device__ __forceinline__ void pipe_gram_mfma_lds(const double *drows, int dstr, int nvalid, const double *lw, int gw,
-                                                   v4f64 (&acc)[PACK ? 2 : T * (T + 1) / 2]) {
+// One call takes the tiles [R0, R0 + RN) of the sub-window's NT (a round of the reduction) for NS slices, gw and (NS = 2) gw + 4,
+// each slice into an accumulator set of its own: every tile of a slice is accumulated over the slice in the same order whichever
+// call takes it.  The operands of the next 8 q are requested in front of the MFMAs of the current ones (pinned by the scheduling
+// barrier): one wave has to cover its own LDS latency — the partner wave of its SIMD, which used to, is not in here — and the
+// MFMAs of the two slices alternate, four independent accumulator chains.
+template <int QPL, int T, bool PACK, int R0, int RN, int NS>
+__device__ __forceinline__ void pipe_gram_mfma_lds(const double *drows, int dstr, int nvalid, const double *lw, int gw, v4f64 (&acc)[NS][RN]) {
     const int lane = threadIdx.x & 63;
     const int m = lane & 15, kk = lane >> 4;
     constexpr int NT = PACK ? 2 : T * (T + 1) / 2;
-    constexpr int NL = PACK ? 3 : T;                          // row operands per lane and step-pair
-    constexpr int SLICE = 64 * QPL / PIPE_WAVES;
+    constexpr int NL = PACK ? 3 : T;                          // row operands per lane, slice and step-pair
+    constexpr int SLICE = 64 * QPL / PIPE_WAVES, STEPS = SLICE / 8;
+    constexpr int SSTR = (PIPE_WAVES / 2) * SLICE;            // from slice gw to slice gw + 4
     static_assert(SLICE >= 8, "too many waves for this q count");
+    static_assert(R0 >= 0 && RN >= 1 && R0 + RN <= NT && (!PACK || (R0 == 0 && RN == 2)) && (NS == 1 || NS == 2), "tiles and slices of the sub-window");
     const int qs = gw * SLICE + kk * 2;
 #pragma unroll
-    for (int i = 0; i < NT; ++i) acc[i] = (v4f64){0., 0., 0., 0.};
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int i = 0; i < RN; ++i) acc[s][i] = (v4f64){0., 0., 0., 0.};
     const double *rowp[NL];
     bool rowok[NL];
 #pragma unroll
@@ -68,31 +76,60 @@ __device__ __forceinline__ void pipe_gram_mfma_lds(const double *drows, int dstr
         rowok[gi] = rr < nvalid;
         rowp[gi] = drows + (size_t)(rowok[gi] ? rr : 0) * dstr + qs;
     }
+    auto fetch = [&](int sp, v2f64 (&x)[NS][NL], v2f64 (&wv)[NS]) {
 #pragma unroll
-    for (int sp = 0; sp < SLICE / 8; ++sp) {
-        v2f64 av[NL], bv[NL];
-        const v2f64 wv = *reinterpret_cast<const v2f64 *>(lw + qs + 8 * sp);
+        for (int s = 0; s < NS; ++s) {
+            wv[s] = *reinterpret_cast<const v2f64 *>(lw + qs + s * SSTR + 8 * sp);
 #pragma unroll
-        for (int gi = 0; gi < NL; ++gi) {
-            const v2f64 x = *reinterpret_cast<const v2f64 *>(rowp[gi] + 8 * sp);
-            av[gi] = rowok[gi] ? x : (v2f64){0., 0.};
-            bv[gi] = av[gi] * wv;
+            for (int gi = 0; gi < NL; ++gi) x[s][gi] = *reinterpret_cast<const v2f64 *>(rowp[gi] + s * SSTR + 8 * sp);   // (a row group no tile of this call needs is not loaded: dead code)
         }
+    };
+    v2f64 cur[NS][NL], cw[NS];
+    fetch(0, cur, cw);
+#pragma unroll
+    for (int sp = 0; sp < STEPS; ++sp) {
+        v2f64 nxt[NS][NL], nw[NS];
+        if (sp + 1 < STEPS) fetch(sp + 1, nxt, nw);
+        __builtin_amdgcn_sched_barrier(0);
+        v2f64 av[NS][NL], bv[NS][NL];
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+#pragma unroll
+            for (int gi = 0; gi < NL; ++gi) {
+                av[s][gi] = rowok[gi] ? cur[s][gi] : (v2f64){0., 0.};
+                bv[s][gi] = av[s][gi] * cw[s];
+            }
         if constexpr (PACK) {
-            acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[0].x, bv[1].x, acc[0], 0, 0, 0);
-            acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[2].x, bv[2].x, acc[1], 0, 0, 0);
-            acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[0].y, bv[1].y, acc[0], 0, 0, 0);
-            acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[2].y, bv[2].y, acc[1], 0, 0, 0);
+#pragma unroll
+            for (int s = 0; s < NS; ++s) acc[s][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s][0].x, bv[s][1].x, acc[s][0], 0, 0, 0);
+#pragma unroll
+            for (int s = 0; s < NS; ++s) acc[s][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s][2].x, bv[s][2].x, acc[s][1], 0, 0, 0);
+#pragma unroll
+            for (int s = 0; s < NS; ++s) acc[s][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s][0].y, bv[s][1].y, acc[s][0], 0, 0, 0);
+#pragma unroll
+            for (int s = 0; s < NS; ++s) acc[s][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s][2].y, bv[s][2].y, acc[s][1], 0, 0, 0);
         } else {
             int ti = 0;
 #pragma unroll
             for (int gi = 0; gi < T; ++gi)
 #pragma unroll
                 for (int gj = gi; gj < T; ++gj) {
-                    acc[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[gi].x, bv[gj].x, acc[ti], 0, 0, 0);
-                    acc[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[gi].y, bv[gj].y, acc[ti], 0, 0, 0);
+                    if (ti >= R0 && ti < R0 + RN) {
+#pragma unroll
+                        for (int s = 0; s < NS; ++s) acc[s][ti - R0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s][gi].x, bv[s][gj].x, acc[s][ti - R0], 0, 0, 0);
+#pragma unroll
+                        for (int s = 0; s < NS; ++s) acc[s][ti - R0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s][gi].y, bv[s][gj].y, acc[s][ti - R0], 0, 0, 0);
+                    }
                     ++ti;
                 }
+        }
+        if (sp + 1 < STEPS) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                cw[s] = nw[s];
+#pragma unroll
+                for (int gi = 0; gi < NL; ++gi) cur[s][gi] = nxt[s][gi];
+            }
         }
     }
 }
@@ -111,47 +148,81 @@ __device__ __forceinline__ void pipe_gram_store_pack(int tsel, int idx, double s
     }
 }
 
-template <int QPL, int T, bool PACK>
-__device__ __forceinline__ void pipe_prod_gram_lds_t(const double *drows, int dstr, int W, int nvalid, const double *lw,
-                                                     double *gred, MCSAS_GLOBAL double *gout, MCSAS_GLOBAL double *scal_sub) {
+// Roles (`split`, the release path): only the MATRIX waves 0-3 — one per SIMD, the older of each pair, whose few operand
+// multiplies win the vector arbitration — issue the MFMAs: wave v takes the two q slices that waves v and v + 4 take with
+// eight Gram waves, each in an accumulator set of its own, in the same order, to the same partial slots v and v + 4 of gred;
+// the sum over the eight partials and the store are unchanged, so the block comes out bit for bit the same.  The matrix pipe
+// of a SIMD sees the same MFMAs either way; its vector pipe is free for the ROW waves 4-7, which come here late (pipe_prod.h:
+// from a row of the next sub-window, evaluated beside the first MFMAs), issue none, and call `behind()` once the barrier
+// behind the LAST operand read is passed.  !split (a tuning build's bit 17): eight Gram waves, nobody calls it.
+// A sub-window of more than PIPE_GRAM_TILES_PER_ROUND tiles takes several rounds of the reduction buffer: the MFMAs of a round's
+// tiles are issued in front of that round (a tile's accumulators — two sets on a matrix wave — live for one round only: the
+// operands are read again from LDS, a tile's MFMAs are issued once).
+// Barriers: every wave passes 2 * ceil(NT / TPR) - 1 of them, whatever its role: one per round, one between two rounds.
+template <int QPL, int T, bool PACK, int R0, class Behind>
+__device__ __forceinline__ void pipe_gram_round(const double *drows, int dstr, int W, int nvalid, const double *lw, double *gred,
+                                                MCSAS_GLOBAL double *gout, MCSAS_GLOBAL double *scal_sub, bool split, bool matrix, Behind &&behind) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int NT = PACK ? 2 : T * (T + 1) / 2;
-    v4f64 acc[NT];
-    pipe_gram_mfma_lds<QPL, T, PACK>(drows, dstr, nvalid, lw, wave, acc);
-    constexpr int TPR = PIPE_GRAM_TILES_PER_ROUND;
+    constexpr int TPR = PIPE_GRAM_TILES_PER_ROUND, RN = NT - R0 < TPR ? NT - R0 : TPR;
+    constexpr int MW = PIPE_WAVES / 2;                        // matrix waves
+    if (matrix) {
+        auto park = [&](int slot, const v4f64 (&acc)[RN]) {   // a slice's partial tiles -> its slots of the reduction buffer
 #pragma unroll
-    for (int r0 = 0; r0 < NT; r0 += TPR) {
+            for (int u = 0; u < RN; ++u)
 #pragma unroll
-        for (int u = 0; u < TPR; ++u)
-            if (r0 + u < NT) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) gred[((size_t)(wave * TPR + u) * 4 + r) * 64 + lane] = acc[r0 + u < NT ? r0 + u : 0][r];
-            }
-        PIPE_LDS_BARRIER();
-        {
-            const int u = tid >> 8, idx = tid & 255;
-            const int tsel = r0 + u;
-            if (tsel < NT) {
-                double sum = 0.;
-#pragma unroll
-                for (int v = 0; v < PIPE_WAVES; ++v) sum += gred[(size_t)(v * TPR + u) * 256 + idx];
-                if constexpr (PACK) pipe_gram_store_pack(tsel, idx, sum, gout, scal_sub);
-                else pipe_gram_store<T>(tsel, idx, sum, W, gout, scal_sub);
-            }
+                for (int r = 0; r < 4; ++r) gred[((size_t)(slot * TPR + u) * 4 + r) * 64 + lane] = acc[u][r];
+        };
+        if (split) {
+            v4f64 acc[2][RN];
+            pipe_gram_mfma_lds<QPL, T, PACK, R0, RN, 2>(drows, dstr, nvalid, lw, wave, acc);
+            park(wave, acc[0]); park(wave + MW, acc[1]);
+        } else {
+            v4f64 acc[1][RN];
+            pipe_gram_mfma_lds<QPL, T, PACK, R0, RN, 1>(drows, dstr, nvalid, lw, wave, acc);
+            park(wave, acc[0]);
         }
-        if (r0 + TPR < NT) PIPE_LDS_BARRIER();
+    }
+    PIPE_LDS_BARRIER();
+    if (R0 + TPR >= NT && !matrix) behind();                  // every operand read lies in front of this round's barrier
+    {
+        const int u = tid >> 8, idx = tid & 255;
+        const int tsel = R0 + u;
+        if (tsel < NT) {
+            double sum = 0.;
+#pragma unroll
+            for (int v = 0; v < PIPE_WAVES; ++v) sum += gred[(size_t)(v * TPR + u) * 256 + idx];
+            if constexpr (PACK) pipe_gram_store_pack(tsel, idx, sum, gout, scal_sub);
+            else pipe_gram_store<T>(tsel, idx, sum, W, gout, scal_sub);
+        }
+    }
+    if constexpr (R0 + TPR < NT) {
+        PIPE_LDS_BARRIER();
+        pipe_gram_round<QPL, T, PACK, R0 + TPR>(drows, dstr, W, nvalid, lw, gred, gout, scal_sub, split, matrix, behind);
     }
 }
 
-template <int QPL>
+template <int QPL, int T, bool PACK, class Behind>
+__device__ __forceinline__ void pipe_prod_gram_lds_t(const double *drows, int dstr, int W, int nvalid, const double *lw,
+                                                     double *gred, MCSAS_GLOBAL double *gout, MCSAS_GLOBAL double *scal_sub,
+                                                     bool split, Behind &&behind) {
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const bool matrix = !split || wave < PIPE_WAVES / 2;      // uniform in the wave
+    pipe_gram_round<QPL, T, PACK, 0>(drows, dstr, W, nvalid, lw, gred, gout, scal_sub, split, matrix, behind);
+}
+
+// (a sub-window of T 16-row groups has at least 2 T - 1 rows per wave: the QPL whose row registers that exceeds never see it,
+// pipe_geometry's pick_w — the same rule as the scan block's cases in chain_pipe.h)
+template <int QPL, class Behind>
 __device__ __forceinline__ void pipe_prod_gram_lds(const double *drows, int dstr, int W, int nvalid, const double *lw,
-                                                   double *gred, MCSAS_GLOBAL double *gout, MCSAS_GLOBAL double *scal_sub) {
-    if (W == 24) { pipe_prod_gram_lds_t<QPL, 2, true>(drows, dstr, W, nvalid, lw, gred, gout, scal_sub); return; }
+                                                   double *gred, MCSAS_GLOBAL double *gout, MCSAS_GLOBAL double *scal_sub,
+                                                   bool split, Behind &&behind) {
+    if (W == 24) { pipe_prod_gram_lds_t<QPL, 2, true>(drows, dstr, W, nvalid, lw, gred, gout, scal_sub, split, behind); return; }
     switch ((W + 15) >> 4) {                                   // uniform for the launch
-        case 1: pipe_prod_gram_lds_t<QPL, 1, false>(drows, dstr, W, nvalid, lw, gred, gout, scal_sub); break;
-        case 2: pipe_prod_gram_lds_t<QPL, 2, false>(drows, dstr, W, nvalid, lw, gred, gout, scal_sub); break;
-        case 3: pipe_prod_gram_lds_t<QPL, 3, false>(drows, dstr, W, nvalid, lw, gred, gout, scal_sub); break;
-        default: pipe_prod_gram_lds_t<QPL, 4, false>(drows, dstr, W, nvalid, lw, gred, gout, scal_sub); break;
+#define PIPE_GRAM_CASE(T) case T: if constexpr ((2 * T - 1) * QPL <= PIPE_MAX_ROW_DOUBLES) pipe_prod_gram_lds_t<QPL, T, false>(drows, dstr, W, nvalid, lw, gred, gout, scal_sub, split, behind); break;
+        PIPE_GRAM_CASE(1) PIPE_GRAM_CASE(2) PIPE_GRAM_CASE(3) PIPE_GRAM_CASE(4)
+#undef PIPE_GRAM_CASE
+        default: break;
     }
 }
 

@@ -216,8 +216,8 @@ __device__ __forceinline__ void pipe_prod_block(const PipeArgs &pa, const PipeHo
         };
         if (pa.g.gram_lds) {
             // ---- default: sub-window by sub-window — the waves evaluate the sub-window's rows (d also into the LDS row
-            // buffer), barrier, the eight waves take the Gram block from LDS, next sub-window.  Only the LDS traffic is waited
-            // for at the barriers: the rows' global stores drain behind the MFMAs.
+            // buffer), barrier, waves 0-3 take the Gram block from LDS while waves 4-7 start on the next sub-window's rows (below),
+            // next sub-window.  Only the LDS traffic is waited for at the barriers: the rows' global stores drain behind the MFMAs.
             // No wave has rows of its own: a wave CLAIMS the block's rows one by one from a counter in LDS (one returning add
             // by lane 0), always the next row before it evaluates the current one, so that the next `old` row is under way a
             // row ahead.  The SIMD arbitrates oldest-first, so of two waves that share one the younger (4-7) is the slower; with a
@@ -296,66 +296,98 @@ __device__ __forceinline__ void pipe_prod_block(const PipeArgs &pa, const PipeHo
 #ifdef MCSAS_STAMPS
             int nmine = 0;                                        // rows this wave has evaluated
 #endif
+            // Roles in the Gram phase (pipe_gram.h): waves 0-3 issue the MFMAs of sub-window ss, waves 4-7 meanwhile go on with the row
+            // they hold a claim on — a row of sub-window ss + 1; one HELD row per wave —: d to the window buffer and (a, e) to scal
+            // as ever, but d stays in registers while dbuf is still being read and goes to its LDS row behind the barrier that ends
+            // the operand reads.  A wave whose claim lies behind the block (always so in the block's last sub-window) goes straight
+            // to that barrier.  Tuning bit 17: eight Gram waves and no held row, as before the roles.
+            // s_barriers per sub-window, the same for EVERY wave of the block (ss, W, nvalid, no_gram and the tuning word are uniform
+            // in the block; a wave's role, its claim and whether it holds a row change what it does BETWEEN barriers only):
+            //   no_gram                      0
+            //   nvalid == 0                  1   rows -> Gram (the Gram block is skipped by all waves: nobody holds a row either)
+            //   else                         1 + (2 R - 1), R = ceil(tiles / PIPE_GRAM_TILES_PER_ROUND) rounds of the reduction
+            //                                (pipe_prod_gram_lds_t: matrix waves, row waves with or without a held row, and the eight
+            //                                Gram waves of bit 17 all pass the same 2 R - 1)
+            // The row loop itself has no barrier: a wave that claims no row of a sub-window passes the same ones.
+            const bool roles = !(MCSAS_TUNE_BITS(a) & (1 << 17));
+            const bool row_wave = roles && __builtin_amdgcn_readfirstlane(wave) >= WPB / 2;
+            // one row of the block: the wave's claim kc, which belongs to sub-window sr; HOLD: no LDS copy, d is the caller's to keep
+            auto eval_row = [&](int sr, auto hold, double (&d)[QPL]) {
+                const int kn = take();
+                const int k = by * BR + kc;
+                Contrib<M> cnew;
+                int sslot = 0;
+                {
+                    Contrib<M> cl;
+                    double tmp[CON];
+#pragma unroll
+                    for (int i = 0; i < (int)(sizeof(Contrib<M>) / 8); ++i) tmp[i] = prec[kc * CON + i];   // one address for the wave
+                    __builtin_memcpy(&cl, tmp, sizeof(Contrib<M>));
+                    cnew = cl.bcast(0);
+                    if (!lazy) sslot = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int32_t *>(prec + kc * CON + CON - 1)[1]);
+                }
+                double nwv[QPL];
+                {
+                    const auto orow = cache + (size_t)oslot_of(kn < BR ? kn : kc) * qpad + lane;
+#pragma unroll
+                    for (int j = 0; j < QPL; ++j) onext[j] = orow[WAVE * j];
+                }
+                // (a row behind max_iter — the last window of a run only — is claimed and evaluated like any other: its proposal
+                // is the generators' midpoint, its stores land in slots nobody reads, the Gram block masks it)
+                const auto nrow = cache + (size_t)sslot * qpad + lane;
+                const auto dr = dwin + (size_t)k * qpad + lane;
+                double *dl = dbuf + (size_t)(kc - sr * W) * dstr + lane;
+                RowEval<M, QPL>::run(cnew, qt, lane, nwv);
+#ifdef MCSAS_STAMPS                                               /* marks 4..11: the first four rows I claimed — evaluated / `old` rows there and stores out */
+                if (nmine < 4) { PIPE_PIN_ROW(nwv); PIPE_TL_MARK(pa, t, 4 + 2 * nmine); }
+#endif
+                PIPE_PIN_ROW(ocur); PIPE_PIN_ROW(onext); PIPE_PIN_ROW(nwv);   // both `old` rows have landed before the first store is issued
+                double s1 = 0., s2 = 0.;
+#pragma unroll
+                for (int j = 0; j < QPL; ++j) {
+                    const int iq = lane + WAVE * j;
+                    if (!lazy) nrow[WAVE * j] = nwv[j];
+                    d[j] = nwv[j] - ocur[j];
+                    dr[WAVE * j] = d[j];
+                    if constexpr (!decltype(hold)::value) dl[WAVE * j] = d[j];
+                    s1 = fma(lw[iq], d[j], s1); s2 = fma(lwI[iq], d[j], s2);
+                }
+                // a = sum w d (even lanes), e = sum wI d (odd lanes); g = sum w d^2 is the Gram block's diagonal
+                const double ae = wave_sum2_split(s1, s2, lane);
+                if (lane < 2) scal[(size_t)k * 4 + lane] = ae;
+#pragma unroll
+                for (int j = 0; j < QPL; ++j) ocur[j] = onext[j];
+#ifdef MCSAS_STAMPS
+                if (nmine < 4) PIPE_TL_MARK(pa, t, 5 + 2 * nmine);
+                ++nmine;
+#endif
+                kc = kn;
+            };
             for (int ss = 0; ss < nsb; ++ss) {
                 while (kc < (ss + 1) * W) {
-                    const int kn = take();
-                    const int k = by * BR + kc;
-                    Contrib<M> cnew;
-                    int sslot = 0;
-                    {
-                        Contrib<M> cl;
-                        double tmp[CON];
-#pragma unroll
-                        for (int i = 0; i < (int)(sizeof(Contrib<M>) / 8); ++i) tmp[i] = prec[kc * CON + i];   // one address for the wave
-                        __builtin_memcpy(&cl, tmp, sizeof(Contrib<M>));
-                        cnew = cl.bcast(0);
-                        if (!lazy) sslot = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int32_t *>(prec + kc * CON + CON - 1)[1]);
-                    }
-                    double d[QPL], nwv[QPL];
-                    {
-                        const auto orow = cache + (size_t)oslot_of(kn < BR ? kn : kc) * qpad + lane;
-#pragma unroll
-                        for (int j = 0; j < QPL; ++j) onext[j] = orow[WAVE * j];
-                    }
-                    // (a row behind max_iter — the last window of a run only — is claimed and evaluated like any other: its proposal
-                    // is the generators' midpoint, its stores land in slots nobody reads, the Gram block masks it)
-                    const auto nrow = cache + (size_t)sslot * qpad + lane;
-                    const auto dr = dwin + (size_t)k * qpad + lane;
-                    double *dl = dbuf + (size_t)(kc - ss * W) * dstr + lane;
-                    RowEval<M, QPL>::run(cnew, qt, lane, nwv);
-#ifdef MCSAS_STAMPS                                               /* marks 4..11: the first four rows I claimed — evaluated / `old` rows there and stores out */
-                    if (nmine < 4) { PIPE_PIN_ROW(nwv); PIPE_TL_MARK(pa, t, 4 + 2 * nmine); }
-#endif
-                    PIPE_PIN_ROW(ocur); PIPE_PIN_ROW(onext); PIPE_PIN_ROW(nwv);   // both `old` rows have landed before the first store is issued
-                    double s1 = 0., s2 = 0.;
-#pragma unroll
-                    for (int j = 0; j < QPL; ++j) {
-                        const int iq = lane + WAVE * j;
-                        if (!lazy) nrow[WAVE * j] = nwv[j];
-                        d[j] = nwv[j] - ocur[j];
-                        dr[WAVE * j] = d[j];
-                        dl[WAVE * j] = d[j];
-                        s1 = fma(lw[iq], d[j], s1); s2 = fma(lwI[iq], d[j], s2);
-                    }
-                    // a = sum w d (even lanes), e = sum wI d (odd lanes); g = sum w d^2 is the Gram block's diagonal
-                    const double ae = wave_sum2_split(s1, s2, lane);
-                    if (lane < 2) scal[(size_t)k * 4 + lane] = ae;
-#pragma unroll
-                    for (int j = 0; j < QPL; ++j) ocur[j] = onext[j];
-#ifdef MCSAS_STAMPS
-                    if (nmine < 4) PIPE_TL_MARK(pa, t, 5 + 2 * nmine);
-                    ++nmine;
-#endif
-                    kc = kn;
+                    double d[QPL];
+                    eval_row(ss, std::false_type{}, d);
                 }
                 PIPE_TL_MARK(pa, t, 2 * (ss < 4 ? ss : 3));
                 if (!no_gram) PIPE_LDS_BARRIER();                 // the sub-window's rows are in LDS
                 const int nvalid = nvalid_of(ss);
-                if (nvalid > 0 && !no_gram)                       // uniform in the block
+                if (nvalid > 0 && !no_gram) {                     // uniform in the block
+                    double dheld[QPL];
+                    int kheld = -1;                               // the row this wave evaluates beside the MFMAs (uniform in the wave)
+                    // (the claims are handed out in order, eight at most beyond a sub-window: the second bound holds for every W
+                    // pipe_geometry picks and keeps the LDS row inside dbuf for any other)
+                    if (row_wave && kc < BR && kc < (ss + 2) * W) { kheld = kc; eval_row(ss + 1, std::true_type{}, dheld); }
                     pipe_prod_gram_lds<QPL>(dbuf, dstr, W, nvalid, lw, gred, gwin + (size_t)(by * nsb + ss) * W * W,
-                                            scal + (size_t)(by * BR + ss * W) * 4);
-                // (the next sub-window's rows overwrite dbuf only behind the reduction's first barrier, which every wave
-                // passes after its last operand read; gred is written again behind the next rows -> Gram barrier)
+                                            scal + (size_t)(by * BR + ss * W) * 4, roles, [&]() {
+                                                if (kheld >= 0) {
+                                                    double *dl = dbuf + (size_t)(kheld - (ss + 1) * W) * dstr + lane;
+#pragma unroll
+                                                    for (int j = 0; j < QPL; ++j) dl[WAVE * j] = dheld[j];
+                                                }
+                                            });
+                }
+                // (the next sub-window's rows — a held one first — overwrite dbuf only behind the barrier of the reduction's last
+                // round, which every wave passes after the last operand read; gred is written again behind the next rows -> Gram barrier)
                 PIPE_TL_MARK(pa, t, 2 * (ss < 4 ? ss : 3) + 1);
             }
             PIPE_TL_MARK(pa, t, 17);
