@@ -458,6 +458,34 @@ int mcsas_hip_histogram_device_rows(const mcsas_problem *problem, const double *
                                     int32_t n_hist, const mcsas_histogram_spec *specs,
                                     double *scaling, double *fractions, double *out);
 
+/* ---- the joint histogram of TWO fit parameters (additive to ABI 5; the reference has no counterpart) ----------------------------
+ * Takes the fractions a histogram call returned and evaluates no model: it serves every path that ends in them, and doubles of the
+ * caller's own.  contribs [n_contrib][n_active][n_reps] as in mcsas_result; fractions [8][n_contrib][n_reps] as mcsas_hip_histogram
+ * returns them (vol, num, int, surf fractions, then their visibility limits).
+ *   specs[h]: param_x / param_y = columns of contribs (they may be equal); weighting 0 vol, 1 num, 2 int, 3 surf; edges_x / edges_y =
+ *             n_bin_x + 1 / n_bin_y + 1 lower edges, finite and non-decreasing (equal neighbours: an empty column); lower_* / upper_*
+ *             = the value ranges of the moments; reserved must be 0.  An axis without bins does not read its edges.
+ *   out = per histogram, one after the other: bins[n_bin_x][n_bin_y][n_reps], obs[n_bin_x][n_bin_y][n_reps], moments[7][n_reps]
+ *         (total, mean x, mean y, variance x, variance y, covariance, correlation).
+ * Per axis the rules are the 1-D call's.  With edges e[0..n] a value x lies in column i = #{k : e[k] <= x} - 1 iff 0 <= i < n (a NaN
+ * in none); a contribution is in cell (i, j) iff it is in column i of x and column j of y.  bins = the sum of the weighting's fraction
+ * over the cell's members in contribution order (a NaN sum is stored as 0), obs = the same sum of their visibility limits over their
+ * count (0 for an empty cell).  The moments run over the contributions with lower_x < x < upper_x && lower_y < y < upper_y, every sum
+ * in contribution order: tot = S f; mx = S x f (/ tot unless tot == 0), my alike; vxx = S ((dx dx) f) / tot with dx = x - mx, vyy
+ * alike; cxy = S ((dx dy) f) / tot; rho = cxy / (sqrt|vxx| sqrt|vyy|) unless that product is exactly 0 (then 0; NaN goes on);
+ * all seven 0 where no contribution is inside.  With a y range that holds every value tot, mx, vxx are the 1-D call's total, mean,
+ * variance bit for bit, and with one y column that holds every value bins and obs are the 1-D call's.
+ * 1 <= n_contrib <= 4096, n_bin_x, n_bin_y >= 0 with n_bin_x * n_bin_y <= 4096 (zero bins on an axis: moments only).
+ * Refused with MCSAS_EINVAL before a device is touched, the message naming the histogram: NULL tables, n_hist < 0, a non-zero
+ * reserved, sizes and indices outside those limits, edges that are not finite or fall.  n_hist == 0: MCSAS_OK, no device touched. */
+typedef struct mcsas_histogram2d_spec {
+    int32_t param_x, param_y, weighting, n_bin_x, n_bin_y, reserved;
+    double  lower_x, upper_x, lower_y, upper_y;
+    const double *edges_x, *edges_y;
+} mcsas_histogram2d_spec;
+int mcsas_hip_histogram2d(int32_t n_contrib, int32_t n_active, int32_t n_reps, const double *contribs, const double *fractions,
+                          int32_t n_hist, const mcsas_histogram2d_spec *specs, double *out, int32_t device);
+
 /* ---- input preparation ----------------------------------------------------------
  * DataObj._prepareUncertainty (dataobj/dataobj.py:204-227): sigma_out = max(sigma_raw, fu_min * I),
  * fu_min * I when sigma_raw is NULL (no uncertainty column), +inf where that is not finite. */

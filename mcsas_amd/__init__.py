@@ -8,7 +8,7 @@ fails loudly if libmcsas_hip.so is not built (there is no CPU fallback).
 from .engine import (ModelSetup, Settings, analyse, model_calc, bgfit, observability, Plan,     # noqa: F401
                      device_count, GEN_UNIFORM, GEN_EXP1, GEN_EXP2, GEN_EXP3)
 from .parameter import (Parameter, FitParameter, RandomUniform, RandomExponential,               # noqa: F401
-                        RandomExponential1, RandomExponential2, RandomExponential3, Histogram)
+                        RandomExponential1, RandomExponential2, RandomExponential3, Histogram, Histogram2D)
 from .scatteringmodels import (ScatteringModel, SASModel, SASModelData, Sphere,                   # noqa: F401
                                CylindersIsotropic, EllipsoidalCoreShell, Kholodenko, EllipsoidsIsotropic,
                                SphericalCoreShell, GaussianChain, LMADenseSphere, CylindersRadiallyIsotropic, setup_from_model)

@@ -721,3 +721,84 @@ extern "C" int mcsas_hip_histogram_batch(int32_t n_sets, const mcsas_problem *pr
     return MCSAS_OK;
 }
 
+
+// ------------------------------------------------------------------------------ two parameters at once: mcsas_hip_histogram2d
+// The joint histogram of two parameter columns from fractions a histogram call returned (include/mcsas_hip.h): no model, no rows.
+// Per axis every rule is hist_bins_body's, so that one y column that holds every value gives that kernel's bins bit for bit.
+#include "hist2d_kernel.h"   // Hist2dSpecDev, hist2d_staged_bytes, hist2d_shared_bytes, hist2d_kernel
+static_assert(HIST2D_MAX_CONTRIBS == HIST_MAX_CONTRIBS, "hist2d_kernel.h: the 1-D cap");
+
+// a histogram's outputs: bins and observability [n_bin_x][n_bin_y][R] each, then the moments [7][R] (hist2d_body)
+static size_t hist2d_out_doubles(size_t cells, size_t R) { return 2 * cells * R + 7 * R; }
+// the n + 1 edges of an axis with bins: finite, and none below the one before it
+static bool hist2d_edges_ok(const double *e, int n) {
+    for (int k = 0; k <= n; ++k)
+        if (!std::isfinite(e[k]) || (k > 0 && e[k] < e[k - 1])) return false;
+    return true;
+}
+
+// One packed upload [contribs | fractions | edges | records], hist2d_kernel on the null stream, one packed download, as HistOnDevice
+// holds a set; every refusal of the arguments comes before a device is touched.
+extern "C" int mcsas_hip_histogram2d(int32_t n_contrib, int32_t n_active, int32_t n_reps, const double *contribs, const double *fractions,
+                                     int32_t n_hist, const mcsas_histogram2d_spec *specs, double *out, int32_t device) {
+    static const char who[] = "histogram2d";
+    if (n_hist < 0) return fail(MCSAS_EINVAL, "%s: n_hist %d", who, n_hist);
+    if (n_hist == 0) return MCSAS_OK;
+    if (!contribs || !fractions || !specs || !out) return fail(MCSAS_EINVAL, "%s: NULL table (contribs, fractions, specs and out are needed)", who);
+    if (n_contrib < 1 || n_contrib > HIST_MAX_CONTRIBS || n_active < 1 || n_reps < 1)
+        return fail(MCSAS_EINVAL, "%s: n_contrib %d (1..%d: a repetition's contributions are staged in LDS), n_active %d, n_reps %d (each >= 1)", who,
+                    n_contrib, HIST_MAX_CONTRIBS, n_active, n_reps);
+    const size_t N = n_contrib, P = n_active, R = n_reps;
+    if ((size_t)n_hist * R > (size_t)INT32_MAX) return fail(MCSAS_EINVAL, "%s: n_hist %d x n_reps %d blocks", who, n_hist, n_reps);
+    size_t n_edges = 0, n_out = 0, shared = 0;
+    for (int h = 0; h < n_hist; ++h) {
+        const mcsas_histogram2d_spec &sp = specs[h];
+        if (sp.reserved != 0) return fail(MCSAS_EINVAL, "%s: histogram %d: reserved %d (must be 0)", who, h, sp.reserved);
+        if (sp.param_x < 0 || sp.param_x >= n_active || sp.param_y < 0 || sp.param_y >= n_active || sp.weighting < 0 || sp.weighting > 3)
+            return fail(MCSAS_EINVAL, "%s: histogram %d: param_x %d, param_y %d (0..%d), weighting %d (0..3)", who, h, sp.param_x, sp.param_y,
+                        n_active - 1, sp.weighting);
+        if (sp.n_bin_x < 0 || sp.n_bin_y < 0 || (int64_t)sp.n_bin_x * sp.n_bin_y > HIST2D_MAX_CELLS)
+            return fail(MCSAS_EINVAL, "%s: histogram %d: n_bin_x %d, n_bin_y %d (each >= 0, at most %d cells)", who, h, sp.n_bin_x, sp.n_bin_y, HIST2D_MAX_CELLS);
+        if ((sp.n_bin_x > 0 && !sp.edges_x) || (sp.n_bin_y > 0 && !sp.edges_y))
+            return fail(MCSAS_EINVAL, "%s: histogram %d: an axis with bins has no edges", who, h);
+        if ((sp.n_bin_x > 0 && !hist2d_edges_ok(sp.edges_x, sp.n_bin_x)) || (sp.n_bin_y > 0 && !hist2d_edges_ok(sp.edges_y, sp.n_bin_y)))
+            return fail(MCSAS_EINVAL, "%s: histogram %d: edges must be finite and non-decreasing", who, h);
+        const size_t cells = (size_t)sp.n_bin_x * sp.n_bin_y;
+        if (cells) n_edges += (size_t)sp.n_bin_x + sp.n_bin_y + 2;
+        n_out += hist2d_out_doubles(cells, R);
+        shared = std::max(shared, hist2d_shared_bytes(N, sp.n_bin_x, sp.n_bin_y));
+    }
+    DeviceGuard dev_guard;
+    if (int rc = select_device(device)) return rc;
+    const size_t f_off = N * P * R, e_off = f_off + 8 * N * R, s_off = e_off + n_edges, n_in = s_off + (sizeof(Hist2dSpecDev) * (size_t)n_hist + 7) / 8;
+    DevBuf<double> din, dout;
+    Pinned hin, hout;
+    SyncGuard sync_guard;                                      // (after the blocks: it waits before they go back)
+    HIPCHK(din.alloc(n_in)); HIPCHK(dout.alloc(n_out)); HIPCHK(hin.alloc(n_in)); HIPCHK(hout.alloc(n_out));
+    memcpy(hin.p, contribs, sizeof(double) * f_off);
+    memcpy(hin.p + f_off, fractions, sizeof(double) * 8 * N * R);
+    Hist2dSpecDev *hs = reinterpret_cast<Hist2dSpecDev *>(hin.p + s_off);
+    size_t eo = 0, oo = 0;
+    for (int h = 0; h < n_hist; ++h) {
+        const mcsas_histogram2d_spec &sp = specs[h];
+        const size_t cells = (size_t)sp.n_bin_x * sp.n_bin_y;
+        hs[h] = Hist2dSpecDev{sp.param_x, sp.param_y, sp.weighting, sp.n_bin_x, sp.n_bin_y, 0, (int64_t)eo, (int64_t)oo, sp.lower_x, sp.upper_x, sp.lower_y, sp.upper_y};
+        if (cells) {
+            memcpy(hin.p + e_off + eo, sp.edges_x, sizeof(double) * ((size_t)sp.n_bin_x + 1));
+            memcpy(hin.p + e_off + eo + sp.n_bin_x + 1, sp.edges_y, sizeof(double) * ((size_t)sp.n_bin_y + 1));
+            eo += (size_t)sp.n_bin_x + sp.n_bin_y + 2;
+        }
+        oo += hist2d_out_doubles(cells, R);
+    }
+    HIPCHK(hipMemcpyAsync(din.p, hin.p, hin.bytes, hipMemcpyHostToDevice, nullptr));
+    const size_t lds = hist2d_staged_bytes(N) + shared;
+    if (lds > LDS_UNRAISED_MAX) HIPCHK(hipFuncSetAttribute((const void *)hist2d_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hist2d_kernel<<<(unsigned)((size_t)n_hist * R), WAVE, lds>>>((int)N, (int)P, (int)R, din.p, din.p + f_off, din.p + e_off,
+                                                                 reinterpret_cast<const Hist2dSpecDev *>(din.p + s_off), dout.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hout.p, dout.p, hout.bytes, hipMemcpyDeviceToHost, nullptr));
+    HIPCHK(hipStreamSynchronize(nullptr));
+    sync_guard.armed = false;
+    memcpy(out, hout.p, sizeof(double) * n_out);
+    return MCSAS_OK;
+}

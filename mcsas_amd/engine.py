@@ -780,6 +780,57 @@ def histogram_device_batch(items):
     return [c.unpack() for c in calls]
 
 
+HISTOGRAM2D_MAX_CELLS = 4096      # mcsas_hip_histogram2d keeps a histogram's cells in LDS
+
+
+def fractions_array(fractions):
+    """The [8][N][R] array mcsas_hip_histogram returns (vol, num, int, surf fractions, then their visibility limits) from the dict
+    McSAS.fractions holds, {'vol': (vf, mv), ...}; an array is taken as it is."""
+    if isinstance(fractions, dict):
+        names = sorted(YWEIGHT_INDEX, key=YWEIGHT_INDEX.get)
+        fractions = np.stack([fractions[k][0] for k in names] + [fractions[k][1] for k in names])
+    return f64(fractions)
+
+
+def histogram2d_device(contribs, fractions, specs, device=-1):
+    """Joint histograms of two parameter columns on the device in one call (mcsas_hip_histogram2d; no model is evaluated).
+    `contribs` [N][P][R]; `fractions`: the dict McSAS.fractions holds or the [8][N][R] array; `specs`: per histogram a dict(param_x,
+    param_y, yweight, edges_x (n_bin_x + 1 lower edges), edges_y, lower_x, upper_x, lower_y, upper_y).  N <= HISTOGRAM_MAX_CONTRIBS
+    and n_bin_x * n_bin_y <= HISTOGRAM2D_MAX_CELLS (beyond: parameter.Histogram2D.calc).
+    Returns, per histogram, dict(bins[n_bin_x][n_bin_y][R], obs[n_bin_x][n_bin_y][R], moments[7][R]: total, mean x, mean y,
+    variance x, variance y, covariance, correlation)."""
+    lib = _lib.load()
+    contribs = f64(contribs)
+    if contribs.ndim != 3:
+        raise ValueError("histogram2d_device: contribs must be (n_contrib, n_active, n_reps), got %r" % (contribs.shape,))
+    N, P, R = contribs.shape
+    frac = fractions_array(fractions)
+    if frac.shape != (8, N, R):
+        raise ValueError("histogram2d_device: fractions must be (8, %d, %d), got %r" % (N, R, frac.shape))
+    specs = list(specs)
+    arr = (_lib.Histogram2dSpec * max(len(specs), 1))()
+    edges, n_out = [], 0
+    for h, sp in enumerate(specs):
+        ex, ey = f64(sp["edges_x"]).ravel(), f64(sp["edges_y"]).ravel()
+        edges.append((ex, ey))                               # (kept alive to the end of the call)
+        a = arr[h]
+        a.param_x = int(sp["param_x"]); a.param_y = int(sp["param_y"]); a.weighting = YWEIGHT_INDEX[sp["yweight"]]
+        a.n_bin_x = len(ex) - 1; a.n_bin_y = len(ey) - 1
+        a.lower_x = float(sp["lower_x"]); a.upper_x = float(sp["upper_x"]); a.lower_y = float(sp["lower_y"]); a.upper_y = float(sp["upper_y"])
+        a.edges_x = as_dp(ex); a.edges_y = as_dp(ey)
+        n_out += 2 * max(a.n_bin_x, 0) * max(a.n_bin_y, 0) * R + 7 * R
+    out = np.zeros(max(n_out, 1))
+    check(lib.mcsas_hip_histogram2d(N, P, R, as_dp(contribs), as_dp(frac), len(specs), arr, as_dp(out), int(device)), lib)
+    hists, off = [], 0
+    for ex, ey in edges:
+        nx, ny = len(ex) - 1, len(ey) - 1
+        n = nx * ny * R
+        hists.append(dict(bins=out[off:off + n].reshape(nx, ny, R), obs=out[off + n:off + 2 * n].reshape(nx, ny, R),
+                          moments=out[off + 2 * n:off + 2 * n + 7 * R].reshape(7, R)))
+        off += 2 * n + 7 * R
+    return hists
+
+
 def histogram_rows_shape(model: ModelSetup, q, st_or_sizes):
     """(min_rows, useful_rows, row_stride) of histogram_device_rows (mcsas_hip_histogram_rows_shape; no device is touched): the
     least and the most rows of a round, and the row pitch of the rows buffer (the q count, dense).  `st_or_sizes`: a Settings, or

@@ -91,6 +91,7 @@ class McSAS(object):
         self.details = None
         self.hostRowWindow = 64          # proposals evaluated ahead per chain for models that exist only as Python (mcsas_hip.h)
         self.deviceRowsHistogram = None  # histogram() of a calcIntensityBatch model on the device: None = DEVICE_ROWS_HISTOGRAM_DEFAULT
+        self.histograms2d = []           # parameter.Histogram2D objects over pairs of the model's active parameters: histogram() fills them
 
     # McSAS.stop is polled once per step in the reference (mcsas.py:357); here the word is
     # forwarded to the running kernel by the library
@@ -282,7 +283,7 @@ class McSAS(object):
                     return model.calcIntensityBatch(qdev(pset), batch_clip(model, pset), c)
                 item = self._histogram_item(setup, None, contribs)
                 del item["comp_exp"], item["smear"]
-                self._histogram_from_device(engine.histogram_device_rows(row_fn=rows_on_device, **item))
+                self._histogram_from_device(engine.histogram_device_rows(row_fn=rows_on_device, **item), contribs)
                 return
             # rows by the model's own calcIntensity (:552, :577-578), the fit on the device (:559), the visibility limits in numpy (:575-590)
             scalingFactors = np.zeros((2, numReps))
@@ -318,7 +319,7 @@ class McSAS(object):
         # the repetitions is taken here.  (More than engine.HISTOGRAM_MAX_CONTRIBS contributions: the two-step path below.)
         if numContribs <= engine.HISTOGRAM_MAX_CONTRIBS:
             item = self._histogram_item(setup, smear, contribs)
-            self._histogram_from_device(engine.histogram_device(**item))
+            self._histogram_from_device(engine.histogram_device(**item), contribs)
             return
         # model.calc, the scale/background fit and the N single-row visibility limits of every repetition
         # (:552, :559, :575-590): one library call for all of them
@@ -344,13 +345,41 @@ class McSAS(object):
                     specs=[h.deviceSpec(pi) for pi, h in self._histogram_todo()], find_background=self.findBackground.value(),
                     positive_background=self.positiveBackground.value(), device=self.device, smear=smear)
 
-    def _histogram_from_device(self, triple):
-        """Takes over what engine.histogram_device returned for the stored result."""
+    def _histogram_from_device(self, triple, contribs=None):
+        """Takes over what engine.histogram_device returned for the stored result (or for `contribs`)."""
         scalingFactors, fractions, res = triple
         self.result[0]['scalingFactors'] = scalingFactors
         self.fractions = fractions
         for (pi, h), r in zip(self._histogram_todo(), res):
             h.setFromDevice(r)
+        self._histograms2d_calc(contribs)
+
+    def _histograms2d_calc(self, contribs=None):
+        """The joint histograms of `histograms2d` from the contributions and `self.fractions`, where histogram() ends: on the device
+        in one call (engine.histogram2d_device) those with no more than engine.HISTOGRAM_MAX_CONTRIBS contributions and
+        engine.HISTOGRAM2D_MAX_CELLS cells, in numpy (Histogram2D.calc) the others.  With an empty list nothing runs."""
+        if not self.histograms2d:
+            return
+        if contribs is None:
+            contribs = self.result[0]['contribs']
+        active = list(self.model.activeParams())
+        on_device, on_host = [], []
+        for h in self.histograms2d:
+            idx = []
+            for p in (h.paramX, h.paramY):
+                where = [i for i, a in enumerate(active) if a is p] or [i for i, a in enumerate(active) if a.name() == p.name()]
+                if not where:
+                    raise ValueError("McSAS.histograms2d: parameter %r is not among the model's active parameters (%s)"
+                                     % (p.name(), ", ".join(a.name() for a in active)))
+                idx.append(where[0])
+            fits = contribs.shape[0] <= engine.HISTOGRAM_MAX_CONTRIBS and h.binCount[0] * h.binCount[1] <= engine.HISTOGRAM2D_MAX_CELLS
+            (on_device if fits else on_host).append((h, idx[0], idx[1]))
+        if on_device:
+            res = engine.histogram2d_device(contribs, self.fractions, [h.deviceSpec(ix, iy) for h, ix, iy in on_device], device=self.device)
+            for (h, ix, iy), r in zip(on_device, res):
+                h.setFromDevice(r)
+        for h, ix, iy in on_host:
+            h.calc(contribs, ix, iy, self.fractions)
 
     def _histogram_tail(self, contribs, scalingFactors, vsets, wsets, ssets, mv):
         """mcsas.py:561-615 from the per-contribution volumes / weights / surfaces and visibility limits of every repetition."""
@@ -372,3 +401,4 @@ class McSAS(object):
         self.fractions = fractions
         for paramIndex, param in enumerate(model.activeParams()):
             param.histograms().calc(contribs, paramIndex, fractions)
+        self._histograms2d_calc(contribs)

@@ -141,6 +141,7 @@ class FitParameter(Parameter):
         self._activeRange = None
         self._generator = generator
         self._histograms = Histograms()
+        self._histograms2d = []
         self._activeValues = []
         if activeRange is not None:
             self.setActiveRange(activeRange)
@@ -159,6 +160,8 @@ class FitParameter(Parameter):
         r = self.clip(np.asarray(newRange, dtype=float))
         self._activeRange = (float(min(r)), float(max(r)))
         for h in self._histograms:
+            h.updateRange()
+        for h in self._histograms2d:                          # (Histogram2D: the joint histograms this parameter is an axis of)
             h.updateRange()
 
     def activeRange(self):
@@ -390,3 +393,162 @@ class Histogram(object):
         """bins / obs / cdf / moments of every repetition as mcsas_hip_histogram returns them (engine.histogram_device)."""
         self._setResults(np.array(res["bins"]), np.array(res["obs"]), np.array(res["cdf"]))
         self.moments = Moments.fromRepetitions(*[np.array(x) for x in res["moments"]])
+
+
+# ------------------------------------------------------------------ joint histogram of two parameters (post-fit; no reference counterpart)
+class CellResult(object):
+    """VectorResult for [nx][ny][R] cells: mean / std over the repetitions (ddof 1 where there is more than one)."""
+
+    def __init__(self, arr):
+        assert arr.ndim == 3
+        self.full = arr
+        numReps = arr.shape[2]
+        self.mean = arr.mean(axis=2) if numReps else np.zeros(arr.shape[:2])
+        self.std = arr.std(axis=2, ddof=1 if numReps > 1 else 0) if numReps else np.zeros(arr.shape[:2])
+
+
+class Moments2D(object):
+    """total, the two means, the two variances, the covariance and the correlation of two parameters over the contributions inside
+    both value ranges (strictly), per repetition in `.full` [7][R], each as (mean, std) over the repetitions."""
+
+    NAMES = ("total", "meanX", "meanY", "varianceX", "varianceY", "covariance", "correlation")
+
+    @staticmethod
+    def perRepetition(x, y, rangeX, rangeY, fraction):
+        """[7][R] from x, y, fraction [N][R]: Moments' ordered sums (a cumulative sum down the contributions with +0.0 in place of
+        the contributions outside), in mcsas_hip_histogram2d's operation order (include/mcsas_hip.h)."""
+        numReps = x.shape[1]
+        x, y, f = (np.ascontiguousarray(np.asarray(a, dtype=np.float64).T) for a in (x, y, fraction))
+        valid = (x > min(rangeX)) & (x < max(rangeX)) & (y > min(rangeY)) & (y < max(rangeY))
+        anyv = valid.any(axis=1)
+
+        def ssum(t):
+            return np.cumsum(np.where(valid, t, 0.0), axis=1)[:, -1] if t.shape[1] else np.zeros(numReps)
+
+        with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
+            tot = ssum(f)
+            nz = tot != 0
+            mx, my = ssum(x * f), ssum(y * f)
+            mx = np.where(nz, mx / np.where(nz, tot, 1.0), mx)
+            my = np.where(nz, my / np.where(nz, tot, 1.0), my)
+            dx, dy = x - mx[:, None], y - my[:, None]
+            vxx, vyy, cxy = ssum((dx * dx) * f) / tot, ssum((dy * dy) * f) / tot, ssum((dx * dy) * f) / tot
+            den = np.sqrt(np.abs(vxx)) * np.sqrt(np.abs(vyy))
+            # (only an exact zero is skipped: a NaN product goes on and gives NaN, like Moments' skew)
+            rho = np.where(den != 0.0, cxy / np.where(den != 0.0, den, 1.0), 0.0)
+        return np.where(anyv[None, :], np.stack([tot, mx, my, vxx, vyy, cxy, rho]), 0.0)
+
+    def __init__(self, full):
+        self.full = np.asarray(full, dtype=np.float64).reshape(7, -1)
+        ddof = 1 if self.full.shape[1] > 1 else 0
+        for name, row in zip(self.NAMES, self.full):
+            setattr(self, name, (row.mean(), row.std(ddof=ddof)))
+
+    @property
+    def fields(self):
+        return sum((getattr(self, name) for name in self.NAMES), ())
+
+
+class Histogram2D(object):
+    """The joint histogram of two active fit parameters: which values of one go with which of the other.  Per axis the rules are
+    Histogram's: a range clipped to the parameter's value range that follows its active range (autoFollow), 'lin' / 'log' edges
+    formed as Histogram._setXLowerEdge forms them, a cell [ex[i], ex[i+1]) x [ey[j], ey[j+1]), every sum in contribution order.
+    McSAS.histograms2d holds them; McSAS.histogram() fills .bins (.full [nx][ny][R], .mean, .std), .obs [nx][ny][R] (a cell's mean
+    visibility limit per repetition), .observability [nx][ny] and .moments (Moments2D)."""
+
+    def __init__(self, paramX, paramY, rangeX, rangeY, binCount=(20, 20), scaleX='log', scaleY='log', yweight='vol', autoFollow=True):
+        self.paramX, self.paramY = paramX, paramY
+        nx, ny = (binCount, binCount) if np.isscalar(binCount) else binCount
+        self.binCount = (max(0, int(nx)), max(0, int(ny)))
+        self.xrange, self.yrange = rangeX, rangeY
+        self.scaleX, self.scaleY = scaleX, scaleY
+        self.yweight = yweight
+        self.autoFollow = bool(autoFollow)
+        self.xLowerEdge = self.yLowerEdge = None
+        self.bins = self.obs = self.observability = self.moments = None
+        for p in (paramX, paramY):                           # (FitParameter.setActiveRange tells its joint histograms too)
+            followers = getattr(p, "_histograms2d", None)
+            if followers is not None and self not in followers:
+                followers.append(self)
+
+    @staticmethod
+    def _scale(kind):                                         # (invalid -> 'log', as Histogram.xscale)
+        kind = str(kind).strip()
+        return kind if kind in Histogram.xscaling() else 'log'
+
+    @staticmethod
+    def _clipped(param, valueRange):                          # (as Histogram.xrange)
+        lo, hi = min(valueRange), max(valueRange)
+        return (max(param.min(), lo), min(param.max(), hi))
+
+    scaleX = property(lambda self: self._scaleX, lambda self, kind: setattr(self, "_scaleX", self._scale(kind)))
+    scaleY = property(lambda self: self._scaleY, lambda self, kind: setattr(self, "_scaleY", self._scale(kind)))
+    xrange = property(lambda self: self._xrange, lambda self, r: setattr(self, "_xrange", self._clipped(self.paramX, r)))
+    yrange = property(lambda self: self._yrange, lambda self, r: setattr(self, "_yrange", self._clipped(self.paramY, r)))
+
+    @property
+    def yweight(self):
+        return self._yweight
+
+    @yweight.setter
+    def yweight(self, kind):                                  # (invalid -> 'vol', as Histogram.yweight)
+        kind = str(kind).strip()
+        self._yweight = kind if kind in Histogram.yweighting() else 'vol'
+
+    def updateRange(self):                                    # (as Histogram.updateRange, per axis)
+        if self.autoFollow:
+            self.xrange, self.yrange = self.paramX.activeRange(), self.paramY.activeRange()
+        self.xrange, self.yrange = self.xrange, self.yrange
+
+    @staticmethod
+    def _edges(valueRange, scale, count):                     # Histogram._setXLowerEdge's expressions
+        lower, upper = valueRange
+        if 'lin' in scale:
+            return np.linspace(lower, upper, count + 1)
+        return np.logspace(np.log10(lower), np.log10(upper), count + 1)
+
+    def _setEdges(self):
+        self.xLowerEdge = self._edges(self.xrange, self.scaleX, self.binCount[0])
+        self.yLowerEdge = self._edges(self.yrange, self.scaleY, self.binCount[1])
+
+    def calc(self, contribs, ix, iy, fractions):
+        """The numpy form of mcsas_hip_histogram2d (include/mcsas_hip.h), by Histogram.calc's method: the column of a value is
+        searchsorted(side='right') - 1, and numpy.bincount over the row-major flattened (contribution, repetition) array adds a
+        cell's members in contribution order.  The path for more contributions or cells than the device call takes."""
+        self._setEdges()
+        numContribs, dummy, numReps = contribs.shape
+        frac, minReq = fractions[self.yweight]
+        frac, minReq = np.asarray(frac, dtype=np.float64), np.asarray(minReq, dtype=np.float64)
+        nx, ny = self.binCount
+        x, y = np.ascontiguousarray(contribs[:, ix, :]), np.ascontiguousarray(contribs[:, iy, :])
+        bx = np.searchsorted(self.xLowerEdge, x.ravel(), side='right').reshape(x.shape) - 1
+        by = np.searchsorted(self.yLowerEdge, y.ravel(), side='right').reshape(y.shape) - 1
+        inb = (bx >= 0) & (bx < nx) & (by >= 0) & (by < ny)
+        cell = ((bx * ny + by) * numReps + np.arange(numReps)[None, :])[inb]
+        ncell = nx * ny * numReps
+        bins = np.bincount(cell, weights=frac[inb], minlength=ncell)[:ncell].reshape(nx, ny, numReps)
+        obsSum = np.bincount(cell, weights=minReq[inb], minlength=ncell)[:ncell].reshape(nx, ny, numReps)
+        cnt = np.bincount(cell, minlength=ncell)[:ncell].reshape(nx, ny, numReps).astype(float)
+        bins[np.isnan(bins)] = 0.
+        with np.errstate(invalid='ignore', divide='ignore'):
+            allObs = np.where(cnt > 0, obsSum / np.where(cnt > 0, cnt, 1.), 0.)
+        self._setResults(bins, allObs, Moments2D.perRepetition(x, y, self.xrange, self.yrange, frac))
+
+    def _setResults(self, bins, allObs, moments):
+        self.bins = CellResult(bins)
+        self.obs = allObs
+        finite = np.where(allObs < np.inf, allObs, -np.inf)   # Histogram._setResults' rule: the largest finite limit, 0 where none
+        best = finite.max(axis=2) if allObs.shape[2] else np.zeros(allObs.shape[:2])
+        self.observability = np.where(np.isfinite(best), best, 0.)
+        self.moments = Moments2D(moments)
+
+    def deviceSpec(self, ix, iy):
+        """What mcsas_hip_histogram2d needs to know about this histogram (engine.histogram2d_device)."""
+        self._setEdges()
+        return dict(param_x=ix, param_y=iy, yweight=self.yweight, edges_x=self.xLowerEdge, edges_y=self.yLowerEdge,
+                    lower_x=min(self.xrange), upper_x=max(self.xrange), lower_y=min(self.yrange), upper_y=max(self.yrange))
+
+    def setFromDevice(self, res):
+        """bins / obs / moments of every repetition as mcsas_hip_histogram2d returns them (engine.histogram2d_device)."""
+        self._setEdges()
+        self._setResults(np.array(res["bins"]), np.array(res["obs"]), np.array(res["moments"]))

@@ -22,6 +22,7 @@ def _histograms_batchable(algo, engine):
 def run_series(algo, datasets, keys=None, replays=None, overlap=False, batch=False, start=None, batch_histograms=None):
     """-> (results, series).  `results[i]` is `algo.result[0]` of data set i (None when nothing
     converged); `series[(param, lower, upper, yweight)]` is the list of `(key_i, moments.fields)`.
+    Every Histogram2D of `algo.histograms2d` adds `series[(paramX, paramY, lowerX, upperX, lowerY, upperY, yweight)]` likewise.
     `keys`: the series key value of each data set (default: its index).  `replays`: per data set, the uniform
     streams of its repetitions (tests replaying the reference: tests/golden/g15_series.npz).  `overlap`: the data sets' analyses
     run side by side on the device instead of one after the other (same results; algo.seed should be set: an unseeded algo draws a
@@ -118,6 +119,9 @@ def run_series(algo, datasets, keys=None, replays=None, overlap=False, batch=Fal
             for h in p.histograms():
                 uid = (p.name(),) + tuple(h.xrange) + (h.yweight,)
                 series.setdefault(uid, []).append((key, h.moments.fields))
+        for h in getattr(algo, "histograms2d", ()):              # (joint histograms: keys that exist only where one is configured)
+            uid = (h.paramX.name(), h.paramY.name()) + tuple(h.xrange) + tuple(h.yrange) + (h.yweight,)
+            series.setdefault(uid, []).append((key, h.moments.fields))
         if algo.stop:
             break
     return results, series
