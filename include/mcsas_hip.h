@@ -458,6 +458,36 @@ int mcsas_hip_histogram_device_rows(const mcsas_problem *problem, const double *
                                     int32_t n_hist, const mcsas_histogram_spec *specs,
                                     double *scaling, double *fractions, double *out);
 
+/* ---- the partial intensities of histogram ranges and bins (additive to ABI 5; Moments.intensity, utils/parameter.py:124-154) -----
+ * mcsas_hip_histogram, and mcsas_hip_histogram_device_rows, with one more result: the scattering curve of only the contributions
+ * inside a histogram's value range, and of each of its bins, scaled by the repetition's fitted scale A = scaling[0][r] — taken on
+ * the device from the rows the call has in HBM anyway, before they are thrown away.  No row crosses the bus, no form factor is
+ * evaluated twice.  With rows[c][k] the (smeared, where the call smears) intensity row of contribution c and x_c = contribs[c][p][r]:
+ *   range[k][r]  = A * sum_c rows[c][k] over lower < x_c < upper, both strict (the mask of the moments); no background is added
+ *   bin[b][k][r] = A * sum_c rows[c][k] over edges[b] <= x_c < edges[b+1] && x_c < edges[n_bin] (the members of bin b)
+ * Each sum runs in contribution order from +0.0 and is multiplied by A ONCE, at the end: an IEEE ordered sum and one product, which
+ * numpy reproduces bit for bit (mcsas_amd/parameter.py: partial_intensities).  An empty selection gives A * 0.0; a NaN parameter
+ * value is in no bin and in no range; NaN or inf in a row propagate by IEEE's rules.
+ *   want[h]: 0 nothing, 1 the range curve, 2 the range curve and the bin curves of histogram h.
+ *   partial = for each histogram with want >= 1, in order: range[nq][n_reps], then, if 2, bin[n_bin][nq][n_reps].
+ * scaling, fractions and out are what the call without `want` returns for the same arguments, bit for bit; with every want 0 (or
+ * n_hist == 0) the call IS that call and partial is not looked at.
+ * Refused with MCSAS_EINVAL before a device is touched, after whatever the plain call refuses (its sentences unchanged), each
+ * message behind "histogram_partial: " and naming the histogram: want NULL with n_hist > 0; a want outside 0..2; partial NULL while
+ * something is wanted; want 2 with n_bin > 256 (a bin's running sums lie in LDS: 256 * 64 doubles; the range curve has no such
+ * cap); want 2 with edges that are not finite and non-decreasing (a contribution is filed under ONE bin; want <= 1 keeps the plain
+ * call's permissiveness); curves of more than 2 GiB in all.  mcsas_hip_histogram_batch has no partial form. */
+int mcsas_hip_histogram_partial(const mcsas_problem *problem, const double *contribs, int32_t n_hist,
+                                const mcsas_histogram_spec *specs, const int32_t *want,
+                                double *scaling, double *fractions, double *out, double *partial);
+/* The same for rows the caller computes on the device: mcsas_hip_histogram_device_rows' arguments, then want and partial as above.
+ * The curves of a round are taken from d_rows as the callback left them, before the next round overwrites them. */
+int mcsas_hip_histogram_partial_device_rows(const mcsas_problem *problem, const double *contribs,
+                                            double *d_pset, double *d_rows, double *d_vws, int64_t capacity_rows,
+                                            mcsas_device_rows_callback rows_cb, void *user,
+                                            int32_t n_hist, const mcsas_histogram_spec *specs, const int32_t *want,
+                                            double *scaling, double *fractions, double *out, double *partial);
+
 /* ---- the joint histogram of TWO fit parameters (additive to ABI 5; the reference has no counterpart) ----------------------------
  * Takes the fractions a histogram call returned and evaluates no model: it serves every path that ends in them, and doubles of the
  * caller's own.  contribs [n_contrib][n_active][n_reps] as in mcsas_result; fractions [8][n_contrib][n_reps] as mcsas_hip_histogram

@@ -27,6 +27,7 @@ SYMBOLS = (
     "mcsas_hip_plan_destroy", "mcsas_hip_plan_launch_batch", "mcsas_hip_analyse_batch", "mcsas_hip_plan_set_start", "mcsas_hip_analyse_from",
     "mcsas_hip_plan_set_trace", "mcsas_hip_plan_fetch_trace", "mcsas_hip_analyse_traced", "mcsas_hip_model_calc", "mcsas_hip_bgfit", "mcsas_hip_observability",
     "mcsas_hip_histogram_prep", "mcsas_hip_histogram", "mcsas_hip_histogram_batch", "mcsas_hip_histogram_rows_shape", "mcsas_hip_histogram_device_rows",
+    "mcsas_hip_histogram_partial", "mcsas_hip_histogram_partial_device_rows",
     "mcsas_hip_histogram2d", "mcsas_hip_prepare_uncertainty", "mcsas_hip_rebin",
     "mcsas_hip_plugin_compile", "mcsas_hip_plugin_log", "mcsas_hip_release_cached_memory", "mcsas_hip_stream_create", "mcsas_hip_stream_destroy",
     "mcsas_hip_device_count", "mcsas_hip_abi_version", "mcsas_hip_is_tuning_build", "mcsas_hip_last_error",
@@ -170,6 +171,10 @@ def load(tuning=False):
     lib.mcsas_hip_histogram_rows_shape.argtypes = [C.POINTER(Problem), _i64p, _i64p, _i32p]
     lib.mcsas_hip_histogram_device_rows.argtypes = [C.POINTER(Problem), _dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, DeviceRowsCallback,
                                                     C.c_void_p, C.c_int32, C.POINTER(HistogramSpec), _dp, _dp, _dp]
+    lib.mcsas_hip_histogram_partial.argtypes = [C.POINTER(Problem), _dp, C.c_int32, C.POINTER(HistogramSpec), _i32p, _dp, _dp, _dp, _dp]
+    lib.mcsas_hip_histogram_partial_device_rows.argtypes = [C.POINTER(Problem), _dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                            DeviceRowsCallback, C.c_void_p, C.c_int32, C.POINTER(HistogramSpec), _i32p,
+                                                            _dp, _dp, _dp, _dp]
     lib.mcsas_hip_histogram2d.argtypes = [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, C.c_int32, C.POINTER(Histogram2dSpec), _dp, C.c_int32]
     lib.mcsas_hip_prepare_uncertainty.argtypes = [C.c_int32, _dp, _dp, C.c_double, C.c_int32, _dp]
     lib.mcsas_hip_rebin.argtypes = [C.c_int32, _dp, _dp, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _i32p]

@@ -1,5 +1,6 @@
 // host_hist.hip — McSAS.histogram() on the device: the hist_* kernels, their batch forms and the entry points mcsas_hip_histogram_prep,
-// mcsas_hip_histogram, mcsas_hip_histogram_batch and mcsas_hip_histogram_device_rows (the rows filled by the caller).  What makes a
+// mcsas_hip_histogram, mcsas_hip_histogram_batch and mcsas_hip_histogram_device_rows (the rows filled by the caller), and the forms of
+// the second and the last that also return partial intensities (hist_partial_kernel.h; mcsas_hip_histogram_partial*).  What makes a
 // set acceptable (check_hist_set), how a set lies in the staging blocks (HistSizes, pack_hist_set, unpack_hist_set) and how many
 // repetitions share a block of rows (hist_rep_chunk) are each said once here, for the single call and the batch alike; how one set
 // is held on the device and finished (HistOnDevice), what follows a block of rows (launch_hist_fit_obs) and how a bins kernel is
@@ -363,9 +364,93 @@ static int launch_hist_fit_obs(const mcsas_problem *p, const HistArrays &a, size
     HIPCHK(hipGetLastError());
     return MCSAS_OK;
 }
+// ---- partial intensities (mcsas_hip_histogram_partial, mcsas_hip_histogram_partial_device_rows): the scattering curve of only the
+// contributions inside a histogram's value range, and of each of its bins, taken from a block of rows while it still lies in HBM.
+#include "hist_partial_kernel.h"   // HistPartialDev, hist_partial_lds_bytes, hist_partial_kernel
+static_assert(HIST_PARTIAL_MAX_CONTRIBS == HIST_MAX_CONTRIBS, "hist_partial_kernel.h: the call's own cap");
+static bool hist2d_edges_ok(const double *e, int n);       // (further down: finite, and none below the one before it)
+
+// What a checked call wants: the records of the wanted histograms in order, the doubles of their curves (per wanted histogram
+// range [nq][R], then bin [n_bin][nq][R] where the bins are wanted too), the most dynamic LDS a block of them asks for.
+struct HistPartialPlan {
+    std::vector<HistPartialDev> recs;
+    size_t n_out = 0, lds = 0;
+};
+constexpr size_t HIST_PARTIAL_MAX_BYTES = (size_t)2 << 30;
+
+// Every check of the wishes, after check_hist_set has passed the set itself: needs no device.  want == NULL with no histogram: nothing wanted.
+static int check_hist_partial(const mcsas_problem *p, int n_hist, const mcsas_histogram_spec *specs, const int32_t *want, const double *partial,
+                              HistPartialPlan *pl) {
+    static const char who[] = "histogram_partial";
+    if (n_hist > 0 && !want)
+        return fail(MCSAS_EINVAL, "%s: want is NULL with %d histograms (per histogram 0: nothing, 1: the range curve, 2: the range curve and the bin curves)", who, n_hist);
+    const size_t Q = p->nq, N = p->n_contrib, R = p->n_reps;
+    size_t e_off = 0;
+    for (int h = 0; h < n_hist; ++h) {
+        const mcsas_histogram_spec &sp = specs[h];
+        const int w = want[h];
+        if (w < 0 || w > 2)
+            return fail(MCSAS_EINVAL, "%s: histogram %d: want %d (0: nothing, 1: the range curve, 2: the range curve and the bin curves)", who, h, w);
+        if (w && !partial) return fail(MCSAS_EINVAL, "%s: histogram %d wants curves (want %d), but partial is NULL", who, h, w);
+        if (w == 2 && sp.n_bin > HIST_PARTIAL_MAX_BINS)
+            return fail(MCSAS_EINVAL, "%s: histogram %d: the bin curves keep every bin's running sums in LDS: n_bin %d > %d (want 1 gives the range curve alone)", who,
+                        h, sp.n_bin, HIST_PARTIAL_MAX_BINS);
+        if (w == 2 && sp.n_bin > 0 && !hist2d_edges_ok(sp.edges, sp.n_bin))
+            return fail(MCSAS_EINVAL, "%s: histogram %d: bin curves need edges that are finite and non-decreasing (a contribution lies in one bin)", who, h);
+        if (w) {
+            pl->recs.push_back(HistPartialDev{sp.param_index, sp.n_bin, w, 0, (int64_t)e_off, (int64_t)pl->n_out, sp.lower, sp.upper});
+            pl->n_out += Q * R * (1 + (w == 2 ? (size_t)sp.n_bin : 0));
+            pl->lds = std::max(pl->lds, hist_partial_lds_bytes(N, sp.n_bin, w));
+            if (pl->n_out * sizeof(double) > HIST_PARTIAL_MAX_BYTES)
+                return fail(MCSAS_EINVAL, "%s: histogram %d: the curves wanted up to here take %zu bytes, more than 2 GiB in all (ask for fewer histograms or bins per call)", who,
+                            h, pl->n_out * sizeof(double));
+        }
+        e_off += (size_t)sp.n_bin + 1;
+    }
+    return MCSAS_OK;
+}
+
+// The wishes on the device: the records (one small upload) and the curves in a block of their own (one more download), beside a
+// HistOnDevice and declared ahead of it, so that they go back only after the set's guard has waited for what is queued.
+struct HistPartialOnDevice {
+    const HistPartialPlan *pl = nullptr;
+    const double *edges = nullptr;                             // the set's edges on the device (HistSizes::edge_off)
+    DevBuf<double> drec, dout;
+    Pinned hrec, hout;
+    size_t rec_doubles() const { return (sizeof(HistPartialDev) * pl->recs.size() + 7) / 8; }
+    int upload(const HistPartialPlan &pl_, const double *edges_on_device) {
+        pl = &pl_; edges = edges_on_device;
+        HIPCHK(drec.alloc(rec_doubles())); HIPCHK(dout.alloc(pl->n_out)); HIPCHK(hrec.alloc(rec_doubles())); HIPCHK(hout.alloc(pl->n_out));
+        memcpy(hrec.p, pl->recs.data(), sizeof(HistPartialDev) * pl->recs.size());
+        HIPCHK(hipMemcpyAsync(drec.p, hrec.p, hrec.bytes, hipMemcpyHostToDevice, nullptr));
+        return MCSAS_OK;
+    }
+    // hist_partial_kernel over repetitions [r0, r0 + nr), whose rows begin at `rows` and whose scales launch_hist_fit_obs has left in a.sc
+    int launch(const mcsas_problem *p, const HistArrays &a, size_t r0, unsigned nr, const double *rows) const {
+        const size_t nq = p->nq, N = p->n_contrib, n_want = pl->recs.size();
+        if (pl->lds > LDS_UNRAISED_MAX) HIPCHK(hipFuncSetAttribute((const void *)hist_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->lds));
+        const unsigned tiles = (unsigned)((nq + HIST_PARTIAL_TILE - 1) / HIST_PARTIAL_TILE);
+        for (size_t z0 = 0; z0 < nr; z0 += GRID_Y_MAX)
+            for (size_t y0 = 0; y0 < n_want; y0 += GRID_Y_MAX) {
+                const dim3 grid(tiles, (unsigned)std::min(GRID_Y_MAX, n_want - y0), (unsigned)std::min<size_t>(GRID_Y_MAX, nr - z0));
+                hist_partial_kernel<<<grid, WAVE, pl->lds>>>(p->nq, p->n_contrib, p->n_active, p->n_reps, (int)(r0 + z0), rows + z0 * N * nq, a.c, a.sc, edges,
+                                                            reinterpret_cast<const HistPartialDev *>(drec.p) + y0, dout.p);
+                HIPCHK(hipGetLastError());
+            }
+        return MCSAS_OK;
+    }
+    int download() {
+        HIPCHK(hipMemcpyAsync(hout.p, dout.p, hout.bytes, hipMemcpyDeviceToHost, nullptr));
+        return MCSAS_OK;
+    }
+    void unpack(double *partial) const { memcpy(partial, hout.p, sizeof(double) * pl->n_out); }
+};
+
 // The first half of histogram() for all repetitions, a chunk of them at a time: per repetition the rows of the problem's model with
-// their volumes, weights and surfaces, then launch_hist_fit_obs.  drows holds chunk * N * Q doubles, a.cum chunk * Q.
-static int launch_hist_reps(const mcsas_problem *p, const ModelArgs &m, size_t chunk, const HistArrays &a, double *drows) {
+// their volumes, weights and surfaces, then launch_hist_fit_obs, then (where curves are wanted) hist_partial_kernel on the same rows.
+// drows holds chunk * N * Q doubles, a.cum chunk * Q.
+static int launch_hist_reps(const mcsas_problem *p, const ModelArgs &m, size_t chunk, const HistArrays &a, double *drows,
+                            const HistPartialOnDevice *partial = nullptr) {
     const size_t R = p->n_reps;
     const size_t lds = sizeof(double) * table_doubles_host(p->model_id, m.int_div);
     for (size_t r0 = 0; r0 < R; r0 += chunk) {
@@ -374,6 +459,8 @@ static int launch_hist_reps(const mcsas_problem *p, const ModelArgs &m, size_t c
                                                          a.c, drows, a.v, a.w, a.s))
             return rc;
         if (int rc = launch_hist_fit_obs(p, a, r0, nr, drows)) return rc;
+        if (partial)
+            if (int rc = partial->launch(p, a, r0, nr, drows)) return rc;
     }
     return MCSAS_OK;
 }
@@ -468,21 +555,41 @@ extern "C" int mcsas_hip_histogram_prep(const mcsas_problem *p, const double *co
 }
 
 // McSAS.histogram() complete (include/mcsas_hip.h): the set on the device (HistOnDevice), its rows by the model's kernel a chunk of
-// repetitions at a time.  Every refusal of the set itself comes before a device is touched.
-extern "C" int mcsas_hip_histogram(const mcsas_problem *p, const double *contribs, int32_t n_hist, const mcsas_histogram_spec *specs,
-                                   double *scaling, double *fractions, double *out) {
-    ModelArgs m; HistSizes sz;
+// repetitions at a time.  Every refusal of the set itself comes before a device is touched.  `asked`: the call is
+// mcsas_hip_histogram_partial, and want / partial say which curves hist_partial_kernel takes from each block of rows; with nothing
+// wanted the call is mcsas_hip_histogram.
+static int histogram_call(const mcsas_problem *p, const double *contribs, int32_t n_hist, const mcsas_histogram_spec *specs, bool asked,
+                          const int32_t *want, double *scaling, double *fractions, double *out, double *partial) {
+    ModelArgs m; HistSizes sz; HistPartialPlan pl;
     if (int rc = check_hist_set(p, contribs, n_hist, specs, scaling, out, &m, &sz)) return rc;
+    if (asked)
+        if (int rc = check_hist_partial(p, n_hist, specs, want, partial, &pl)) return rc;
+    const bool curves = !pl.recs.empty();
     DeviceGuard dev_guard;
     if (int rc = select_device(p->device)) return rc;
     const size_t Q = p->nq, N = p->n_contrib, chunk = hist_rep_chunk(N, Q, p->n_reps);
     DevBuf<double> drows;                                      // (ahead of the set: it goes back after the set's guard has waited)
+    HistPartialOnDevice pt;                                    // (the same)
     HistOnDevice d;
     HIPCHK(drows.alloc(chunk * N * Q));
     if (int rc = d.upload(p, contribs, n_hist, specs, sz, chunk)) return rc;
     if (int rc = d.smear.upload(p, p->nq, &m)) return rc;
-    if (int rc = launch_hist_reps(p, m, chunk, d.a, drows.p)) return rc;
-    return d.finish(scaling, fractions, out);
+    if (curves)
+        if (int rc = pt.upload(pl, d.din.p + sz.edge_off)) return rc;
+    if (int rc = launch_hist_reps(p, m, chunk, d.a, drows.p, curves ? &pt : nullptr)) return rc;
+    if (curves)
+        if (int rc = pt.download()) return rc;
+    if (int rc = d.finish(scaling, fractions, out)) return rc;
+    if (curves) pt.unpack(partial);
+    return MCSAS_OK;
+}
+extern "C" int mcsas_hip_histogram(const mcsas_problem *p, const double *contribs, int32_t n_hist, const mcsas_histogram_spec *specs,
+                                   double *scaling, double *fractions, double *out) {
+    return histogram_call(p, contribs, n_hist, specs, false, nullptr, scaling, fractions, out, nullptr);
+}
+extern "C" int mcsas_hip_histogram_partial(const mcsas_problem *p, const double *contribs, int32_t n_hist, const mcsas_histogram_spec *specs,
+                                           const int32_t *want, double *scaling, double *fractions, double *out, double *partial) {
+    return histogram_call(p, contribs, n_hist, specs, true, want, scaling, fractions, out, partial);
 }
 
 // ------------------------------------------------------------------------------ one set, the rows filled by the caller: mcsas_hip_histogram_device_rows
@@ -514,9 +621,11 @@ extern "C" int mcsas_hip_histogram_rows_shape(const mcsas_problem *p, int64_t *m
 // d_vws, hist_take_vws_kernel files the three per-row values, and launch_hist_fit_obs reads the rows where they lie.
 // After the last round the call is mcsas_hip_histogram again.  Every refusal of the arguments comes before a device is touched, the
 // buffers are looked at before anything is queued, and from the upload on the set's guard waits on every way out, a failing callback's too.
-extern "C" int mcsas_hip_histogram_device_rows(const mcsas_problem *p, const double *contribs, double *d_pset, double *d_rows, double *d_vws,
-                                               int64_t capacity_rows, mcsas_device_rows_callback rows_cb, void *user, int32_t n_hist,
-                                               const mcsas_histogram_spec *specs, double *scaling, double *fractions, double *out) {
+// (`asked`, want, partial: as histogram_call takes them, for mcsas_hip_histogram_partial_device_rows)
+static int histogram_device_rows_call(const mcsas_problem *p, const double *contribs, double *d_pset, double *d_rows, double *d_vws,
+                                      int64_t capacity_rows, mcsas_device_rows_callback rows_cb, void *user, int32_t n_hist,
+                                      const mcsas_histogram_spec *specs, bool asked, const int32_t *want, double *scaling, double *fractions,
+                                      double *out, double *partial) {
     static const char who[] = "histogram_device_rows";
     const struct { const char *name; const void *ptr; } needed[] = {{"problem", p}, {"contribs", contribs}, {"d_pset", d_pset}, {"d_rows", d_rows},
                                                                     {"d_vws", d_vws}, {"rows_cb", (const void *)rows_cb}, {"out", out}};
@@ -531,6 +640,10 @@ extern "C" int mcsas_hip_histogram_device_rows(const mcsas_problem *p, const dou
                     (long long)capacity_rows, p->n_contrib);
     if (p->smear_nk != 0 || p->smear_locs || p->smear_q_offset || p->smear_weights)
         return fail(MCSAS_EINVAL, "%s: a smearing table (smear_nk %d) is given, but the rows are the caller's: nothing here would apply it", who, p->smear_nk);
+    HistPartialPlan pl;
+    if (asked)
+        if (int rc = check_hist_partial(p, n_hist, specs, want, partial, &pl)) return rc;
+    const bool curves = !pl.recs.empty();
     DeviceGuard dev_guard;
     if (int rc = select_device(p->device)) return rc;
     int dev = 0;
@@ -540,8 +653,11 @@ extern "C" int mcsas_hip_histogram_device_rows(const mcsas_problem *p, const dou
     if (int rc = check_device_buffer(who, "d_vws", d_vws, dev)) return rc;
     const size_t P = p->n_active, N = p->n_contrib, R = p->n_reps, cap = (size_t)capacity_rows;
     const size_t per_round = std::min<size_t>({R, cap / N, GRID_Y_MAX});       // (whole repetitions)
+    HistPartialOnDevice pt;                                    // (ahead of the set: it goes back after the set's guard has waited)
     HistOnDevice d;
     if (int rc = d.upload(p, contribs, n_hist, specs, sz, per_round)) return rc;
+    if (curves)
+        if (int rc = pt.upload(pl, d.din.p + sz.edge_off)) return rc;
     for (size_t r0 = 0; r0 < R; r0 += per_round) {
         const unsigned nr = (unsigned)std::min(per_round, R - r0);
         const size_t n_rows = nr * N;
@@ -553,8 +669,27 @@ extern "C" int mcsas_hip_histogram_device_rows(const mcsas_problem *p, const dou
         hist_take_vws_kernel<<<(unsigned)((n_rows + 255) / 256), 256>>>((int)N, (int)R, (int)r0, n_rows, cap, d_vws, d.a.v, d.a.w, d.a.s);
         HIPCHK(hipGetLastError());
         if (int rc2 = launch_hist_fit_obs(p, d.a, r0, nr, d_rows)) return rc2;
+        if (curves)                                                            // (the round's rows are still the caller's last answer)
+            if (int rc2 = pt.launch(p, d.a, r0, nr, d_rows)) return rc2;
     }
-    return d.finish(scaling, fractions, out);
+    if (curves)
+        if (int rc = pt.download()) return rc;
+    if (int rc = d.finish(scaling, fractions, out)) return rc;
+    if (curves) pt.unpack(partial);
+    return MCSAS_OK;
+}
+extern "C" int mcsas_hip_histogram_device_rows(const mcsas_problem *p, const double *contribs, double *d_pset, double *d_rows, double *d_vws,
+                                               int64_t capacity_rows, mcsas_device_rows_callback rows_cb, void *user, int32_t n_hist,
+                                               const mcsas_histogram_spec *specs, double *scaling, double *fractions, double *out) {
+    return histogram_device_rows_call(p, contribs, d_pset, d_rows, d_vws, capacity_rows, rows_cb, user, n_hist, specs, false, nullptr, scaling, fractions,
+                                      out, nullptr);
+}
+extern "C" int mcsas_hip_histogram_partial_device_rows(const mcsas_problem *p, const double *contribs, double *d_pset, double *d_rows, double *d_vws,
+                                                       int64_t capacity_rows, mcsas_device_rows_callback rows_cb, void *user, int32_t n_hist,
+                                                       const mcsas_histogram_spec *specs, const int32_t *want, double *scaling, double *fractions,
+                                                       double *out, double *partial) {
+    return histogram_device_rows_call(p, contribs, d_pset, d_rows, d_vws, capacity_rows, rows_cb, user, n_hist, specs, true, want, scaling, fractions,
+                                      out, partial);
 }
 
 // ------------------------------------------------------------------------------ a batch of sets: mcsas_hip_histogram_batch

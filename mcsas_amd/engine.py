@@ -713,16 +713,29 @@ HISTOGRAM_MAX_CONTRIBS = 4096     # mcsas_hip_histogram stages a repetition's co
 YWEIGHT_INDEX = {"vol": 0, "num": 1, "int": 2, "surf": 3}
 
 
+HISTOGRAM_PARTIAL_MAX_BINS = 256  # bin curves keep a bin's 64 running sums in LDS (csrc/hist_partial_kernel.h)
+PARTIAL_WANT = {None: 0, False: 0, 0: 0, 1: 1, 2: 2, "range": 1, "bins": 2}
+
+
 def histogram_device(model: ModelSetup, q, intensity, sigma, contribs, comp_exp, specs, find_background=True,
-                     positive_background=False, device=-1, smear=None):
+                     positive_background=False, device=-1, smear=None, partial=None):
     """McSAS.histogram() (mcsas.py:445-615) for all repetitions on the device in one call (mcsas_hip_histogram).
     `specs`: per histogram a dict(param_index, yweight, edges (n_bin + 1 lower edges), lower, upper).
     Returns (scaling[2][R], fractions dict like mcsas.histogram's {'vol': (vf, mv), ...}, per histogram a dict with
-    bins[n_bin][R], obs[n_bin][R], cdf[n_bin][R], moments[5][R])."""
+    bins[n_bin][R], obs[n_bin][R], cdf[n_bin][R], moments[5][R]).
+    `partial`: per spec 0, 1 (or "range") or 2 (or "bins"), or each spec dict may carry `partial` — the partial intensities
+    (mcsas_hip_histogram_partial): a histogram that asks gains intensity[nq][R], the scattering curve of the contributions inside
+    lower < x < upper times the repetition's scale, and with 2 also bin_intensity[n_bin][nq][R], the same of each bin's members
+    (n_bin <= HISTOGRAM_PARTIAL_MAX_BINS); parameter.partial_intensities is the numpy form, equal bit for bit.  Without a request
+    the call is the plain one."""
     lib = _lib.load()
-    call = _HistogramCall(model, q, intensity, sigma, contribs, comp_exp, specs, find_background, positive_background, device, smear)
-    check(lib.mcsas_hip_histogram(C.byref(call.prob.c), as_dp(call.contribs), len(call.specs), call.arr, as_dp(call.sc), as_dp(call.frac),
-                                  as_dp(call.out)), lib)
+    call = _HistogramCall(model, q, intensity, sigma, contribs, comp_exp, specs, find_background, positive_background, device, smear, partial)
+    if call.want is None:
+        check(lib.mcsas_hip_histogram(C.byref(call.prob.c), as_dp(call.contribs), len(call.specs), call.arr, as_dp(call.sc), as_dp(call.frac),
+                                      as_dp(call.out)), lib)
+    else:
+        check(lib.mcsas_hip_histogram_partial(C.byref(call.prob.c), as_dp(call.contribs), len(call.specs), call.arr, call.want_p(), as_dp(call.sc),
+                                              as_dp(call.frac), as_dp(call.out), as_dp(call.partial)), lib)
     return call.unpack()
 
 
@@ -731,7 +744,7 @@ class _HistogramCall:
     every numpy buffer the C structures point at."""
 
     def __init__(self, model, q, intensity, sigma, contribs, comp_exp, specs, find_background=True, positive_background=False,
-                 device=-1, smear=None):
+                 device=-1, smear=None, partial=None):
         self.contribs = f64(contribs)
         N, P, R = self.contribs.shape
         st = Settings(n_contrib=N, n_reps=R, comp_exp=comp_exp, device=device, find_background=find_background,
@@ -748,6 +761,22 @@ class _HistogramCall:
             a.n_bin = len(e) - 1; a.lower = float(sp["lower"]); a.upper = float(sp["upper"]); a.edges = as_dp(e)
             n_out += 3 * (len(e) - 1) * R + 5 * R
         self.sc = np.zeros((2, R)); self.frac = np.zeros((8, N, R)); self.out = np.zeros(max(n_out, 1))
+        # the partial intensities asked for: `partial` per spec, or a spec's own entry; want None: nobody asks, the plain call
+        if partial is not None and len(partial) != len(self.specs):
+            raise ValueError("partial: %d entries for %d histograms" % (len(partial), len(self.specs)))
+        asked = list(partial) if partial is not None else [sp.get("partial") for sp in self.specs]
+        for a in asked:
+            if isinstance(a, (bool, np.bool_)) and a or (a is not None and a not in PARTIAL_WANT):
+                raise ValueError("partial: %r (0, 1 or 'range', 2 or 'bins')" % (a,))
+        self.want = None
+        if any(PARTIAL_WANT[a] for a in asked):
+            nq = len(self.prob.q)
+            self.want = np.array([PARTIAL_WANT[a] for a in asked], dtype=np.int32)
+            n_part = sum(nq * R * (1 + (len(e) - 1 if w == 2 else 0)) for e, w in zip(self.edges, self.want) if w)
+            self.partial = np.zeros(max(n_part, 1))
+
+    def want_p(self):
+        return self.want.ctypes.data_as(C.POINTER(C.c_int32))
 
     def unpack(self):
         frac, out, R = self.frac, self.out, self.contribs.shape[2]
@@ -759,6 +788,16 @@ class _HistogramCall:
             hists.append(dict(bins=blk[:nb * R].reshape(nb, R), obs=blk[nb * R:2 * nb * R].reshape(nb, R),
                               cdf=blk[2 * nb * R:3 * nb * R].reshape(nb, R), moments=blk[3 * nb * R:].reshape(5, R)))
             off += 3 * nb * R + 5 * R
+        if self.want is not None:                            # per wanted histogram: range [nq][R], then bin [n_bin][nq][R]
+            nq, off = len(self.prob.q), 0
+            for h, e, w in zip(hists, self.edges, self.want):
+                if w:
+                    h["intensity"] = self.partial[off:off + nq * R].reshape(nq, R)
+                    off += nq * R
+                if w == 2:
+                    nb = len(e) - 1
+                    h["bin_intensity"] = self.partial[off:off + nb * nq * R].reshape(nb, nq, R)
+                    off += nb * nq * R
         return self.sc, fractions, hists
 
 
@@ -770,6 +809,8 @@ def histogram_device_batch(items):
     lib = _lib.load()
     calls = [_HistogramCall(**it) if isinstance(it, dict) else _HistogramCall(*it) for it in items]   # (kept alive to the end of the call)
     n = len(calls)
+    if any(c.want is not None for c in calls):
+        raise ValueError("histogram_device_batch: the batch call has no partial intensities (histogram_device(partial=...) per set)")
     if n:
         dpp = C.POINTER(C.c_double) * n
         probs = (Problem * n)(*[c.prob.c for c in calls])
@@ -845,13 +886,15 @@ def histogram_rows_shape(model: ModelSetup, q, st_or_sizes):
 
 
 def histogram_device_rows(model: ModelSetup, q, intensity, sigma, contribs, specs, row_fn, find_background=True,
-                          positive_background=False, device=-1, capacity=None):
+                          positive_background=False, device=-1, capacity=None, partial=None):
     """histogram_device for a model whose rows the caller computes ON THE DEVICE with torch (mcsas_hip_histogram_device_rows,
     include/mcsas_hip.h): a round of whole repetitions at a time the library lays the parameter sets out in a torch tensor,
     `row_fn(pset[n][n_active]) -> (it[n][nq], v[n], w[n], s[n])` — calcIntensityBatch's return; pset is not yet clipped — gives the
     rows and each row's volume, weight and surface, which are copied into the library's views, and the scale / background fit, the
     visibility limits, fractions, bins and moments are taken on the device from the rows where they lie.  `capacity`: rows of the
     tensors (default: the most a round uses, histogram_rows_shape; at least n_contrib).  Returns histogram_device's triple.
+    `partial`: as histogram_device takes it (mcsas_hip_histogram_partial_device_rows): the curves of a round are taken from the
+    rows tensor as row_fn's answer was copied into it.
     torch is imported here, not with the package."""
     import torch                                 # (ahead of the library's first load: see _one_hip_runtime)
     lib = _lib.load()
@@ -859,7 +902,7 @@ def histogram_device_rows(model: ModelSetup, q, intensity, sigma, contribs, spec
     if c3.ndim != 3 or c3.shape[1] != model.n_active or model.n_active < 1:
         raise ValueError("histogram_device_rows: contribs must be (n_contrib, n_active, n_reps) with n_active = %d >= 1, got %r"
                          % (model.n_active, c3.shape))
-    call = _HistogramCall(model, q, intensity, sigma, c3, 0.0, specs, find_background, positive_background, device, None)
+    call = _HistogramCall(model, q, intensity, sigma, c3, 0.0, specs, find_background, positive_background, device, None, partial)
     call.prob.c.model_id = MODEL_HOST
     nq = len(call.prob.q)
     capacity, dev, pset, rows, vws = _device_rows_tensors(
@@ -875,9 +918,15 @@ def histogram_device_rows(model: ModelSetup, q, intensity, sigma, contribs, spec
             torch.cuda.current_stream(dev).synchronize()
 
     cb, failure = _rows_callback(_lib.DeviceRowsCallback, fill)
-    rc = lib.mcsas_hip_histogram_device_rows(C.byref(call.prob.c), as_dp(call.contribs), C.c_void_p(pset.data_ptr()),
-                                             C.c_void_p(rows.data_ptr()), C.c_void_p(vws.data_ptr()), capacity,
-                                             cb, None, len(call.specs), call.arr, as_dp(call.sc), as_dp(call.frac), as_dp(call.out))
+    if call.want is None:
+        rc = lib.mcsas_hip_histogram_device_rows(C.byref(call.prob.c), as_dp(call.contribs), C.c_void_p(pset.data_ptr()),
+                                                 C.c_void_p(rows.data_ptr()), C.c_void_p(vws.data_ptr()), capacity,
+                                                 cb, None, len(call.specs), call.arr, as_dp(call.sc), as_dp(call.frac), as_dp(call.out))
+    else:
+        rc = lib.mcsas_hip_histogram_partial_device_rows(C.byref(call.prob.c), as_dp(call.contribs), C.c_void_p(pset.data_ptr()),
+                                                         C.c_void_p(rows.data_ptr()), C.c_void_p(vws.data_ptr()), capacity,
+                                                         cb, None, len(call.specs), call.arr, call.want_p(), as_dp(call.sc),
+                                                         as_dp(call.frac), as_dp(call.out), as_dp(call.partial))
     if failure:
         raise failure[0]
     check(rc, lib)

@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 from . import engine
-from .parameter import isActiveFitParam
+from .parameter import isActiveFitParam, partial_intensities
 from .scatteringmodels import (setup_from_model, host_model_calc, is_batch_model, batch_model_calc, batch_clip,
                                refuse_batch_smearing)
 
@@ -65,6 +65,29 @@ _DEFAULTS = (
     ("findBackground", True, None), ("positiveBackground", False, None),
     ("startFromMinimum", False, None), ("maxRetries", 5, (1, 100)), ("showIncomplete", False, None),
 )
+
+
+class _HostPartial(object):
+    """The partial intensities of the histograms `todo` [(paramIndex, histogram)] in numpy, a repetition at a time
+    (parameter.partial_intensities: the operation order of csrc/hist_partial_kernel.h)."""
+
+    def __init__(self, todo, nq, numReps):
+        self.todo = list(todo)
+        for _, h in self.todo:
+            h._setXLowerEdge()
+        self.range = [np.zeros((nq, numReps)) for _ in self.todo]
+        self.bins = [np.zeros((h.binCount, nq, numReps)) if h.partialIntensity == "bins" else None for _, h in self.todo]
+
+    def add(self, ri, rows, pset, scale):
+        for k, (pi, h) in enumerate(self.todo):
+            rng, bins = partial_intensities(rows, pset[:, pi], scale, min(h.xrange), max(h.xrange), h.xLowerEdge, self.bins[k] is not None)
+            self.range[k][:, ri] = rng
+            if bins is not None:
+                self.bins[k][:, :, ri] = bins
+
+    def finish(self):
+        for k, (pi, h) in enumerate(self.todo):
+            h.setIntensity(self.range[k], self.bins[k])
 
 
 class McSAS(object):
@@ -284,6 +307,7 @@ class McSAS(object):
                 item = self._histogram_item(setup, None, contribs)
                 del item["comp_exp"], item["smear"]
                 self._histogram_from_device(engine.histogram_device_rows(row_fn=rows_on_device, **item), contribs)
+                self._partial_on_host(contribs, setup, smear, [(pi, h) for pi, h in self._partial_todo() if not h.partialOnDevice()])
                 return
             # rows by the model's own calcIntensity (:552, :577-578), the fit on the device (:559), the visibility limits in numpy (:575-590)
             scalingFactors = np.zeros((2, numReps))
@@ -292,6 +316,7 @@ class McSAS(object):
             # (a batch model: the sets of a block of repetitions in one calcIntensityBatch call, at most ~256 MB of rows at a time)
             batch = is_batch_model(model)
             per_block = max(1, (256 << 20) // (8 * data.count * numContribs)) if batch else 1
+            partial = _HostPartial(self._partial_todo(), data.count, numReps)      # (from the rows held here anyway)
             for ri in range(numReps):
                 if batch:
                     if ri % per_block == 0:
@@ -312,7 +337,9 @@ class McSAS(object):
                     part = sc[0] * rows[ci]
                     nz = part != 0.
                     mv[ci, ri] = (sig[nz] * vf_r[ci] / part[nz]).min()
+                partial.add(ri, rows, contribs[:, :, ri], sc[0])
             self._histogram_tail(contribs, scalingFactors, vsets, wsets, ssets, mv)
+            partial.finish()
             return
         # Everything on the device in one call (mcsas_hip_histogram): model.calc, the scale / background fit, the visibility
         # limits, the fractions, and per configured histogram the bins, CDF and moments of every repetition — their mean / std over
@@ -320,6 +347,7 @@ class McSAS(object):
         if numContribs <= engine.HISTOGRAM_MAX_CONTRIBS:
             item = self._histogram_item(setup, smear, contribs)
             self._histogram_from_device(engine.histogram_device(**item), contribs)
+            self._partial_on_host(contribs, setup, smear, [(pi, h) for pi, h in self._partial_todo() if not h.partialOnDevice()])
             return
         # model.calc, the scale/background fit and the N single-row visibility limits of every repetition
         # (:552, :559, :575-590): one library call for all of them
@@ -327,9 +355,36 @@ class McSAS(object):
             setup, data.q, data.f.binnedData, sig, contribs, c, self.findBackground.value(),
             self.positiveBackground.value(), device=self.device, smear=smear)
         self._histogram_tail(contribs, scalingFactors, vsets, wsets, ssets, mv)
+        self._partial_on_host(contribs, setup, smear, self._partial_todo())
 
     def _histogram_todo(self):
         return [(pi, h) for pi, param in enumerate(self.model.activeParams()) for h in param.histograms()]
+
+    def _partial_todo(self):
+        """the histograms that ask for partial intensities (Histogram(partialIntensity=...))"""
+        return [(pi, h) for pi, h in self._histogram_todo() if getattr(h, "partialIntensity", None)]
+
+    def _partial_on_host(self, contribs, setup, smear, todo):
+        """The partial intensities the device call did not take — more than engine.HISTOGRAM_MAX_CONTRIBS contributions, more than
+        engine.HISTOGRAM_PARTIAL_MAX_BINS bins, edges that are not finite — in numpy (parameter.partial_intensities) from the rows of
+        a repetition at a time: engine.model_calc(want_rows=True), or the host model's own.  After the histograms have their moments
+        and result[0]['scalingFactors'] is set; with nobody asking nothing runs."""
+        if not todo:
+            return
+        data, model, c = self.data, self.model, self.compensationExponent()
+        numReps = contribs.shape[2]
+        scale = self.result[0]['scalingFactors'][0]
+        partial = _HostPartial(todo, data.count, numReps)
+        for ri in range(numReps):
+            pset = np.ascontiguousarray(contribs[:, :, ri])
+            if setup.model_id != engine.MODEL_HOST:
+                rows = engine.model_calc(setup, data.q, pset, c, want_rows=True, device=self.device, smear=smear)[4]
+            elif is_batch_model(model):
+                rows = batch_model_calc(model, data, pset, c, want_rows=True, device=self.device)[4]
+            else:
+                rows = host_model_calc(model, data, pset, c, want_rows=True)[4]
+            partial.add(ri, np.asarray(rows).reshape(len(pset), -1), pset, scale[ri])
+        partial.finish()
 
     def _histogram_item(self, setup=None, smear=None, contribs=None):
         """engine.histogram_device's arguments (by name) for the stored result with the current data, model and histograms

@@ -220,8 +220,40 @@ class VectorResult(object):
         self.std = vec.std(axis=1, ddof=1 if len(vec) > 1 else 0)
 
 
+def partial_intensities(rows, x, A, lower, upper, edges=None, bins=False):
+    """The partial intensities of one repetition in numpy: the transcription of hist_partial_kernel's operation order
+    (csrc/hist_partial_kernel.h), equal to it bit for bit.  `rows` [N][nq]: the contributions' intensity rows; `x` [N]: their values
+    of the histogram's parameter; `A`: the repetition's scale.  Returns (range[nq], bin[n_bin][nq] or None):
+        range[k]  = A * sum_c rows[c][k] over lower < x_c < upper (strict: the mask of the moments)
+        bin[b][k] = A * sum_c rows[c][k] over edges[b] <= x_c < edges[b+1] and x_c < edges[-1] (Histogram.calc's members)
+    Each sum is a cumulative sum down the contributions, in order, from +0.0, and is multiplied by A once, at the end.  The
+    contributions outside add +0.0, which leaves a running sum that began at +0.0 as it is: the cumulative sum over the selected
+    rows alone, behind a row of zeros, is the same additions.  Nobody selected: A * 0.0.  A NaN value is in no bin and no range."""
+    rows = np.asarray(rows, dtype=np.float64)
+    rows = rows.reshape(len(rows), rows.size // max(len(rows), 1) if len(rows) else (rows.shape[1] if rows.ndim > 1 else 0))
+    x = np.asarray(x, dtype=np.float64).ravel()
+    A = np.float64(A)
+    zero = np.zeros((1, rows.shape[1]))
+
+    def osum(mask):
+        return np.cumsum(np.concatenate([zero, rows[mask]]), axis=0)[-1]
+
+    with np.errstate(all='ignore'):
+        rng = A * osum((x > lower) & (x < upper))
+        if not bins:
+            return rng, None
+        e = np.asarray(edges, dtype=np.float64).ravel()
+        out = np.zeros((max(len(e) - 1, 0), rows.shape[1]))
+        for b in range(len(e) - 1):
+            out[b] = A * osum((x >= e[b]) & (x < e[b + 1]) & (x < e[-1]))
+    return rng, out
+
+
 class Moments(object):
-    """utils/parameter.py:20-122 (partial intensities :124-154 are not on the path)."""
+    """utils/parameter.py:20-154.  `intensity`: the partial intensity of the value range, (mean[nq], std[nq]) over the repetitions
+    (:124-154), where the histogram asks for it (Histogram(partialIntensity=...)); None otherwise."""
+    intensity = None
+
     @staticmethod
     def fieldNames():
         return ("totalValue", "totalValueStd", "mean", "meanStd", "variance", "varianceStd",
@@ -282,7 +314,15 @@ class Moments(object):
 class Histogram(object):
     """utils/parameter.py:187-538: bins, CDF, observability and moments of one parameter."""
 
-    def __init__(self, param, lower, upper, binCount=50, xscale=None, yweight=None, autoFollow=True):
+    PARTIAL = (None, "range", "bins")
+
+    def __init__(self, param, lower, upper, binCount=50, xscale=None, yweight=None, autoFollow=True, partialIntensity=None):
+        """partialIntensity: None, "range" (the scattering curve of the contributions inside the value range: .intensity,
+        .moments.intensity) or "bins" (that, and the curve of every bin: .binIntensity); McSAS.histogram() fills them."""
+        if partialIntensity not in self.PARTIAL:
+            raise ValueError("Histogram: partialIntensity %r (None, 'range' or 'bins')" % (partialIntensity,))
+        self.partialIntensity = partialIntensity
+        self.intensity = self.binIntensity = None
         self.param = param
         self.binCount = max(0, int(binCount))
         self.xrange = (float(lower), float(upper))
@@ -375,6 +415,7 @@ class Histogram(object):
             cdf = np.where(top[None, :] == 0.0, 0., cdf / top[None, :])
         self._setResults(bins, allObs, cdf)
         self.moments = Moments(contribs, paramIndex, self.xrange, frac)
+        self.intensity = self.binIntensity = None             # (McSAS.histogram() fills them after this where they are asked for)
 
     def _setResults(self, bins, allObs, cdf):
         nb, numReps = bins.shape
@@ -387,12 +428,39 @@ class Histogram(object):
     def deviceSpec(self, paramIndex):
         """What mcsas_hip_histogram needs to know about this histogram (engine.histogram_device)."""
         self._setXLowerEdge()
-        return dict(param_index=paramIndex, yweight=self.yweight, edges=self.xLowerEdge, lower=min(self.xrange), upper=max(self.xrange))
+        spec = dict(param_index=paramIndex, yweight=self.yweight, edges=self.xLowerEdge, lower=min(self.xrange), upper=max(self.xrange))
+        if self.partialOnDevice():
+            spec["partial"] = self.partialIntensity
+        return spec
+
+    def partialOnDevice(self, maxBins=256):
+        """Whether the device call takes this histogram's partial intensities: asked for, and for the bin curves no more bins than
+        engine.HISTOGRAM_PARTIAL_MAX_BINS and edges that are finite and ascend (McSAS.histogram() takes the others in numpy)."""
+        if self.partialIntensity != "bins":
+            return self.partialIntensity is not None
+        if self.xLowerEdge is None:
+            self._setXLowerEdge()
+        e = np.asarray(self.xLowerEdge, dtype=float)
+        return self.binCount <= maxBins and bool(np.isfinite(e).all() and (np.diff(e) >= 0).all())
+
+    def setIntensity(self, rangeCurves, binCurves=None):
+        """The partial intensities of every repetition, range [nq][R] and bin [n_bin][nq][R] or None: .intensity (VectorResult),
+        .moments.intensity = (mean[nq], std[nq]) with ddof 1 beyond one repetition (utils/parameter.py:150-154), .binIntensity
+        (.full, .mean, .std over the repetitions)."""
+        rangeCurves = np.array(rangeCurves, dtype=np.float64)
+        self.intensity = VectorResult(rangeCurves)
+        ddof = 1 if rangeCurves.shape[1] > 1 else 0
+        if self.moments is not None:
+            self.moments.intensity = (rangeCurves.mean(axis=1), rangeCurves.std(axis=1, ddof=ddof))
+        self.binIntensity = CellResult(np.array(binCurves, dtype=np.float64)) if binCurves is not None else None
 
     def setFromDevice(self, res):
         """bins / obs / cdf / moments of every repetition as mcsas_hip_histogram returns them (engine.histogram_device)."""
         self._setResults(np.array(res["bins"]), np.array(res["obs"]), np.array(res["cdf"]))
         self.moments = Moments.fromRepetitions(*[np.array(x) for x in res["moments"]])
+        self.intensity = self.binIntensity = None
+        if "intensity" in res:
+            self.setIntensity(res["intensity"], res.get("bin_intensity"))
 
 
 # ------------------------------------------------------------------ joint histogram of two parameters (post-fit; no reference counterpart)

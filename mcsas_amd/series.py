@@ -13,8 +13,11 @@ BATCH_HISTOGRAMS_DEFAULT = True
 
 def _histograms_batchable(algo, engine):
     """A batched histogram pass needs what McSAS.histogram()'s one-call device path needs: a device model, and no more than
-    engine.HISTOGRAM_MAX_CONTRIBS contributions."""
+    engine.HISTOGRAM_MAX_CONTRIBS contributions.  The batch call has no partial intensities: when any histogram asks for them
+    (Histogram(partialIntensity=...)) the answer is False and the series takes each data set's own McSAS.histogram() call."""
     from .scatteringmodels import setup_from_model
+    if algo._partial_todo():
+        return False
     return (algo.data is not None and setup_from_model(algo.model, algo.data).model_id != engine.MODEL_HOST
             and algo.numContribs() <= engine.HISTOGRAM_MAX_CONTRIBS)
 
