@@ -362,6 +362,40 @@ int mcsas_hip_plan_set_trace(mcsas_plan *plan, int32_t capacity);
 int mcsas_hip_plan_fetch_trace(mcsas_plan *plan, int32_t slot, mcsas_trace *trace);
 int mcsas_hip_analyse_traced(const mcsas_problem *problem, const double *start, mcsas_result *result, mcsas_trace *trace);
 
+/* ---- one population fitted to several data sets, each with a scale and a background of its own (ABI 5, additive) ---------------
+ * The same specimen measured more than once (two detector distances, SAXS + WAXS, two instruments): curves that overlap in q,
+ * whose relative scale is not known well enough to merge them and whose backgrounds differ.  mcFit (mcsas.py:354-404) and
+ * BackgroundScalingFit.calc (backgroundscalingfit.py:112-139) know one curve; this call extends them.  A chain holds ONE set of
+ * n_contrib contributions; a row (calcIntensity) is evaluated at the q-points of all n_sets sets with the model's one parameter
+ * vector.  At every fit — initial, per step, final — each set s gets the closed-form least-squares scale (and, with
+ * find_background, background) of its own points, and the chain minimises the reduced chi-squared over ALL points:
+ *   chi² nq = X = sum_s (S_s - num_s²/den_s),   a step is accepted iff X_t < X (strict, mcsas.py:379),
+ * where S, num, den are SII, SIC, SCC of the set, centred (S = SII - SI²/Sw, num = SIC - SI SC/Sw, den = SCC - SC²/Sw) when a
+ * background is fitted.  Convergence, retries and max_iter use chi² = X / nq as the single-set chain uses its chi².  Everything else
+ * is mcsas_hip_analyse in MCSAS_EXEC_WAVE with cached rows: the draw order, the replay stream, Philox keyed by rep_offset + rep,
+ * start_from_minimum, `stop`; with n_sets = 1 the chain takes that call's decisions.
+ * problem->q / intensity / sigma hold the sets one after the other, set_nq[s] points each (>= 3), nq == sum set_nq.  One wavefront
+ *   per chain: set s takes ceil(set_nq[s] / 64) register slots of 64 entries, and all sets together at most 16 slots.
+ * result: as mcsas_hip_analyse; fit[nq][n_reps] holds every point with its own set's scale and background, chisq is the direct
+ *   residual sum over all points / nq, scaling and background are set 0's.  sets (caller-allocated, arrays [n_sets][n_reps], an
+ *   array left NULL is not written): each set's scale, background and sum over the set of ((I - fit) / sigma)² / set_nq[s].
+ * Refused with MCSAS_EINVAL and a message that names the cause, before a device is touched: n_sets outside 1..MCSAS_MAX_SETS, a
+ *   set of fewer than 3 points, sum set_nq != nq, more than 16 slots, positive_background, smearing (smear_nk > 0), a device list
+ *   (n_devices > 1), a model plug-in or a model that exists only as host code, n_active == 0, cache_intensities == 0, an exec_mode
+ *   other than MCSAS_EXEC_AUTO or MCSAS_EXEC_WAVE, a wrong struct_size.  There is no plan, slot, batch, start or trace form.
+ * Not offered: one scale shared by the sets (absolutely calibrated data), fixed model parameters per set (contrast
+ *   variation). */
+#define MCSAS_MAX_SETS 4
+typedef struct mcsas_sets_result {
+    uint32_t struct_size;  /* sizeof(mcsas_sets_result) */
+    int32_t  n_sets;       /* rows of the arrays below: the call's n_sets */
+    double  *scaling;      /* [n_sets][n_reps] */
+    double  *background;   /* [n_sets][n_reps] */
+    double  *chisq;        /* [n_sets][n_reps] sum over the set / set_nq[s] */
+} mcsas_sets_result;
+int mcsas_hip_analyse_sets(const mcsas_problem *problem, int32_t n_sets, const int32_t *set_nq,
+                           mcsas_result *result, mcsas_sets_result *sets);
+
 /* ---- ScatteringModel.calc(data, pset, compensationExponent) (scatteringmodel.py:79-109) ------
  * Uses problem->{model_id, params, n_active, active_index, clip_*, nq, q, comp_exp, device}.
  * pset[n][n_active] -> cum_int[nq] (rows summed in order), vset/wset/sset[n], optional

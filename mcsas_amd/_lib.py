@@ -15,6 +15,7 @@ MAX_ACTIVE = 4
 MAX_PARAMS = 8
 ABI_VERSION = 5
 MAX_DEVICES = 16
+MAX_SETS = 4            # data sets one population is fitted to at once (include/mcsas_hip.h: MCSAS_MAX_SETS)
 
 # MCSAS_HIP_LIB selects another build of the SAME library (e.g. the -DMCSAS_STAMPS diagnostic build)
 LIB_PATH = os.environ.get("MCSAS_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmcsas_hip.so")
@@ -25,7 +26,7 @@ SYMBOLS = (
     "mcsas_hip_plan_launch_slot", "mcsas_hip_plan_fetch_slot",
     "mcsas_hip_plan_last_ms", "mcsas_hip_plan_total_steps", "mcsas_hip_plan_reseed", "mcsas_hip_plan_info",
     "mcsas_hip_plan_destroy", "mcsas_hip_plan_launch_batch", "mcsas_hip_analyse_batch", "mcsas_hip_plan_set_start", "mcsas_hip_analyse_from",
-    "mcsas_hip_plan_set_trace", "mcsas_hip_plan_fetch_trace", "mcsas_hip_analyse_traced", "mcsas_hip_model_calc", "mcsas_hip_bgfit", "mcsas_hip_observability",
+    "mcsas_hip_plan_set_trace", "mcsas_hip_plan_fetch_trace", "mcsas_hip_analyse_traced", "mcsas_hip_analyse_sets", "mcsas_hip_model_calc", "mcsas_hip_bgfit", "mcsas_hip_observability",
     "mcsas_hip_histogram_prep", "mcsas_hip_histogram", "mcsas_hip_histogram_batch", "mcsas_hip_histogram_rows_shape", "mcsas_hip_histogram_device_rows",
     "mcsas_hip_histogram_partial", "mcsas_hip_histogram_partial_device_rows",
     "mcsas_hip_histogram2d", "mcsas_hip_prepare_uncertainty", "mcsas_hip_rebin",
@@ -103,6 +104,14 @@ class Trace(C.Structure):
     ]
 
 
+class SetsResult(C.Structure):
+    """mcsas_sets_result (include/mcsas_hip.h): per data set of a joint fit, [n_sets][n_reps] each."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_sets", C.c_int32),
+        ("scaling", _dp), ("background", _dp), ("chisq", _dp),
+    ]
+
+
 class McSASHipError(RuntimeError):
     def __init__(self, code, message):
         super().__init__("libmcsas_hip error %d: %s" % (code, message))
@@ -159,6 +168,7 @@ def load(tuning=False):
     lib.mcsas_hip_plan_set_trace.argtypes = [C.c_void_p, C.c_int32]
     lib.mcsas_hip_plan_fetch_trace.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Trace)]
     lib.mcsas_hip_analyse_traced.argtypes = [C.POINTER(Problem), _dp, C.POINTER(Result), C.POINTER(Trace)]
+    lib.mcsas_hip_analyse_sets.argtypes = [C.POINTER(Problem), C.c_int32, _i32p, C.POINTER(Result), C.POINTER(SetsResult)]
     lib.mcsas_hip_plan_destroy.argtypes = [C.c_void_p]
     lib.mcsas_hip_plan_destroy.restype = None
     lib.mcsas_hip_model_calc.argtypes = [C.POINTER(Problem), _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp]

@@ -1,6 +1,6 @@
 // host_internal.h — what the host units of libmcsas_hip.so share (mcsas_hip.hip: plans; host_decide.hip: what is decided without a device; host_analyse.hip:
 // one-shot analyses; host_rows.hip: rows evaluated by the caller; host_plugin.hip: run-time compiler of model plug-ins; host_calls.hip: small one-call entry points; host_hist.hip:
-// McSAS.histogram(); small_launch.h: from a model id to a small kernel's instance, for the last two).  Host code only: the run-time compiler never sees this file (it is not among the embedded headers).
+// McSAS.histogram(); host_sets.hip: one population fitted to several data sets; small_launch.h: from a model id to a small kernel's instance, for the last two).  Host code only: the run-time compiler never sees this file (it is not among the embedded headers).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>

@@ -246,3 +246,57 @@ class SASData(object):
                 continue
         arr = np.array([r for r in rows if len(r) == 3])
         return cls(arr[:, 0] * q_unit, arr[:, 1], arr[:, 2], title=filename)
+
+
+class DataSets(object):
+    """Several measurements of ONE specimen — two detector distances, SAXS + WAXS, two instruments — for a joint fit: wraps the
+    members' SASData objects.  With `algo.data = DataSets([d0, d1, ...])` McSAS.analyse() fits one population to all members at once,
+    each with a least-squares scale and background of its own at every step (engine.analyse_sets; include/mcsas_hip.h:
+    mcsas_hip_analyse_sets); 1 to engine.MAX_SETS members of at least 3 points each.  The vectors the fit reads (`q`, `f.binnedData`,
+    `f.binnedDataU`, `x0`) are the members' one after the other, and `slices` says where each member lies in them.
+    `histogramSet` (default 0): the member histogram() and the partial / 2-D histograms run against.  They take the existing
+    single-set path with that member's data alone, whose scale fit is exactly the joint fit's for that member, so fractions are
+    consistent with it — and the visibility limits are those "as seen by that set": a size another member would see and this one
+    does not counts as invisible.  Smearing configurations of the members are not used (the joint fit refuses smearing)."""
+
+    def __init__(self, members, histogramSet=0, title="data sets"):
+        self.members = list(members)
+        if not self.members:
+            raise ValueError("DataSets: needs at least one SASData")
+        for d in self.members:
+            if not (hasattr(d, "x0") and hasattr(d, "f")) or d.f.binnedDataU is None:
+                raise ValueError("DataSets: every member is a SASData with q, intensity and sigma")
+        self.title = title
+        self.histogramSet = int(histogramSet)
+        self.x0 = DataVector("q", np.concatenate([d.x0.binnedData for d in self.members]))
+        self.f = DataVector("I", np.concatenate([d.f.binnedData for d in self.members]),
+                            np.concatenate([d.f.binnedDataU for d in self.members]))
+        self.f.limit = [min(d.f.limit[0] for d in self.members), max(d.f.limit[1] for d in self.members)]
+        edges = np.concatenate([[0], np.cumsum([d.count for d in self.members])])
+        self.slices = [slice(int(a), int(b)) for a, b in zip(edges[:-1], edges[1:])]
+
+    def __len__(self):
+        return len(self.members)
+
+    def histogramMember(self):
+        if not 0 <= self.histogramSet < len(self.members):
+            raise ValueError("DataSets.histogramSet %d: there are %d members" % (self.histogramSet, len(self.members)))
+        return self.members[self.histogramSet]
+
+    def triples(self):
+        """[(q, I, sigma)] of the members: engine.analyse_sets' `sets`"""
+        return [(d.x0.binnedData, d.f.binnedData, d.f.binnedDataU) for d in self.members]
+
+    def smearArgs(self, model):
+        return None
+
+    @property
+    def q(self):
+        return self.x0.binnedData
+
+    @property
+    def count(self):
+        return len(self.x0.binnedData)
+
+    def sphericalSizeEst(self):
+        return np.array([np.pi / self.x0.limit[1], np.pi / self.x0.limit[0]])

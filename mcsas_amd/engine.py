@@ -12,7 +12,7 @@ from dataclasses import dataclass, field, replace
 import numpy as np
 
 from . import _lib
-from ._lib import MAX_ACTIVE, MAX_DEVICES, MAX_PARAMS, Problem, Result, as_dp, check, f64
+from ._lib import MAX_ACTIVE, MAX_DEVICES, MAX_PARAMS, MAX_SETS, Problem, Result, as_dp, check, f64
 
 MODEL_SPHERE, MODEL_CYL_ISO, MODEL_ELL_CS, MODEL_KHOLODENKO = 0, 1, 2, 3
 MODEL_ELL_ISO, MODEL_SPH_CS, MODEL_GAUSS_CHAIN, MODEL_LMA_SPHERE = 4, 5, 6, 7
@@ -299,6 +299,58 @@ def analyse(model: ModelSetup, q, intensity, sigma, st: Settings, replay=None, s
         check(lib.mcsas_hip_analyse_from(C.byref(prob.c), as_dp(a), C.byref(res.c)), lib)
     else:
         check(lib.mcsas_hip_analyse(C.byref(prob.c), C.byref(res.c)), lib)
+    return res
+
+
+class SetsResults(ChainResults):
+    """A joint fit of several data sets (analyse_sets): ChainResults over the concatenated points — `fit` holds every point with its
+    own set's scale and background, `chisq` the reduced chi-squared over all points, `scaling` / `background` set 0's — plus, per set,
+    set_scaling[S][R], set_background[S][R], set_chisq[S][R] (the sum over the set / its number of points) and `slices`, where each
+    set lies among the points."""
+
+    def __init__(self, n_contrib, n_active, n_reps, set_nq):
+        super().__init__(n_contrib, n_active, n_reps, int(sum(set_nq)))
+        S = len(set_nq)
+        self.set_nq = np.ascontiguousarray(set_nq, dtype=np.int32)
+        edges = np.concatenate([[0], np.cumsum(self.set_nq)])
+        self.slices = [slice(int(a), int(b)) for a, b in zip(edges[:-1], edges[1:])]
+        self.set_scaling = np.zeros((S, n_reps)); self.set_background = np.zeros((S, n_reps)); self.set_chisq = np.zeros((S, n_reps))
+        s = _lib.SetsResult()
+        s.struct_size = C.sizeof(_lib.SetsResult)
+        s.n_sets = S
+        s.scaling, s.background, s.chisq = as_dp(self.set_scaling), as_dp(self.set_background), as_dp(self.set_chisq)
+        self.sets_c = s
+
+
+def analyse_sets(model: ModelSetup, sets, st: Settings, replay=None, stop=None) -> SetsResults:
+    """One population fitted to several data sets at once (mcsas_hip_analyse_sets, include/mcsas_hip.h): `sets` is a list of 1 to
+    MAX_SETS triples (q, I, sigma) of at least 3 points each — measurements of the same specimen whose relative scale and whose
+    backgrounds are not known.  Every chain holds one set of contributions and is judged by all sets: at every step each set gets its
+    own least-squares scale and background, and the chain minimises the reduced chi-squared over all points.  One wavefront per chain,
+    cached rows; together the sets, each padded to a multiple of 64 points, take at most 1024 entries.  Refused (ValueError here or
+    MCSAS_EINVAL from the library, before a device is touched): positive_background, a device list, a model plug-in or a model that
+    exists only as host code, no active parameter, cache_intensities == 0, an exec_mode other than EXEC_AUTO / EXEC_WAVE; there is
+    no plan, batch, start, trace or smearing form."""
+    triples = [tuple(f64(v).ravel() for v in trip) for trip in sets]
+    if any(len(trip) != 3 for trip in triples):
+        raise ValueError("analyse_sets: sets is a list of (q, I, sigma)")
+    for s, (q, i, e) in enumerate(triples):
+        if not (len(q) == len(i) == len(e)):
+            raise ValueError("analyse_sets: set %d: q, intensity and sigma must have the same length" % s)
+    if model.model_id == MODEL_HOST:
+        raise ValueError("analyse_sets: a model that exists only as host code is not supported (built-in models only)")
+    if model.model_id >= MODEL_PLUGIN0:
+        raise ValueError("analyse_sets: a model plug-in is not supported (built-in models only)")
+    if st.devices:
+        raise ValueError("analyse_sets: a device list %r was given; the joint fit runs on one device" % (tuple(st.devices),))
+    if st.debug_flags:
+        raise ValueError("analyse_sets: debug_flags select variants of the pipeline mode; the joint fit has none")
+    lib = _lib.load()
+    cat = [np.concatenate([trip[k] for trip in triples]) if triples else np.zeros(0) for k in range(3)]
+    prob = HipProblem(model, cat[0], cat[1], cat[2], st, replay, stop, None)
+    res = SetsResults(st.n_contrib, model.n_active, st.n_reps, [len(trip[0]) for trip in triples])
+    check(lib.mcsas_hip_analyse_sets(C.byref(prob.c), len(triples), res.set_nq.ctypes.data_as(C.POINTER(C.c_int32)),
+                                     C.byref(res.c), C.byref(res.sets_c)), lib)
     return res
 
 

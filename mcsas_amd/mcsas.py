@@ -15,6 +15,7 @@ import os
 import numpy as np
 
 from . import engine
+from .dataobj import DataSets
 from .parameter import isActiveFitParam, partial_intensities
 from .scatteringmodels import (setup_from_model, host_model_calc, is_batch_model, batch_model_calc, batch_clip,
                                refuse_batch_smearing)
@@ -194,6 +195,8 @@ class McSAS(object):
         `trace`: K >= 1 stores the first K accepted moves of every repetition's last attempt under result[0]['trace'] (count, chisq0,
         step[K][R], chisq[K][R], values[K][P][R]: engine.ChainTrace); one wavefront per chain, or the q-split workgroup kernel where
         execMode asks for it (_check_trace_mode)."""
+        if isinstance(self.data, DataSets):
+            return self._analyse_sets(replay, start, trace)
         trace_mode = self._check_trace_mode(trace)
         if self.result is None:
             self.result = []
@@ -231,10 +234,35 @@ class McSAS(object):
         if trace is not None and res.trace is not None and len(self.result):
             self.result[0]['trace'] = res.trace.asdict()
 
+    def _analyse_sets(self, replay=None, start=None, trace=None):
+        """analyse() where `data` is a DataSets: one population fitted to all members at once, each with a scale and a background of
+        its own (engine.analyse_sets).  result[0] keeps its keys, the q-indexed ones over the members one after the other (scaling and
+        background: member 0's), and gains 'sets': per member a dict of `slice` (where it lies among the points), `scaling` and
+        `background` (mean, std over the repetitions) and `chisq` (per repetition: the sum over the member / its number of points).
+        A start and a trace are refused, and so is everything engine.analyse_sets refuses."""
+        if start is not None or trace is not None:
+            raise ValueError("McSAS: the joint fit of a DataSets takes no %s" % ("start" if start is not None else "trace"))
+        if self.result is None:
+            self.result = []
+        data, model = self.data, self.model
+        if not any(isActiveFitParam(p) for p in model.params()):
+            raise ValueError("McSAS: the joint fit of a DataSets needs an active fit parameter")
+        numReps = self.numReps()
+        st = self._settings(self.numContribs(), numReps)
+        res = engine.analyse_sets(setup_from_model(model, data), data.triples(), st, replay=replay, stop=self._stop)
+        self._store(res, numReps)
+        if len(self.result):
+            ddof = 1 if numReps > 1 else 0
+            self.result[0]['sets'] = [dict(slice=sl, scaling=(res.set_scaling[s].mean(), res.set_scaling[s].std(ddof=ddof)),
+                                           background=(res.set_background[s].mean(), res.set_background[s].std(ddof=ddof)),
+                                           chisq=res.set_chisq[s].copy()) for s, sl in enumerate(res.slices)]
+
     def _problem(self, numContribs=None, numReps=None, replay=None, start=None):
         """What analyse() hands to the library for the current data / model / settings (engine.analyse_many takes a list of these).
         With a `start` (see analyse) the problem asks for the mode of _check_start_mode and carries the checked array under "start"."""
         data, model = self.data, self.model
+        if isinstance(data, DataSets):
+            raise ValueError("McSAS: the joint fit of a DataSets runs through analyse() / calc() alone; it has no plan, batch or series form")
         if numContribs is None:
             active = any(isActiveFitParam(p) for p in model.params())
             numContribs, numReps = (self.numContribs(), self.numReps()) if active else (1, 1)
@@ -281,6 +309,15 @@ class McSAS(object):
             times=res.seconds, numIter=res.num_iter.astype(float).mean()))
 
     def histogram(self, contribs=None):                      # mcsas.py:445-615
+        """With a DataSets as `data` everything below runs against ONE member, DataSets.histogramSet, through the single-set path:
+        its scale fit is the joint fit's for that member, and the visibility limits are those as seen by that set."""
+        if isinstance(self.data, DataSets):
+            sets = self.data
+            self.data = sets.histogramMember()
+            try:
+                return self.histogram(contribs)
+            finally:
+                self.data = sets
         if not isinstance(self.result, list) or not len(self.result):
             logging.info("There are no results to histogram, breaking up.")
             return

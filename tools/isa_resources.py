@@ -71,16 +71,17 @@ def demangle(names):
 def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else "r04"
     jobs = int(sys.argv[sys.argv.index("-j") + 1]) if "-j" in sys.argv else 4
-    work = [(fam, m, []) for fam in ("pipe", "wave", "wg", "wide") for m in models()]
+    work = [(fam, m, []) for fam in ("pipe", "wave", "wave_sets", "wg", "wide") for m in models()]
     with ThreadPoolExecutor(jobs) as ex:
         res = list(ex.map(compile_one, work))
     commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
     out = ["# ISA resources of the chain kernels (%s, tree at %s%s)" % (tag, commit, "+" if subprocess.run(["git", "-C", ROOT, "diff", "--quiet"]).returncode else ""), "",
-           "`hipcc %s -Rpass-analysis=kernel-resource-usage` on `mcsas_amd/csrc/kern_{pipe,wave,wg,wide}.hip` per model (tools/isa_resources.py)." % " ".join(FLAGS),
+           "`hipcc %s -Rpass-analysis=kernel-resource-usage` on `mcsas_amd/csrc/kern_{pipe,wave,wave_sets,wg,wide}.hip` per model (tools/isa_resources.py)." % " ".join(FLAGS),
            "gfx950: 512 registers per lane and SIMD shared by a wave's VGPRs + AGPRs; the pipeline / workgroup kernels run 8 waves per",
            "workgroup (2 waves per SIMD: up to 256 registers each), LDS is dynamic (not in this table: see DESIGN.md). `scratch` > 0 means",
            "spilled vector registers (bytes per lane); SGPR spills go to VGPR lanes (v_writelane / v_readlane), not to memory.", ""]
     for fam, title in (("pipe", "pipe_tick_kernel<M, QPL> — whole-chip pipeline"), ("wave", "chain_wave_kernel<M, QPL, CACHE> — one wavefront per chain"),
+                       ("wave_sets", "chain_sets_kernel<M, QPL> — one wavefront per chain, several data sets (no more scratch than chain_wave_kernel<M, QPL, true, false>)"),
                        ("wg", "chain_wg_kernel<M, QPL> — one workgroup per chain"), ("wide", "chain_wide_kernel<M, QPL> — more than 1024 q-points")):
         out += ["## " + title, "", "| model | kernel | VGPRs | AGPRs | SGPRs | scratch B/lane | VGPR spills | SGPR spills | occupancy waves/SIMD |", "|---|---|---|---|---|---|---|---|---|"]
         for f, m, text in res:
