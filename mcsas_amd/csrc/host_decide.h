@@ -1,8 +1,10 @@
 // host_decide.h — what libmcsas_hip.so decides without a device (host_decide.hip), beside what host_internal.h declares of that unit
 // for every host unit (the refusals, the family table, the trace block's layout): how a problem runs, how a kernel family is launched
-// and named, a fetched trace block's transposition, a pipeline launch's ticks.  None of it calls the HIP runtime.
+// and named, the settings block every chain kernel takes, the request, layout and data of several sets fitted with one population, a
+// fetched trace block's transposition, a pipeline launch's ticks.  None of it calls the HIP runtime.
 #pragma once
 #include "host_internal.h"
+#include "chain_sets.h"  // SetsArgs / SetConst only; the kernel is instantiated in kern_wave_sets.hip
 #include "chain_wg.h"    // WgGeom / wg_geometry only; the kernels are instantiated in kern_*.hip
 #include "pipe_layout.h" // the pipeline's argument blocks, constants and pipe_geometry (no kernel templates)
 
@@ -26,6 +28,28 @@ struct PlanShape {
     mcsas::PipeGeom pipe{};
 };
 int decide_shape(const mcsas_problem *p, const mcsas::ModelArgs &margs, int n_cus, size_t free_bytes, const TuneWord &tw, PlanShape *s);
+
+// The settings block of a chain kernel's argument block (n_contrib ... conv_crit, the generators, seed and rep_offset) from the
+// problem, for every unit that runs chains; find_bg, pos_bg and start_from_min as 0 / 1.  Nothing else of `a` is written.
+void fill_chain_settings(const mcsas_problem *p, mcsas::ChainArgs *a);
+
+// ------------------------------------------------------------------------------ one population fitted to several data sets (host_sets.hip runs it)
+constexpr int SETS_MAX_SLOTS = Q_MAX_WINDOW / mcsas::WAVE;        // 16 register slots of 64 entries: the largest instance
+// Where the sets lie in the padded vectors: set s at [pad_off[s], pad_off[s] + 64 slots[s]), its points at [off[s], off[s] + nq[s]) of
+// the caller's; qpl is the smallest instantiated slot count that holds them all, bit j of end_mask marks a set's last slot.
+struct SetsLayout {
+    int S = 0, qpl = 0, total_slots = 0;
+    int nq[MCSAS_MAX_SETS] = {}, off[MCSAS_MAX_SETS] = {}, slots[MCSAS_MAX_SETS] = {}, pad_off[MCSAS_MAX_SETS] = {};
+    uint32_t end_mask = 0;
+    size_t lds_bytes = 0;
+};
+// Everything mcsas_hip_analyse_sets refuses but a shape without a kernel, in order; fills the layout and the model's argument block.
+int check_sets_request(const mcsas_problem *p, int32_t n_sets, const int32_t *set_nq, const mcsas_result *res,
+                       const mcsas_sets_result *sets, SetsLayout *L, mcsas::ModelArgs *margs);
+// The padded vectors, 64 qpl entries each (pad: q of the set's first point — behind the last set, of the first set's —, w = wI = I = 0),
+// and what the kernel's second argument holds of the sets: their number, end_mask and each set's SetConst (`out` is the caller's).
+struct SetsData { std::vector<double> q, w, wI, I; };
+void lay_out_sets(const mcsas_problem *p, const SetsLayout &L, SetsData *d, mcsas::SetsArgs *sa);
 
 // ------------------------------------------------------------------------------ how a kernel family is launched and named
 // threads per block of the family's kernel, `waves` being the plan's waves per chain

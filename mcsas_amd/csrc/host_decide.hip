@@ -1,5 +1,6 @@
 // host_decide.hip — what libmcsas_hip.so decides without a device: the refusals of a problem, a start and a trace, the execution mode
-// and geometry of a problem (decide_shape), how a kernel family is launched and what a plug-in's instance of it is called, the
+// and geometry of a problem (decide_shape), the settings block and the weights of every chain run, the request, layout and padded data
+// of several sets fitted with one population, how a kernel family is launched and what a plug-in's instance of it is called, the
 // transposition of a fetched trace block, the tick budget of a pipeline launch, and the error text every unit leaves.  No function
 // in here calls the HIP runtime: tests/plan_decisions_check.hip links this file alone and runs on a machine without a GPU.  Like
 // mcsas_hip.hip it tests MCSAS_TUNING (validate_problem, tune_word) and is built twice.
@@ -233,6 +234,98 @@ int decide_shape(const mcsas_problem *p, const ModelArgs &margs, int n_cus, size
     }
     s->qpl = qpl; s->qpad = qpad; s->wide = wide; s->waves = waves; s->mode = mode; s->cache_rows = cache_rows;
     return MCSAS_OK;
+}
+
+void fill_chain_settings(const mcsas_problem *p, ChainArgs *a) {
+    a->n_contrib = p->n_contrib; a->n_reps = p->n_reps;
+    a->find_bg = p->find_background != 0; a->pos_bg = p->positive_background != 0;
+    a->start_from_min = p->start_from_minimum != 0; a->max_retries = p->max_retries;
+    a->max_iter = p->max_iter; a->conv_crit = p->conv_crit;
+    for (int c = 0; c < MCSAS_MAX_ACTIVE; ++c) {
+        a->gen_lo[c] = p->gen_lo[c]; a->gen_hi[c] = p->gen_hi[c]; a->start_value[c] = p->start_value[c];
+        a->gen_kind[c] = p->gen_kind[c];
+    }
+    a->seed = p->seed; a->rep_offset = p->rep_offset;
+}
+
+WeighedSums weigh_points(const double *I, const double *sigma, int n, double *w, double *wI, double *Iout) {
+    WeighedSums s{0, 0, 0, 0};
+    for (int i = 0; i < n; ++i) {
+        const double e = sigma[i] == 0.0 ? 1.0 : sigma[i], wi = 1.0 / (e * e);
+        w[i] = wi; wI[i] = wi * I[i]; Iout[i] = I[i];
+        s.Sw += wi; s.SI += wi * I[i]; s.SII += wi * I[i] * I[i]; s.Ssig2 += e * e;
+    }
+    return s;
+}
+
+// ------------------------------------------------------------------------------ one population fitted to several data sets
+int check_sets_request(const mcsas_problem *p, int32_t n_sets, const int32_t *set_nq, const mcsas_result *res,
+                       const mcsas_sets_result *sets, SetsLayout *L, ModelArgs *margs) {
+    const char *const who = "analyse_sets";
+    if (!p || !res || !sets || !set_nq) return fail(MCSAS_EINVAL, "%s: null argument", who);
+    if (p->struct_size != sizeof(mcsas_problem))
+        return fail(MCSAS_EINVAL, "%s: mcsas_problem size %u, library expects %zu (ABI mismatch)", who, p->struct_size, sizeof(mcsas_problem));
+    if (res->struct_size != sizeof(mcsas_result)) return fail(MCSAS_EINVAL, "%s: mcsas_result size mismatch", who);
+    if (sets->struct_size != sizeof(mcsas_sets_result))
+        return fail(MCSAS_EINVAL, "%s: mcsas_sets_result size %u, library expects %zu", who, sets->struct_size, sizeof(mcsas_sets_result));
+    if (n_sets < 1 || n_sets > MCSAS_MAX_SETS) return fail(MCSAS_EINVAL, "%s: n_sets %d (1..%d)", who, (int)n_sets, MCSAS_MAX_SETS);
+    if (sets->n_sets != n_sets) return fail(MCSAS_EINVAL, "%s: mcsas_sets_result.n_sets %d, the call's n_sets is %d", who, (int)sets->n_sets, (int)n_sets);
+    if (p->reserved0) return fail(MCSAS_EINVAL, "%s: mcsas_problem.reserved0 must be 0 (it is %d)", who, p->reserved0);
+    if (p->nq < 1 || !p->q || !p->intensity || !p->sigma) return fail(MCSAS_EINVAL, "%s: nq/q/intensity/sigma missing", who);
+    if (p->n_active == 0)
+        return fail(MCSAS_EINVAL, "%s: n_active == 0: without an active parameter there is no chain (mcsas_hip_analyse answers that case for one set)", who);
+    if (p->model_id == -1) return fail(MCSAS_EINVAL, "%s: a host model (model_id -1: rows evaluated by the caller) is not supported", who);
+    if (is_plugin_model(p->model_id)) return fail(MCSAS_EINVAL, "%s: a model plug-in (model_id %d) is not supported; built-in models only", who, p->model_id);
+    if (p->model_id < 0 || p->model_id >= MCSAS_MODEL_COUNT) return fail(MCSAS_EINVAL, "%s: unknown model_id %d", who, p->model_id);
+    if (p->exec_mode != MCSAS_EXEC_AUTO && p->exec_mode != MCSAS_EXEC_WAVE)
+        return fail(MCSAS_EINVAL, "%s: exec_mode %d (%s) asked; several sets run one wavefront per chain (exec_mode 0 or %d)", who, p->exec_mode, exec_mode_name(p->exec_mode), MCSAS_EXEC_WAVE);
+    if (p->n_devices > 1) return fail(MCSAS_EINVAL, "%s: n_devices %d: a device list is not supported, the call runs on one device", who, p->n_devices);
+    if (p->positive_background) return fail(MCSAS_EINVAL, "%s: positive_background is not supported with several sets", who);
+    if (p->smear_nk > 0) return fail(MCSAS_EINVAL, "%s: smearing (smear_nk %d) is not supported with several sets", who, p->smear_nk);
+    if (p->cache_intensities == 0) return fail(MCSAS_EINVAL, "%s: cache_intensities == 0: the kernel keeps every contribution's row (cached rows only)", who);
+    if (p->n_contrib < 1 || p->n_reps < 1) return fail(MCSAS_EINVAL, "%s: n_contrib and n_reps must be >= 1", who);
+    if (p->max_iter < 0 || p->max_retries < 0) return fail(MCSAS_EINVAL, "%s: max_iter/max_retries negative", who);
+    if (p->replay_stream && p->replay_len < 1) return fail(MCSAS_EINVAL, "%s: replay_len must be >= 1", who);
+    for (int c = 0; c < p->n_active && c < MCSAS_MAX_ACTIVE; ++c)
+        if (p->gen_kind[c] < MCSAS_GEN_UNIFORM || p->gen_kind[c] > MCSAS_GEN_EXP3) return fail(MCSAS_EINVAL, "%s: gen_kind[%d]=%d", who, c, p->gen_kind[c]);
+
+    *L = SetsLayout{};
+    L->S = n_sets;
+    long long sum = 0, slot_sum = 0;
+    for (int s = 0; s < n_sets; ++s) {
+        if (set_nq[s] < 3) return fail(MCSAS_EINVAL, "%s: set %d has %d points; every set needs at least 3", who, s, (int)set_nq[s]);
+        sum += set_nq[s]; slot_sum += ((long long)set_nq[s] + WAVE - 1) / WAVE;
+    }
+    if (sum != p->nq) return fail(MCSAS_EINVAL, "%s: sum of set_nq %lld != nq %d", who, sum, p->nq);
+    if (slot_sum > SETS_MAX_SLOTS)
+        return fail(MCSAS_EINVAL, "%s: the sets padded to whole slots of %d take %lld padded slots (%lld entries) > %d (%d entries)", who, WAVE, slot_sum,
+                    slot_sum * WAVE, SETS_MAX_SLOTS, SETS_MAX_SLOTS * WAVE);
+    for (int s = 0, o = 0, k = 0; s < n_sets; ++s) {
+        L->nq[s] = set_nq[s]; L->off[s] = o; L->slots[s] = (set_nq[s] + WAVE - 1) / WAVE; L->pad_off[s] = k * WAVE;
+        o += set_nq[s]; k += L->slots[s];
+        L->end_mask |= 1u << (k - 1);
+        L->total_slots = k;
+    }
+    for (L->qpl = 1; L->qpl < L->total_slots;) L->qpl *= 2;
+    if (int rc = fill_model_args(p, margs)) return rc;
+    L->lds_bytes = sizeof(double) * (SETS_LDS_DOUBLES + 4 * (size_t)L->qpl * WAVE + table_doubles_block(p->model_id, margs->int_div, 1));
+    if (L->lds_bytes > 160 * 1024) return fail(MCSAS_EINVAL, "%s: LDS need %zu B > 160 KiB", who, L->lds_bytes);
+    return MCSAS_OK;
+}
+
+void lay_out_sets(const mcsas_problem *p, const SetsLayout &L, SetsData *d, SetsArgs *sa) {
+    const size_t qpad = (size_t)L.qpl * WAVE;
+    d->q.assign(qpad, p->q[0]); d->w.assign(qpad, 0.); d->wI.assign(qpad, 0.); d->I.assign(qpad, 0.);
+    memset(sa, 0, sizeof *sa);
+    sa->n_sets = L.S; sa->end_mask = L.end_mask;
+    for (int s = 0; s < L.S; ++s) {
+        const int src = L.off[s], dst = L.pad_off[s];
+        std::fill_n(&d->q[dst], L.slots[s] * WAVE, p->q[src]);
+        std::copy_n(p->q + src, L.nq[s], &d->q[dst]);
+        const WeighedSums t = weigh_points(p->intensity + src, p->sigma + src, L.nq[s], &d->w[dst], &d->wI[dst], &d->I[dst]);
+        // (1 / Sw, SI / Sw, SII - SI² / Sw: the operations of chain_body.inc, unfused here as there)
+        sa->set[s] = SetConst{t.Sw, t.SI, t.SII, 1.0 / t.Sw, t.SI / t.Sw, t.SII - t.SI * t.SI / t.Sw, (double)L.nq[s]};
+    }
 }
 
 // ------------------------------------------------------------------------------ what a start and a trace are refused for

@@ -1,8 +1,10 @@
-// host_internal.h — what the host units of libmcsas_hip.so share (mcsas_hip.hip: plans; host_decide.hip: what is decided without a device; host_analyse.hip:
-// one-shot analyses; host_rows.hip: rows evaluated by the caller; host_plugin.hip: run-time compiler of model plug-ins; host_calls.hip: small one-call entry points; host_hist.hip:
-// McSAS.histogram(); host_sets.hip: one population fitted to several data sets; small_launch.h: from a model id to a small kernel's instance, for the last two).  Host code only: the run-time compiler never sees this file (it is not among the embedded headers).
+// host_internal.h — what the host units of libmcsas_hip.so share (mcsas_hip.hip: plans, the memory cache, the stop word; host_decide.hip: what is decided without a
+// device, the chain settings and the weights among it; host_analyse.hip: one-shot analyses; host_rows.hip: rows evaluated by the caller; host_plugin.hip: run-time compiler of
+// model plug-ins; host_calls.hip: small one-call entry points; host_hist.hip: McSAS.histogram(); host_sets.hip: the device half of one population fitted to several data sets;
+// small_launch.h: from a model id to a small kernel's instance, for host_calls.hip and host_hist.hip).  Host code only: the run-time compiler never sees this file (it is not among the embedded headers).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -21,6 +23,11 @@ int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
             return fail(e_ == hipErrorOutOfMemory ? MCSAS_ENOMEM : MCSAS_EHIP, "%s: %s (%s:%d)", \
                         #expr, hipGetErrorString(e_), __FILE__, __LINE__);                   \
     } while (0)
+
+// the C boundary of the one-shot chain calls (host_rows.hip, host_sets.hip): a host vector that cannot be had is MCSAS_ENOMEM, no exception
+template <class F> int no_bad_alloc(const char *who, F f) {
+    try { return f(); } catch (const std::bad_alloc &) { return fail(MCSAS_ENOMEM, "%s: out of host memory", who); }
+}
 
 int select_device(int device);
 // A buffer the caller hands over as device memory (host_rows.hip; mcsas_hip_analyse_device_rows, mcsas_hip_histogram_device_rows):
@@ -43,6 +50,24 @@ void cached_dev_free(void *p, size_t n, int d);
 hipError_t cached_host_malloc(void **p, size_t n, unsigned flags);
 void cached_host_free(void *p, size_t n, unsigned flags);
 hipError_t cached_copy_stream(hipStream_t *st);
+
+// McSAS.stop as the kernels see it (chain_common.h: stop_requested): one pinned, mapped word from the cache, `d` its device address;
+// back to the cache with its owner — a plan, a batch, a call of mcsas_hip_analyse_sets
+struct StopWord {
+    int32_t *h = nullptr, *d = nullptr;
+    hipError_t make();                                     // *h = 0
+    ~StopWord() { cached_host_free(h, sizeof(int32_t), hipHostMallocMapped); }
+    StopWord() = default;
+    StopWord(const StopWord &) = delete;
+    StopWord &operator=(const StopWord &) = delete;
+};
+// Waits for `done`, forwarding the caller's stop word to the device-visible one every 50 us meanwhile (McSAS.stop, mcsas.py:357);
+// no caller's word: nothing to forward, a plain wait.  An error of the event is "<who>kernel failed: ...".
+int wait_forwarding_stop(const char *who, hipEvent_t done, const volatile int32_t *caller_stop, int32_t *h_stop);
+// the caller's replay streams, [R][replay_len], to the device
+inline hipError_t copy_replay(double *dst, const mcsas_problem *p, size_t R) {
+    return hipMemcpy(dst, p->replay_stream, sizeof(double) * R * (size_t)p->replay_len, hipMemcpyHostToDevice);
+}
 
 // scratch arrays of the one-call entry points and of mcsas_hip_analyse_host_rows: from / back to the process-level cache (a
 // histogram() makes a dozen of them)
@@ -122,6 +147,10 @@ inline int table_doubles_host(int model_id, int K) { return model_traits(model_i
 // K = 256 the chain kernels evaluate the integrand directly
 inline int rowtab_doubles_host(int model_id, int K) { return K > 256 ? 0 : model_traits(model_id).rowtab * K; }
 int fill_model_args(const mcsas_problem *p, mcsas::ModelArgs *m);
+// The weight rule, once: sigma == 0 -> 1 (backgroundscalingfit.py:117), w = 1 / e², wI = w I, and the sums over the n points in order,
+// each first onto 0.0 (DESIGN §4.1e rests on these being the same IEEE operations for one set and for several)
+struct WeighedSums { double Sw, SI, SII, Ssig2; };
+WeighedSums weigh_points(const double *I, const double *sigma, int n, double *w, double *wI, double *Iout);
 
 // Device copy of the smearing tables of a problem: locs transposed to [K][stride] (pad columns repeat
 // column 0, like the padded q) and cw[m] = 2 * trapezoid coefficient(q_offset)[m] * weights[m], so that
@@ -173,19 +202,13 @@ inline WaveRequest wave_request(int exec_mode, int nq) {
 #pragma GCC visibility pop
 
 // ------------------------------------------------------------------------------ the data of a problem as the chains read them
-// the weights and weighted data, padded with zeros, and their sums in the argument block; sigma == 0 -> 1 (backgroundscalingfit.py:117).
-// Plan creation (mcsas_hip.hip) and the chains whose rows the caller evaluates (host_rows.hip) prepare them alike.  (Outside the hidden
-// region above: the library has always exported this constructor, and its list of symbols stays what it was.)
+// the weights and weighted data (weigh_points), padded with zeros, and their sums in the argument block.  Plan creation (mcsas_hip.hip)
+// and the chains whose rows the caller evaluates (host_rows.hip) prepare them alike.  (Outside the hidden region above, and kept out of
+// line: the library has always exported this constructor, and its list of symbols stays what it was.)
 struct WeighedData {
     std::vector<double> w, wI, I;
-    WeighedData(const mcsas_problem *p, size_t qpad, mcsas::ChainArgs *a) : w(qpad, 0.), wI(qpad, 0.), I(qpad, 0.) {
-        double Sw = 0, SI = 0, SII = 0, Ss2 = 0;
-        for (int i = 0; i < p->nq; ++i) {
-            double e = p->sigma[i] == 0.0 ? 1.0 : p->sigma[i];
-            double wi = 1.0 / (e * e);
-            w[i] = wi; wI[i] = wi * p->intensity[i]; I[i] = p->intensity[i];
-            Sw += wi; SI += wi * p->intensity[i]; SII += wi * p->intensity[i] * p->intensity[i]; Ss2 += e * e;
-        }
-        a->nq = p->nq; a->qpad = (int)qpad; a->Sw = Sw; a->SI = SI; a->SII = SII; a->Ssig2 = Ss2;
+    __attribute__((noinline)) WeighedData(const mcsas_problem *p, size_t qpad, mcsas::ChainArgs *a) : w(qpad, 0.), wI(qpad, 0.), I(qpad, 0.) {
+        const WeighedSums s = weigh_points(p->intensity, p->sigma, p->nq, w.data(), wI.data(), I.data());
+        a->nq = p->nq; a->qpad = (int)qpad; a->Sw = s.Sw; a->SI = s.SI; a->SII = s.SII; a->Ssig2 = s.Ssig2;
     }
 };

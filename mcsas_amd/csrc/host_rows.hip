@@ -6,10 +6,9 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
-#include <new>
 #include <vector>
 
-#include "host_internal.h"
+#include "host_decide.h"     // fill_chain_settings
 #include "host_result.h"
 #include "chain_feed.h"     // feed_rows_kernel, feed_draw_kernel
 
@@ -78,7 +77,7 @@ struct FeedRun {
     int64_t *pos() { return meta.data(); }
     int32_t *rows_of() { return reinterpret_cast<int32_t *>(meta.data() + 2 * R); }
 
-    // data vectors and their sums, as mcsas_hip_plan_create prepares them; the rows and parameter sets of a round at `rows`, `pvals`
+    // data vectors, their sums and the settings, as mcsas_hip_plan_create prepares them; the rows and parameter sets of a round at `rows`, `pvals`
     int setup(const double *rows, const double *pvals) {
         memset(&fa, 0, sizeof fa);
         ChainArgs &a = fa.c;
@@ -94,8 +93,7 @@ struct FeedRun {
 
         a.model.n_active = (int)P;
         a.w = dw.p; a.wI = dwI.p; a.I = dI.p;
-        a.n_contrib = (int)N; a.n_reps = (int)R; a.find_bg = p->find_background; a.pos_bg = p->positive_background;
-        a.start_from_min = p->start_from_minimum; a.max_retries = p->max_retries; a.max_iter = p->max_iter; a.conv_crit = p->conv_crit;
+        fill_chain_settings(p, &a);                                             // (feed_draw_kernel reads the generators, seed and rep_offset)
         a.rset = drset.p; a.cache = dcache.p; a.cache_rows = (int)N; a.fit = dfit.p;
         fa.ft = dft.p; fa.state = dstate.p; fa.rows = rows; fa.pvals = pvals;
         const int32_t *dm = reinterpret_cast<const int32_t *>(dmeta.p + 2 * R);
@@ -154,11 +152,7 @@ struct FeedRun {
     int results(mcsas_result *res);
 };
 
-extern "C" int mcsas_hip_analyse_host_rows(const mcsas_problem *p, mcsas_rows_callback rows_cb, void *user, int32_t window,
-                                           mcsas_result *res) {
-    if (!p || !rows_cb || !res) return fail(MCSAS_EINVAL, "null argument");
-    if (int rc = check_rows_problem(p)) return rc;
-    if (window < 1) window = 64;
+static int host_rows_run(const mcsas_problem *p, mcsas_rows_callback rows_cb, void *user, int32_t window, mcsas_result *res) {
     DeviceGuard guard;
     { int rc = select_device(p->device); if (rc) return rc; }
     size_t blk, round_rows, qpad;
@@ -212,6 +206,13 @@ extern "C" int mcsas_hip_analyse_host_rows(const mcsas_problem *p, mcsas_rows_ca
         if (int rc = run.decide()) return rc;
     }
     return run.results(res);
+}
+
+extern "C" int mcsas_hip_analyse_host_rows(const mcsas_problem *p, mcsas_rows_callback rows_cb, void *user, int32_t window,
+                                           mcsas_result *res) {
+    if (!p || !rows_cb || !res) return fail(MCSAS_EINVAL, "null argument");
+    if (int rc = check_rows_problem(p)) return rc;
+    return no_bad_alloc("analyse_host_rows", [&] { return host_rows_run(p, rows_cb, user, window < 1 ? 64 : window, res); });
 }
 
 // results in the layout of mcsas_result (mcsas.py:203-210,233-251)
@@ -281,13 +282,7 @@ static int device_rows_run(const mcsas_problem *p, double *d_pset, double *d_row
     if (int rc = check_device_buffer("analyse_device_rows", "d_rows", d_rows, dev)) return rc;
     FeedRun run(p, qpad, window);
     if (int rc = run.setup(d_rows, d_pset)) return rc;
-    // what feed_draw_kernel reads of the problem beside the round's metadata
     ChainArgs &a = run.fa.c;
-    for (size_t c = 0; c < run.P; ++c) {
-        a.gen_lo[c] = p->gen_lo[c]; a.gen_hi[c] = p->gen_hi[c]; a.start_value[c] = p->start_value[c];
-        a.gen_kind[c] = p->gen_kind[c];
-    }
-    a.seed = p->seed; a.rep_offset = p->rep_offset;
     DevBuf<double> dreplay;
     if (p->replay_stream) {
         const size_t len = (size_t)std::max<int64_t>(p->replay_len, 0);
@@ -325,9 +320,5 @@ extern "C" int mcsas_hip_analyse_device_rows(const mcsas_problem *p, double *d_p
         return fail(MCSAS_EINVAL, "analyse_device_rows: capacity_rows %lld < %lld = max(n_contrib, window), the rows of one chain's round (mcsas_hip_device_rows_shape)",
                     (long long)capacity_rows, (long long)blk);
     const size_t round_rows = std::min((size_t)capacity_rows, useful);
-    try {
-        return device_rows_run(p, d_pset, d_rows, round_rows, (size_t)capacity_rows, qpad, rows_cb, user, window, res);
-    } catch (const std::bad_alloc &) {
-        return fail(MCSAS_ENOMEM, "analyse_device_rows: out of host memory");
-    }
+    return no_bad_alloc("analyse_device_rows", [&] { return device_rows_run(p, d_pset, d_rows, round_rows, (size_t)capacity_rows, qpad, rows_cb, user, window, res); });
 }

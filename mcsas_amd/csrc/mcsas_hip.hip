@@ -1,8 +1,10 @@
 // mcsas_hip.hip — libmcsas_hip.so: C ABI (include/mcsas_hip.h) over the gfx950 chain kernels.  This unit holds the plans: their
 // creation, start and trace, launches, fetches and batch launches, with the memory cache, the streams and the ABI queries.  What
-// it decides without a device is host_decide.hip, the one-shot analyses over plans are host_analyse.hip, the chains whose rows the
-// caller evaluates host_rows.hip, the run-time compiler of model plug-ins host_plugin.hip, the small one-call entry points (model.calc,
-// input preparation) host_calls.hip, McSAS.histogram() host_hist.hip; what they share is host_internal.h, and host_result.h writes every mcsas_result.
+// it decides without a device is host_decide.hip (the chain settings and the weights of every unit's chains among it), the one-shot
+// analyses over plans are host_analyse.hip, the chains whose rows the caller evaluates host_rows.hip, several data sets fitted with one
+// population host_sets.hip, the run-time compiler of model plug-ins host_plugin.hip, the small one-call entry points (model.calc, input
+// preparation) host_calls.hip, McSAS.histogram() host_hist.hip; what they share is host_internal.h (the stop word and the wait that
+// forwards McSAS.stop stand here, beside the cache the word comes from), and host_result.h writes every mcsas_result.
 // Built only for MI355X (gfx950); there is no CPU path in here.
 #include <hip/hip_runtime.h>
 
@@ -136,6 +138,22 @@ hipError_t cached_copy_stream(hipStream_t *st) {
     *st = it->second;
     return hipSuccess;
 }
+hipError_t StopWord::make() {
+    hipError_t e = cached_host_malloc((void **)&h, sizeof(int32_t), hipHostMallocMapped);
+    if (e == hipSuccess) { *h = 0; e = hipHostGetDevicePointer((void **)&d, h, 0); }
+    return e;
+}
+int wait_forwarding_stop(const char *who, hipEvent_t done, const volatile int32_t *caller_stop, int32_t *h_stop) {
+    while (caller_stop) {                                // (no stop word: nothing to forward, plain wait below)
+        hipError_t q = hipEventQuery(done);
+        if (q == hipSuccess) break;
+        if (q != hipErrorNotReady) return fail(MCSAS_EHIP, "%skernel failed: %s", who, hipGetErrorString(q));
+        if (*caller_stop) *h_stop = 1;
+        std::this_thread::sleep_for(std::chrono::microseconds(50));
+    }
+    HIPCHK(hipEventSynchronize(done));
+    return MCSAS_OK;
+}
 extern "C" int mcsas_hip_release_cached_memory(void) {
     MemCache &c = mem_cache();
     std::lock_guard<std::mutex> lk(c.mu);
@@ -185,11 +203,10 @@ struct BatchShared {
     size_t bytes = 0;
     char *d_block = nullptr;            // [0, 256): relay; then ChainArgs[n]; then ChainRef[chains]
     char *h_block = nullptr;            // pinned staging copy of d_block (the upload is asynchronous)
-    int32_t *h_stop = nullptr;          // pinned + mapped
+    StopWord stop;
     ~BatchShared() {
         if (d_block) cached_dev_free(d_block, bytes, dev);
         cached_host_free(h_block, bytes, hipHostMallocDefault);
-        cached_host_free(h_stop, sizeof(int32_t), hipHostMallocMapped);
     }
 };
 
@@ -206,7 +223,7 @@ struct mcsas_plan {
     double *d_start = nullptr;          // [n_reps][n_contrib][n_active], the layout of rset: the set every launch starts from (mcsas_hip_plan_set_start)
     bool has_start = false;             // ... while this holds; the buffer stays with the plan once made
     int32_t trace_capacity = 0;         // > 0: every launch runs the traced kernel and keeps this many moves per repetition (mcsas_hip_plan_set_trace)
-    int32_t *h_stop = nullptr;          // pinned + mapped: McSAS.stop as the kernels see it
+    StopWord stop;                      // McSAS.stop as the kernels see it
     int32_t *d_stop_relay = nullptr;    // device memory, 16 bytes: the relayed stop word and the time stamp of the last look at h_stop (chain_common.h: stop_requested)
     hipStream_t stream = nullptr;
     bool enqueue_failed = false;        // a launch returned an error after it had put work on `stream`: nothing marks where that work ends
@@ -369,7 +386,6 @@ extern "C" void mcsas_hip_plan_destroy(mcsas_plan *pl) {
     }
     (void)wait_for_slots(pl);
     pl->pool.release();                 // every device array of the plan
-    cached_host_free(pl->h_stop, sizeof(int32_t), hipHostMallocMapped);
     for (int i = 0; i < mcsas_plan::RING; ++i)
         if (pl->evS[i]) hipEventDestroy(pl->evS[i]);
     for (mcsas_plan::Slot &sl : pl->slots) {              // (a slot that was never made, or only half made, holds nulls)
@@ -431,9 +447,8 @@ static int alloc_rows(mcsas_plan *pl, const mcsas_problem *p, int cache_rows) {
     if (use_cache) HIPCHK(pl->pool.get(&pl->d_cache, cache_bytes));
 
     if (p->replay_stream) {
-        size_t rb = sizeof(double) * R * (size_t)p->replay_len;
-        HIPCHK(pl->pool.get(&pl->d_replay, rb));
-        HIPCHK(hipMemcpy(pl->d_replay, p->replay_stream, rb, hipMemcpyHostToDevice));
+        HIPCHK(pl->pool.get(&pl->d_replay, sizeof(double) * R * (size_t)p->replay_len));
+        HIPCHK(copy_replay(pl->d_replay, p, R));
     }
     ChainArgs &a = pl->args;
     a.cache = pl->d_cache; a.cache_rows = cache_rows;
@@ -443,22 +458,12 @@ static int alloc_rows(mcsas_plan *pl, const mcsas_problem *p, int cache_rows) {
 
 // the rest of the kernels' argument block: the model, the problem's settings and the stop word with its relay
 static int fill_chain_args(mcsas_plan *pl, const mcsas_problem *p, const ModelArgs &margs) {
-    HIPCHK(cached_host_malloc((void **)&pl->h_stop, sizeof(int32_t), hipHostMallocMapped));
-    *pl->h_stop = 0;
-    int32_t *d_stop = nullptr;
-    HIPCHK(hipHostGetDevicePointer((void **)&d_stop, pl->h_stop, 0));
+    HIPCHK(pl->stop.make());
     ChainArgs &a = pl->args;
     a.model = margs;
-    a.n_contrib = p->n_contrib; a.n_reps = p->n_reps;
-    a.find_bg = p->find_background != 0; a.pos_bg = p->positive_background != 0;
-    a.start_from_min = p->start_from_minimum != 0; a.max_retries = p->max_retries;
-    a.max_iter = p->max_iter; a.conv_crit = p->conv_crit;
-    for (int c = 0; c < MCSAS_MAX_ACTIVE; ++c) {
-        a.gen_lo[c] = p->gen_lo[c]; a.gen_hi[c] = p->gen_hi[c]; a.start_value[c] = p->start_value[c];
-        a.gen_kind[c] = p->gen_kind[c];
-    }
-    a.seed = p->seed; a.rep_offset = p->rep_offset; a.pad0 = p->reserved0;   // (0 in the release library: validate_problem)
-    a.stop_flag = d_stop;
+    fill_chain_settings(p, &a);
+    a.pad0 = p->reserved0;                               // (0 in the release library: validate_problem)
+    a.stop_flag = pl->stop.d;
     HIPCHK(pl->pool.get(&pl->d_stop_relay, 16));
     a.stop_relay = pl->d_stop_relay;
     return MCSAS_OK;
@@ -710,7 +715,7 @@ static int pipeline_launch(mcsas_plan *pl, const KernelRef &tick, hipStream_t st
         if (t >= mcsas_plan::RING && (t % 16) == 0) {
             // throttle: stay at most ~RING ticks ahead of the GPU, forward the stop word, leave when all chains are done
             HIPCHK(hipEventSynchronize(pl->evS[((t - mcsas_plan::RING) / 16) % mcsas_plan::RING]));
-            if (pl->prob.stop && *pl->prob.stop) *pl->h_stop = 1;
+            if (pl->prob.stop && *pl->prob.stop) *pl->stop.h = 1;
             if (*(volatile int32_t *)s.h_done >= R) break;
         }
         int32_t tk = (int32_t)t, stop_now = (pl->prob.stop && *(volatile int32_t *)pl->prob.stop) ? 1 : 0;
@@ -738,7 +743,7 @@ extern "C" int mcsas_hip_plan_launch_slot(mcsas_plan *pl, void *hip_stream, int3
         if (k != pl->cur_slot && pl->slots[k].launched && pl->slots[k].ev1) HIPCHK(hipStreamWaitEvent(st, pl->slots[k].ev1, 0));
     if (s.launched && s.ev1) HIPCHK(hipEventSynchronize(s.ev1));
     s.batch_of.reset();
-    *pl->h_stop = (pl->prob.stop && *pl->prob.stop) ? 1 : 0;
+    *pl->stop.h = (pl->prob.stop && *pl->prob.stop) ? 1 : 0;
     pl->stream = st;
     if (pl->mode != MCSAS_EXEC_PIPELINE) HIPCHK(hipMemsetAsync(pl->d_stop_relay, 0, 16, st));   // (the pipeline's ticks get McSAS.stop as a kernel argument)
     FailGuard guard{&pl, 1};                              // (any error return below leaves work on `st` that no end event covers)
@@ -777,15 +782,7 @@ extern "C" int mcsas_hip_plan_fetch_slot(mcsas_plan *pl, int32_t slot, mcsas_res
     if (res && res->struct_size != sizeof(mcsas_result))
         return fail(MCSAS_EINVAL, "mcsas_result size %u, library expects %zu", res->struct_size, sizeof(mcsas_result));
     // wait, forwarding the caller's stop word to the device-visible one (McSAS.stop, mcsas.py:357)
-    int32_t *const h_stop = s.batch_of ? s.batch_of->h_stop : pl->h_stop;
-    while (pl->prob.stop) {                              // (no stop word: nothing to forward, plain wait below)
-        hipError_t q = hipEventQuery(s.ev1);
-        if (q == hipSuccess) break;
-        if (q != hipErrorNotReady) return fail(MCSAS_EHIP, "kernel failed: %s", hipGetErrorString(q));
-        if (*pl->prob.stop) *h_stop = 1;
-        std::this_thread::sleep_for(std::chrono::microseconds(50));
-    }
-    HIPCHK(hipEventSynchronize(s.ev1));
+    if (int rc = wait_forwarding_stop("", s.ev1, pl->prob.stop, s.batch_of ? s.batch_of->stop.h : pl->stop.h)) return rc;
     if (!pl->sCopy) HIPCHK(cached_copy_stream(&pl->sCopy));      // (one per device, shared by every plan)
     // device -> host on the copy stream (the data is complete: ev1 has passed)
     auto d2h = [&](void *dst, const void *src, size_t n) -> hipError_t {
@@ -923,20 +920,18 @@ extern "C" int mcsas_hip_plan_launch_batch(mcsas_plan *const *plans, int32_t n, 
     bs->bytes = off_chains + sizeof(ChainRef) * n_chains;
     HIPCHK(cached_dev_malloc((void **)&bs->d_block, bs->bytes));
     HIPCHK(cached_host_malloc((void **)&bs->h_block, bs->bytes, hipHostMallocDefault));
-    HIPCHK(cached_host_malloc((void **)&bs->h_stop, sizeof(int32_t), hipHostMallocMapped));
+    HIPCHK(bs->stop.make());
     const volatile int32_t *stop = plans[0]->prob.stop;
-    *bs->h_stop = (stop && *stop) ? 1 : 0;
-    int32_t *d_stop = nullptr;
-    HIPCHK(hipHostGetDevicePointer((void **)&d_stop, bs->h_stop, 0));
+    *bs->stop.h = (stop && *stop) ? 1 : 0;
     // the relay starts as the stop word is now: a stop set before the launch is seen by every chain at its first poll (through the
     // host word alone only the chain that reads it would, the others one poll later)
     memset(bs->h_block, 0, off_sets);
-    ((int32_t *)bs->h_block)[0] = *bs->h_stop;
+    ((int32_t *)bs->h_block)[0] = *bs->stop.h;
     ChainArgs *h_sets = (ChainArgs *)(bs->h_block + off_sets);
     ChainRef *h_chains = (ChainRef *)(bs->h_block + off_chains);
     for (int i = 0; i < n; ++i) {
         h_sets[i] = plans[i]->args;                                          // (slot 0's outputs, the plan's seed / rep_offset)
-        h_sets[i].stop_flag = d_stop;
+        h_sets[i].stop_flag = bs->stop.d;
         h_sets[i].stop_relay = (int32_t *)bs->d_block;
     }
     std::vector<size_t> g_first(groups.size() + 1, 0), g_lds(groups.size(), 0);

@@ -1,14 +1,20 @@
 // plan_decisions_check.hip — what the library decides without a device (csrc/host_decide.hip), as a stand-alone host program:
 // tests/test_plan_decisions_host.py compiles this file together with host_decide.hip under AddressSanitizer and
 // UndefinedBehaviorSanitizer and runs it.  No GPU: nothing in here or in that unit calls the HIP runtime.
-//   plan_decisions_check                 the family table, the trace block's layout and transposition, the tick budget; prints "ok"
+//   plan_decisions_check                 the family table, the trace block's layout and transposition, the tick budget, the settings
+//                                        block of a chain run, the padded data and constants of several sets; prints "ok"
 //   plan_decisions_check shapes < cases  one line per problem: what plan creation decides for it on a 256-CU device with nothing
 //                                        ruled out by memory, or its refusal
 //   plan_decisions_check gate < case     the free-memory gate of MCSAS_EXEC_AUTO on one problem; prints "ok" and the figures
+//   plan_decisions_check sets < cases    one line per request of mcsas_hip_analyse_sets (id nq n_sets set_nq...): where the sets lie, or
+//                                        the refusal
+//   plan_decisions_check refusals < rows one line per request with one thing spoiled (id model_id n_active n_devices
+//                                        positive_background smear_nk cache_intensities exec_mode): code and message
 // A problem is a line of text: id model_id nq n_contrib n_reps exec_mode waves_per_chain smear_nk n_active, the active indices,
 // the MCSAS_MAX_PARAMS parameters.
 #include <cinttypes>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -182,12 +188,129 @@ static void tick_budget() {
     CHECK(pipeline_tick_budget(20000, 5, 192) == 652);                       // 6 (104 + 4) + 4
 }
 
+// ------------------------------------------------------------------------------ the settings block of a chain run
+static void chain_settings() {
+    mcsas_problem p;
+    memset(&p, 0, sizeof p);
+    p.n_contrib = 11; p.n_reps = 12; p.find_background = 2; p.positive_background = 0; p.start_from_minimum = -1; p.max_retries = 13;
+    p.max_iter = ((int64_t)1 << 40) + 14; p.conv_crit = 15.5; p.seed = 0x123456789abcdef0ull; p.rep_offset = 16; p.reserved0 = 17;
+    for (int c = 0; c < MCSAS_MAX_ACTIVE; ++c) { p.gen_lo[c] = 20. + c; p.gen_hi[c] = 30. + c; p.start_value[c] = 40. + c; p.gen_kind[c] = c % 4; }
+    ChainArgs a, untouched;
+    memset((void *)&a, 0xA5, sizeof a); memset((void *)&untouched, 0xA5, sizeof untouched);
+    fill_chain_settings(&p, &a);
+    CHECK(a.find_bg == 1 && a.pos_bg == 0 && a.start_from_min == 1);
+    CHECK(a.n_contrib == 11 && a.n_reps == 12 && a.max_retries == 13 && a.max_iter == p.max_iter && a.conv_crit == 15.5);
+    CHECK(a.seed == p.seed && a.rep_offset == 16);
+    for (int c = 0; c < MCSAS_MAX_ACTIVE; ++c)
+        CHECK(a.gen_lo[c] == p.gen_lo[c] && a.gen_hi[c] == p.gen_hi[c] && a.start_value[c] == p.start_value[c] && a.gen_kind[c] == p.gen_kind[c]);
+    // nothing else is written: the settings block [n_contrib, seed) and seed, rep_offset put back, the rest is as it was (pad0 too)
+    memset((char *)&a + offsetof(ChainArgs, n_contrib), 0xA5, offsetof(ChainArgs, pad0) - offsetof(ChainArgs, n_contrib));
+    CHECK(!memcmp((const void *)&a, (const void *)&untouched, sizeof a));
+}
+
+// ------------------------------------------------------------------------------ several sets fitted with one population
+// A valid request over spheres: nq points with distinct q (1e7 (i + 1)), I = 5 + 0.37 i, sigma = 0.1 + 0.01 i; the caller breaks one thing.
+struct SetsRequest {
+    mcsas_problem p;
+    mcsas_result res;
+    mcsas_sets_result sets;
+    std::vector<double> q, I, sig;
+    std::vector<int32_t> set_nq;
+    SetsLayout L;
+    ModelArgs margs;
+    SetsRequest(int nq, std::vector<int32_t> nqs) : q(nq), I(nq), sig(nq), set_nq(nqs) {
+        memset(&p, 0, sizeof p); memset(&res, 0, sizeof res); memset(&sets, 0, sizeof sets);
+        for (int i = 0; i < nq; ++i) { q[i] = 1e7 * (i + 1); I[i] = 5. + 0.37 * i; sig[i] = 0.1 + 0.01 * i; }
+        p.struct_size = sizeof p; res.struct_size = sizeof res; sets.struct_size = sizeof sets; sets.n_sets = (int32_t)nqs.size();
+        p.model_id = MCSAS_MODEL_SPHERE; p.nq = nq; p.q = q.data(); p.intensity = I.data(); p.sigma = sig.data();
+        p.n_active = 1; p.params[0] = 1e-8; p.gen_lo[0] = 2e-9; p.gen_hi[0] = 3e-7; p.clip_hi[0] = 1.;
+        p.n_contrib = 8; p.n_reps = 2; p.max_iter = 10; p.cache_intensities = -1; p.device = -1;
+    }
+    int check() { return check_sets_request(&p, (int32_t)set_nq.size(), set_nq.data(), &res, &sets, &L, &margs); }
+};
+
+static int sets_layouts() {
+    char id[64];
+    int nq, S;
+    static_assert(SETS_LDS_DOUBLES == 40 && WAVE == 64, "the rule restated below");
+    while (scanf("%63s %d %d", id, &nq, &S) == 3) {
+        std::vector<int32_t> nqs(S);
+        for (int s = 0; s < S; ++s) CHECK(scanf("%d", &nqs[s]) == 1);
+        SetsRequest r(nq, nqs);
+        if (const int rc = r.check()) { printf("%s error %d %s\n", id, rc, g_err.c_str()); continue; }
+        const SetsLayout &L = r.L;
+        CHECK(L.S == S && L.lds_bytes == 8 * (size_t)(40 + 4 * 64 * L.qpl + table_doubles_block(MCSAS_MODEL_SPHERE, r.margs.int_div, 1)));
+        printf("%s layout %d %d %#x", id, L.total_slots, L.qpl, L.end_mask);
+        for (int s = 0, o = 0; s < S; o += nqs[s++]) { CHECK(L.nq[s] == nqs[s] && L.off[s] == o); printf(" %d %d", L.slots[s], L.pad_off[s]); }
+        printf("\n");
+    }
+    return 0;
+}
+
+static int sets_refusals() {
+    char id[64];
+    for (;;) {
+        SetsRequest r(90, {40, 50});
+        mcsas_problem &p = r.p;
+        if (scanf("%63s %d %d %d %d %d %d %d", id, &p.model_id, &p.n_active, &p.n_devices, &p.positive_background, &p.smear_nk, &p.cache_intensities, &p.exec_mode) != 8) return 0;
+        const int rc = r.check();
+        printf("%s %d %s\n", id, rc, rc ? g_err.c_str() : "");
+    }
+}
+
+// (37, 100) points, one of set 1 with sigma == 0: the padded vectors and each set's constants; 65 points in one set: the sums are WeighedData's
+static void sets_data() {
+    SetsRequest r(137, {37, 100});
+    r.sig[40] = 0.;
+    CHECK(r.check() == MCSAS_OK && r.L.qpl == 4);
+    SetsData d;
+    SetsArgs sa;
+    memset((void *)&sa, 0xA5, sizeof sa);
+    lay_out_sets(&r.p, r.L, &d, &sa);
+    CHECK(d.q.size() == 256 && d.w.size() == 256 && d.wI.size() == 256 && d.I.size() == 256);
+    CHECK(sa.n_sets == 2 && sa.end_mask == 0x5 && sa.out == nullptr);
+    const int first[2] = {0, 37}, count[2] = {37, 100}, at[2] = {0, 64};
+    for (int i = 0; i < 256; ++i) {
+        const int s = i < 64 ? 0 : 1, k = i - at[s];
+        if (i < 192 && k < count[s]) {                                         // entries 0-36 and 64-163: the sets' own points
+            const int src = first[s] + k;
+            const double e = r.sig[src] == 0. ? 1. : r.sig[src], w = 1. / (e * e);
+            CHECK(d.q[i] == r.q[src] && d.I[i] == r.I[src] && d.w[i] == w && d.wI[i] == w * r.I[src]);
+        } else {                                                               // 37-63 and 192-255 repeat q[0], 164-191 set 1's first point
+            CHECK(d.q[i] == r.q[(i >= 164 && i < 192) ? 37 : 0] && d.w[i] == 0. && d.wI[i] == 0. && d.I[i] == 0.);
+        }
+    }
+    CHECK(d.w[64 + 3] == 1. && d.wI[64 + 3] == r.I[40]);                       // sigma == 0 -> 1
+    for (int s = 0; s < MCSAS_MAX_SETS; ++s) {
+        const SetConst &c = sa.set[s];
+        if (s >= 2) { const SetConst zero{}; CHECK(!memcmp(&c, &zero, sizeof c)); continue; }
+        double Sw = 0, SI = 0, SII = 0;
+        for (int k = 0; k < count[s]; ++k) { const int i = at[s] + k; Sw += d.w[i]; SI += d.wI[i]; SII += d.wI[i] * d.I[i]; }
+        CHECK(c.Sw == Sw && c.SI == SI && c.SII == SII);
+        CHECK(c.invSw == 1.0 / c.Sw && c.SIoSw == c.SI / c.Sw && c.Scen == c.SII - c.SI * c.SI / c.Sw && c.nq == (double)count[s]);
+    }
+
+    SetsRequest one(65, {65});
+    one.sig[9] = 0.;
+    CHECK(one.check() == MCSAS_OK && one.L.qpl == 2 && one.L.end_mask == 0x2);
+    lay_out_sets(&one.p, one.L, &d, &sa);
+    ChainArgs a;
+    memset((void *)&a, 0, sizeof a);
+    const WeighedData h(&one.p, 128, &a);
+    CHECK(!memcmp(&sa.set[0].Sw, &a.Sw, 8) && !memcmp(&sa.set[0].SI, &a.SI, 8) && !memcmp(&sa.set[0].SII, &a.SII, 8));
+    CHECK(a.nq == 65 && a.qpad == 128 && d.w == h.w && d.wI == h.wI && d.I == h.I);
+}
+
 int main(int argc, char **argv) {
     if (argc > 1 && !strcmp(argv[1], "shapes")) return shapes();
     if (argc > 1 && !strcmp(argv[1], "gate")) return gate();
+    if (argc > 1 && !strcmp(argv[1], "sets")) return sets_layouts();
+    if (argc > 1 && !strcmp(argv[1], "refusals")) return sets_refusals();
     family_table();
     trace_block();
     tick_budget();
+    chain_settings();
+    sets_data();
     printf("ok\n");
     return 0;
 }

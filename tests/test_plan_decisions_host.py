@@ -3,7 +3,8 @@ UndefinedBehaviorSanitizer: tests/plan_decisions_check.hip, compiled here togeth
 No GPU, nothing loaded into this process.  The recorded plan shapes (tests/golden/plan_shapes_mi355x.json) are replayed through
 decide_shape with the recording's CU count; the free-memory gate of MCSAS_EXEC_AUTO, which no device of the library's own kind
 exercises, is checked at its threshold; the family table, the trace block's layout and the tick budget against values worked
-out by hand."""
+out by hand.  Of a joint fit of several sets (mcsas_hip_analyse_sets): where the sets lie in the padded vectors, the vectors and
+each set's constants, its refusals; of every chain run the settings block of the kernels' arguments."""
 import json
 import os
 import shutil
@@ -89,8 +90,66 @@ def free_memory_gate(check):
     assert 2 * int(out[2]) > 288 * 2 ** 30, out
 
 
+# set_nq -> slots per set, padded offsets, q slots per lane, end_mask: each set padded to whole slots of 64 entries, one after the
+# other; qpl the next power of two that holds them; a bit of end_mask for every set's last slot
+SETS_LAYOUTS = [
+    ((3,), (1,), (0,), 1, 0x1),
+    ((64,), (1,), (0,), 1, 0x1),
+    ((65,), (2,), (0,), 2, 0x2),
+    ((37, 100), (1, 2), (0, 64), 4, 0x5),
+    ((64, 3, 63, 130), (1, 1, 1, 3), (0, 64, 128, 192), 8, 0x27),
+    ((193, 193, 193, 193), (4, 4, 4, 4), (0, 256, 512, 768), 16, 0x8888),
+]
+# (nq, set_nq) -> words of the refusal
+SETS_SHAPE_REFUSALS = [
+    (836, (257, 193, 193, 193), ("17 padded slots", "1024")),
+    (90, (88, 2), ("set 1 has 2 points", "at least 3")),
+    (90, (40, 49), ("sum of set_nq 89 != nq 90",)),
+]
+
+
+def sets_layouts(check):
+    """Where the sets of a joint fit lie (host_decide.hip: check_sets_request); the LDS need is checked by the program against the
+    rule restated there."""
+    lines = ["L%d %d %d %s\n" % (i, sum(nqs), len(nqs), " ".join(map(str, nqs))) for i, (nqs, *_) in enumerate(SETS_LAYOUTS)]
+    lines += ["R%d %d %d %s\n" % (i, nq, len(nqs), " ".join(map(str, nqs))) for i, (nq, nqs, _) in enumerate(SETS_SHAPE_REFUSALS)]
+    out = dict(line.split(" ", 1) for line in check("sets", text="".join(lines)).splitlines())
+    assert len(out) == len(lines)
+    for i, (nqs, slots, pad_off, qpl, end_mask) in enumerate(SETS_LAYOUTS):
+        kind, total, got_qpl, got_mask, *per_set = out["L%d" % i].split()
+        assert kind == "layout" and (int(total), int(got_qpl), int(got_mask, 16)) == (sum(slots), qpl, end_mask), (nqs, out["L%d" % i])
+        assert tuple(int(x) for x in per_set[0::2]) == slots and tuple(int(x) for x in per_set[1::2]) == pad_off, (nqs, per_set)
+    for i, (nq, nqs, words) in enumerate(SETS_SHAPE_REFUSALS):
+        kind, code, msg = out["R%d" % i].split(" ", 2)
+        assert kind == "error" and int(code) == -1 and msg.startswith("analyse_sets:") and all(w in msg for w in words), (nqs, msg)
+
+
+def sets_refusals(check):
+    """Every row of test_sets_host.REFUSALS through the function that makes them, in the stand-alone program: the same words."""
+    from test_sets_host import REFUSALS, _request
+    lines = []
+    for what in sorted(REFUSALS):
+        st_kw, spoil, _ = REFUSALS[what]
+        prob = _request(**st_kw)[0]
+        if spoil:
+            spoil(prob)
+        c = prob.c
+        lines.append("%s %d %d %d %d %d %d %d\n" % (what, c.model_id, c.n_active, c.n_devices, c.positive_background, c.smear_nk,
+                                                    c.cache_intensities, c.exec_mode))
+    lines.append("valid %d 1 0 0 0 -1 0\n" % engine.MODEL_SPHERE)
+    out = dict(line.split(" ", 1) for line in check("refusals", text="".join(lines)).splitlines())
+    assert len(out) == len(REFUSALS) + 1 and out["valid"].strip() == "0"
+    for what, (_, _, words) in REFUSALS.items():
+        code, msg = out[what].split(" ", 1)
+        assert int(code) == -1 and words in msg and msg.startswith("analyse_sets:"), (what, msg)
+
+
 def test_plan_decisions_without_a_device(tmp_path):
     check = build_check(tmp_path)
-    assert check().strip() == "ok"                      # the family table, the trace block's layout and transposition, the tick budget
+    # the family table, the trace block's layout and transposition, the tick budget; the settings block of a chain run; the padded
+    # vectors and constants of (37, 100) points in two sets, and of 65 in one against the single-set sums
+    assert check().strip() == "ok"
+    sets_layouts(check)
+    sets_refusals(check)
     recorded_plan_shapes(check)
     free_memory_gate(check)

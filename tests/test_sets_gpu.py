@@ -123,3 +123,43 @@ def test_two_overlapping_ranges_through_the_front_end():
     assert h.bins.mean.shape == (30,) and np.isfinite(h.bins.mean).all() and h.bins.mean.sum() > 0
     # the histogram's own scale fit for member 0 is the joint fit's for that member
     np.testing.assert_allclose(r["scalingFactors"][0], d.set_scaling[0], rtol=1e-6)
+
+
+# ------------------------------------------------------------------------------------------------ McSAS.stop
+def test_a_stop_word_set_before_the_call_ends_every_chain_at_its_first_poll():
+    """What test_stop_flag_ends_the_run asks of the wavefront kernel, of the joint fit on (37, 100) points: no step, no retry."""
+    import ctypes
+    c = SX.case("b2")
+    m, _ = make_models(c["tag"], c["lo"], c["hi"])
+    st = engine.Settings(n_contrib=c["st"].n_contrib, n_reps=2, max_iter=10**9, conv_crit=0.0, max_retries=0, seed=1, device=0)
+    res = engine.analyse_sets(m.setup(), c["sets"], st, stop=ctypes.c_int32(1))
+    print("iter", res.num_iter, "converged", res.converged, "attempts", res.attempts)
+    assert (res.num_iter == 0).all() and (res.converged == 0).all() and (res.attempts == 1).all()
+
+
+# steps: without a stop the call below ends by this budget.  Measured on one MI355X (profiles/r30_summary.md): 39.3 s at 10**6 steps,
+# 4.0 s at 10**5; the budget is the largest power of ten that stays below 5 s
+STOP_BUDGET = 10**5
+
+
+def _cylinder_chains(max_iter, stop):
+    """Six free-running chains of 64 cylinders (the model and sets of test_a_row_with_an_integral) that never converge."""
+    c = SX.case("cyl")
+    m, _ = make_models(c["tag"], c["lo"], c["hi"], **c["fixed"])
+    st = engine.Settings(n_contrib=64, n_reps=6, max_iter=max_iter, conv_crit=0.0, max_retries=0, seed=3, device=0)
+    return engine.analyse_sets(m.setup(), c["sets"], st, stop=stop)
+
+
+def test_a_stop_word_raised_while_the_chains_run_ends_them():
+    """McSAS.stop raised from another thread 30 ms into the call, as test_stop_word_set_while_chains_with_an_integral_are_running
+    does for plans: the host forwards the word while it waits, every chain leaves early, not converged, without another attempt.
+    The budget ends the call if the word is never seen."""
+    import ctypes, threading
+    _cylinder_chains(64, None)                                # (library, memory and kernel warm: the timer below is about the run)
+    stop = ctypes.c_int32(0)
+    timer = threading.Timer(0.03, lambda: setattr(stop, "value", 1))
+    timer.start()
+    res = _cylinder_chains(STOP_BUDGET, stop)
+    timer.cancel()
+    print("iter", res.num_iter, "converged", res.converged, "attempts", res.attempts)
+    assert (res.num_iter < STOP_BUDGET).all() and (res.converged == 0).all() and (res.attempts == 1).all()
