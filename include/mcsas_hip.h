@@ -362,7 +362,7 @@ int mcsas_hip_plan_set_trace(mcsas_plan *plan, int32_t capacity);
 int mcsas_hip_plan_fetch_trace(mcsas_plan *plan, int32_t slot, mcsas_trace *trace);
 int mcsas_hip_analyse_traced(const mcsas_problem *problem, const double *start, mcsas_result *result, mcsas_trace *trace);
 
-/* ---- one population fitted to several data sets, each with a scale and a background of its own (ABI 5, additive) ---------------
+/* ---- one population fitted to several data sets: a scale per set or one for all, a background per set (ABI 5, additive) ---------
  * The same specimen measured more than once (two detector distances, SAXS + WAXS, two instruments): curves that overlap in q,
  * whose relative scale is not known well enough to merge them and whose backgrounds differ.  mcFit (mcsas.py:354-404) and
  * BackgroundScalingFit.calc (backgroundscalingfit.py:112-139) know one curve; this call extends them.  A chain holds ONE set of
@@ -383,8 +383,19 @@ int mcsas_hip_analyse_traced(const mcsas_problem *problem, const double *start, 
  *   set of fewer than 3 points, sum set_nq != nq, more than 16 slots, positive_background, smearing (smear_nk > 0), a device list
  *   (n_devices > 1), a model plug-in or a model that exists only as host code, n_active == 0, cache_intensities == 0, an exec_mode
  *   other than MCSAS_EXEC_AUTO or MCSAS_EXEC_WAVE, a wrong struct_size.  There is no plan, slot, batch, start or trace form.
- * Not offered: one scale shared by the sets (absolutely calibrated data), fixed model parameters per set (contrast
- *   variation). */
+ * Scale mode (mcsas_hip_analyse_sets_mode; mcsas_hip_analyse_sets is the call with MCSAS_SETS_SCALE_PER_SET):
+ *   MCSAS_SETS_SCALE_PER_SET  every set has a scale of its own, as above: curves whose relative scale is not known.
+ *   MCSAS_SETS_SCALE_SHARED   curves on an absolute scale: ONE scale A for all sets, a background per set — the closed form of the
+ *     (1 + n_sets)-unknown least-squares problem from the same per-set sums: with S_s, num_s, den_s as above,
+ *       X_t = sum_s S_s - (sum_s num_s)² / (sum_s den_s),   accepted iff X_t < X,
+ *     the three sums taken in set order; at the initial and final fit A = sum num_s / sum den_s, b_s = (SI_s - A SC_s) / Sw_s (0
+ *     without find_background) and X is the sum of the sets' residual sums at (A, b_s).  sets->scaling[s] is A for every s,
+ *     backgrounds and chisq are per set, result->scaling / background are A and b_0.  With n_sets = 1 the two modes are the same
+ *     chain bit for bit.  A known relative scale k_s between the curves is the caller's: divide that set's intensity and sigma by it.
+ *   An unknown mode is refused with MCSAS_EINVAL.
+ * Not offered: fixed model parameters per set (contrast variation). */
+#define MCSAS_SETS_SCALE_PER_SET 0
+#define MCSAS_SETS_SCALE_SHARED  1
 #define MCSAS_MAX_SETS 4
 typedef struct mcsas_sets_result {
     uint32_t struct_size;  /* sizeof(mcsas_sets_result) */
@@ -395,6 +406,31 @@ typedef struct mcsas_sets_result {
 } mcsas_sets_result;
 int mcsas_hip_analyse_sets(const mcsas_problem *problem, int32_t n_sets, const int32_t *set_nq,
                            mcsas_result *result, mcsas_sets_result *sets);
+int mcsas_hip_analyse_sets_mode(const mcsas_problem *problem, int32_t n_sets, const int32_t *set_nq, int32_t scale_mode,
+                                mcsas_result *result, mcsas_sets_result *sets);
+
+/* ---- McSAS.histogram() of a joint fit: the sets of mcsas_hip_analyse_sets seen together (ABI 5, additive) -------------------------
+ * mcsas_hip_histogram where problem->q / intensity / sigma hold n_sets sets one after the other, unpadded, set_nq[s] points each
+ * (>= 3, nq == sum set_nq).  Per repetition: the rows and their sum over all nq points as there; then
+ *   the fit: MCSAS_SETS_SCALE_PER_SET the closed-form scale and background of each set on its own points (the sums as
+ *     mcsas_hip_histogram forms them for one curve), MCSAS_SETS_SCALE_SHARED the one scale and per-set backgrounds of
+ *     mcsas_hip_analyse_sets_mode; A_ref is the scale of set ref_set (the shared scale in shared mode);
+ *   the visibility limit of a contribution: with vf = w A_ref / v, the minimum over the points k of the sets named in visible_sets
+ *     (bit s: set s) of (sigma[k] vf) / (A_s(k) row[k]), points whose A_s(k) row[k] is zero left out, +inf where none is kept;
+ *   fractions, bins, cumulative distribution and moments: as mcsas_hip_histogram with A_ref.
+ * scaling[2][n_reps] = (A_ref, b of ref_set); sets (arrays [n_sets][n_reps], caller-allocated): every set's scale and background;
+ *   sets->chisq may be NULL and is not written.  fractions, out, specs: as mcsas_hip_histogram.  With n_sets == 1 every number is
+ *   mcsas_hip_histogram's bit for bit; in per-set mode with visible_sets == 1 << ref_set the scaling, fractions and histograms are
+ *   those of mcsas_hip_histogram on that set alone.
+ * Refused with MCSAS_EINVAL and a message that names the cause, before a device is touched: whatever mcsas_hip_histogram refuses,
+ *   n_sets outside 1..MCSAS_MAX_SETS, sum set_nq != nq, a set of fewer than 3 points, ref_set outside the sets, visible_sets empty
+ *   or naming a set that is not there, an unknown scale_mode, positive_background, smearing, a model plug-in or a host model.
+ * The call takes no partial-intensity wishes (`want`) and has no batch and no device-rows form; 2-D histograms are made from the
+ *   fractions (mcsas_hip_histogram2d) and need nothing of their own. */
+struct mcsas_histogram_spec;   /* (defined with mcsas_hip_histogram, further down) */
+int mcsas_hip_histogram_sets(const mcsas_problem *problem, const double *contribs, int32_t n_hist, const struct mcsas_histogram_spec *specs,
+                             int32_t n_sets, const int32_t *set_nq, int32_t scale_mode, int32_t ref_set, uint32_t visible_sets,
+                             double *scaling, double *fractions, double *out, mcsas_sets_result *sets);
 
 /* ---- ScatteringModel.calc(data, pset, compensationExponent) (scatteringmodel.py:79-109) ------
  * Uses problem->{model_id, params, n_active, active_index, clip_*, nq, q, comp_exp, device}.

@@ -16,6 +16,7 @@ MAX_PARAMS = 8
 ABI_VERSION = 5
 MAX_DEVICES = 16
 MAX_SETS = 4            # data sets one population is fitted to at once (include/mcsas_hip.h: MCSAS_MAX_SETS)
+SETS_SCALE = {"per_set": 0, "shared": 1}    # MCSAS_SETS_SCALE_PER_SET, MCSAS_SETS_SCALE_SHARED
 
 # MCSAS_HIP_LIB selects another build of the SAME library (e.g. the -DMCSAS_STAMPS diagnostic build)
 LIB_PATH = os.environ.get("MCSAS_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmcsas_hip.so")
@@ -26,7 +27,7 @@ SYMBOLS = (
     "mcsas_hip_plan_launch_slot", "mcsas_hip_plan_fetch_slot",
     "mcsas_hip_plan_last_ms", "mcsas_hip_plan_total_steps", "mcsas_hip_plan_reseed", "mcsas_hip_plan_info",
     "mcsas_hip_plan_destroy", "mcsas_hip_plan_launch_batch", "mcsas_hip_analyse_batch", "mcsas_hip_plan_set_start", "mcsas_hip_analyse_from",
-    "mcsas_hip_plan_set_trace", "mcsas_hip_plan_fetch_trace", "mcsas_hip_analyse_traced", "mcsas_hip_analyse_sets", "mcsas_hip_model_calc", "mcsas_hip_bgfit", "mcsas_hip_observability",
+    "mcsas_hip_plan_set_trace", "mcsas_hip_plan_fetch_trace", "mcsas_hip_analyse_traced", "mcsas_hip_analyse_sets", "mcsas_hip_analyse_sets_mode", "mcsas_hip_histogram_sets", "mcsas_hip_model_calc", "mcsas_hip_bgfit", "mcsas_hip_observability",
     "mcsas_hip_histogram_prep", "mcsas_hip_histogram", "mcsas_hip_histogram_batch", "mcsas_hip_histogram_rows_shape", "mcsas_hip_histogram_device_rows",
     "mcsas_hip_histogram_partial", "mcsas_hip_histogram_partial_device_rows",
     "mcsas_hip_histogram2d", "mcsas_hip_prepare_uncertainty", "mcsas_hip_rebin",
@@ -169,6 +170,9 @@ def load(tuning=False):
     lib.mcsas_hip_plan_fetch_trace.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Trace)]
     lib.mcsas_hip_analyse_traced.argtypes = [C.POINTER(Problem), _dp, C.POINTER(Result), C.POINTER(Trace)]
     lib.mcsas_hip_analyse_sets.argtypes = [C.POINTER(Problem), C.c_int32, _i32p, C.POINTER(Result), C.POINTER(SetsResult)]
+    lib.mcsas_hip_analyse_sets_mode.argtypes = [C.POINTER(Problem), C.c_int32, _i32p, C.c_int32, C.POINTER(Result), C.POINTER(SetsResult)]
+    lib.mcsas_hip_histogram_sets.argtypes = [C.POINTER(Problem), _dp, C.c_int32, C.POINTER(HistogramSpec), C.c_int32, _i32p, C.c_int32, C.c_int32,
+                                             C.c_uint32, _dp, _dp, _dp, C.POINTER(SetsResult)]
     lib.mcsas_hip_plan_destroy.argtypes = [C.c_void_p]
     lib.mcsas_hip_plan_destroy.restype = None
     lib.mcsas_hip_model_calc.argtypes = [C.POINTER(Problem), _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp]

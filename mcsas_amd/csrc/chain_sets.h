@@ -1,9 +1,13 @@
-// chain_sets.h — one wavefront = one Monte-Carlo chain judged by SEVERAL data sets at once (mcsas_hip_analyse_sets): one population of
-// contributions, one running intensity over the q-points of all sets, and at every fit (initial, per step, final) a least-squares
-// scale and background of its own for each set.  The chain minimises the reduced chi² over all points,
+// chain_sets.h — one wavefront = one Monte-Carlo chain judged by SEVERAL data sets at once (mcsas_hip_analyse_sets,
+// mcsas_hip_analyse_sets_mode): one population of contributions, one running intensity over the q-points of all sets, and at every fit
+// (initial, per step, final) a least-squares scale and background of its own for each set.  The chain minimises the reduced chi² over
+// all points,
 //   chi²·Q = X = sum over the sets of (S_s - num_s²/den_s)      (the closed-form optimum of each set from its own five sums),
 // and accepts a step iff X_t < X (strict, mcsas.py:379).  What it extends: McSAS.mcFit (mcsas.py:354-404) and
 // BackgroundScalingFit.calc (backgroundscalingfit.py:112-139), which know one curve.
+// SHARED (MCSAS_SETS_SCALE_SHARED): ONE scale for all sets, a background per set — the same per-set sums and pieces, meeting as
+//   X = sum S_s - (sum num_s)² / (sum den_s)                     (the closed-form optimum of the (1 + S)-unknown problem);
+// with one set both modes are the same chain bit for bit.
 //
 // Everything else is the chain of chain_body.inc — draw order (N·P at an attempt's start, P per step, retries going on in the
 // stream), round-robin index, ft + (new - old), clip and generator transforms, start_from_minimum, the stop word, Philox keyed by
@@ -38,6 +42,7 @@ struct SetsArgs {
     uint32_t end_mask;                 // bit j: register slot j is the last slot of its set (S bits are set)
     SetConst set[MCSAS_MAX_SETS];
     SetsOut *out;                      // [n_reps]
+    int32_t  scale_mode, pad;          // MCSAS_SETS_SCALE_*: which instance the host launches (chain_sets_kernel<M, QPL, SHARED>); behind `out`: no earlier field moves
 };
 // in front of the wave kernels' LDS layout: each set's final scale, background and chi-squared, then its SetConst (as doubles),
 // padded to 16 bytes
@@ -74,11 +79,24 @@ __device__ __forceinline__ void sets_walk(const double (&c)[QPL], const double *
     }
 }
 
-// chi²·Q_s of a set at its optimum: S - num²/den, centred sums when a background is fitted
+// the pieces of a set's chi²·Q_s at an optimum: S, num, den, centred sums when a background is fitted
+struct SetParts { double S, num, den; };
+__device__ __forceinline__ SetParts set_parts(bool find_bg, const SetConst &c, const Sums3 &s) {
+    SetParts p{c.SII, s.s3, s.s2};
+    if (find_bg) { p.S = c.Scen; p.num = fma(-c.SIoSw, s.s1, s.s3); p.den = fma(-(s.s1 * c.invSw), s.s1, s.s2); }
+    return p;
+}
+// chi²·Q_s of a set at its own optimum: S - num²/den
 __device__ __forceinline__ double set_x(bool find_bg, const SetConst &c, const Sums3 &s) {
     double S = c.SII, num = s.s3, den = s.s2;
     if (find_bg) { S = c.Scen; num = fma(-c.SIoSw, s.s1, s.s3); den = fma(-(s.s1 * c.invSw), s.s1, s.s2); }
     return S - num * num / den;
+}
+
+// the residual sum Σ w (I - A C - b)² of one set at (A, b), expanded in its sums
+__device__ __forceinline__ double set_resid(const SetConst &c, const Sums3 &s, double A, double b) {
+    const double SC = s.s1, SCC = s.s2, SIC = s.s3;
+    return c.SII - 2. * A * SIC - 2. * b * c.SI + A * A * SCC + 2. * A * b * SC + b * b * c.Sw;
 }
 
 // argmin_{A,b} Σ w (I - A C - b)² of one set and the residual sum at that optimum: solve_fit (chain_common.h) without
@@ -92,12 +110,48 @@ __device__ __forceinline__ double set_fit(bool find_bg, const SetConst &c, const
     } else {
         A = SIC / SCC; b = 0.;
     }
-    return c.SII - 2. * A * SIC - 2. * b * c.SI + A * A * SCC + 2. * A * b * SC + b * b * c.Sw;
+    return set_resid(c, s, A, b);
+}
+
+// MCSAS_SETS_SCALE_SHARED: ONE scale for all sets and a background per set, argmin over (A, b_0 .. b_{S-1}) of the residual sum over all
+// points.  In: fit[3 s ..] = s1, s2, s3 of set s (LDS, where the walk left them).  Out: fit[3 s] = A = Σ num_s / Σ den_s,
+// fit[3 s + 1] = b_s = (SI_s - A s1_s) / Sw_s (0 without a background); returns the sum of the sets' residual sums there.  With one set
+// the pair is that set's own optimum by set_fit's operations: the one-set chain is the per-set mode's bit for bit.  Wave-uniform; the
+// sets are walked through LDS, nothing per set is held in registers.
+__device__ __forceinline__ double sets_fit_shared(bool find_bg, int n_sets, double *fit, const double *lset) {
+    if (n_sets == 1) {
+        const Sums3 s{fit[0], fit[1], fit[2]};
+        double A, b;
+        const double X = set_fit(find_bg, set_const(lset, 0), s, A, b);
+        fit[0] = A; fit[1] = b;
+        return X;
+    }
+    double Num = 0., Den = 0.;
+    for (int s = 0; s < n_sets; ++s) {
+        const double *f = fit + SETS_FIT_DOUBLES * s;
+        const SetParts p = set_parts(find_bg, set_const(lset, s), Sums3{f[0], f[1], f[2]});
+        Num += p.num; Den += p.den;
+    }
+    const double A = Num / Den;
+    double X = 0.;
+    for (int s = 0; s < n_sets; ++s) {
+        double *f = fit + SETS_FIT_DOUBLES * s;
+        const SetConst c = set_const(lset, s);
+        const Sums3 sums{f[0], f[1], f[2]};
+        const double b = find_bg ? (c.SI - A * sums.s1) / c.Sw : 0.;
+        X += set_resid(c, sums, A, b);
+        f[0] = A; f[1] = b;
+    }
+    return X;
 }
 
 #define MCSAS_SETS_MIN_WAVES(QPL) ((QPL) <= 8 ? 2 : 1)     // (chain_wave.h's, with cached rows)
 
-template <int M, int QPL>
+// The chain of both scale modes, one wavefront: SHARED says how the sets' pieces meet in X_t and what the fits solve.
+// chain_sets_kernel<M, QPL> is the MCSAS_SETS_SCALE_PER_SET instance (kern_wave_sets.hip), chain_sets_kernel<M, QPL, true> the
+// MCSAS_SETS_SCALE_SHARED one (kern_wave_sets_shared.hip).  The kernel itself carries the text: handed on to a function, the argument
+// blocks reach it another way and the per-set instances' registers and scratch move (the table of DESIGN §4.1e).
+template <int M, int QPL, bool SHARED = false>
 __global__ __launch_bounds__(64, MCSAS_SETS_MIN_WAVES(QPL)) void chain_sets_kernel(const ChainArgs a, const SetsArgs sa) {
     extern __shared__ double lds[];
     const int lane = threadIdx.x;
@@ -181,9 +235,21 @@ __global__ __launch_bounds__(64, MCSAS_SETS_MIN_WAVES(QPL)) void chain_sets_kern
         // ------------------------------------------------------------ initial fit (mcsas.py:327-343), set by set
         double X = 0.;
         sets_walk<QPL>(ft, lw, lwI, lset, lane, end_mask, [&](int s, const SetConst &c, const Sums3 &sums) {
-            double A, b;
-            X += set_fit(find_bg, c, sums, A, b);
+            if constexpr (SHARED) {                                                            // (the sums wait in LDS for sets_fit_shared)
+                lfit[SETS_FIT_DOUBLES * s] = sums.s1; lfit[SETS_FIT_DOUBLES * s + 1] = sums.s2; lfit[SETS_FIT_DOUBLES * s + 2] = sums.s3;
+            } else {
+                double A, b;
+                X += set_fit(find_bg, c, sums, A, b);
+            }
         });
+        if constexpr (SHARED) {
+            X = sets_fit_shared(find_bg, sa.n_sets, lfit, lset);
+            // Σ S_s in set order does not depend on the step: taken once per attempt and kept in set 0's chi² word, which is free until
+            // the final fit (a register held across the row evaluation costs the integral models scratch)
+            double Ssum = 0.;
+            for (int s = 0; s < sa.n_sets; ++s) { const SetConst c = set_const(lset, s); Ssum += find_bg ? c.Scen : c.SII; }
+            lfit[2] = Ssum;
+        }
         chi2 = X / nqd;
         X = chi2 * nqd;
         num_iter = 0; num_moves = 0;
@@ -221,6 +287,7 @@ __global__ __launch_bounds__(64, MCSAS_SETS_MIN_WAVES(QPL)) void chain_sets_kern
                 // (ft + (new - old) as in every execution mode, chain_body.inc; the walk of sets_walk with the candidate formed on the way)
                 double Xt = 0.;
                 {
+                    [[maybe_unused]] double Num = 0., Den = 0.;                        // (SHARED: the sets' pieces in set order)
                     Sums3 run{0., 0., 0.};
                     int s = 0;
 #pragma unroll
@@ -230,10 +297,16 @@ __global__ __launch_bounds__(64, MCSAS_SETS_MIN_WAVES(QPL)) void chain_sets_kern
                         run.s1 += wt; run.s2 = fma(wt, test[j], run.s2); run.s3 = fma(lwI[lane + WAVE * j], test[j], run.s3);
                         if ((end_mask >> j) & 1u) {
                             wave_sum3(run.s1, run.s2, run.s3);
-                            Xt += set_x(find_bg, set_const(lset, s), run);
+                            if constexpr (SHARED) {
+                                const SetParts p = set_parts(find_bg, set_const(lset, s), run);
+                                Num += p.num; Den += p.den;
+                            } else {
+                                Xt += set_x(find_bg, set_const(lset, s), run);
+                            }
                             ++s; run = Sums3{0., 0., 0.};
                         }
                     }
+                    if constexpr (SHARED) Xt = lfit[2] - Num * Num / Den;
                 }
                 if (Xt < X) {                                                          // mcsas.py:379-390
                     X = Xt;
@@ -260,10 +333,15 @@ __global__ __launch_bounds__(64, MCSAS_SETS_MIN_WAVES(QPL)) void chain_sets_kern
 
         // ------------------------------------------------------------ final fit on ft (mcsas.py:424-426), set by set
         sets_walk<QPL>(ft, lw, lwI, lset, lane, end_mask, [&](int s, const SetConst &c, const Sums3 &sums) {
-            double A, b;
-            (void)set_fit(find_bg, c, sums, A, b);
-            lfit[SETS_FIT_DOUBLES * s] = A; lfit[SETS_FIT_DOUBLES * s + 1] = b;
+            if constexpr (SHARED) {
+                lfit[SETS_FIT_DOUBLES * s] = sums.s1; lfit[SETS_FIT_DOUBLES * s + 1] = sums.s2; lfit[SETS_FIT_DOUBLES * s + 2] = sums.s3;
+            } else {
+                double A, b;
+                (void)set_fit(find_bg, c, sums, A, b);
+                lfit[SETS_FIT_DOUBLES * s] = A; lfit[SETS_FIT_DOUBLES * s + 1] = b;
+            }
         });
+        if constexpr (SHARED) (void)sets_fit_shared(find_bg, sa.n_sets, lfit, lset);
         // (every lane wrote each set's pair itself: its own reads below follow in program order)
         // reported chi-squared: direct residual sums, like chiSqr (backgroundscalingfit.py:72-77), each slot with its own set's fit;
         // the fit itself goes out on the way (ifinal*sc[0]+sc[1], mcsas.py:430: the last attempt's stays)

@@ -41,13 +41,18 @@ struct SetsLayout {
     int S = 0, qpl = 0, total_slots = 0;
     int nq[MCSAS_MAX_SETS] = {}, off[MCSAS_MAX_SETS] = {}, slots[MCSAS_MAX_SETS] = {}, pad_off[MCSAS_MAX_SETS] = {};
     uint32_t end_mask = 0;
+    int scale_mode = 0;                                        // MCSAS_SETS_SCALE_*
     size_t lds_bytes = 0;
 };
-// Everything mcsas_hip_analyse_sets refuses but a shape without a kernel, in order; fills the layout and the model's argument block.
+// Everything mcsas_hip_analyse_sets_mode refuses but a shape without a kernel, in order; fills the layout and the model's argument block.
 int check_sets_request(const mcsas_problem *p, int32_t n_sets, const int32_t *set_nq, const mcsas_result *res,
-                       const mcsas_sets_result *sets, SetsLayout *L, mcsas::ModelArgs *margs);
+                       const mcsas_sets_result *sets, SetsLayout *L, mcsas::ModelArgs *margs, int32_t scale_mode = MCSAS_SETS_SCALE_PER_SET);
+// What mcsas_hip_histogram_sets refuses beyond what mcsas_hip_histogram refuses of the set (host_hist.hip: check_hist_set runs first),
+// in order; fills off[s], the first point of set s among the nq points (off[n_sets .. MCSAS_MAX_SETS] = nq).
+int check_hist_sets_request(const mcsas_problem *p, int32_t n_sets, const int32_t *set_nq, int32_t scale_mode, int32_t ref_set,
+                            uint32_t visible_sets, const mcsas_sets_result *sets, int32_t off[MCSAS_MAX_SETS + 1]);
 // The padded vectors, 64 qpl entries each (pad: q of the set's first point — behind the last set, of the first set's —, w = wI = I = 0),
-// and what the kernel's second argument holds of the sets: their number, end_mask and each set's SetConst (`out` is the caller's).
+// and what the kernel's second argument holds of the sets: their number, end_mask, the scale mode and each set's SetConst (`out` is the caller's).
 struct SetsData { std::vector<double> q, w, wI, I; };
 void lay_out_sets(const mcsas_problem *p, const SetsLayout &L, SetsData *d, mcsas::SetsArgs *sa);
 

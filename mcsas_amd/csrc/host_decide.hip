@@ -260,7 +260,7 @@ WeighedSums weigh_points(const double *I, const double *sigma, int n, double *w,
 
 // ------------------------------------------------------------------------------ one population fitted to several data sets
 int check_sets_request(const mcsas_problem *p, int32_t n_sets, const int32_t *set_nq, const mcsas_result *res,
-                       const mcsas_sets_result *sets, SetsLayout *L, ModelArgs *margs) {
+                       const mcsas_sets_result *sets, SetsLayout *L, ModelArgs *margs, int32_t scale_mode) {
     const char *const who = "analyse_sets";
     if (!p || !res || !sets || !set_nq) return fail(MCSAS_EINVAL, "%s: null argument", who);
     if (p->struct_size != sizeof(mcsas_problem))
@@ -270,6 +270,9 @@ int check_sets_request(const mcsas_problem *p, int32_t n_sets, const int32_t *se
         return fail(MCSAS_EINVAL, "%s: mcsas_sets_result size %u, library expects %zu", who, sets->struct_size, sizeof(mcsas_sets_result));
     if (n_sets < 1 || n_sets > MCSAS_MAX_SETS) return fail(MCSAS_EINVAL, "%s: n_sets %d (1..%d)", who, (int)n_sets, MCSAS_MAX_SETS);
     if (sets->n_sets != n_sets) return fail(MCSAS_EINVAL, "%s: mcsas_sets_result.n_sets %d, the call's n_sets is %d", who, (int)sets->n_sets, (int)n_sets);
+    if (scale_mode != MCSAS_SETS_SCALE_PER_SET && scale_mode != MCSAS_SETS_SCALE_SHARED)
+        return fail(MCSAS_EINVAL, "%s: unknown scale_mode %d (%d: a scale per set, %d: one scale shared by the sets)", who, (int)scale_mode,
+                    MCSAS_SETS_SCALE_PER_SET, MCSAS_SETS_SCALE_SHARED);
     if (p->reserved0) return fail(MCSAS_EINVAL, "%s: mcsas_problem.reserved0 must be 0 (it is %d)", who, p->reserved0);
     if (p->nq < 1 || !p->q || !p->intensity || !p->sigma) return fail(MCSAS_EINVAL, "%s: nq/q/intensity/sigma missing", who);
     if (p->n_active == 0)
@@ -290,7 +293,7 @@ int check_sets_request(const mcsas_problem *p, int32_t n_sets, const int32_t *se
         if (p->gen_kind[c] < MCSAS_GEN_UNIFORM || p->gen_kind[c] > MCSAS_GEN_EXP3) return fail(MCSAS_EINVAL, "%s: gen_kind[%d]=%d", who, c, p->gen_kind[c]);
 
     *L = SetsLayout{};
-    L->S = n_sets;
+    L->S = n_sets; L->scale_mode = scale_mode;
     long long sum = 0, slot_sum = 0;
     for (int s = 0; s < n_sets; ++s) {
         if (set_nq[s] < 3) return fail(MCSAS_EINVAL, "%s: set %d has %d points; every set needs at least 3", who, s, (int)set_nq[s]);
@@ -317,7 +320,7 @@ void lay_out_sets(const mcsas_problem *p, const SetsLayout &L, SetsData *d, Sets
     const size_t qpad = (size_t)L.qpl * WAVE;
     d->q.assign(qpad, p->q[0]); d->w.assign(qpad, 0.); d->wI.assign(qpad, 0.); d->I.assign(qpad, 0.);
     memset(sa, 0, sizeof *sa);
-    sa->n_sets = L.S; sa->end_mask = L.end_mask;
+    sa->n_sets = L.S; sa->end_mask = L.end_mask; sa->scale_mode = L.scale_mode;
     for (int s = 0; s < L.S; ++s) {
         const int src = L.off[s], dst = L.pad_off[s];
         std::fill_n(&d->q[dst], L.slots[s] * WAVE, p->q[src]);
@@ -326,6 +329,44 @@ void lay_out_sets(const mcsas_problem *p, const SetsLayout &L, SetsData *d, Sets
         // (1 / Sw, SI / Sw, SII - SI² / Sw: the operations of chain_body.inc, unfused here as there)
         sa->set[s] = SetConst{t.Sw, t.SI, t.SII, 1.0 / t.Sw, t.SI / t.Sw, t.SII - t.SI * t.SI / t.Sw, (double)L.nq[s]};
     }
+}
+
+// ------------------------------------------------------------------------------ the histogram of a joint fit
+int check_hist_sets_request(const mcsas_problem *p, int32_t n_sets, const int32_t *set_nq, int32_t scale_mode, int32_t ref_set,
+                            uint32_t visible_sets, const mcsas_sets_result *sets, int32_t off[MCSAS_MAX_SETS + 1]) {
+    const char *const who = "histogram_sets";
+    if (!p || !set_nq || !sets) return fail(MCSAS_EINVAL, "%s: null argument", who);
+    if (p->struct_size != sizeof(mcsas_problem))
+        return fail(MCSAS_EINVAL, "%s: mcsas_problem size %u, library expects %zu (ABI mismatch)", who, p->struct_size, sizeof(mcsas_problem));
+    if (sets->struct_size != sizeof(mcsas_sets_result))
+        return fail(MCSAS_EINVAL, "%s: mcsas_sets_result size %u, library expects %zu", who, sets->struct_size, sizeof(mcsas_sets_result));
+    if (n_sets < 1 || n_sets > MCSAS_MAX_SETS) return fail(MCSAS_EINVAL, "%s: n_sets %d (1..%d)", who, (int)n_sets, MCSAS_MAX_SETS);
+    if (sets->n_sets != n_sets) return fail(MCSAS_EINVAL, "%s: mcsas_sets_result.n_sets %d, the call's n_sets is %d", who, (int)sets->n_sets, (int)n_sets);
+    if (!sets->scaling || !sets->background) return fail(MCSAS_EINVAL, "%s: mcsas_sets_result.scaling and .background receive every set's fit; one is NULL", who);
+    long long sum = 0;
+    for (int s = 0; s < n_sets; ++s) {
+        if (set_nq[s] < 3) return fail(MCSAS_EINVAL, "%s: set %d has %d points; every set needs at least 3", who, s, (int)set_nq[s]);
+        sum += set_nq[s];
+    }
+    if (sum != p->nq) return fail(MCSAS_EINVAL, "%s: sum of set_nq %lld != nq %d", who, sum, p->nq);
+    if (ref_set < 0 || ref_set >= n_sets) return fail(MCSAS_EINVAL, "%s: ref_set %d: there are %d sets", who, (int)ref_set, (int)n_sets);
+    if (visible_sets == 0) return fail(MCSAS_EINVAL, "%s: visible_sets is empty: no set's points would judge what is visible", who);
+    if (visible_sets >> n_sets) return fail(MCSAS_EINVAL, "%s: visible_sets 0x%x names a set that is not there (%d sets)", who, visible_sets, (int)n_sets);
+    if (scale_mode != MCSAS_SETS_SCALE_PER_SET && scale_mode != MCSAS_SETS_SCALE_SHARED)
+        return fail(MCSAS_EINVAL, "%s: unknown scale_mode %d (%d: a scale per set, %d: one scale shared by the sets)", who, (int)scale_mode,
+                    MCSAS_SETS_SCALE_PER_SET, MCSAS_SETS_SCALE_SHARED);
+    if (p->positive_background) return fail(MCSAS_EINVAL, "%s: positive_background is not supported with several sets", who);
+    if (p->smear_nk != 0 || p->smear_locs || p->smear_q_offset || p->smear_weights)
+        return fail(MCSAS_EINVAL, "%s: smearing (smear_nk %d) is not supported with several sets", who, p->smear_nk);
+    if (p->model_id == -1) return fail(MCSAS_EINVAL, "%s: a host model (model_id -1: rows evaluated by the caller) is not supported", who);
+    if (is_plugin_model(p->model_id)) return fail(MCSAS_EINVAL, "%s: a model plug-in (model_id %d) is not supported; built-in models only", who, p->model_id);
+    if (p->model_id < 0 || p->model_id >= MCSAS_MODEL_COUNT) return fail(MCSAS_EINVAL, "%s: unknown model_id %d", who, p->model_id);
+    int o = 0;
+    for (int s = 0; s <= MCSAS_MAX_SETS; ++s) {
+        off[s] = o;
+        if (s < n_sets) o += set_nq[s];
+    }
+    return MCSAS_OK;
 }
 
 // ------------------------------------------------------------------------------ what a start and a trace are refused for

@@ -1,5 +1,6 @@
 // host_hist.hip — McSAS.histogram() on the device: the hist_* kernels, their batch forms and the entry points mcsas_hip_histogram_prep,
-// mcsas_hip_histogram, mcsas_hip_histogram_batch and mcsas_hip_histogram_device_rows (the rows filled by the caller), and the forms of
+// mcsas_hip_histogram, mcsas_hip_histogram_sets (the sets of a joint fit seen together), mcsas_hip_histogram_batch and
+// mcsas_hip_histogram_device_rows (the rows filled by the caller), and the forms of
 // the second and the last that also return partial intensities (hist_partial_kernel.h; mcsas_hip_histogram_partial*).  What makes a
 // set acceptable (check_hist_set), how a set lies in the staging blocks (HistSizes, pack_hist_set, unpack_hist_set) and how many
 // repetitions share a block of rows (hist_rep_chunk) are each said once here, for the single call and the batch alike; how one set
@@ -13,6 +14,7 @@
 #include <cstring>
 #include <vector>
 
+#include "host_decide.h"     // check_hist_sets_request, HistSetOffs' MCSAS_MAX_SETS
 #include "small_launch.h"    // hist_rows_kernel, hist_rows_batch_kernel (from a model id to the instance), HistSetDev, visibility_limit
 
 using namespace mcsas;
@@ -83,6 +85,79 @@ __global__ __launch_bounds__(64) void hist_fit_cum_kernel(int nq, const double *
     const int rl = blockIdx.x;
     hist_fit_cum_body(nq, I, sigma, R, r0 + rl, cum + (size_t)rl * nq, find_bg, pos_bg, scaling);
 }
+// ---- the same two for a joint fit (mcsas_hip_histogram_sets): the nq points are n_sets sets one after the other.  Where the sets begin
+// goes by value and is indexed by unrolled loops alone (a run-time index would send the block to scratch); each set's fit lies in
+// set_fit[2][MCSAS_MAX_SETS][R] (scales, then backgrounds), which the visibility kernel reads.
+struct HistSetOffs { int32_t o[MCSAS_MAX_SETS + 1]; };        // set s: points [o[s], o[s + 1]); o[n_sets ..] = nq
+// One wave per repetition.  Each set's six sums as hist_fit_cum_body forms them on the set's own points; then per set solve_fit
+// (MCSAS_SETS_SCALE_PER_SET), or ONE scale A = Σ num_s / Σ den_s and b_s = (SI_s - A SC_s) / Sw_s with the centred pieces of
+// chain_sets.h: set_parts (MCSAS_SETS_SCALE_SHARED; with one set solve_fit, as the chain does).  scaling[2][R] = set ref_set's pair.
+__global__ __launch_bounds__(64) void hist_fit_sets_kernel(int nq, const double *I, const double *sigma, int R, int r0, const double *cum_all,
+                                                           int find_bg, int n_sets, HistSetOffs off, int shared, int ref_set, double *scaling,
+                                                           double *set_fit) {
+    const int lane = threadIdx.x, rl = blockIdx.x, r = r0 + rl;
+    const double *cum = cum_all + (size_t)rl * nq;
+    double sw[MCSAS_MAX_SETS], si[MCSAS_MAX_SETS], sc[MCSAS_MAX_SETS], A[MCSAS_MAX_SETS], b[MCSAS_MAX_SETS];
+    double Num = 0., Den = 0.;
+#pragma unroll
+    for (int s = 0; s < MCSAS_MAX_SETS; ++s) {
+        sw[s] = si[s] = sc[s] = A[s] = b[s] = 0.;
+        if (s < n_sets) {
+            double w0 = 0, i0 = 0, ii0 = 0, c0 = 0, cc0 = 0, ic0 = 0;
+            for (int k = off.o[s] + lane; k < off.o[s + 1]; k += WAVE) {
+                const double C = cum[k];
+                const double e = sigma[k] == 0.0 ? 1.0 : sigma[k];
+                const double w = 1.0 / (e * e);
+                w0 += w; i0 += w * I[k]; ii0 += w * I[k] * I[k];
+                c0 += w * C; cc0 += w * C * C; ic0 += w * I[k] * C;
+            }
+            wave_sum3(w0, i0, ii0); wave_sum3(c0, cc0, ic0);
+            if (!shared || n_sets == 1) {
+                ChainArgs a{};
+                a.Sw = w0; a.SI = i0; a.SII = ii0; a.nq = off.o[s + 1] - off.o[s]; a.find_bg = find_bg; a.pos_bg = 0;
+                const FitResult f = solve_fit(a, c0, cc0, ic0);
+                A[s] = f.A; b[s] = f.b;
+            } else {
+                double num = ic0, den = cc0;
+                if (find_bg) { num = fma(-(i0 / w0), c0, ic0); den = fma(-(c0 * (1.0 / w0)), c0, cc0); }
+                Num += num; Den += den;
+                sw[s] = w0; si[s] = i0; sc[s] = c0;
+            }
+        }
+    }
+    double Aref = 0., bref = 0.;
+    const double Ashared = Num / Den;
+#pragma unroll
+    for (int s = 0; s < MCSAS_MAX_SETS; ++s)
+        if (s < n_sets) {
+            if (shared && n_sets > 1) { A[s] = Ashared; b[s] = find_bg ? (si[s] - Ashared * sc[s]) / sw[s] : 0.; }
+            if (s == ref_set) { Aref = A[s]; bref = b[s]; }
+            if (lane == 0) { set_fit[(size_t)s * R + r] = A[s]; set_fit[((size_t)MCSAS_MAX_SETS + s) * R + r] = b[s]; }
+        }
+    if (lane == 0) { scaling[r] = Aref; scaling[R + r] = bref; }
+}
+// One wave per (contribution, repetition): visibility_limit over the points of the sets named in `visible`, each point's product taken
+// with its OWN set's scale, at the volume fraction the reference scale (scaling[r]) gives the contribution.
+__global__ __launch_bounds__(64) void hist_obs_sets_kernel(int nq, const double *sigma, int N, int R, int r0, const double *rows, const double *scaling,
+                                                           const double *set_fit, int n_sets, HistSetOffs off, uint32_t visible, const double *vset,
+                                                           const double *wset, double *min_req) {
+    const int c = blockIdx.x, rl = blockIdx.y, r = r0 + rl;
+    const double *row = rows + ((size_t)rl * N + c) * nq;
+    const double vf = wset[(size_t)c * R + r] * scaling[r] / vset[(size_t)c * R + r];   // modeldata.py:57-61
+    double best = __builtin_inf();
+#pragma unroll
+    for (int s = 0; s < MCSAS_MAX_SETS; ++s)
+        if (s < n_sets && ((visible >> s) & 1u)) {
+            const double A = set_fit[(size_t)s * R + r];
+            for (int k = off.o[s] + (int)threadIdx.x; k < off.o[s + 1]; k += WAVE) {
+                const double scaled = A * row[k];
+                if (scaled != 0.) best = fmin(best, (sigma[k] * vf) / scaled);
+            }
+        }
+    best = wave_min(best);
+    if (threadIdx.x == 0) min_req[(size_t)c * R + r] = best;
+}
+
 // fractions and their visibility limits, normalised per repetition (mcsas.py:561-604): frac8 = [vf nf qf sf | mv mn mq ms][N][R].
 // One wave per rep; the three totals are taken by one lane each, over the contributions in order (builtin sum()).
 __device__ __forceinline__ void hist_fractions_body(int N, int R, int r, const double *scaling, const double *vset, const double *wset,
@@ -590,6 +665,57 @@ extern "C" int mcsas_hip_histogram(const mcsas_problem *p, const double *contrib
 extern "C" int mcsas_hip_histogram_partial(const mcsas_problem *p, const double *contribs, int32_t n_hist, const mcsas_histogram_spec *specs,
                                            const int32_t *want, double *scaling, double *fractions, double *out, double *partial) {
     return histogram_call(p, contribs, n_hist, specs, true, want, scaling, fractions, out, partial);
+}
+
+// ------------------------------------------------------------------------------ the sets of a joint fit: mcsas_hip_histogram_sets
+// The frame of histogram_call over the points of all sets: the rows kernel and the column sums take nq = Σ set_nq as it is, the fit
+// and the visibility limits know the sets (hist_fit_sets_kernel, hist_obs_sets_kernel), HistOnDevice::finish goes on with the
+// reference scale.  Every set's fit comes back behind the set's own coming-back block, in the one download.  What the call refuses
+// beyond check_hist_set is host_decide.hip's (check_hist_sets_request), before a device is touched.
+extern "C" int mcsas_hip_histogram_sets(const mcsas_problem *p, const double *contribs, int32_t n_hist, const mcsas_histogram_spec *specs, int32_t n_sets,
+                                        const int32_t *set_nq, int32_t scale_mode, int32_t ref_set, uint32_t visible_sets, double *scaling,
+                                        double *fractions, double *out, mcsas_sets_result *sets) {
+    HistSetOffs off;
+    if (int rc = check_hist_sets_request(p, n_sets, set_nq, scale_mode, ref_set, visible_sets, sets, off.o)) return rc;
+    ModelArgs m; HistSizes sz;
+    if (const int rc = check_hist_set(p, contribs, n_hist, specs, scaling, out, &m, &sz)) { const std::string why = g_err; return fail(rc, "histogram_sets: %s", why.c_str()); }
+    return no_bad_alloc("histogram_sets", [&]() -> int {
+        DeviceGuard dev_guard;
+        if (int rc = select_device(p->device)) return rc;
+        const size_t Q = p->nq, N = p->n_contrib, R = p->n_reps, chunk = hist_rep_chunk(N, Q, R);
+        const size_t fit_off = sz.n_back;                          // [2][MCSAS_MAX_SETS][R] behind the set's coming-back block
+        sz.n_back += 2 * (size_t)MCSAS_MAX_SETS * R;
+        DevBuf<double> drows;                                      // (ahead of the set: it goes back after the set's guard has waited)
+        HistOnDevice d;
+        HIPCHK(drows.alloc(chunk * N * Q));
+        if (int rc = d.upload(p, contribs, n_hist, specs, sz, chunk)) return rc;
+        if (int rc = d.smear.upload(p, p->nq, &m)) return rc;      // (smearing is refused: the model's arguments say "none")
+        double *const dfit = d.dback.p + fit_off;
+        HIPCHK(hipMemsetAsync(dfit, 0, sizeof(double) * 2 * MCSAS_MAX_SETS * R, nullptr));
+        const size_t lds = sizeof(double) * table_doubles_host(p->model_id, m.int_div);
+        const int shared = scale_mode == MCSAS_SETS_SCALE_SHARED;
+        for (size_t r0 = 0; r0 < R; r0 += chunk) {
+            const unsigned nr = (unsigned)std::min(chunk, R - r0);
+            if (int rc = launch_small_kernel<HistRowsFamily>(p->model_id, dim3((unsigned)N, nr), lds, m, p->nq, d.a.q, p->n_contrib, p->n_reps, r0, d.a.c,
+                                                             drows.p, d.a.v, d.a.w, d.a.s))
+                return rc;
+            hist_colsum_kernel<<<dim3((unsigned)((Q + 255) / 256), nr), 256>>>(p->nq, p->n_contrib, drows.p, d.a.cum);
+            HIPCHK(hipGetLastError());
+            hist_fit_sets_kernel<<<nr, WAVE>>>(p->nq, d.a.I, d.a.sg, (int)R, (int)r0, d.a.cum, p->find_background != 0, n_sets, off, shared, ref_set, d.a.sc,
+                                               dfit);
+            HIPCHK(hipGetLastError());
+            hist_obs_sets_kernel<<<dim3((unsigned)N, nr), WAVE>>>(p->nq, d.a.sg, (int)N, (int)R, (int)r0, drows.p, d.a.sc, dfit, n_sets, off, visible_sets,
+                                                                  d.a.v, d.a.w, d.a.m);
+            HIPCHK(hipGetLastError());
+        }
+        if (int rc = d.finish(scaling, fractions, out)) return rc;
+        const double *hfit = d.hback.p + fit_off;
+        for (int s = 0; s < n_sets; ++s) {
+            memcpy(sets->scaling + (size_t)s * R, hfit + (size_t)s * R, sizeof(double) * R);
+            memcpy(sets->background + (size_t)s * R, hfit + ((size_t)MCSAS_MAX_SETS + s) * R, sizeof(double) * R);
+        }
+        return MCSAS_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------ one set, the rows filled by the caller: mcsas_hip_histogram_device_rows

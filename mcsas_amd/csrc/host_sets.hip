@@ -1,5 +1,6 @@
-// host_sets.hip — mcsas_hip_analyse_sets: one population fitted to several data sets, each with a scale and a background of its own
-// (include/mcsas_hip.h; the kernel: chain_sets.h, instantiated per model in kern_wave_sets.hip).  A one-shot call without a plan, and of
+// host_sets.hip — mcsas_hip_analyse_sets and mcsas_hip_analyse_sets_mode: one population fitted to several data sets, each with a
+// background of its own and a scale of its own or one for all (include/mcsas_hip.h; the kernels: chain_sets.h, instantiated per model
+// in kern_wave_sets.hip and kern_wave_sets_shared.hip).  A one-shot call without a plan, and of
 // it what needs a device: what the call refuses, where the sets lie (each padded to whole register slots of 64 entries) and the padded
 // data are host_decide.hip's; here the kernel is looked up, one wavefront per repetition launched on the null stream and the results
 // placed through host_result.h.
@@ -13,14 +14,18 @@
 
 using namespace mcsas;
 
-// the lookups of the built-in models (kern_wave_sets.hip: `void *(int qpl, bool)`, the flag is not read)
+// the lookups of the built-in models (kern_wave_sets.hip, kern_wave_sets_shared.hip: `void *(int qpl, bool)`, the flag is not read),
+// one row per scale mode
 typedef void *SetsLookup(int qpl, bool flag);
-#define DECL_SETS(m) SetsLookup mcsas_wave_sets_kernel_m##m;
+#define DECL_SETS(m) SetsLookup mcsas_wave_sets_kernel_m##m, mcsas_wave_sets_shared_kernel_m##m;
 #define ROW_SETS(m) mcsas_wave_sets_kernel_m##m,
+#define ROW_SETS_SHARED(m) mcsas_wave_sets_shared_kernel_m##m,
 MCSAS_FOR_MODELS(DECL_SETS)
-static SetsLookup *const SETS_KERNEL[MCSAS_MODEL_COUNT] = {MCSAS_FOR_MODELS(ROW_SETS)};
+static SetsLookup *const SETS_KERNEL[2][MCSAS_MODEL_COUNT] = {{MCSAS_FOR_MODELS(ROW_SETS)}, {MCSAS_FOR_MODELS(ROW_SETS_SHARED)}};
+static_assert(MCSAS_SETS_SCALE_PER_SET == 0 && MCSAS_SETS_SCALE_SHARED == 1, "SETS_KERNEL's rows");
 #undef DECL_SETS
 #undef ROW_SETS
+#undef ROW_SETS_SHARED
 
 static int run_sets(const mcsas_problem *p, const SetsLayout &L, const ModelArgs &margs, mcsas_result *res, mcsas_sets_result *sets) {
     DeviceGuard guard;
@@ -68,7 +73,7 @@ static int run_sets(const mcsas_problem *p, const SetsLayout &L, const ModelArgs
     a.rset = drset.p; a.cache = dcache.p; a.cache_rows = (int)cache_rows; a.fit = dfit.p; a.out = dout.p;
     sa.out = dsout.p;
 
-    void *const kernel = SETS_KERNEL[p->model_id](L.qpl, true);
+    void *const kernel = SETS_KERNEL[sa.scale_mode][p->model_id](L.qpl, true);
     if (L.lds_bytes > 64 * 1024) HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes));
     void *kargs[2] = {(void *)&a, (void *)&sa};
     HIPCHK(hipLaunchKernel(kernel, dim3((unsigned)R), dim3(WAVE), kargs, L.lds_bytes, nullptr));
@@ -113,11 +118,15 @@ static int run_sets(const mcsas_problem *p, const SetsLayout &L, const ModelArgs
     return MCSAS_OK;
 }
 
-extern "C" int mcsas_hip_analyse_sets(const mcsas_problem *p, int32_t n_sets, const int32_t *set_nq, mcsas_result *res,
-                                      mcsas_sets_result *sets) {
+extern "C" int mcsas_hip_analyse_sets_mode(const mcsas_problem *p, int32_t n_sets, const int32_t *set_nq, int32_t scale_mode, mcsas_result *res,
+                                           mcsas_sets_result *sets) {
     SetsLayout L;
     ModelArgs margs;
-    if (int rc = check_sets_request(p, n_sets, set_nq, res, sets, &L, &margs)) return rc;
-    if (!SETS_KERNEL[p->model_id](L.qpl, true)) return fail(MCSAS_EINVAL, "analyse_sets: no kernel for model %d qpl %d", p->model_id, L.qpl);
+    if (int rc = check_sets_request(p, n_sets, set_nq, res, sets, &L, &margs, scale_mode)) return rc;
+    if (!SETS_KERNEL[scale_mode][p->model_id](L.qpl, true)) return fail(MCSAS_EINVAL, "analyse_sets: no kernel for model %d qpl %d", p->model_id, L.qpl);
     return no_bad_alloc("analyse_sets", [&] { return run_sets(p, L, margs, res, sets); });
+}
+extern "C" int mcsas_hip_analyse_sets(const mcsas_problem *p, int32_t n_sets, const int32_t *set_nq, mcsas_result *res,
+                                      mcsas_sets_result *sets) {
+    return mcsas_hip_analyse_sets_mode(p, n_sets, set_nq, MCSAS_SETS_SCALE_PER_SET, res, sets);
 }

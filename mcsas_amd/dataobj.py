@@ -252,14 +252,22 @@ class DataSets(object):
     """Several measurements of ONE specimen — two detector distances, SAXS + WAXS, two instruments — for a joint fit: wraps the
     members' SASData objects.  With `algo.data = DataSets([d0, d1, ...])` McSAS.analyse() fits one population to all members at once,
     each with a least-squares scale and background of its own at every step (engine.analyse_sets; include/mcsas_hip.h:
-    mcsas_hip_analyse_sets); 1 to engine.MAX_SETS members of at least 3 points each.  The vectors the fit reads (`q`, `f.binnedData`,
-    `f.binnedDataU`, `x0`) are the members' one after the other, and `slices` says where each member lies in them.
-    `histogramSet` (default 0): the member histogram() and the partial / 2-D histograms run against.  They take the existing
-    single-set path with that member's data alone, whose scale fit is exactly the joint fit's for that member, so fractions are
-    consistent with it — and the visibility limits are those "as seen by that set": a size another member would see and this one
-    does not counts as invisible.  Smearing configurations of the members are not used (the joint fit refuses smearing)."""
+    mcsas_hip_analyse_sets_mode); 1 to engine.MAX_SETS members of at least 3 points each.  The vectors the fit reads (`q`,
+    `f.binnedData`, `f.binnedDataU`, `x0`) are the members' one after the other, and `slices` says where each member lies in them.
+    `sharedScale` (default False): the members are on an absolute scale — ONE least-squares scale for all of them, a background per
+    member, and so one volume fraction per contribution.  A known relative scale k_s between the members is the caller's: divide
+    that member's intensity and uncertainty by it before wrapping it here.
+    `histogramSet` (default 0): whose points judge what is visible in histogram() — a member's index or "all".  With an index and
+    sharedScale=False histogram() and the partial histograms take the existing single-set path with that member's data alone, whose
+    scale fit is exactly the joint fit's for that member, so fractions are consistent with it — and the visibility limits are those
+    "as seen by that set": a size another member would see and this one does not counts as invisible.  With "all" (or with
+    sharedScale=True) histogram() runs over the points of all members (engine.histogram_sets): every member is fitted to the summed
+    intensity as the joint fit does, a contribution is visible where ANY named member's points show it, and volume fractions are by
+    member `scaleSet`'s scale (default 0; with sharedScale the shared scale).  That path offers no partial intensities
+    (Histogram(partialIntensity=...) raises ValueError).  Smearing configurations of the members are not used (the joint fit refuses
+    smearing)."""
 
-    def __init__(self, members, histogramSet=0, title="data sets"):
+    def __init__(self, members, histogramSet=0, title="data sets", sharedScale=False, scaleSet=0):
         self.members = list(members)
         if not self.members:
             raise ValueError("DataSets: needs at least one SASData")
@@ -267,7 +275,16 @@ class DataSets(object):
             if not (hasattr(d, "x0") and hasattr(d, "f")) or d.f.binnedDataU is None:
                 raise ValueError("DataSets: every member is a SASData with q, intensity and sigma")
         self.title = title
-        self.histogramSet = int(histogramSet)
+        if isinstance(histogramSet, str):
+            if histogramSet != "all":
+                raise ValueError("DataSets.histogramSet %r: a member's index or \"all\"" % (histogramSet,))
+            self.histogramSet = "all"
+        else:
+            self.histogramSet = int(histogramSet)
+        self.sharedScale = bool(sharedScale)
+        self.scaleSet = int(scaleSet)
+        if not 0 <= self.scaleSet < len(self.members):
+            raise ValueError("DataSets.scaleSet %d: there are %d members" % (self.scaleSet, len(self.members)))
         self.x0 = DataVector("q", np.concatenate([d.x0.binnedData for d in self.members]))
         self.f = DataVector("I", np.concatenate([d.f.binnedData for d in self.members]),
                             np.concatenate([d.f.binnedDataU for d in self.members]))
@@ -278,7 +295,20 @@ class DataSets(object):
     def __len__(self):
         return len(self.members)
 
+    def jointHistogram(self):
+        """histogram() runs over the points of all members (engine.histogram_sets), not against one member alone"""
+        return self.sharedScale or self.histogramSet == "all"
+
+    def visibleSets(self):
+        """the members whose points judge what is visible"""
+        if self.histogramSet == "all":
+            return list(range(len(self.members)))
+        self.histogramMember()
+        return [self.histogramSet]
+
     def histogramMember(self):
+        if self.histogramSet == "all":
+            raise ValueError("DataSets.histogramSet \"all\": the histogram is judged by all members, not by one")
         if not 0 <= self.histogramSet < len(self.members):
             raise ValueError("DataSets.histogramSet %d: there are %d members" % (self.histogramSet, len(self.members)))
         return self.members[self.histogramSet]

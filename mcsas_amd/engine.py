@@ -322,21 +322,36 @@ class SetsResults(ChainResults):
         self.sets_c = s
 
 
-def analyse_sets(model: ModelSetup, sets, st: Settings, replay=None, stop=None) -> SetsResults:
-    """One population fitted to several data sets at once (mcsas_hip_analyse_sets, include/mcsas_hip.h): `sets` is a list of 1 to
-    MAX_SETS triples (q, I, sigma) of at least 3 points each — measurements of the same specimen whose relative scale and whose
-    backgrounds are not known.  Every chain holds one set of contributions and is judged by all sets: at every step each set gets its
-    own least-squares scale and background, and the chain minimises the reduced chi-squared over all points.  One wavefront per chain,
+def _sets_scale_mode(scale, who):
+    if not isinstance(scale, str) or scale not in _lib.SETS_SCALE:
+        raise ValueError("%s: scale %r ('per_set': a scale per set, 'shared': one scale for all sets)" % (who, scale))
+    return _lib.SETS_SCALE[scale]
+
+
+def _sets_triples(sets, who):
+    triples = [tuple(f64(v).ravel() for v in trip) for trip in sets]
+    if any(len(trip) != 3 for trip in triples):
+        raise ValueError("%s: sets is a list of (q, I, sigma)" % who)
+    for s, (q, i, e) in enumerate(triples):
+        if not (len(q) == len(i) == len(e)):
+            raise ValueError("%s: set %d: q, intensity and sigma must have the same length" % (who, s))
+    cat = [np.concatenate([trip[k] for trip in triples]) if triples else np.zeros(0) for k in range(3)]
+    return triples, cat
+
+
+def analyse_sets(model: ModelSetup, sets, st: Settings, replay=None, stop=None, scale="per_set") -> SetsResults:
+    """One population fitted to several data sets at once (mcsas_hip_analyse_sets_mode, include/mcsas_hip.h): `sets` is a list of 1 to
+    MAX_SETS triples (q, I, sigma) of at least 3 points each — measurements of the same specimen whose backgrounds are not known.
+    `scale`: "per_set" (curves whose relative scale is not known: every set gets its own least-squares scale and background at every
+    step) or "shared" (curves on an absolute scale: ONE least-squares scale for all sets, a background per set; set_scaling then
+    holds the same number for every set).  Every chain holds one set of contributions and is judged by all sets, and the chain
+    minimises the reduced chi-squared over all points.  One wavefront per chain,
     cached rows; together the sets, each padded to a multiple of 64 points, take at most 1024 entries.  Refused (ValueError here or
     MCSAS_EINVAL from the library, before a device is touched): positive_background, a device list, a model plug-in or a model that
     exists only as host code, no active parameter, cache_intensities == 0, an exec_mode other than EXEC_AUTO / EXEC_WAVE; there is
     no plan, batch, start, trace or smearing form."""
-    triples = [tuple(f64(v).ravel() for v in trip) for trip in sets]
-    if any(len(trip) != 3 for trip in triples):
-        raise ValueError("analyse_sets: sets is a list of (q, I, sigma)")
-    for s, (q, i, e) in enumerate(triples):
-        if not (len(q) == len(i) == len(e)):
-            raise ValueError("analyse_sets: set %d: q, intensity and sigma must have the same length" % s)
+    mode = _sets_scale_mode(scale, "analyse_sets")
+    triples, cat = _sets_triples(sets, "analyse_sets")
     if model.model_id == MODEL_HOST:
         raise ValueError("analyse_sets: a model that exists only as host code is not supported (built-in models only)")
     if model.model_id >= MODEL_PLUGIN0:
@@ -346,11 +361,10 @@ def analyse_sets(model: ModelSetup, sets, st: Settings, replay=None, stop=None) 
     if st.debug_flags:
         raise ValueError("analyse_sets: debug_flags select variants of the pipeline mode; the joint fit has none")
     lib = _lib.load()
-    cat = [np.concatenate([trip[k] for trip in triples]) if triples else np.zeros(0) for k in range(3)]
     prob = HipProblem(model, cat[0], cat[1], cat[2], st, replay, stop, None)
     res = SetsResults(st.n_contrib, model.n_active, st.n_reps, [len(trip[0]) for trip in triples])
-    check(lib.mcsas_hip_analyse_sets(C.byref(prob.c), len(triples), res.set_nq.ctypes.data_as(C.POINTER(C.c_int32)),
-                                     C.byref(res.c), C.byref(res.sets_c)), lib)
+    check(lib.mcsas_hip_analyse_sets_mode(C.byref(prob.c), len(triples), res.set_nq.ctypes.data_as(C.POINTER(C.c_int32)), mode,
+                                          C.byref(res.c), C.byref(res.sets_c)), lib)
     return res
 
 
@@ -789,6 +803,40 @@ def histogram_device(model: ModelSetup, q, intensity, sigma, contribs, comp_exp,
         check(lib.mcsas_hip_histogram_partial(C.byref(call.prob.c), as_dp(call.contribs), len(call.specs), call.arr, call.want_p(), as_dp(call.sc),
                                               as_dp(call.frac), as_dp(call.out), as_dp(call.partial)), lib)
     return call.unpack()
+
+
+def histogram_sets(model: ModelSetup, sets, contribs, comp_exp, specs, find_background=True, device=-1, scale="per_set", ref_set=0,
+                   visible=None):
+    """McSAS.histogram() of a joint fit (mcsas_hip_histogram_sets, include/mcsas_hip.h): histogram_device over the points of all
+    `sets` (analyse_sets' list of (q, I, sigma)).  Per repetition the summed intensity is fitted per set (`scale` "per_set") or with
+    one scale for all sets ("shared"); volume fractions are by set `ref_set`'s scale (the shared one in shared mode), and a
+    contribution's visibility limit is the lowest over the points of the sets in `visible` (indices; None: all sets), each point with
+    its own set's scale.  -> (scaling[2][R] of ref_set, fractions, histograms) as histogram_device, then set_scaling[S][R] and
+    set_background[S][R].  No partial intensities, smearing or positive background; built-in models only."""
+    mode = _sets_scale_mode(scale, "histogram_sets")
+    triples, cat = _sets_triples(sets, "histogram_sets")
+    S = len(triples)
+    vis = range(S) if visible is None else [int(v) for v in visible]
+    if any(v < 0 or v >= 32 for v in vis):
+        raise ValueError("histogram_sets: visible %r names a set that is not there (%d sets)" % (list(vis), S))
+    mask = 0
+    for v in vis:
+        mask |= 1 << v
+    if any(sp.get("partial") for sp in specs):
+        raise ValueError("histogram_sets: partial intensities are not offered for the histogram of a joint fit")
+    lib = _lib.load()
+    call = _HistogramCall(model, cat[0], cat[1], cat[2], contribs, comp_exp, specs, find_background, False, device, None)
+    R = call.contribs.shape[2]
+    set_nq = np.ascontiguousarray([len(t[0]) for t in triples], dtype=np.int32)
+    set_scaling, set_background = np.zeros((max(S, 1), R)), np.zeros((max(S, 1), R))
+    sr = _lib.SetsResult()
+    sr.struct_size = C.sizeof(_lib.SetsResult)
+    sr.n_sets = S
+    sr.scaling, sr.background, sr.chisq = as_dp(set_scaling), as_dp(set_background), None
+    check(lib.mcsas_hip_histogram_sets(C.byref(call.prob.c), as_dp(call.contribs), len(call.specs), call.arr, S,
+                                       set_nq.ctypes.data_as(C.POINTER(C.c_int32)), mode, int(ref_set), mask, as_dp(call.sc), as_dp(call.frac),
+                                       as_dp(call.out), C.byref(sr)), lib)
+    return call.unpack() + (set_scaling[:S], set_background[:S])
 
 
 class _HistogramCall:

@@ -238,7 +238,8 @@ class McSAS(object):
         """analyse() where `data` is a DataSets: one population fitted to all members at once, each with a scale and a background of
         its own (engine.analyse_sets).  result[0] keeps its keys, the q-indexed ones over the members one after the other (scaling and
         background: member 0's), and gains 'sets': per member a dict of `slice` (where it lies among the points), `scaling` and
-        `background` (mean, std over the repetitions) and `chisq` (per repetition: the sum over the member / its number of points).
+        `background` (mean, std over the repetitions) and `chisq` (per repetition: the sum over the member / its number of points),
+        and 'setsScale': "per_set", or "shared" where DataSets.sharedScale asks for one scale for all members.
         A start and a trace are refused, and so is everything engine.analyse_sets refuses."""
         if start is not None or trace is not None:
             raise ValueError("McSAS: the joint fit of a DataSets takes no %s" % ("start" if start is not None else "trace"))
@@ -249,10 +250,13 @@ class McSAS(object):
             raise ValueError("McSAS: the joint fit of a DataSets needs an active fit parameter")
         numReps = self.numReps()
         st = self._settings(self.numContribs(), numReps)
-        res = engine.analyse_sets(setup_from_model(model, data), data.triples(), st, replay=replay, stop=self._stop)
+        scale = "shared" if getattr(data, "sharedScale", False) else "per_set"
+        mode = dict(scale=scale) if scale != "per_set" else {}   # (the per-set call is what it was, argument for argument)
+        res = engine.analyse_sets(setup_from_model(model, data), data.triples(), st, replay=replay, stop=self._stop, **mode)
         self._store(res, numReps)
         if len(self.result):
             ddof = 1 if numReps > 1 else 0
+            self.result[0]['setsScale'] = scale
             self.result[0]['sets'] = [dict(slice=sl, scaling=(res.set_scaling[s].mean(), res.set_scaling[s].std(ddof=ddof)),
                                            background=(res.set_background[s].mean(), res.set_background[s].std(ddof=ddof)),
                                            chisq=res.set_chisq[s].copy()) for s, sl in enumerate(res.slices)]
@@ -309,10 +313,13 @@ class McSAS(object):
             times=res.seconds, numIter=res.num_iter.astype(float).mean()))
 
     def histogram(self, contribs=None):                      # mcsas.py:445-615
-        """With a DataSets as `data` everything below runs against ONE member, DataSets.histogramSet, through the single-set path:
-        its scale fit is the joint fit's for that member, and the visibility limits are those as seen by that set."""
+        """With a DataSets as `data`: histogramSet an index and sharedScale False — everything below runs against ONE member through
+        the single-set path: its scale fit is the joint fit's for that member, and the visibility limits are those as seen by that
+        set.  histogramSet "all" or sharedScale True — _histogram_sets: the points of all members in one device call."""
         if isinstance(self.data, DataSets):
             sets = self.data
+            if sets.jointHistogram():
+                return self._histogram_sets(contribs)
             self.data = sets.histogramMember()
             try:
                 return self.histogram(contribs)
@@ -393,6 +400,32 @@ class McSAS(object):
             self.positiveBackground.value(), device=self.device, smear=smear)
         self._histogram_tail(contribs, scalingFactors, vsets, wsets, ssets, mv)
         self._partial_on_host(contribs, setup, smear, self._partial_todo())
+
+    def _histogram_sets(self, contribs=None):
+        """histogram() over the points of all members of a DataSets (engine.histogram_sets): per repetition every member is fitted to
+        the summed intensity — a scale per member, or one for all with DataSets.sharedScale —, volume fractions are by member
+        scaleSet's scale (the shared one), and a contribution's visibility limit is the lowest any member named by histogramSet
+        gives it.  result[0]['scalingFactors'] is the reference pair.  Partial intensities and more than
+        engine.HISTOGRAM_MAX_CONTRIBS contributions are refused: there is no single-member path to fall back to."""
+        if not isinstance(self.result, list) or not len(self.result):
+            logging.info("There are no results to histogram, breaking up.")
+            return
+        if contribs is None:
+            contribs = self.result[0]['contribs']
+        if not all(np.array(contribs.shape, dtype=bool)):
+            return
+        sets, model = self.data, self.model
+        if self._partial_todo():
+            raise ValueError("McSAS.histogram: Histogram(partialIntensity=...) is not offered where a DataSets is histogrammed over all "
+                             "members (histogramSet=\"all\" or sharedScale=True); use histogramSet=<index> with sharedScale=False")
+        if contribs.shape[0] > engine.HISTOGRAM_MAX_CONTRIBS:
+            raise ValueError("McSAS.histogram: %d contributions; the histogram of a DataSets over all members takes at most %d"
+                             % (contribs.shape[0], engine.HISTOGRAM_MAX_CONTRIBS))
+        out = engine.histogram_sets(setup_from_model(model, sets), sets.triples(), contribs, self.compensationExponent(),
+                                    [h.deviceSpec(pi) for pi, h in self._histogram_todo()], find_background=self.findBackground.value(),
+                                    device=self.device, scale="shared" if sets.sharedScale else "per_set", ref_set=sets.scaleSet,
+                                    visible=sets.visibleSets())
+        self._histogram_from_device(out[:3], contribs)
 
     def _histogram_todo(self):
         return [(pi, h) for pi, param in enumerate(self.model.activeParams()) for h in param.histograms()]
