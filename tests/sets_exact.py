@@ -110,10 +110,112 @@ def population_sets(tag, nqs, scales, backgrounds, seed, lo=None, hi=None, **fix
     return sets
 
 
+# ------------------------------------------------------------------------------------------------ the instance matrix and the chain text's edges
+# chain_sets_kernel<M, QPL, SHARED> exists for 8 built-in models x 5 slot counts x 2 scale modes; one generated input per (model, QPL),
+# seen by both modes (tests/sets_shared_exact.py builds the shared twin from the same recipe), and a family of inputs at the edges of the
+# chain text.  The shapes are the smallest that still select the instance and use its last slot.
+MATRIX_MODELS = ("sphere", "cyl_aspect", "ellcs", "kholodenko", "elliso", "sphcs", "gausschain", "lmasphere")
+MATRIX_SHAPES = {
+    1: (50,),                      # S = 1
+    2: (30, 64),                   # slots 1 + 1: a set of exactly 64 points
+    4: (37, 100),                  # slots 1 + 2 of 4: one slot is all padding
+    8: (65, 3, 128, 70),           # slots 2 + 1 + 2 + 2 = 7 of 8: a 3-point set, a set that ends on a slot edge
+    16: (300, 64, 385, 129),       # slots 5 + 1 + 7 + 3 = 16: bit 15 of end_mask, no padding slot
+}
+# Kholodenko's oracle row is a QUADPACK integral per point: 12 slots (1 + 2 + 3 + 6, 524 real points) still select the 16-slot instance
+KHOLODENKO_16 = (3, 70, 130, 321)
+INT_DIV = {"cyl_aspect": 12, "ellcs": 12, "elliso": 12}          # (the models that have an orientation integral)
+# GaussianChain over chain_cases.RANGES (rg and bp both 1e-9 .. 1e-7) makes proposals that change nothing visible at these q: margins of
+# 3.6e-10 to 1.8e-8.  rg from 1e-8 on keeps q rg >= 0.1 at every point, bp within a factor 10 keeps every contribution visible.
+GAUSSCHAIN_RANGE = ([1e-8, 1e-8], [1e-7, 1e-7])
+PER_SET_SCALES = (2e3, 2e6, 2e1, 4e8)                          # every pair a factor >= 100 apart
+SHARED_SCALE = 2e4
+BACKGROUNDS = (0.5, 90., 0., 7.)
+# the replay seed of a generated input where the default (1) gives the restatement fewer than 5 moves in its short Kholodenko chain or
+# takes it below chi² = 1 (where the Kholodenko margin's derivation ends): (name, shared) -> seed, chosen on the CPU from the
+# restatement alone (tests/test_sets_host.py, tests/test_sets_shared_host.py print every margin)
+GENERATED_SEED = {("mx_kholodenko_q2", False): 6, ("mx_kholodenko_q2", True): 3, ("mx_kholodenko_q8", False): 2,
+                  ("mx_kholodenko_q16", False): 2}
+
+
+def matrix_name(tag, qpl):
+    return "mx_%s_q%d" % (tag, qpl)
+
+
+def matrix_shape(tag, qpl):
+    return KHOLODENKO_16 if (tag, qpl) == ("kholodenko", 16) else MATRIX_SHAPES[qpl]
+
+
+def model_range(tag):
+    from chain_cases import RANGES
+    lo, hi = GAUSSCHAIN_RANGE if tag == "gausschain" else RANGES[tag]
+    return list(lo), list(hi), ({"intDiv": INT_DIV[tag]} if tag in INT_DIV else {})
+
+
+MATRIX = tuple(matrix_name(tag, qpl) for tag in MATRIX_MODELS for qpl in sorted(MATRIX_SHAPES))
+EDGE_COUNTS = (1, 64, 65, 128)      # N == 1 skips the Monte-Carlo loop, 64 fills the initial wave exactly, 65 and 128 are the neighbours
+# name -> (model, set_nq, what differs from the matrix's chain)
+EDGES = {}
+for _tag, _nqs in (("sphere", MATRIX_SHAPES[4]), ("sphcs", MATRIX_SHAPES[2])):
+    for _n in EDGE_COUNTS:
+        EDGES["ed_%s_n%d" % (_tag, _n)] = (_tag, _nqs, dict(n_contrib=_n))
+    EDGES["ed_%s_min" % _tag] = (_tag, _nqs, dict(start_from_min=True))             # (both lower bounds are non-zero)
+EDGES["ed_sphcs_gen12"] = ("sphcs", MATRIX_SHAPES[2], dict(gen=(1, 2)))
+EDGES["ed_sphcs_gen30"] = ("sphcs", MATRIX_SHAPES[2], dict(gen=(3, 0)))
+EDGES["ed_ellcs_nobg"] = ("ellcs", MATRIX_SHAPES[2], dict(find_bg=False))           # three active parameters
+GENERATED = MATRIX + tuple(EDGES)
+
+
+def generated_shape(name):
+    """-> (model, set_nq, the slot count QPL of the instance the input is to select) of a generated input, without building it"""
+    if name in EDGES:
+        tag, nqs, _ = EDGES[name]
+        return tag, nqs, {v: k for k, v in MATRIX_SHAPES.items()}[nqs]
+    if name not in MATRIX:
+        raise KeyError(name)
+    tag, qpl = name[3:].rsplit("_q", 1)
+    return tag, matrix_shape(tag, int(qpl)), int(qpl)
+
+
+def generated_case(name, shared):
+    """The generated input `name` for one scale mode -> case()'s dict plus set_nq, qpl, gen.  Per set: scales a factor >= 100 apart;
+    shared: equal scales; both: different backgrounds.  12 contributions and 80 steps (Kholodenko: 8 and 60, at 16 slots 8 and 40, to
+    keep its QUADPACK reference under 10 s), criterion 1e-12, no retry."""
+    from helpers import make_models
+    kw = dict(n_contrib=12, n_reps=1, max_iter=80, conv_crit=1e-12, max_retries=0)
+    tag, nqs, qpl = generated_shape(name)
+    gen = None
+    if name in EDGES:
+        diff = dict(EDGES[name][2])
+        gen = diff.pop("gen", None)
+        kw.update(diff)
+    elif tag == "kholodenko":
+        kw.update(n_contrib=8, max_iter=40 if qpl == 16 else 60)
+    lo, hi, fixed = model_range(tag)
+    S = len(nqs)
+    scales = (SHARED_SCALE,) * S if shared else PER_SET_SCALES[:S]
+    pop_seed = 300 + sum(map(ord, name)) % 97 + (50 if shared else 0)
+    sets = population_sets(tag, nqs, scales, BACKGROUNDS[:S], pop_seed, lo, hi, **fixed)
+    _, spec = make_models(tag, lo, hi, gen, **fixed)
+    st = O.Settings(comp_exp=0.6666666, **kw)
+    ndraw = (st.n_contrib + st.max_iter) * spec.n_active + 8
+    seed = GENERATED_SEED.get((name, shared), 1)
+    replay = np.random.RandomState(3000 + 1000 * seed + (500 if shared else 0) + sum(map(ord, name))).uniform(size=(1, ndraw))
+    return dict(tag=tag, lo=lo, hi=hi, fixed=fixed, gen=gen, sets=sets, st=st, replay=replay, set_nq=tuple(nqs), qpl=qpl)
+
+
+def case_models(c):
+    """-> (product model, oracle spec) of a case() dict"""
+    from helpers import make_models
+    return make_models(c["tag"], c["lo"], c["hi"], c.get("gen"), **c["fixed"])
+
+
 @functools.lru_cache(maxsize=None)
 def case(name):
     """-> dict(tag, lo, hi, fixed, sets, st (O.Settings), replay [R][len]) of the named input."""
     from helpers import make_models
+    if name in GENERATED:
+        return generated_case(name, shared=False)
     tag, lo, hi, fixed = "sphere", [LO], [HI], {}
     kw = dict(n_contrib=20, n_reps=1, max_iter=300, conv_crit=1e-12, max_retries=0)
     if name.startswith("s1_"):                              # one set of 65 points: two slots, one nearly empty
@@ -156,15 +258,14 @@ def case(name):
     return dict(tag=tag, lo=lo, hi=hi, fixed=fixed, sets=sets, st=st, replay=replay)
 
 
-REPLAYED = ("s1_n5_bg", "s1_n5_nobg", "s1_n70_bg", "s1_n70_nobg", "b2", "b4", "cyl", "end_crit", "end_retry", "end_odd")
+REPLAYED = ("s1_n5_bg", "s1_n5_nobg", "s1_n70_bg", "s1_n70_nobg", "b2", "b4", "cyl", "end_crit", "end_retry", "end_odd") + GENERATED
 
 
 @functools.lru_cache(maxsize=None)
 def reference(name):
     """The restatement's result on case(name), computed once."""
-    from helpers import make_models
     c = case(name)
-    _, spec = make_models(c["tag"], c["lo"], c["hi"], **c["fixed"])
+    _, spec = case_models(c)
     return sets_analyse(spec, c["sets"], c["st"], O.ReplayStream(c["replay"][0]))
 
 

@@ -72,7 +72,8 @@ def sets_analyse(spec, sets, st, stream):
 
 # the replay seeds, chosen on the CPU so that the restatement alone keeps |X_t - X| / X >= 1e-9 at every step (tests/test_sets_shared_host.py)
 REPLAY_SEED = dict(sh2=1, sh4=1, sh_cyl=1, sh_nobg=1, sh_end_odd=1, sh_end_retry=3)
-REPLAYED = tuple(REPLAY_SEED)
+# ... and the shared twins of sets_exact's generated inputs (the instance matrix, the chain text's edges): the same names
+REPLAYED = tuple(REPLAY_SEED) + SX.GENERATED
 
 
 @functools.lru_cache(maxsize=None)
@@ -80,6 +81,8 @@ def case(name):
     """-> dict(tag, lo, hi, fixed, sets, st (O.Settings), replay [1][len]) of the named input: one population seen through EQUAL scales
     and different backgrounds (sets_exact.population_sets)."""
     from helpers import make_models
+    if name in SX.GENERATED:
+        return SX.generated_case(name, shared=True)
     tag, lo, hi, fixed = "sphere", [SX.LO], [SX.HI], {}
     kw = dict(n_contrib=20, n_reps=1, max_iter=300, conv_crit=1e-12, max_retries=0)
     if name == "sh4":                                       # slots 1 + 1 + 1 + 3 of 8
@@ -118,9 +121,8 @@ def case(name):
 @functools.lru_cache(maxsize=None)
 def reference(name):
     """The shared restatement's result on case(name), computed once."""
-    from helpers import make_models
     c = case(name)
-    _, spec = make_models(c["tag"], c["lo"], c["hi"], **c["fixed"])
+    _, spec = SX.case_models(c)
     return sets_analyse(spec, c["sets"], c["st"], O.ReplayStream(c["replay"][0]))
 
 

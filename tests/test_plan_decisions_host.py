@@ -124,6 +124,24 @@ def sets_layouts(check):
         assert kind == "error" and int(code) == -1 and msg.startswith("analyse_sets:") and all(w in msg for w in words), (nqs, msg)
 
 
+def generated_sets_layouts(check):
+    """Every generated input of the joint fit's GPU tests (sets_exact.GENERATED: the instance matrix, the chain text's edges) selects
+    the slot count its name says, uses that instance's last slot, and ends its last set there or one slot before a padding slot."""
+    import sets_exact as SX
+    shapes = {name: SX.generated_shape(name) for name in SX.GENERATED}
+    assert sorted({(tag, qpl) for tag, _, qpl in (shapes[n] for n in SX.MATRIX)}) == sorted((t, q) for t in SX.MATRIX_MODELS for q in (1, 2, 4, 8, 16))
+    lines = ["%s %d %d %s\n" % (name, sum(nqs), len(nqs), " ".join(map(str, nqs))) for name, (_, nqs, _) in shapes.items()]
+    out = dict(line.split(" ", 1) for line in check("sets", text="".join(lines)).splitlines())
+    assert len(out) == len(lines)
+    for name, (tag, nqs, qpl) in shapes.items():
+        kind, total, got_qpl, got_mask, *per_set = out[name].split()
+        print(name, nqs, "slots", total, "qpl", got_qpl, "end_mask", got_mask)
+        assert kind == "layout" and int(got_qpl) == qpl and qpl // 2 < int(total) <= qpl, (name, out[name])
+        assert bin(int(got_mask, 16)).count("1") == len(nqs) and int(got_mask, 16) >> (int(total) - 1) == 1, (name, got_mask)
+    full = out[SX.matrix_name("sphere", 16)].split()
+    assert (int(full[1]), int(full[3], 16) >> 15) == (16, 1)                  # bit 15 of end_mask, no padding slot
+
+
 def sets_refusals(check):
     """Every row of test_sets_host.REFUSALS through the function that makes them, in the stand-alone program: the same words."""
     from test_sets_host import REFUSALS, _request
@@ -150,6 +168,7 @@ def test_plan_decisions_without_a_device(tmp_path):
     # vectors and constants of (37, 100) points in two sets, and of 65 in one against the single-set sums
     assert check().strip() == "ok"
     sets_layouts(check)
+    generated_sets_layouts(check)
     sets_refusals(check)
     recorded_plan_shapes(check)
     free_memory_gate(check)

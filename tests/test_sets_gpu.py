@@ -9,6 +9,7 @@ import pytest
 import mcsas_amd
 from mcsas_amd import engine
 from helpers import make_models
+import sets_checks
 import sets_exact as SX
 
 pytestmark = pytest.mark.gpu
@@ -16,25 +17,11 @@ pytestmark = pytest.mark.gpu
 
 def _run(name, **st_kw):
     c = SX.case(name)
-    m, _ = make_models(c["tag"], c["lo"], c["hi"], **c["fixed"])
-    ost = c["st"]
-    st = engine.Settings(n_contrib=ost.n_contrib, n_reps=1, max_iter=ost.max_iter, comp_exp=ost.comp_exp, conv_crit=ost.conv_crit,
-                         find_background=ost.find_bg, max_retries=ost.max_retries, device=0, **st_kw)
-    return c, m, st, engine.analyse_sets(m.setup(), c["sets"], st, replay=c["replay"])
+    return (c,) + sets_checks.run_case(c, **st_kw)
 
 
 def _check(name, res, ref):
-    got = (res.num_iter[0], res.num_moves[0], res.draws[0], res.attempts[0])
-    print(name, "iter, moves, draws, attempts =", got, "restatement", (ref.num_iter, ref.num_moves, ref.draws, ref.attempts),
-          "chi2", res.chisq[0], ref.conval, "per set", res.set_chisq[:, 0], ref.set_chisq)
-    assert got == (ref.num_iter, ref.num_moves, ref.draws, ref.attempts)
-    np.testing.assert_allclose(res.contribs[:, :, 0], ref.rset, rtol=1e-12)
-    np.testing.assert_allclose(res.chisq[0], ref.conval, rtol=1e-9)
-    np.testing.assert_allclose(res.set_chisq[:, 0], ref.set_chisq, rtol=1e-9)
-    np.testing.assert_allclose(res.set_scaling[:, 0], ref.set_scaling, rtol=1e-9)
-    np.testing.assert_allclose(res.set_background[:, 0], ref.set_background, rtol=1e-9, atol=1e-300)
-    np.testing.assert_allclose(res.fit[:, 0], ref.fit, rtol=1e-9)
-    assert res.scaling[0] == res.set_scaling[0, 0] and res.background[0] == res.set_background[0, 0]
+    sets_checks.check(name, res, ref)                        # (rtol 1e-9)
 
 
 @pytest.mark.parametrize("name", ["s1_n5_bg", "s1_n5_nobg", "s1_n70_bg", "s1_n70_nobg"])

@@ -38,13 +38,60 @@ def test_with_one_set_the_restatement_is_the_oracles_chain(name):
     np.testing.assert_allclose(got.fit, ref.fit, rtol=1e-9)
 
 
+# Kholodenko's device row follows the oracle's QUADPACK integral only to 2e-8 relatively (test_kholodenko_active_ranges_vs_quadpack_500_sets),
+# not to float64 rounding as every other model's row (test_model_calc_vs_reference_vectors).  The inputs carry 1 % uncertainties: a
+# relative row error eps moves every residual (I - fit) / sigma by at most eps / 0.01, so X = sum of their squares by at most about
+# 2 (eps / 0.01) sqrt(X Q) absolutely, 2 (eps / 0.01) / sqrt(chi²) relatively: 4e-6 at chi² >= 1.  A margin of 1e-5 lies above that,
+# as long as the chain stays at chi² >= 1, which is asserted.
+KHOLODENKO_MARGIN = 1e-5
+
+
+def check_margin(name, c, ref):
+    """What the GPU comparisons rest on, of a replayed input and the restatement's chain on it (also tests/test_sets_shared_host.py's)."""
+    print(name, "min margin %.3e" % ref.min_margin, "steps", ref.num_iter, "moves", ref.num_moves, "attempts", ref.attempts)
+    if c["st"].n_contrib == 1:                                                # the Monte-Carlo loop is skipped
+        P = len(c["lo"])
+        assert (ref.num_iter, ref.num_moves, ref.draws, ref.attempts) == (0, 0, P, 1) and ref.rset.shape == (1, P)
+        return
+    assert ref.num_moves >= 5
+    if c["tag"] == "kholodenko":
+        lowest = min([chi2 for _, chi2 in ref.trajectory] + [ref.conval])
+        print(name, "lowest chi2", lowest)
+        assert ref.min_margin >= KHOLODENKO_MARGIN and lowest >= 1.0
+    else:
+        assert ref.min_margin >= MARGIN
+
+
 @pytest.mark.parametrize("name", SX.REPLAYED)
 def test_no_decision_of_the_gpu_tests_inputs_is_a_near_tie(name):
-    """|X_t - X| / X >= 1e-9 at every step of every replayed input of tests/test_sets_gpu.py: then "the device takes the
-    restatement's decisions" is a fair demand, and inputs changed later cannot quietly make it an unfair one."""
-    ref = SX.reference(name)
-    print(name, "min margin %.3e" % ref.min_margin, "steps", ref.num_iter, "moves", ref.num_moves, "attempts", ref.attempts)
-    assert ref.min_margin >= MARGIN and ref.num_moves >= 5
+    """|X_t - X| / X >= 1e-9 at every step of every replayed input of tests/test_sets_gpu.py and tests/test_sets_matrix_gpu.py (1e-5 for
+    Kholodenko): then "the device takes the restatement's decisions" is a fair demand, and inputs changed later cannot quietly make
+    it an unfair one."""
+    check_margin(name, SX.case(name), SX.reference(name))
+
+
+def test_the_generated_inputs_are_what_their_names_say():
+    """One input per (model, slot count); per-set scales a factor >= 100 apart, different backgrounds, intDiv <= 12; the edges' settings."""
+    assert len(SX.MATRIX) == 40 and len(set(SX.GENERATED)) == len(SX.GENERATED) == 53
+    for name in SX.GENERATED:
+        c = SX.case(name)
+        tag, nqs, qpl = SX.generated_shape(name)
+        assert tuple(len(s[0]) for s in c["sets"]) == nqs == c["set_nq"] and c["qpl"] == qpl
+        assert sum(-(-n // 64) for n in nqs) in range(qpl // 2 + 1, qpl + 1)
+        assert all(v <= 12 for k, v in c["fixed"].items() if k == "intDiv") and (tag in SX.INT_DIV) == ("intDiv" in c["fixed"])
+        assert 8 <= c["st"].n_contrib <= 12 or name in SX.EDGES
+        assert c["st"].conv_crit == 1e-12 and c["st"].max_retries == 0 and 40 <= c["st"].max_iter <= 80
+    scales = SX.PER_SET_SCALES
+    assert all(max(a, b) / min(a, b) >= 100. for i, a in enumerate(scales) for b in scales[i + 1:]) and len(set(SX.BACKGROUNDS)) == 4
+    assert sorted(SX.case("ed_%s_n%d" % (t, n))["st"].n_contrib for t in ("sphere", "sphcs") for n in SX.EDGE_COUNTS) == sorted(2 * SX.EDGE_COUNTS)
+    for t in ("sphere", "sphcs"):
+        c = SX.case("ed_%s_min" % t)
+        assert c["st"].start_from_min and min(c["lo"]) > 0
+        ref = SX.reference("ed_%s_min" % t)
+        assert ref.draws == len(c["lo"]) * ref.num_iter                      # the initial set costs no draws
+    assert SX.case("ed_sphcs_gen12")["gen"] == (1, 2) and SX.case("ed_sphcs_gen30")["gen"] == (3, 0)
+    c = SX.case("ed_ellcs_nobg")
+    assert not c["st"].find_bg and len(c["lo"]) == 3 and (SX.reference("ed_ellcs_nobg").set_background == 0.).all()
 
 
 def test_the_inputs_end_where_their_tests_say():

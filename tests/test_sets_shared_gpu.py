@@ -29,7 +29,7 @@ def _run(c, scale):
     return engine.analyse_sets(m.setup(), c["sets"], _settings(c), replay=c["replay"], scale=scale)
 
 
-@pytest.mark.parametrize("name", SH.REPLAYED)
+@pytest.mark.parametrize("name", tuple(SH.REPLAY_SEED))          # (the generated inputs: tests/test_sets_matrix_gpu.py)
 def test_against_the_restatement(name):
     """(37, 100) points: slots 1 + 2 of 4; (64, 3, 63, 130): 1 + 1 + 1 + 3 of 8; a row with an integral; no background; max_iter not a
     multiple of 64; a repetition that needs a further attempt."""

@@ -29,8 +29,11 @@ def test_no_decision_of_the_gpu_tests_inputs_is_a_near_tie(name):
     below that, cannot turn a decision of the restatement."""
     ref = SH.reference(name)
     print(name, "steps", ref.num_iter, "moves", ref.num_moves, "attempts", ref.attempts, "smallest margin %.3g" % ref.min_margin)
+    if name in SX.GENERATED:                                 # >= 5 moves; Kholodenko: 1e-5 at chi² >= 1 (test_sets_host.KHOLODENKO_MARGIN)
+        from test_sets_host import check_margin
+        check_margin(name, SH.case(name), ref)
     assert ref.min_margin >= 1e-9
-    assert ref.num_moves > 3
+    assert ref.num_moves > 3 or SH.case(name)["st"].n_contrib == 1
     assert len(set(ref.set_scaling)) == 1                    # one scale
 
 
