@@ -123,7 +123,8 @@ TuneWord tune_word(const mcsas_problem *p) {
     // proposal's `new` row stored and row slots swapped on acceptance (no lazy re-evaluation of stale rows), 17 all eight producer waves
     // on a sub-window's Gram MFMAs and no row beside them (pipe_gram.h: no matrix / row roles; read by the kernel), 18 the overlapped
     // producer (Gram MFMAs of sub-window s between the rows of s + 1, operands from HBM/L2), 19-20 row shares of a SIMD's two
-    // producer waves, 7 XCD-aware block map; bits 0-6 switch stages OFF and give invalid results
+    // producer waves, 21 matrix / row roles in EVERY sub-window's Gram phase, a block's last one included (pipe_prod.h; read by the kernel),
+    // 7 XCD-aware block map; bits 0-6 switch stages OFF and give invalid results
     t.rpw = (p->reserved0 >> 8) & 15; t.sub = (p->reserved0 >> 12) & 15; t.gram_global = (p->reserved0 >> 18) & 1; t.eager = (p->reserved0 >> 16) & 1;
 #else
     (void)p;

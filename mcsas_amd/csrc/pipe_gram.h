@@ -53,7 +53,10 @@ __device__ __forceinline__ void pipe_gram_store(int tsel, int idx, double sum, i
 // call takes it.  The operands of the next 8 q are requested in front of the MFMAs of the current ones (pinned by the scheduling
 // barrier): one wave has to cover its own LDS latency — the partner wave of its SIMD, which used to, is not in here — and the
 // MFMAs of the two slices alternate, four independent accumulator chains.
-template <int QPL, int T, bool PACK, int R0, int RN, int NS>
+// FULL: every row an operand is read from is a valid row of the sub-window (nvalid == W and the row groups end at W: every
+// window but a run's last) — no clamp of the row and no select per operand (two v_cndmask per double, three operands, every
+// step); the values that reach the MFMAs are the ones the masked form lets through, so the bits are the same.
+template <int QPL, int T, bool PACK, int R0, int RN, int NS, bool FULL>
 __device__ __forceinline__ void pipe_gram_mfma_lds(const double *drows, int dstr, int nvalid, const double *lw, int gw, v4f64 (&acc)[NS][RN]) {
     const int lane = threadIdx.x & 63;
     const int m = lane & 15, kk = lane >> 4;
@@ -73,7 +76,7 @@ __device__ __forceinline__ void pipe_gram_mfma_lds(const double *drows, int dstr
 #pragma unroll
     for (int gi = 0; gi < NL; ++gi) {
         const int rr = PACK ? (gi == 0 ? m : gi == 1 ? 8 + m : (m < 8 ? m : m + 8)) : 16 * gi + m;
-        rowok[gi] = rr < nvalid;
+        rowok[gi] = FULL || rr < nvalid;
         rowp[gi] = drows + (size_t)(rowok[gi] ? rr : 0) * dstr + qs;
     }
     auto fetch = [&](int sp, v2f64 (&x)[NS][NL], v2f64 (&wv)[NS]) {
@@ -96,7 +99,8 @@ __device__ __forceinline__ void pipe_gram_mfma_lds(const double *drows, int dstr
         for (int s = 0; s < NS; ++s)
 #pragma unroll
             for (int gi = 0; gi < NL; ++gi) {
-                av[s][gi] = rowok[gi] ? cur[s][gi] : (v2f64){0., 0.};
+                if constexpr (FULL) av[s][gi] = cur[s][gi];
+                else av[s][gi] = rowok[gi] ? cur[s][gi] : (v2f64){0., 0.};
                 bv[s][gi] = av[s][gi] * cw[s];
             }
         if constexpr (PACK) {
@@ -148,39 +152,48 @@ __device__ __forceinline__ void pipe_gram_store_pack(int tsel, int idx, double s
     }
 }
 
-// Roles (`split`, the release path): only the MATRIX waves 0-3 — one per SIMD, the older of each pair, whose few operand
-// multiplies win the vector arbitration — issue the MFMAs: wave v takes the two q slices that waves v and v + 4 take with
-// eight Gram waves, each in an accumulator set of its own, in the same order, to the same partial slots v and v + 4 of gred;
-// the sum over the eight partials and the store are unchanged, so the block comes out bit for bit the same.  The matrix pipe
-// of a SIMD sees the same MFMAs either way; its vector pipe is free for the ROW waves 4-7, which come here late (pipe_prod.h:
-// from a row of the next sub-window, evaluated beside the first MFMAs), issue none, and call `behind()` once the barrier
-// behind the LAST operand read is passed.  !split (a tuning build's bit 17): eight Gram waves, nobody calls it.
+// a matrix wave's share of a round: the partial tiles of its NS slices, wave and (NS = 2) wave + 4, into their slots of gred
+template <int QPL, int T, bool PACK, int R0, int RN, int NS, bool FULL>
+__device__ __forceinline__ void pipe_gram_partials(const double *drows, int dstr, int nvalid, const double *lw, double *gred, int wave) {
+    const int lane = threadIdx.x & 63;
+    constexpr int TPR = PIPE_GRAM_TILES_PER_ROUND;
+    v4f64 acc[NS][RN];
+    pipe_gram_mfma_lds<QPL, T, PACK, R0, RN, NS, FULL>(drows, dstr, nvalid, lw, wave, acc);
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int u = 0; u < RN; ++u)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) gred[((size_t)((wave + s * (PIPE_WAVES / 2)) * TPR + u) * 4 + r) * 64 + lane] = acc[s][u][r];
+}
+
+// Roles (`split`: a sub-window whose successor in the block lends the row waves a row, pipe_prod.h): only the MATRIX waves 0-3 —
+// one per SIMD, the older of each pair, whose few operand multiplies win the vector arbitration — issue the MFMAs: wave v takes
+// the two q slices that waves v and v + 4 take with eight Gram waves, each in an accumulator set of its own, in the same order,
+// to the same partial slots v and v + 4 of gred; the sum over the eight partials and the store are unchanged, so the block comes
+// out bit for bit the same.  The matrix pipe of a SIMD sees the same MFMAs either way; its vector pipe is free for the ROW waves
+// 4-7, which come here late (from a row of the next sub-window, evaluated beside the first MFMAs), issue none, and call
+// `behind()` once the barrier behind the LAST operand read is passed.  !split (a block's last or only sub-window — no row to
+// hold, and a lone matrix wave's operand work would only lengthen the phase —; a tuning build's bit 17: everywhere): eight Gram
+// waves with one slice each, a SIMD's partner wave hides a wave's operand latency, nobody calls `behind()`.
+// `full` (uniform in the block): the unmasked operand reads, see pipe_gram_mfma_lds.
 // A sub-window of more than PIPE_GRAM_TILES_PER_ROUND tiles takes several rounds of the reduction buffer: the MFMAs of a round's
 // tiles are issued in front of that round (a tile's accumulators — two sets on a matrix wave — live for one round only: the
 // operands are read again from LDS, a tile's MFMAs are issued once).
 // Barriers: every wave passes 2 * ceil(NT / TPR) - 1 of them, whatever its role: one per round, one between two rounds.
 template <int QPL, int T, bool PACK, int R0, class Behind>
 __device__ __forceinline__ void pipe_gram_round(const double *drows, int dstr, int W, int nvalid, const double *lw, double *gred,
-                                                MCSAS_GLOBAL double *gout, MCSAS_GLOBAL double *scal_sub, bool split, bool matrix, Behind &&behind) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+                                                MCSAS_GLOBAL double *gout, MCSAS_GLOBAL double *scal_sub, bool split, bool full, bool matrix, Behind &&behind) {
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int NT = PACK ? 2 : T * (T + 1) / 2;
     constexpr int TPR = PIPE_GRAM_TILES_PER_ROUND, RN = NT - R0 < TPR ? NT - R0 : TPR;
-    constexpr int MW = PIPE_WAVES / 2;                        // matrix waves
     if (matrix) {
-        auto park = [&](int slot, const v4f64 (&acc)[RN]) {   // a slice's partial tiles -> its slots of the reduction buffer
-#pragma unroll
-            for (int u = 0; u < RN; ++u)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) gred[((size_t)(slot * TPR + u) * 4 + r) * 64 + lane] = acc[u][r];
-        };
         if (split) {
-            v4f64 acc[2][RN];
-            pipe_gram_mfma_lds<QPL, T, PACK, R0, RN, 2>(drows, dstr, nvalid, lw, wave, acc);
-            park(wave, acc[0]); park(wave + MW, acc[1]);
+            if (full) pipe_gram_partials<QPL, T, PACK, R0, RN, 2, true>(drows, dstr, nvalid, lw, gred, wave);
+            else pipe_gram_partials<QPL, T, PACK, R0, RN, 2, false>(drows, dstr, nvalid, lw, gred, wave);
         } else {
-            v4f64 acc[1][RN];
-            pipe_gram_mfma_lds<QPL, T, PACK, R0, RN, 1>(drows, dstr, nvalid, lw, wave, acc);
-            park(wave, acc[0]);
+            if (full) pipe_gram_partials<QPL, T, PACK, R0, RN, 1, true>(drows, dstr, nvalid, lw, gred, wave);
+            else pipe_gram_partials<QPL, T, PACK, R0, RN, 1, false>(drows, dstr, nvalid, lw, gred, wave);
         }
     }
     PIPE_LDS_BARRIER();
@@ -198,7 +211,7 @@ __device__ __forceinline__ void pipe_gram_round(const double *drows, int dstr, i
     }
     if constexpr (R0 + TPR < NT) {
         PIPE_LDS_BARRIER();
-        pipe_gram_round<QPL, T, PACK, R0 + TPR>(drows, dstr, W, nvalid, lw, gred, gout, scal_sub, split, matrix, behind);
+        pipe_gram_round<QPL, T, PACK, R0 + TPR>(drows, dstr, W, nvalid, lw, gred, gout, scal_sub, split, full, matrix, behind);
     }
 }
 
@@ -208,7 +221,9 @@ __device__ __forceinline__ void pipe_prod_gram_lds_t(const double *drows, int ds
                                                      bool split, Behind &&behind) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool matrix = !split || wave < PIPE_WAVES / 2;      // uniform in the wave
-    pipe_gram_round<QPL, T, PACK, 0>(drows, dstr, W, nvalid, lw, gred, gout, scal_sub, split, matrix, behind);
+    // (the row groups of a sub-window of 8 rows reach past it — rows the LDS buffer does not hold —: masked whatever nvalid is)
+    const bool full = nvalid == W && (PACK || W == 16 * T);   // uniform in the block
+    pipe_gram_round<QPL, T, PACK, 0>(drows, dstr, W, nvalid, lw, gred, gout, scal_sub, split, full, matrix, behind);
 }
 
 // (a sub-window of T 16-row groups has at least 2 T - 1 rows per wave: the QPL whose row registers that exceeds never see it,

@@ -216,8 +216,8 @@ __device__ __forceinline__ void pipe_prod_block(const PipeArgs &pa, const PipeHo
         };
         if (pa.g.gram_lds) {
             // ---- default: sub-window by sub-window — the waves evaluate the sub-window's rows (d also into the LDS row
-            // buffer), barrier, waves 0-3 take the Gram block from LDS while waves 4-7 start on the next sub-window's rows (below),
-            // next sub-window.  Only the LDS traffic is waited for at the barriers: the rows' global stores drain behind the MFMAs.
+            // buffer), barrier, waves 0-3 take the Gram block from LDS while waves 4-7 start on the next sub-window's rows (below; all
+            // eight take it where there is no next sub-window), next sub-window.  Only the LDS traffic is waited for at the barriers: the rows' global stores drain behind the MFMAs.
             // No wave has rows of its own: a wave CLAIMS the block's rows one by one from a counter in LDS (one returning add
             // by lane 0), always the next row before it evaluates the current one, so that the next `old` row is under way a
             // row ahead.  The SIMD arbitrates oldest-first, so of two waves that share one the younger (4-7) is the slower; with a
@@ -296,21 +296,27 @@ __device__ __forceinline__ void pipe_prod_block(const PipeArgs &pa, const PipeHo
 #ifdef MCSAS_STAMPS
             int nmine = 0;                                        // rows this wave has evaluated
 #endif
-            // Roles in the Gram phase (pipe_gram.h): waves 0-3 issue the MFMAs of sub-window ss, waves 4-7 meanwhile go on with the row
-            // they hold a claim on — a row of sub-window ss + 1; one HELD row per wave —: d to the window buffer and (a, e) to scal
-            // as ever, but d stays in registers while dbuf is still being read and goes to its LDS row behind the barrier that ends
-            // the operand reads.  A wave whose claim lies behind the block (always so in the block's last sub-window) goes straight
-            // to that barrier.  Tuning bit 17: eight Gram waves and no held row, as before the roles.
-            // s_barriers per sub-window, the same for EVERY wave of the block (ss, W, nvalid, no_gram and the tuning word are uniform
-            // in the block; a wave's role, its claim and whether it holds a row change what it does BETWEEN barriers only):
+            // Roles in the Gram phase (pipe_gram.h), chosen per sub-window (`split` below): waves 0-3 issue the MFMAs of sub-window ss,
+            // waves 4-7 meanwhile go on with the row they hold a claim on — a row of sub-window ss + 1; one HELD row per wave —: d to
+            // the window buffer and (a, e) to scal as ever, but d stays in registers while dbuf is still being read and goes to its LDS
+            // row behind the barrier that ends the operand reads.  A wave whose claim lies behind sub-window ss + 1 goes straight to
+            // that barrier.  The block's LAST sub-window (its only one where sub_per_block == 1) has no successor to hold a row of:
+            // there the roles would only leave four waves idle and four with twice the operand work, so all eight are Gram waves, one
+            // slice each.  Both forms fill the same eight partial slots, summed in the same order: the same bits.
+            // Tuning bit 17: eight Gram waves and no held row in EVERY sub-window, as before the roles; bit 21: the roles in every
+            // sub-window, the last one included (idle row waves there), as before they were chosen per sub-window.  Word 0, bit 17 and
+            // bit 21 are three forms inside one measurement library: AB_WORDS=0,0x200000 tools/ab_pair.py <tuning> <tuning>.
+            // s_barriers per sub-window, the same for EVERY wave of the block (ss, nsb, W, nvalid, no_gram and the tuning word are uniform
+            // in the block, and so is `split`, which depends on nothing else — not on a wave's claim; a wave's role, its claim and
+            // whether it holds a row change what it does BETWEEN barriers only):
             //   no_gram                      0
             //   nvalid == 0                  1   rows -> Gram (the Gram block is skipped by all waves: nobody holds a row either)
             //   else                         1 + (2 R - 1), R = ceil(tiles / PIPE_GRAM_TILES_PER_ROUND) rounds of the reduction
             //                                (pipe_prod_gram_lds_t: matrix waves, row waves with or without a held row, and the eight
-            //                                Gram waves of bit 17 all pass the same 2 R - 1)
+            //                                Gram waves of an unsplit sub-window all pass the same 2 R - 1)
             // The row loop itself has no barrier: a wave that claims no row of a sub-window passes the same ones.
-            const bool roles = !(MCSAS_TUNE_BITS(a) & (1 << 17));
-            const bool row_wave = roles && __builtin_amdgcn_readfirstlane(wave) >= WPB / 2;
+            const bool roles = !(MCSAS_TUNE_BITS(a) & (1 << 17)), roles_last = MCSAS_TUNE_BITS(a) & (1 << 21);
+            const bool upper_wave = __builtin_amdgcn_readfirstlane(wave) >= WPB / 2;
             // one row of the block: the wave's claim kc, which belongs to sub-window sr; HOLD: no LDS copy, d is the caller's to keep
             auto eval_row = [&](int sr, auto hold, double (&d)[QPL]) {
                 const int kn = take();
@@ -372,13 +378,14 @@ __device__ __forceinline__ void pipe_prod_block(const PipeArgs &pa, const PipeHo
                 if (!no_gram) PIPE_LDS_BARRIER();                 // the sub-window's rows are in LDS
                 const int nvalid = nvalid_of(ss);
                 if (nvalid > 0 && !no_gram) {                     // uniform in the block
+                    const bool split = roles && (roles_last || ss + 1 < nsb);   // uniform in the block: a row of sub-window ss + 1 can be held
                     double dheld[QPL];
                     int kheld = -1;                               // the row this wave evaluates beside the MFMAs (uniform in the wave)
                     // (the claims are handed out in order, eight at most beyond a sub-window: the second bound holds for every W
                     // pipe_geometry picks and keeps the LDS row inside dbuf for any other)
-                    if (row_wave && kc < BR && kc < (ss + 2) * W) { kheld = kc; eval_row(ss + 1, std::true_type{}, dheld); }
+                    if (split && upper_wave && kc < BR && kc < (ss + 2) * W) { kheld = kc; eval_row(ss + 1, std::true_type{}, dheld); }
                     pipe_prod_gram_lds<QPL>(dbuf, dstr, W, nvalid, lw, gred, gwin + (size_t)(by * nsb + ss) * W * W,
-                                            scal + (size_t)(by * BR + ss * W) * 4, roles, [&]() {
+                                            scal + (size_t)(by * BR + ss * W) * 4, split, [&]() {
                                                 if (kheld >= 0) {
                                                     double *dl = dbuf + (size_t)(kheld - (ss + 1) * W) * dstr + lane;
 #pragma unroll

@@ -6,7 +6,8 @@ hits both builds alike.  Several plans per build because a plan's speed also dep
 builds' BEST plans and their medians over plans.
 usage: tools/ab_pair.py libA.so libB.so [launches per plan] [plans per build]
 AB_WORDS=a,b gives the two sides a tuning word each (mcsas_problem.reserved0; both paths then name a measurement build, usually the
-same one: two variants inside one library, e.g. AB_WORDS=0,131072)."""
+same one: two variants inside one library, e.g. AB_WORDS=0,131072).  AB_REPS=7 runs config 2's data with 7 chains (a GPU's share under
+strong scaling: producer blocks of one sub-window); the geometry of the first plan is printed."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -20,7 +21,7 @@ K = int(sys.argv[4]) if len(sys.argv) > 4 else 3
 q, I, sig = synthetic_data(512)
 m = mcsas_amd.Sphere(); m.radius.setActiveRange((np.pi / q.max(), np.pi / q.min()))
 words = [int(w, 0) for w in os.environ.get("AB_WORDS", "0,0").split(",")]
-sts = [engine.Settings(n_contrib=400, n_reps=50, max_iter=int(os.environ.get("AB_STEPS", "20000")), conv_crit=0.0, max_retries=0, seed=20250101,
+sts = [engine.Settings(n_contrib=400, n_reps=int(os.environ.get("AB_REPS", "50")), max_iter=int(os.environ.get("AB_STEPS", "20000")), conv_crit=0.0, max_retries=0, seed=20250101,
                        debug_flags=w) for w in words]
 plans = []
 for k in range(K):
@@ -29,6 +30,7 @@ for k in range(K):
         _lib.LIB_PATH = _lib.TUNING_LIB_PATH = p              # (a non-zero word loads "the tuning library": this side's path)
         os.environ["MCSAS_HIP_LIB"] = p
         plans.append((which, engine.Plan(m.setup(), q, I, sig, sts[which])))
+print("plan:", {k: plans[0][1].info[k] for k in ("exec_mode", "window", "q_per_lane") if k in plans[0][1].info}, "chains", sts[0].n_reps)
 ms = [[] for _ in plans]
 for i in range(n + 10):
     for k, (_, pl) in enumerate(plans):
