@@ -1,6 +1,6 @@
 // hist2d_kernel.h — the joint histogram of two parameter columns (include/mcsas_hip.h: mcsas_hip_histogram2d): the record of a
 // histogram on the device, the LDS a (histogram, repetition) needs, and hist2d_kernel.  host_hist.hip packs the records and launches
-// it; tools/microbench_hist2d.hip times it alone.  Per axis every rule is hist_bins_body's (host_hist.hip), so that one y column
+// it; tools/microbench_hist2d.hip times it alone.  Per axis every rule is hist_bins_body's (hist_kernels.h), so that one y column
 // that holds every value gives that kernel's bins bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,7 +1,7 @@
 // hist_partial_kernel.h — the partial intensities of histogram ranges and bins (include/mcsas_hip.h: mcsas_hip_histogram_partial,
 // mcsas_hip_histogram_partial_device_rows; the reference's Moments.intensity, utils/parameter.py:124-154): the record of a wanted
 // histogram on the device, the LDS a block needs, and hist_partial_kernel.  host_hist.hip packs the records and launches it on a
-// block of repetitions' rows while they still lie in HBM, behind launch_hist_fit_obs (the scale of a repetition is known by then).
+// block of repetitions' rows while they still lie in HBM, behind the fit (HistOnDevice::run; the scale of a repetition is known by then).
 //   range[k][r]  = A * sum_c rows[c][k] over the contributions with lower < x_c < upper        (hist_bins_body's `ok`)
 //   bin[b][k][r] = A * sum_c rows[c][k] over those with edges[b] <= x_c < edges[b+1] && x_c < edges[n_bin]   (its bins)
 // each sum in contribution order from +0.0, ONE product with A = scaling[0][r] at the end; with -ffp-contract=off that is what

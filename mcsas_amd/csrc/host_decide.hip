@@ -28,6 +28,12 @@ int fail(int code, const char *fmt, ...) {
     g_err = buf;
     return code;
 }
+int fail_within(int code, const char *fmt, ...) {
+    const std::string why = g_err;
+    char who[512];
+    va_list ap; va_start(ap, fmt); vsnprintf(who, sizeof who, fmt, ap); va_end(ap);
+    return fail(code, "%s: %s", who, why.c_str());
+}
 
 // ------------------------------------------------------------------------------ models and smearing: what a problem is refused for
 ModelTraits model_traits(int model_id) {

@@ -1,11 +1,13 @@
-// host_hist.hip — McSAS.histogram() on the device: the hist_* kernels, their batch forms and the entry points mcsas_hip_histogram_prep,
-// mcsas_hip_histogram, mcsas_hip_histogram_sets (the sets of a joint fit seen together), mcsas_hip_histogram_batch and
-// mcsas_hip_histogram_device_rows (the rows filled by the caller), and the forms of
-// the second and the last that also return partial intensities (hist_partial_kernel.h; mcsas_hip_histogram_partial*).  What makes a
-// set acceptable (check_hist_set), how a set lies in the staging blocks (HistSizes, pack_hist_set, unpack_hist_set) and how many
+// host_hist.hip — McSAS.histogram() on the device, the host side: the entry points mcsas_hip_histogram_prep, mcsas_hip_histogram,
+// mcsas_hip_histogram_sets (the sets of a joint fit seen together), mcsas_hip_histogram_batch, mcsas_hip_histogram_device_rows (the
+// rows filled by the caller), the forms of the second and the last that also return partial intensities
+// (mcsas_hip_histogram_partial*) and mcsas_hip_histogram2d.  Every kernel they launch lies in a header: hist_kernels.h (the hist_*
+// kernels and their batch forms), hist_partial_kernel.h, hist2d_kernel.h, and small_kernels.h for the rows.  What makes a set
+// acceptable (check_hist_set), how a set lies in the staging blocks (HistSizes, pack_hist_set, unpack_hist_set) and how many
 // repetitions share a block of rows (hist_rep_chunk) are each said once here, for the single call and the batch alike; how one set
-// is held on the device and finished (HistOnDevice), what follows a block of rows (launch_hist_fit_obs) and how a bins kernel is
-// launched (launch_hist_bins) once for the entry points that differ only in who fills the rows.  Nothing here knows about plans.
+// is held on the device, taken through its blocks of rows and finished (HistOnDevice: upload, run, finish) and how a bins kernel is
+// launched (launch_hist_bins) once for the entry points that differ only in who fills the rows and which fit follows them.  Every
+// entry point runs under no_bad_alloc.  Nothing here knows about plans.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,343 +16,39 @@
 #include <cstring>
 #include <vector>
 
-#include "host_decide.h"     // check_hist_sets_request, HistSetOffs' MCSAS_MAX_SETS
-#include "small_launch.h"    // hist_rows_kernel, hist_rows_batch_kernel (from a model id to the instance), HistSetDev, visibility_limit
+#include "host_decide.h"          // check_hist_sets_request
+#include "small_launch.h"         // hist_rows_kernel, hist_rows_batch_kernel (from a model id to the instance)
+#include "hist_kernels.h"         // the hist_* kernels of one set and of a batch, HistSetOffs, HistSpecDev
+#include "hist_partial_kernel.h"  // HistPartialDev, hist_partial_lds_bytes, hist_partial_kernel
+#include "hist2d_kernel.h"        // Hist2dSpecDev, hist2d_staged_bytes, hist2d_shared_bytes, hist2d_kernel
 
 using namespace mcsas;
 
 // mcsas_hip_histogram stages a repetition's contributions in LDS (hist_bins_body: 3 N doubles); engine.HISTOGRAM_MAX_CONTRIBS
 constexpr int HIST_MAX_CONTRIBS = 4096;
+static_assert(HIST_PARTIAL_MAX_CONTRIBS == HIST_MAX_CONTRIBS, "hist_partial_kernel.h: the call's own cap");
+static_assert(HIST2D_MAX_CONTRIBS == HIST_MAX_CONTRIBS, "hist2d_kernel.h: the 1-D cap");
 // what a kernel may ask of dynamic LDS without its limit being raised first, and where a grid's y extent ends
 constexpr size_t LDS_UNRAISED_MAX = 64 * 1024, GRID_Y_MAX = 65535;
-
-// ------------------------------------------------------------------------------ kernels
-// The arithmetic of each kernel is a device function of one (data set, repetition): the single call's kernel hands it its own
-// arguments, the batch kernel (further down) what its set's record says.
-
-// the visibility limit (visibility_limit, small_kernels.h) of contribution c of repetition r from its stored row, at the volume
-// fraction its fitted scale gives it
-__device__ __forceinline__ void hist_obs_body(int nq, const double *sigma, int R, int c, int r, const double *row, const double *scaling,
-                                              const double *vset, const double *wset, double *min_req) {
-    const double A = scaling[r];
-    const double vf = wset[(size_t)c * R + r] * A / vset[(size_t)c * R + r];      // modeldata.py:57-61
-    visibility_limit(nq, sigma, vf, A, [&](int k) { return row[k]; }, min_req + (size_t)c * R + r);
-}
-__global__ __launch_bounds__(64) void hist_obs_kernel(int nq, const double *sigma, int N, int R, int r0, const double *rows,
-                                                      const double *scaling, const double *vset, const double *wset, double *min_req) {
-    const int c = blockIdx.x, rl = blockIdx.y, r = r0 + rl;
-    hist_obs_body(nq, sigma, R, c, r, rows + ((size_t)rl * N + c) * nq, scaling, vset, wset, min_req);
-}
-
-// cum[k] = sum_n rows[n][k] of one repetition in contribution order (scatteringmodel.py:101): one thread per q, loads in batches of 8
-__device__ __forceinline__ void hist_colsum_body(int nq, int N, int k, const double *rows, double *cum) {
-    if (k >= nq) return;
-    const double *base = rows + k;
-    double s = 0.;
-    int n = 0;
-    for (; n + 8 <= N; n += 8) {
-        double v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = base[(size_t)(n + i) * nq];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s += v[i];
-    }
-    for (; n < N; ++n) s += base[(size_t)n * nq];
-    cum[k] = s;
-}
-__global__ void hist_colsum_kernel(int nq, int N, const double *rows, double *cum) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x, rl = blockIdx.y;
-    hist_colsum_body(nq, N, k, rows + (size_t)rl * N * nq, cum + (size_t)rl * nq);
-}
-// the closed-form scale / background fit (mcsas.py:559) of repetition r against its summed intensity `cum`: one wave
-__device__ __forceinline__ void hist_fit_cum_body(int nq, const double *I, const double *sigma, int R, int r, const double *cum,
-                                                  int find_bg, int pos_bg, double *scaling) {
-    const int lane = threadIdx.x;
-    double sw = 0, si = 0, sii = 0, sc = 0, scc = 0, sic = 0;
-    for (int k = lane; k < nq; k += WAVE) {
-        const double C = cum[k];
-        const double e = sigma[k] == 0.0 ? 1.0 : sigma[k];
-        const double w = 1.0 / (e * e);
-        sw += w; si += w * I[k]; sii += w * I[k] * I[k];
-        sc += w * C; scc += w * C * C; sic += w * I[k] * C;
-    }
-    wave_sum3(sw, si, sii); wave_sum3(sc, scc, sic);
-    ChainArgs a{};
-    a.Sw = sw; a.SI = si; a.SII = sii; a.nq = nq; a.find_bg = find_bg; a.pos_bg = pos_bg;
-    const FitResult f = solve_fit(a, sc, scc, sic);
-    if (lane == 0) { scaling[r] = f.A; scaling[R + r] = f.b; }
-}
-__global__ __launch_bounds__(64) void hist_fit_cum_kernel(int nq, const double *I, const double *sigma, int R, int r0, const double *cum,
-                                                          int find_bg, int pos_bg, double *scaling) {
-    const int rl = blockIdx.x;
-    hist_fit_cum_body(nq, I, sigma, R, r0 + rl, cum + (size_t)rl * nq, find_bg, pos_bg, scaling);
-}
-// ---- the same two for a joint fit (mcsas_hip_histogram_sets): the nq points are n_sets sets one after the other.  Where the sets begin
-// goes by value and is indexed by unrolled loops alone (a run-time index would send the block to scratch); each set's fit lies in
-// set_fit[2][MCSAS_MAX_SETS][R] (scales, then backgrounds), which the visibility kernel reads.
-struct HistSetOffs { int32_t o[MCSAS_MAX_SETS + 1]; };        // set s: points [o[s], o[s + 1]); o[n_sets ..] = nq
-// One wave per repetition.  Each set's six sums as hist_fit_cum_body forms them on the set's own points; then per set solve_fit
-// (MCSAS_SETS_SCALE_PER_SET), or ONE scale A = Σ num_s / Σ den_s and b_s = (SI_s - A SC_s) / Sw_s with the centred pieces of
-// chain_sets.h: set_parts (MCSAS_SETS_SCALE_SHARED; with one set solve_fit, as the chain does).  scaling[2][R] = set ref_set's pair.
-__global__ __launch_bounds__(64) void hist_fit_sets_kernel(int nq, const double *I, const double *sigma, int R, int r0, const double *cum_all,
-                                                           int find_bg, int n_sets, HistSetOffs off, int shared, int ref_set, double *scaling,
-                                                           double *set_fit) {
-    const int lane = threadIdx.x, rl = blockIdx.x, r = r0 + rl;
-    const double *cum = cum_all + (size_t)rl * nq;
-    double sw[MCSAS_MAX_SETS], si[MCSAS_MAX_SETS], sc[MCSAS_MAX_SETS], A[MCSAS_MAX_SETS], b[MCSAS_MAX_SETS];
-    double Num = 0., Den = 0.;
-#pragma unroll
-    for (int s = 0; s < MCSAS_MAX_SETS; ++s) {
-        sw[s] = si[s] = sc[s] = A[s] = b[s] = 0.;
-        if (s < n_sets) {
-            double w0 = 0, i0 = 0, ii0 = 0, c0 = 0, cc0 = 0, ic0 = 0;
-            for (int k = off.o[s] + lane; k < off.o[s + 1]; k += WAVE) {
-                const double C = cum[k];
-                const double e = sigma[k] == 0.0 ? 1.0 : sigma[k];
-                const double w = 1.0 / (e * e);
-                w0 += w; i0 += w * I[k]; ii0 += w * I[k] * I[k];
-                c0 += w * C; cc0 += w * C * C; ic0 += w * I[k] * C;
-            }
-            wave_sum3(w0, i0, ii0); wave_sum3(c0, cc0, ic0);
-            if (!shared || n_sets == 1) {
-                ChainArgs a{};
-                a.Sw = w0; a.SI = i0; a.SII = ii0; a.nq = off.o[s + 1] - off.o[s]; a.find_bg = find_bg; a.pos_bg = 0;
-                const FitResult f = solve_fit(a, c0, cc0, ic0);
-                A[s] = f.A; b[s] = f.b;
-            } else {
-                double num = ic0, den = cc0;
-                if (find_bg) { num = fma(-(i0 / w0), c0, ic0); den = fma(-(c0 * (1.0 / w0)), c0, cc0); }
-                Num += num; Den += den;
-                sw[s] = w0; si[s] = i0; sc[s] = c0;
-            }
-        }
-    }
-    double Aref = 0., bref = 0.;
-    const double Ashared = Num / Den;
-#pragma unroll
-    for (int s = 0; s < MCSAS_MAX_SETS; ++s)
-        if (s < n_sets) {
-            if (shared && n_sets > 1) { A[s] = Ashared; b[s] = find_bg ? (si[s] - Ashared * sc[s]) / sw[s] : 0.; }
-            if (s == ref_set) { Aref = A[s]; bref = b[s]; }
-            if (lane == 0) { set_fit[(size_t)s * R + r] = A[s]; set_fit[((size_t)MCSAS_MAX_SETS + s) * R + r] = b[s]; }
-        }
-    if (lane == 0) { scaling[r] = Aref; scaling[R + r] = bref; }
-}
-// One wave per (contribution, repetition): visibility_limit over the points of the sets named in `visible`, each point's product taken
-// with its OWN set's scale, at the volume fraction the reference scale (scaling[r]) gives the contribution.
-__global__ __launch_bounds__(64) void hist_obs_sets_kernel(int nq, const double *sigma, int N, int R, int r0, const double *rows, const double *scaling,
-                                                           const double *set_fit, int n_sets, HistSetOffs off, uint32_t visible, const double *vset,
-                                                           const double *wset, double *min_req) {
-    const int c = blockIdx.x, rl = blockIdx.y, r = r0 + rl;
-    const double *row = rows + ((size_t)rl * N + c) * nq;
-    const double vf = wset[(size_t)c * R + r] * scaling[r] / vset[(size_t)c * R + r];   // modeldata.py:57-61
-    double best = __builtin_inf();
-#pragma unroll
-    for (int s = 0; s < MCSAS_MAX_SETS; ++s)
-        if (s < n_sets && ((visible >> s) & 1u)) {
-            const double A = set_fit[(size_t)s * R + r];
-            for (int k = off.o[s] + (int)threadIdx.x; k < off.o[s + 1]; k += WAVE) {
-                const double scaled = A * row[k];
-                if (scaled != 0.) best = fmin(best, (sigma[k] * vf) / scaled);
-            }
-        }
-    best = wave_min(best);
-    if (threadIdx.x == 0) min_req[(size_t)c * R + r] = best;
-}
-
-// fractions and their visibility limits, normalised per repetition (mcsas.py:561-604): frac8 = [vf nf qf sf | mv mn mq ms][N][R].
-// One wave per rep; the three totals are taken by one lane each, over the contributions in order (builtin sum()).
-__device__ __forceinline__ void hist_fractions_body(int N, int R, int r, const double *scaling, const double *vset, const double *wset,
-                                                    const double *sset, const double *mv, double *frac8) {
-    __shared__ double tot[3];
-    const int lane = threadIdx.x;
-    const size_t NR = (size_t)N * R;
-    const double A = scaling[r];
-    double *vf = frac8, *nf = frac8 + NR, *qf = frac8 + 2 * NR, *sf = frac8 + 3 * NR;
-    double *omv = frac8 + 4 * NR, *mn = frac8 + 5 * NR, *mq = frac8 + 6 * NR, *ms = frac8 + 7 * NR;
-    for (int c = lane; c < N; c += WAVE) {
-        const size_t i = (size_t)c * R + r;
-        const double v = vset[i], w = wset[i], s = sset[i], m = mv[i];
-        const double vfc = w * A / v;                          // modeldata.py:57-61
-        const double nfc = vfc / v, mnc = m / v;               // mcsas.py:567-571, :591-594
-        vf[i] = vfc; nf[i] = nfc; qf[i] = vfc * v; sf[i] = nfc * s;
-        omv[i] = m; mn[i] = mnc; mq[i] = mnc * m * m; ms[i] = mnc * s;
-    }
-    __syncthreads();
-    if (lane < 3) {
-        const double *src = lane == 0 ? nf : (lane == 1 ? qf : sf);
-        double t = 0.;
-        for (int c = 0; c < N; ++c) t += src[(size_t)c * R + r];
-        tot[lane] = t;
-    }
-    __syncthreads();
-    const double tn = tot[0], tq = tot[1], ts = tot[2];
-    for (int c = lane; c < N; c += WAVE) {
-        const size_t i = (size_t)c * R + r;
-        if (tn != 0.) { nf[i] /= tn; mn[i] /= tn; }           // :596-604
-        if (tq != 0.) { qf[i] /= tq; mq[i] /= tq; }
-        if (ts != 0.) { sf[i] /= ts; ms[i] /= ts; }
-    }
-}
-__global__ __launch_bounds__(64) void hist_fractions_kernel(int N, int R, const double *scaling, const double *vset, const double *wset,
-                                                            const double *sset, const double *mv, double *frac8) {
-    hist_fractions_body(N, R, blockIdx.x, scaling, vset, wset, sset, mv, frac8);
-}
-struct HistSpecDev { int32_t pidx, weight, nb, pad; int64_t edge_off, out_off; double lo, hi; };
-// One wave per (histogram, repetition).  The repetition's parameter values, fractions and limits are staged in LDS (hl: 3 N doubles);
-// lane b owns bin b (64 bins per pass) and walks the contributions in order; the cumulative distribution and the moments are
-// sequential sums again, taken by one lane (two for skew and kurtosis).  utils/parameter.py:84-122, :441-479.
-__device__ __forceinline__ void hist_bins_body(int N, int P, int R, int r, const HistSpecDev s, const double *contribs, const double *frac8,
-                                               const double *edges_all, double *out, double *hl) {
-    __shared__ double mom[8];
-    const int lane = threadIdx.x, nb = s.nb;
-    const size_t NR = (size_t)N * R;
-    const double *fr = frac8 + (size_t)s.weight * NR, *lim = frac8 + (size_t)(4 + s.weight) * NR;
-    const double *edges = edges_all + s.edge_off;
-    double *bins = out + s.out_off, *obs = bins + (size_t)nb * R, *cdf = obs + (size_t)nb * R, *mo = cdf + (size_t)nb * R;
-    double *lx = hl, *lf = hl + N, *ll = hl + 2 * (size_t)N;
-    for (int c = lane; c < N; c += WAVE) {
-        lx[c] = contribs[((size_t)c * P + s.pidx) * R + r];
-        lf[c] = fr[(size_t)c * R + r]; ll[c] = lim[(size_t)c * R + r];
-    }
-    __syncthreads();
-    const double last = nb > 0 ? edges[nb] : 0.;
-    for (int b0 = 0; b0 < nb; b0 += WAVE) {
-        const int b = b0 + lane;
-        if (b < nb) {
-            const double elo = edges[b], ehi = edges[b + 1];
-            double sb = 0., so = 0., cnt = 0.;
-            for (int c = 0; c < N; ++c) {
-                const double x = lx[c];
-                if (x >= elo && x < ehi && x < last) { sb += lf[c]; so += ll[c]; cnt += 1.; }
-            }
-            bins[(size_t)b * R + r] = (sb != sb) ? 0. : sb;    // bins[isnan(bins)] = 0
-            obs[(size_t)b * R + r] = cnt > 0. ? so / cnt : 0.;
-        }
-    }
-    __syncthreads();
-    if (lane == 0) {
-        double run = 0., top = -__builtin_inf();
-        for (int b = 0; b < nb; ++b) { run += bins[(size_t)b * R + r]; cdf[(size_t)b * R + r] = run; top = fmax(top, run); }
-        for (int b = 0; b < nb; ++b) cdf[(size_t)b * R + r] = (top == 0.) ? 0. : cdf[(size_t)b * R + r] / top;
-    }
-    // moments: total, mean, variance by lane 32 (runs beside lane 0's distribution), then skew / kurtosis by lanes 32 / 33
-    if (lane == 32) {
-        double tot = 0., m1 = 0.;
-        int any = 0;
-        for (int c = 0; c < N; ++c) { const double x = lx[c]; const bool ok = x > s.lo && x < s.hi; any |= ok; tot += ok ? lf[c] : 0.; }
-        for (int c = 0; c < N; ++c) { const double x = lx[c]; const bool ok = x > s.lo && x < s.hi; m1 += ok ? x * lf[c] : 0.; }
-        if (tot != 0.) m1 /= tot;
-        double v2 = 0.;
-        for (int c = 0; c < N; ++c) { const double x = lx[c], d = x - m1; const bool ok = x > s.lo && x < s.hi; v2 += ok ? (d * d) * lf[c] : 0.; }
-        const double var = v2 / tot, sg = sqrt(fabs(var));
-        mom[0] = tot; mom[1] = m1; mom[2] = var; mom[3] = sg; mom[4] = (double)any;
-    }
-    __syncthreads();
-    if (lane == 32 || lane == 33) {
-        const double tot = mom[0], m1 = mom[1], sg = mom[3];
-        const bool any = mom[4] != 0., ok3 = any && (tot * sg) != 0.;      // (utils/parameter.py:106-107: only an exact zero is skipped; NaN goes on)
-        const double sg2 = sg * sg;
-        double acc = 0.;
-        for (int c = 0; c < N; ++c) {
-            const double x = lx[c], d = x - m1, d2 = d * d;
-            const bool ok = x > s.lo && x < s.hi;
-            acc += ok ? (lane == 32 ? d2 * d : d2 * d2) * lf[c] : 0.;
-        }
-        const double val = ok3 ? acc / (tot * (lane == 32 ? sg2 * sg : sg2 * sg2)) : 0.;
-        mo[(size_t)(3 + (lane - 32)) * R + r] = val;
-        if (lane == 32) { mo[r] = any ? tot : 0.; mo[(size_t)R + r] = any ? m1 : 0.; mo[(size_t)2 * R + r] = any ? mom[2] : 0.; }
-    }
-}
-__global__ __launch_bounds__(64) void hist_bins_kernel(int N, int P, int R, const double *contribs, const double *frac8, const double *edges_all,
-                                                       const HistSpecDev *specs, double *out) {
-    extern __shared__ double hl[];
-    hist_bins_body(N, P, R, blockIdx.y, specs[blockIdx.x], contribs, frac8, edges_all, out, hl);
-}
-
-// ---- a round of mcsas_hip_histogram_device_rows: n_rows = k N rows of the caller's, row rl N + c = contribution c of repetition r0 + rl.
-// Plain loads and stores, one thread per element; the host reads neither buffer.
-// the round's parameter sets, unclipped, in activeParams() order: pset[row][p] = contribs[c][p][r0 + rl]
-__global__ void hist_pset_kernel(int N, int P, int R, int r0, size_t n_rows, const double *__restrict__ contribs, double *__restrict__ pset) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_rows * P) return;
-    const size_t row = i / P, rl = row / N, c = row % N, p = i % P;
-    pset[i] = contribs[(c * P + p) * R + r0 + rl];
-}
-// the round's volumes, weights and surfaces, vws[3][capacity] as the caller filled them, into the [c R + r] arrays of the kernels above
-__global__ void hist_take_vws_kernel(int N, int R, int r0, size_t n_rows, size_t capacity, const double *__restrict__ vws,
-                                     double *__restrict__ vset, double *__restrict__ wset, double *__restrict__ sset) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_rows) return;
-    const size_t j = (i % N) * R + r0 + i / N;
-    vset[j] = vws[i]; wset[j] = vws[capacity + i]; sset[j] = vws[2 * capacity + i];
-}
-
-// ---- the same for a batch of data sets (mcsas_hip_histogram_batch): one launch each over the (set, repetition) blocks of a chunk.
-// A set's record (HistSetDev, small_kernels.h) says where its arrays lie in the packed upload `in`, the packed download `back` and
-// the scratch blocks; blockIdx.x picks the (set, repetition), blockIdx.y runs to the chunk's largest extent (contributions, q blocks,
-// histograms): a block beyond its own set's returns on its index alone, ahead of any barrier.
-struct HistSetView {
-    const HistSetDev &s;
-    const int r;
-    const size_t NR;
-    __device__ HistSetView(const HistSetDev *sets, const ChainRef *blocks)
-        : s(sets[__builtin_amdgcn_readfirstlane(blocks[blockIdx.x].set)]), r(__builtin_amdgcn_readfirstlane(blocks[blockIdx.x].rep)),
-          NR((size_t)s.N * s.R) {}
-    __device__ double *scaling(double *back) const { return back + s.back_off; }
-    __device__ double *frac8(double *back) const { return back + s.back_off + 2 * (size_t)s.R; }
-    __device__ double *out(double *back) const { return back + s.back_off + 2 * (size_t)s.R + 8 * NR; }
-};
-__global__ void hist_colsum_batch_kernel(const HistSetDev *__restrict__ sets, const ChainRef *__restrict__ blocks, const double *rows, double *cum) {
-    const HistSetView v(sets, blocks);
-    const HistSetDev &s = v.s;
-    if ((int)(blockIdx.y * blockDim.x) >= s.nq) return;
-    hist_colsum_body(s.nq, s.N, blockIdx.y * blockDim.x + threadIdx.x, rows + s.rows_off + (size_t)v.r * s.N * s.nq, cum + s.cum_off + (size_t)v.r * s.nq);
-}
-__global__ __launch_bounds__(64) void hist_fit_cum_batch_kernel(const HistSetDev *__restrict__ sets, const ChainRef *__restrict__ blocks,
-                                                                const double *__restrict__ in, const double *cum, double *back) {
-    const HistSetView v(sets, blocks);
-    const HistSetDev &s = v.s;
-    hist_fit_cum_body(s.nq, in + s.I_off, in + s.sg_off, s.R, v.r, cum + s.cum_off + (size_t)v.r * s.nq, s.find_bg, s.pos_bg, v.scaling(back));
-}
-__global__ __launch_bounds__(64) void hist_obs_batch_kernel(const HistSetDev *__restrict__ sets, const ChainRef *__restrict__ blocks,
-                                                            const double *__restrict__ in, const double *rows, const double *back, double *vws) {
-    const HistSetView v(sets, blocks);
-    const HistSetDev &s = v.s;
-    const int c = blockIdx.y;
-    if (c >= s.N) return;
-    double *w = vws + s.vws_off;
-    hist_obs_body(s.nq, in + s.sg_off, s.R, c, v.r, rows + s.rows_off + ((size_t)v.r * s.N + c) * s.nq, back + s.back_off, w, w + v.NR, w + 3 * v.NR);
-}
-__global__ __launch_bounds__(64) void hist_fractions_batch_kernel(const HistSetDev *__restrict__ sets, const ChainRef *__restrict__ blocks,
-                                                                  const double *vws, double *back) {
-    const HistSetView v(sets, blocks);
-    const HistSetDev &s = v.s;
-    const double *w = vws + s.vws_off;
-    hist_fractions_body(s.N, s.R, v.r, v.scaling(back), w, w + v.NR, w + 2 * v.NR, w + 3 * v.NR, v.frac8(back));
-}
-// histograms [h0, h0 + gridDim.y) of every set that has that many
-__global__ __launch_bounds__(64) void hist_bins_batch_kernel(const HistSetDev *__restrict__ sets, const ChainRef *__restrict__ blocks, int h0,
-                                                             const double *__restrict__ in, double *back) {
-    extern __shared__ double hl[];
-    const HistSetView v(sets, blocks);
-    const HistSetDev &s = v.s;
-    const int h = h0 + blockIdx.y;
-    if (h >= s.n_hist) return;
-    const HistSpecDev *specs = reinterpret_cast<const HistSpecDev *>(in + s.spec_off);
-    hist_bins_body(s.N, s.P, s.R, v.r, specs[h], in + s.c_off, v.frac8(back), in + s.edge_off, v.out(back), hl);
-}
 
 // ------------------------------------------------------------------------------ one set: what is acceptable, and where it lies
 // The staging blocks of a set, in doubles.  Going in: [q | I | sigma | contribs | edges | specs] — the edges of its histograms one after
 // the other, then their HistSpecDev records, whose edge_off / out_off count from the set's own edges and outputs.  Coming back:
 // [scaling 2R | fractions 8NR | out].  The *_off are the places of the parts in their block; the device reads the coming-back ones
-// through HistSetView.
+// through HistSetView.  vws_back (mcsas_hip_histogram_prep): [scaling 2R | volumes, weights, surfaces, visibility limits 4NR] instead.
 struct HistSizes {
     size_t n_edges = 0, n_out = 0;                             // edges and output doubles of all the set's histograms
     size_t I_off = 0, sg_off = 0, c_off = 0, edge_off = 0, spec_off = 0, n_in = 0, frac_off = 0, out_off = 0, n_back = 0;
     size_t rows = 0;                                           // the rows of all repetitions: N R Q
+    bool vws_back = false;
 };
+// the places, once n_edges and n_out are known
+static void lay_out_hist_set(HistSizes *sz, const mcsas_problem *p, int n_hist) {
+    const size_t Q = p->nq, P = p->n_active, N = p->n_contrib, R = p->n_reps;
+    sz->I_off = Q; sz->sg_off = 2 * Q; sz->c_off = 3 * Q; sz->edge_off = sz->c_off + N * P * R; sz->spec_off = sz->edge_off + sz->n_edges;
+    sz->n_in = sz->spec_off + (sizeof(HistSpecDev) * (size_t)n_hist + 7) / 8;
+    sz->frac_off = 2 * R; sz->out_off = sz->frac_off + 8 * N * R; sz->n_back = sz->out_off + sz->n_out; sz->rows = N * R * Q;
+}
 // a histogram's outputs: bins, observability and cumulative distribution [n_bin][R] each, then the moments [5][R] (hist_bins_body)
 static size_t hist_out_doubles(int n_bin, size_t R) { return (size_t)3 * n_bin * R + 5 * R; }
 
@@ -367,7 +65,7 @@ static int check_hist_set(const mcsas_problem *p, const double *contribs, int n_
         if (int rc = fill_model_args(p, m)) return rc;
         if (int rc = SmearDev::check(p)) return rc;
     }
-    const size_t Q = p->nq, P = p->n_active, N = p->n_contrib, R = p->n_reps;
+    const size_t P = p->n_active, R = p->n_reps;
     *sz = HistSizes{};
     for (int h = 0; h < n_hist; ++h) {
         const mcsas_histogram_spec &sp = specs[h];
@@ -377,9 +75,7 @@ static int check_hist_set(const mcsas_problem *p, const double *contribs, int n_
         sz->n_edges += (size_t)sp.n_bin + 1;
         sz->n_out += hist_out_doubles(sp.n_bin, R);
     }
-    sz->I_off = Q; sz->sg_off = 2 * Q; sz->c_off = 3 * Q; sz->edge_off = sz->c_off + N * P * R; sz->spec_off = sz->edge_off + sz->n_edges;
-    sz->n_in = sz->spec_off + (sizeof(HistSpecDev) * (size_t)n_hist + 7) / 8;
-    sz->frac_off = 2 * R; sz->out_off = sz->frac_off + 8 * N * R; sz->n_back = sz->out_off + sz->n_out; sz->rows = N * R * Q;
+    lay_out_hist_set(sz, p, n_hist);
     return MCSAS_OK;
 }
 
@@ -426,31 +122,17 @@ static size_t hist_rep_chunk(size_t N, size_t Q, size_t R) { return std::max<siz
 // repetitions, Q doubles each; scaling [2][R]; volumes, weights, surfaces and visibility limits, [N][R] each.
 struct HistArrays { const double *q, *I, *sg, *c; double *cum, *sc, *v, *w, *s, *m; };
 
-// Of repetitions [r0, r0 + nr), whose rows begin at `rows` (row rl N + c = contribution c of repetition r0 + rl): cumInt = the sum
-// of the rows in contribution order (scatteringmodel.py:101), the closed-form scale / background fit (mcsas.py:559) and the
-// visibility limits.  Whoever filled the rows has filed their volumes and weights.
-static int launch_hist_fit_obs(const mcsas_problem *p, const HistArrays &a, size_t r0, unsigned nr, const double *rows) {
-    const int nq = p->nq, N = p->n_contrib, R = p->n_reps;
-    hist_colsum_kernel<<<dim3((unsigned)(((size_t)nq + 255) / 256), nr), 256>>>(nq, N, rows, a.cum);
-    HIPCHK(hipGetLastError());
-    hist_fit_cum_kernel<<<nr, WAVE>>>(nq, a.I, a.sg, R, (int)r0, a.cum, p->find_background != 0, p->positive_background != 0, a.sc);
-    HIPCHK(hipGetLastError());
-    hist_obs_kernel<<<dim3((unsigned)N, nr), WAVE>>>(nq, a.sg, N, R, (int)r0, rows, a.sc, a.v, a.w, a.m);
-    HIPCHK(hipGetLastError());
-    return MCSAS_OK;
-}
 // ---- partial intensities (mcsas_hip_histogram_partial, mcsas_hip_histogram_partial_device_rows): the scattering curve of only the
 // contributions inside a histogram's value range, and of each of its bins, taken from a block of rows while it still lies in HBM.
-#include "hist_partial_kernel.h"   // HistPartialDev, hist_partial_lds_bytes, hist_partial_kernel
-static_assert(HIST_PARTIAL_MAX_CONTRIBS == HIST_MAX_CONTRIBS, "hist_partial_kernel.h: the call's own cap");
-static bool hist2d_edges_ok(const double *e, int n);       // (further down: finite, and none below the one before it)
-
+// the n + 1 edges of an axis with bins: finite, and none below the one before it (the bin curves here, both axes of mcsas_hip_histogram2d)
+static bool hist2d_edges_ok(const double *e, int n) {
+    for (int k = 0; k <= n; ++k)
+        if (!std::isfinite(e[k]) || (k > 0 && e[k] < e[k - 1])) return false;
+    return true;
+}
 // What a checked call wants: the records of the wanted histograms in order, the doubles of their curves (per wanted histogram
 // range [nq][R], then bin [n_bin][nq][R] where the bins are wanted too), the most dynamic LDS a block of them asks for.
-struct HistPartialPlan {
-    std::vector<HistPartialDev> recs;
-    size_t n_out = 0, lds = 0;
-};
+struct HistPartialPlan { std::vector<HistPartialDev> recs; size_t n_out = 0, lds = 0; };
 constexpr size_t HIST_PARTIAL_MAX_BYTES = (size_t)2 << 30;
 
 // Every check of the wishes, after check_hist_set has passed the set itself: needs no device.  want == NULL with no histogram: nothing wanted.
@@ -485,60 +167,6 @@ static int check_hist_partial(const mcsas_problem *p, int n_hist, const mcsas_hi
     return MCSAS_OK;
 }
 
-// The wishes on the device: the records (one small upload) and the curves in a block of their own (one more download), beside a
-// HistOnDevice and declared ahead of it, so that they go back only after the set's guard has waited for what is queued.
-struct HistPartialOnDevice {
-    const HistPartialPlan *pl = nullptr;
-    const double *edges = nullptr;                             // the set's edges on the device (HistSizes::edge_off)
-    DevBuf<double> drec, dout;
-    Pinned hrec, hout;
-    size_t rec_doubles() const { return (sizeof(HistPartialDev) * pl->recs.size() + 7) / 8; }
-    int upload(const HistPartialPlan &pl_, const double *edges_on_device) {
-        pl = &pl_; edges = edges_on_device;
-        HIPCHK(drec.alloc(rec_doubles())); HIPCHK(dout.alloc(pl->n_out)); HIPCHK(hrec.alloc(rec_doubles())); HIPCHK(hout.alloc(pl->n_out));
-        memcpy(hrec.p, pl->recs.data(), sizeof(HistPartialDev) * pl->recs.size());
-        HIPCHK(hipMemcpyAsync(drec.p, hrec.p, hrec.bytes, hipMemcpyHostToDevice, nullptr));
-        return MCSAS_OK;
-    }
-    // hist_partial_kernel over repetitions [r0, r0 + nr), whose rows begin at `rows` and whose scales launch_hist_fit_obs has left in a.sc
-    int launch(const mcsas_problem *p, const HistArrays &a, size_t r0, unsigned nr, const double *rows) const {
-        const size_t nq = p->nq, N = p->n_contrib, n_want = pl->recs.size();
-        if (pl->lds > LDS_UNRAISED_MAX) HIPCHK(hipFuncSetAttribute((const void *)hist_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->lds));
-        const unsigned tiles = (unsigned)((nq + HIST_PARTIAL_TILE - 1) / HIST_PARTIAL_TILE);
-        for (size_t z0 = 0; z0 < nr; z0 += GRID_Y_MAX)
-            for (size_t y0 = 0; y0 < n_want; y0 += GRID_Y_MAX) {
-                const dim3 grid(tiles, (unsigned)std::min(GRID_Y_MAX, n_want - y0), (unsigned)std::min<size_t>(GRID_Y_MAX, nr - z0));
-                hist_partial_kernel<<<grid, WAVE, pl->lds>>>(p->nq, p->n_contrib, p->n_active, p->n_reps, (int)(r0 + z0), rows + z0 * N * nq, a.c, a.sc, edges,
-                                                            reinterpret_cast<const HistPartialDev *>(drec.p) + y0, dout.p);
-                HIPCHK(hipGetLastError());
-            }
-        return MCSAS_OK;
-    }
-    int download() {
-        HIPCHK(hipMemcpyAsync(hout.p, dout.p, hout.bytes, hipMemcpyDeviceToHost, nullptr));
-        return MCSAS_OK;
-    }
-    void unpack(double *partial) const { memcpy(partial, hout.p, sizeof(double) * pl->n_out); }
-};
-
-// The first half of histogram() for all repetitions, a chunk of them at a time: per repetition the rows of the problem's model with
-// their volumes, weights and surfaces, then launch_hist_fit_obs, then (where curves are wanted) hist_partial_kernel on the same rows.
-// drows holds chunk * N * Q doubles, a.cum chunk * Q.
-static int launch_hist_reps(const mcsas_problem *p, const ModelArgs &m, size_t chunk, const HistArrays &a, double *drows,
-                            const HistPartialOnDevice *partial = nullptr) {
-    const size_t R = p->n_reps;
-    const size_t lds = sizeof(double) * table_doubles_host(p->model_id, m.int_div);
-    for (size_t r0 = 0; r0 < R; r0 += chunk) {
-        const unsigned nr = (unsigned)std::min(chunk, R - r0);
-        if (int rc = launch_small_kernel<HistRowsFamily>(p->model_id, dim3((unsigned)p->n_contrib, nr), lds, m, p->nq, a.q, p->n_contrib, p->n_reps, r0,
-                                                         a.c, drows, a.v, a.w, a.s))
-            return rc;
-        if (int rc = launch_hist_fit_obs(p, a, r0, nr, drows)) return rc;
-        if (partial)
-            if (int rc = partial->launch(p, a, r0, nr, drows)) return rc;
-    }
-    return MCSAS_OK;
-}
 // A bins kernel — hist_bins_kernel or its batch form — over `grid`: its dynamic LDS is 3 N doubles (hist_bins_body), and the limit of
 // that is raised first where N asks for more than a kernel gets unasked
 template <class... P>
@@ -550,37 +178,116 @@ static int launch_hist_bins(void (*kernel)(P...), dim3 grid, size_t N, typename 
     return MCSAS_OK;
 }
 
-// A checked set on the device, as mcsas_hip_histogram and mcsas_hip_histogram_device_rows hold it: ONE packed upload (data vectors,
-// parameter sets, bin edges, histogram records) from a pinned staging block, the kernels back to back on the null stream, ONE packed
-// download — a call costs two transfers and no allocation once its block sizes have been seen (MemCache).  Between upload() and
-// finish() the entry point fills the rows its own way and calls launch_hist_fit_obs on them.
-// The members go in the reverse of this order: first the guard waits for what is queued, on every way out; only then the smearing
-// tables the kernels read, the staging blocks the copies read and write, and the device blocks go back to where the next call
-// would take them from.  (In an unnamed namespace: the library's list of symbols stays what it was.)
+// A checked set on the device and the one frame of every call that has one: ONE packed upload (data vectors, parameter sets, bin
+// edges, histogram records) from a pinned staging block, the kernels back to back on the null stream, ONE packed download — a call
+// costs two transfers and no allocation once its block sizes have been seen (MemCache).  An entry point is its checks, upload(),
+// run() with who fills a block of rows and which fit follows them, finish() (mcsas_hip_histogram_prep: download()), and what it
+// alone unpacks.  The members go in the reverse of this order: first the guard waits for what is queued, on every way out, a
+// failing rows callback's too; only then the smearing tables the kernels read, the staging blocks the copies read and write, the
+// device blocks and the rows go back to where the next call would take them from.  (In an unnamed namespace:
+// the library's list of symbols stays what it was.)
 namespace {
 struct HistOnDevice {
     const mcsas_problem *p = nullptr;
+    const ModelArgs *m = nullptr;                              // the model that fills the rows, or NULL: the caller does
     int n_hist = 0;
+    size_t block = 0;                                          // repetitions per block of rows
+    const double *rows = nullptr;                              // a block's rows: row rl N + c = contribution c of repetition r0 + rl
+    const HistPartialPlan *pl = nullptr;                       // the curves wanted: their records (one small upload) and the curves in a
+    bool curves = false;                                       // block of their own (one more download), where there are any
     HistSizes sz;
-    DevBuf<double> din, dback, dcum, dvws;
-    Pinned hin, hback;
+    DevBuf<double> drows;                                      // (the model's rows; the caller's are the caller's)
+    DevBuf<double> din, dback, dcum, dvws, drec, dcurves;
+    Pinned hin, hback, hrec, hcurves;
     SmearDev smear;                                            // (the built-in rows' tables; none where the rows are the caller's)
     SyncGuard sync_guard;
     HistArrays a{};
 
-    // `block_reps`: how many repetitions' summed rows a.cum holds
-    int upload(const mcsas_problem *p_, const double *contribs, int n_hist_, const mcsas_histogram_spec *specs, const HistSizes &sz_, size_t block_reps) {
-        p = p_; n_hist = n_hist_; sz = sz_;
+    // The set and the wishes (or NULL) to the device.  `block_reps`: how many repetitions share a block of rows.  m_: the problem's
+    // model fills them (its smearing tables go up here), or NULL and caller_rows is where the caller fills them.
+    int upload(const mcsas_problem *p_, const double *contribs, int n_hist_, const mcsas_histogram_spec *specs, const HistSizes &sz_, size_t block_reps,
+               ModelArgs *m_, const double *caller_rows, const HistPartialPlan *wishes) {
+        p = p_; m = m_; n_hist = n_hist_; sz = sz_; block = block_reps; pl = wishes; curves = pl && !pl->recs.empty();
         const size_t NR = (size_t)p->n_contrib * p->n_reps;
-        HIPCHK(din.alloc(sz.n_in)); HIPCHK(dback.alloc(sz.n_back)); HIPCHK(dcum.alloc(block_reps * p->nq)); HIPCHK(dvws.alloc(4 * NR));
+        if (m) HIPCHK(drows.alloc(block * p->n_contrib * p->nq));
+        rows = m ? drows.p : caller_rows;
+        HIPCHK(din.alloc(sz.n_in)); HIPCHK(dback.alloc(sz.n_back)); HIPCHK(dcum.alloc(block * p->nq));
+        if (!sz.vws_back) HIPCHK(dvws.alloc(4 * NR));
         HIPCHK(hin.alloc(sz.n_in)); HIPCHK(hback.alloc(sz.n_back));
         pack_hist_set(hin.p, p, contribs, n_hist, specs, sz);
         HIPCHK(hipMemcpyAsync(din.p, hin.p, hin.bytes, hipMemcpyHostToDevice, nullptr));
-        a = HistArrays{din.p, din.p + sz.I_off, din.p + sz.sg_off, din.p + sz.c_off, dcum.p, dback.p, dvws.p, dvws.p + NR, dvws.p + 2 * NR, dvws.p + 3 * NR};
+        double *vws = sz.vws_back ? dback.p + sz.frac_off : dvws.p;
+        a = HistArrays{din.p, din.p + sz.I_off, din.p + sz.sg_off, din.p + sz.c_off, dcum.p, dback.p, vws, vws + NR, vws + 2 * NR, vws + 3 * NR};
+        if (m)
+            if (int rc = smear.upload(p, p->nq, m_)) return rc;
+        if (curves) {
+            const size_t rec_bytes = sizeof(HistPartialDev) * pl->recs.size(), rec_doubles = (rec_bytes + 7) / 8;
+            HIPCHK(drec.alloc(rec_doubles)); HIPCHK(dcurves.alloc(pl->n_out)); HIPCHK(hrec.alloc(rec_doubles)); HIPCHK(hcurves.alloc(pl->n_out));
+            memcpy(hrec.p, pl->recs.data(), rec_bytes);
+            HIPCHK(hipMemcpyAsync(drec.p, hrec.p, hrec.bytes, hipMemcpyHostToDevice, nullptr));
+        }
+        return MCSAS_OK;
+    }
+    // who fills the rows, unless the caller: the problem's model, with their volumes, weights and surfaces
+    auto model_rows() {
+        return [this](size_t r0, unsigned nr) {
+            return launch_small_kernel<HistRowsFamily>(p->model_id, dim3((unsigned)p->n_contrib, nr), sizeof(double) * table_doubles_host(p->model_id, m->int_div),
+                                                       *m, p->nq, a.q, p->n_contrib, p->n_reps, r0, a.c, drows.p, a.v, a.w, a.s);
+        };
+    }
+    // which fit follows, where the points are one set: the closed-form scale / background fit (mcsas.py:559), the visibility limits
+    auto fit_obs() {
+        return [this](size_t r0, unsigned nr) {
+            const int nq = p->nq, N = p->n_contrib, R = p->n_reps;
+            hist_fit_cum_kernel<<<nr, WAVE>>>(nq, a.I, a.sg, R, (int)r0, a.cum, p->find_background != 0, p->positive_background != 0, a.sc);
+            HIPCHK(hipGetLastError());
+            hist_obs_kernel<<<dim3((unsigned)N, nr), WAVE>>>(nq, a.sg, N, R, (int)r0, rows, a.sc, a.v, a.w, a.m);
+            HIPCHK(hipGetLastError());
+            return (int)MCSAS_OK;
+        };
+    }
+    // hist_partial_kernel over repetitions [r0, r0 + nr), whose rows begin at `rows` and whose scales the fit has left in a.sc
+    int launch_curves(size_t r0, unsigned nr) {
+        const size_t nq = p->nq, N = p->n_contrib, n_want = pl->recs.size();
+        if (pl->lds > LDS_UNRAISED_MAX) HIPCHK(hipFuncSetAttribute((const void *)hist_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->lds));
+        const unsigned tiles = (unsigned)((nq + HIST_PARTIAL_TILE - 1) / HIST_PARTIAL_TILE);
+        for (size_t z0 = 0; z0 < nr; z0 += GRID_Y_MAX)
+            for (size_t y0 = 0; y0 < n_want; y0 += GRID_Y_MAX) {
+                const dim3 grid(tiles, (unsigned)std::min(GRID_Y_MAX, n_want - y0), (unsigned)std::min<size_t>(GRID_Y_MAX, nr - z0));
+                hist_partial_kernel<<<grid, WAVE, pl->lds>>>(p->nq, p->n_contrib, p->n_active, p->n_reps, (int)(r0 + z0), rows + z0 * N * nq, a.c, a.sc,
+                                                            din.p + sz.edge_off, reinterpret_cast<const HistPartialDev *>(drec.p) + y0, dcurves.p);
+                HIPCHK(hipGetLastError());
+            }
+        return MCSAS_OK;
+    }
+    // The first half of histogram(), a block of repetitions at a time: fill_rows(r0, nr) leaves the rows of repetitions [r0, r0 + nr)
+    // at `rows` and files their volumes, weights and surfaces; cumInt = the sum of the rows in contribution order
+    // (scatteringmodel.py:101); fit(r0, nr) leaves every repetition's scale in a.sc and every contribution's visibility limit in
+    // a.m; then, where curves are wanted, hist_partial_kernel on the same rows while they still lie in HBM.
+    template <class Rows, class Fit>
+    int run(Rows fill_rows, Fit fit) {
+        const size_t R = p->n_reps;
+        for (size_t r0 = 0; r0 < R; r0 += block) {
+            const unsigned nr = (unsigned)std::min(block, R - r0);
+            if (int rc = fill_rows(r0, nr)) return rc;
+            hist_colsum_kernel<<<dim3((unsigned)(((size_t)p->nq + 255) / 256), nr), 256>>>(p->nq, p->n_contrib, rows, a.cum);
+            HIPCHK(hipGetLastError());
+            if (int rc = fit(r0, nr)) return rc;
+            if (curves)
+                if (int rc = launch_curves(r0, nr)) return rc;
+        }
+        if (curves) HIPCHK(hipMemcpyAsync(hcurves.p, dcurves.p, hcurves.bytes, hipMemcpyDeviceToHost, nullptr));
+        return MCSAS_OK;
+    }
+    // the coming-back block, and the wait for everything queued
+    int download() {
+        HIPCHK(hipMemcpyAsync(hback.p, dback.p, hback.bytes, hipMemcpyDeviceToHost, nullptr));
+        HIPCHK(hipStreamSynchronize(nullptr));
+        sync_guard.armed = false;
         return MCSAS_OK;
     }
     // the second half of histogram() once every repetition has its scale and limits: fractions, bins, the download, the results
-    int finish(double *scaling, double *fractions, double *out) {
+    int finish(double *scaling, double *fractions, double *out, double *partial = nullptr) {
         const int N = p->n_contrib, R = p->n_reps;
         double *dfrac = dback.p + sz.frac_off;
         hist_fractions_kernel<<<(unsigned)R, WAVE>>>(N, R, a.sc, a.v, a.w, a.s, a.m, dfrac);
@@ -589,10 +296,9 @@ struct HistOnDevice {
             if (int rc = launch_hist_bins(hist_bins_kernel, dim3((unsigned)n_hist, (unsigned)R), N, N, p->n_active, R, a.c, dfrac, din.p + sz.edge_off,
                                           reinterpret_cast<const HistSpecDev *>(din.p + sz.spec_off), dback.p + sz.out_off))
                 return rc;
-        HIPCHK(hipMemcpyAsync(hback.p, dback.p, hback.bytes, hipMemcpyDeviceToHost, nullptr));
-        HIPCHK(hipStreamSynchronize(nullptr));
-        sync_guard.armed = false;
+        if (int rc = download()) return rc;
         unpack_hist_set(hback.p, sz, scaling, fractions, out);
+        if (curves) memcpy(partial, hcurves.p, sizeof(double) * pl->n_out);
         return MCSAS_OK;
     }
 };
@@ -600,33 +306,32 @@ struct HistOnDevice {
 
 // ------------------------------------------------------------------------------ one set: mcsas_hip_histogram_prep, mcsas_hip_histogram
 
+// The first half of histogram() alone (McSAS.histogram() goes on in Python, whatever the number of contributions): HistOnDevice
+// with no histograms and its own coming-back block, [scaling | volumes, weights, surfaces, visibility limits] in the one download.
+// check_hist_set's cap on the contributions is the bins kernel's and does not hold here.
 extern "C" int mcsas_hip_histogram_prep(const mcsas_problem *p, const double *contribs, double *scaling, double *vset,
                                         double *wset, double *sset, double *min_req_vol) {
-    if (!p || !contribs || !scaling || !vset || !wset || !sset || !min_req_vol || !p->q || !p->intensity || !p->sigma ||
-        p->nq < 1 || p->n_contrib < 1 || p->n_reps < 1)
-        return fail(MCSAS_EINVAL, "bad argument");
-    ModelArgs m;
-    if (int rc = fill_model_args(p, &m)) return rc;
-    DeviceGuard dev_guard;
-    if (int rc = select_device(p->device)) return rc;
-    const size_t Q = p->nq, P = p->n_active, N = p->n_contrib, R = p->n_reps;
-    const size_t chunk = hist_rep_chunk(N, Q, R);
-    DevBuf<double> dq, dI, dsg, dc, drows, dcum, dsc, dv, dw, ds, dm;
-    HIPCHK(dq.alloc(Q)); HIPCHK(dI.alloc(Q)); HIPCHK(dsg.alloc(Q)); HIPCHK(dc.alloc(N * P * R)); HIPCHK(drows.alloc(chunk * N * Q));
-    HIPCHK(dcum.alloc(chunk * Q)); HIPCHK(dsc.alloc(2 * R)); HIPCHK(dv.alloc(N * R)); HIPCHK(dw.alloc(N * R)); HIPCHK(ds.alloc(N * R)); HIPCHK(dm.alloc(N * R));
-    HIPCHK(hipMemcpy(dq.p, p->q, sizeof(double) * Q, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dI.p, p->intensity, sizeof(double) * Q, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dsg.p, p->sigma, sizeof(double) * Q, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dc.p, contribs, sizeof(double) * N * P * R, hipMemcpyHostToDevice));
-    SmearDev smear;
-    if (int rc = smear.upload(p, p->nq, &m)) return rc;
-    if (int rc = launch_hist_reps(p, m, chunk, HistArrays{dq.p, dI.p, dsg.p, dc.p, dcum.p, dsc.p, dv.p, dw.p, ds.p, dm.p}, drows.p)) return rc;
-    HIPCHK(hipMemcpy(scaling, dsc.p, sizeof(double) * 2 * R, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(vset, dv.p, sizeof(double) * N * R, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(wset, dw.p, sizeof(double) * N * R, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(sset, ds.p, sizeof(double) * N * R, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(min_req_vol, dm.p, sizeof(double) * N * R, hipMemcpyDeviceToHost));
-    return MCSAS_OK;
+    return no_bad_alloc("histogram_prep", [&]() -> int {
+        if (!p || !contribs || !scaling || !vset || !wset || !sset || !min_req_vol || !p->q || !p->intensity || !p->sigma ||
+            p->nq < 1 || p->n_contrib < 1 || p->n_reps < 1)
+            return fail(MCSAS_EINVAL, "bad argument");
+        ModelArgs m;
+        if (int rc = fill_model_args(p, &m)) return rc;
+        DeviceGuard dev_guard;
+        if (int rc = select_device(p->device)) return rc;
+        const size_t NR = (size_t)p->n_contrib * p->n_reps;
+        HistSizes sz;
+        lay_out_hist_set(&sz, p, 0);
+        sz.vws_back = true; sz.n_back = sz.frac_off + 4 * NR;
+        HistOnDevice d;
+        if (int rc = d.upload(p, contribs, 0, nullptr, sz, hist_rep_chunk(p->n_contrib, p->nq, p->n_reps), &m, nullptr, nullptr)) return rc;
+        if (int rc = d.run(d.model_rows(), d.fit_obs())) return rc;
+        if (int rc = d.download()) return rc;
+        memcpy(scaling, d.hback.p, sizeof(double) * sz.frac_off);
+        double *const back[4] = {vset, wset, sset, min_req_vol};
+        for (int i = 0; i < 4; ++i) memcpy(back[i], d.hback.p + sz.frac_off + i * NR, sizeof(double) * NR);
+        return MCSAS_OK;
+    });
 }
 
 // McSAS.histogram() complete (include/mcsas_hip.h): the set on the device (HistOnDevice), its rows by the model's kernel a chunk of
@@ -639,32 +344,20 @@ static int histogram_call(const mcsas_problem *p, const double *contribs, int32_
     if (int rc = check_hist_set(p, contribs, n_hist, specs, scaling, out, &m, &sz)) return rc;
     if (asked)
         if (int rc = check_hist_partial(p, n_hist, specs, want, partial, &pl)) return rc;
-    const bool curves = !pl.recs.empty();
     DeviceGuard dev_guard;
     if (int rc = select_device(p->device)) return rc;
-    const size_t Q = p->nq, N = p->n_contrib, chunk = hist_rep_chunk(N, Q, p->n_reps);
-    DevBuf<double> drows;                                      // (ahead of the set: it goes back after the set's guard has waited)
-    HistPartialOnDevice pt;                                    // (the same)
     HistOnDevice d;
-    HIPCHK(drows.alloc(chunk * N * Q));
-    if (int rc = d.upload(p, contribs, n_hist, specs, sz, chunk)) return rc;
-    if (int rc = d.smear.upload(p, p->nq, &m)) return rc;
-    if (curves)
-        if (int rc = pt.upload(pl, d.din.p + sz.edge_off)) return rc;
-    if (int rc = launch_hist_reps(p, m, chunk, d.a, drows.p, curves ? &pt : nullptr)) return rc;
-    if (curves)
-        if (int rc = pt.download()) return rc;
-    if (int rc = d.finish(scaling, fractions, out)) return rc;
-    if (curves) pt.unpack(partial);
-    return MCSAS_OK;
+    if (int rc = d.upload(p, contribs, n_hist, specs, sz, hist_rep_chunk(p->n_contrib, p->nq, p->n_reps), &m, nullptr, &pl)) return rc;
+    if (int rc = d.run(d.model_rows(), d.fit_obs())) return rc;
+    return d.finish(scaling, fractions, out, partial);
 }
 extern "C" int mcsas_hip_histogram(const mcsas_problem *p, const double *contribs, int32_t n_hist, const mcsas_histogram_spec *specs,
                                    double *scaling, double *fractions, double *out) {
-    return histogram_call(p, contribs, n_hist, specs, false, nullptr, scaling, fractions, out, nullptr);
+    return no_bad_alloc("histogram", [&] { return histogram_call(p, contribs, n_hist, specs, false, nullptr, scaling, fractions, out, nullptr); });
 }
 extern "C" int mcsas_hip_histogram_partial(const mcsas_problem *p, const double *contribs, int32_t n_hist, const mcsas_histogram_spec *specs,
                                            const int32_t *want, double *scaling, double *fractions, double *out, double *partial) {
-    return histogram_call(p, contribs, n_hist, specs, true, want, scaling, fractions, out, partial);
+    return no_bad_alloc("histogram_partial", [&] { return histogram_call(p, contribs, n_hist, specs, true, want, scaling, fractions, out, partial); });
 }
 
 // ------------------------------------------------------------------------------ the sets of a joint fit: mcsas_hip_histogram_sets
@@ -675,40 +368,30 @@ extern "C" int mcsas_hip_histogram_partial(const mcsas_problem *p, const double 
 extern "C" int mcsas_hip_histogram_sets(const mcsas_problem *p, const double *contribs, int32_t n_hist, const mcsas_histogram_spec *specs, int32_t n_sets,
                                         const int32_t *set_nq, int32_t scale_mode, int32_t ref_set, uint32_t visible_sets, double *scaling,
                                         double *fractions, double *out, mcsas_sets_result *sets) {
-    HistSetOffs off;
-    if (int rc = check_hist_sets_request(p, n_sets, set_nq, scale_mode, ref_set, visible_sets, sets, off.o)) return rc;
-    ModelArgs m; HistSizes sz;
-    if (const int rc = check_hist_set(p, contribs, n_hist, specs, scaling, out, &m, &sz)) { const std::string why = g_err; return fail(rc, "histogram_sets: %s", why.c_str()); }
     return no_bad_alloc("histogram_sets", [&]() -> int {
+        HistSetOffs off;
+        if (int rc = check_hist_sets_request(p, n_sets, set_nq, scale_mode, ref_set, visible_sets, sets, off.o)) return rc;
+        ModelArgs m; HistSizes sz;
+        if (int rc = check_hist_set(p, contribs, n_hist, specs, scaling, out, &m, &sz)) return fail_within(rc, "histogram_sets");
         DeviceGuard dev_guard;
         if (int rc = select_device(p->device)) return rc;
-        const size_t Q = p->nq, N = p->n_contrib, R = p->n_reps, chunk = hist_rep_chunk(N, Q, R);
+        const int nq = p->nq, N = p->n_contrib, R = p->n_reps, shared = scale_mode == MCSAS_SETS_SCALE_SHARED;
         const size_t fit_off = sz.n_back;                          // [2][MCSAS_MAX_SETS][R] behind the set's coming-back block
         sz.n_back += 2 * (size_t)MCSAS_MAX_SETS * R;
-        DevBuf<double> drows;                                      // (ahead of the set: it goes back after the set's guard has waited)
-        HistOnDevice d;
-        HIPCHK(drows.alloc(chunk * N * Q));
-        if (int rc = d.upload(p, contribs, n_hist, specs, sz, chunk)) return rc;
-        if (int rc = d.smear.upload(p, p->nq, &m)) return rc;      // (smearing is refused: the model's arguments say "none")
+        HistOnDevice d;                                            // (smearing is refused: the model's arguments say "none")
+        if (int rc = d.upload(p, contribs, n_hist, specs, sz, hist_rep_chunk(N, nq, R), &m, nullptr, nullptr)) return rc;
         double *const dfit = d.dback.p + fit_off;
         HIPCHK(hipMemsetAsync(dfit, 0, sizeof(double) * 2 * MCSAS_MAX_SETS * R, nullptr));
-        const size_t lds = sizeof(double) * table_doubles_host(p->model_id, m.int_div);
-        const int shared = scale_mode == MCSAS_SETS_SCALE_SHARED;
-        for (size_t r0 = 0; r0 < R; r0 += chunk) {
-            const unsigned nr = (unsigned)std::min(chunk, R - r0);
-            if (int rc = launch_small_kernel<HistRowsFamily>(p->model_id, dim3((unsigned)N, nr), lds, m, p->nq, d.a.q, p->n_contrib, p->n_reps, r0, d.a.c,
-                                                             drows.p, d.a.v, d.a.w, d.a.s))
-                return rc;
-            hist_colsum_kernel<<<dim3((unsigned)((Q + 255) / 256), nr), 256>>>(p->nq, p->n_contrib, drows.p, d.a.cum);
+        const HistArrays &a = d.a;
+        const int rc = d.run(d.model_rows(), [&](size_t r0, unsigned nr) {
+            hist_fit_sets_kernel<<<nr, WAVE>>>(nq, a.I, a.sg, R, (int)r0, a.cum, p->find_background != 0, n_sets, off, shared, ref_set, a.sc, dfit);
             HIPCHK(hipGetLastError());
-            hist_fit_sets_kernel<<<nr, WAVE>>>(p->nq, d.a.I, d.a.sg, (int)R, (int)r0, d.a.cum, p->find_background != 0, n_sets, off, shared, ref_set, d.a.sc,
-                                               dfit);
+            hist_obs_sets_kernel<<<dim3((unsigned)N, nr), WAVE>>>(nq, a.sg, N, R, (int)r0, d.rows, a.sc, dfit, n_sets, off, visible_sets, a.v, a.w, a.m);
             HIPCHK(hipGetLastError());
-            hist_obs_sets_kernel<<<dim3((unsigned)N, nr), WAVE>>>(p->nq, d.a.sg, (int)N, (int)R, (int)r0, drows.p, d.a.sc, dfit, n_sets, off, visible_sets,
-                                                                  d.a.v, d.a.w, d.a.m);
-            HIPCHK(hipGetLastError());
-        }
-        if (int rc = d.finish(scaling, fractions, out)) return rc;
+            return (int)MCSAS_OK;
+        });
+        if (rc) return rc;
+        if (int rc2 = d.finish(scaling, fractions, out)) return rc2;
         const double *hfit = d.hback.p + fit_off;
         for (int s = 0; s < n_sets; ++s) {
             memcpy(sets->scaling + (size_t)s * R, hfit + (size_t)s * R, sizeof(double) * R);
@@ -735,74 +418,67 @@ static int check_hist_rows_problem(const char *who, const mcsas_problem *p) {
     return MCSAS_OK;
 }
 extern "C" int mcsas_hip_histogram_rows_shape(const mcsas_problem *p, int64_t *min_rows, int64_t *useful_rows, int32_t *row_stride) {
-    if (int rc = check_hist_rows_problem("histogram_rows_shape", p)) return rc;
-    if (min_rows) *min_rows = p->n_contrib;
-    if (useful_rows) *useful_rows = (int64_t)hist_rows_useful(p->n_contrib, p->nq, p->n_reps);
-    if (row_stride) *row_stride = p->nq;
-    return MCSAS_OK;
+    return no_bad_alloc("histogram_rows_shape", [&]() -> int {
+        if (int rc = check_hist_rows_problem("histogram_rows_shape", p)) return rc;
+        if (min_rows) *min_rows = p->n_contrib;
+        if (useful_rows) *useful_rows = (int64_t)hist_rows_useful(p->n_contrib, p->nq, p->n_reps);
+        if (row_stride) *row_stride = p->nq;
+        return MCSAS_OK;
+    });
 }
 
 // The second half of mcsas_hip_histogram with the first half's rows handed over by the caller, a round of whole repetitions at a
 // time (include/mcsas_hip.h): hist_pset_kernel lays the round's parameter sets out for the callback, the callback fills d_rows and
-// d_vws, hist_take_vws_kernel files the three per-row values, and launch_hist_fit_obs reads the rows where they lie.
+// d_vws, hist_take_vws_kernel files the three per-row values, and HistOnDevice::run goes on with the rows where they lie.
 // After the last round the call is mcsas_hip_histogram again.  Every refusal of the arguments comes before a device is touched, the
 // buffers are looked at before anything is queued, and from the upload on the set's guard waits on every way out, a failing callback's too.
-// (`asked`, want, partial: as histogram_call takes them, for mcsas_hip_histogram_partial_device_rows)
+// (`asked`, want, partial: as histogram_call takes them, for mcsas_hip_histogram_partial_device_rows; the body runs under no_bad_alloc)
 static int histogram_device_rows_call(const mcsas_problem *p, const double *contribs, double *d_pset, double *d_rows, double *d_vws,
                                       int64_t capacity_rows, mcsas_device_rows_callback rows_cb, void *user, int32_t n_hist,
                                       const mcsas_histogram_spec *specs, bool asked, const int32_t *want, double *scaling, double *fractions,
                                       double *out, double *partial) {
     static const char who[] = "histogram_device_rows";
-    const struct { const char *name; const void *ptr; } needed[] = {{"problem", p}, {"contribs", contribs}, {"d_pset", d_pset}, {"d_rows", d_rows},
-                                                                    {"d_vws", d_vws}, {"rows_cb", (const void *)rows_cb}, {"out", out}};
-    for (const auto &a : needed)
-        if (!a.ptr) return fail(MCSAS_EINVAL, "%s: %s is NULL", who, a.name);
-    if (int rc = check_hist_rows_problem(who, p)) return rc;
-    HistSizes sz;
-    if (const int rc = check_hist_set(p, contribs, n_hist, specs, scaling, out, nullptr, &sz)) { const std::string why = g_err; return fail(rc, "%s: %s", who, why.c_str()); }
-    if (p->n_active < 1 || p->n_active > MCSAS_MAX_ACTIVE) return fail(MCSAS_EINVAL, "%s: n_active %d (1..%d)", who, p->n_active, MCSAS_MAX_ACTIVE);
-    if (capacity_rows < p->n_contrib)
-        return fail(MCSAS_EINVAL, "%s: capacity_rows %lld < %d = n_contrib, the rows of one repetition (mcsas_hip_histogram_rows_shape)", who,
-                    (long long)capacity_rows, p->n_contrib);
-    if (p->smear_nk != 0 || p->smear_locs || p->smear_q_offset || p->smear_weights)
-        return fail(MCSAS_EINVAL, "%s: a smearing table (smear_nk %d) is given, but the rows are the caller's: nothing here would apply it", who, p->smear_nk);
-    HistPartialPlan pl;
-    if (asked)
-        if (int rc = check_hist_partial(p, n_hist, specs, want, partial, &pl)) return rc;
-    const bool curves = !pl.recs.empty();
-    DeviceGuard dev_guard;
-    if (int rc = select_device(p->device)) return rc;
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    if (int rc = check_device_buffer(who, "d_pset", d_pset, dev)) return rc;
-    if (int rc = check_device_buffer(who, "d_rows", d_rows, dev)) return rc;
-    if (int rc = check_device_buffer(who, "d_vws", d_vws, dev)) return rc;
-    const size_t P = p->n_active, N = p->n_contrib, R = p->n_reps, cap = (size_t)capacity_rows;
-    const size_t per_round = std::min<size_t>({R, cap / N, GRID_Y_MAX});       // (whole repetitions)
-    HistPartialOnDevice pt;                                    // (ahead of the set: it goes back after the set's guard has waited)
-    HistOnDevice d;
-    if (int rc = d.upload(p, contribs, n_hist, specs, sz, per_round)) return rc;
-    if (curves)
-        if (int rc = pt.upload(pl, d.din.p + sz.edge_off)) return rc;
-    for (size_t r0 = 0; r0 < R; r0 += per_round) {
-        const unsigned nr = (unsigned)std::min(per_round, R - r0);
-        const size_t n_rows = nr * N;
-        hist_pset_kernel<<<(unsigned)((n_rows * P + 255) / 256), 256>>>((int)N, (int)P, (int)R, (int)r0, n_rows, d.a.c, d_pset);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(nullptr));                                 // the sets are complete before the caller reads them
-        const int rc = rows_cb(user, (int32_t)n_rows);
-        if (rc) return fail(MCSAS_ECALLBACK, "%s: rows callback returned %d", who, rc);
-        hist_take_vws_kernel<<<(unsigned)((n_rows + 255) / 256), 256>>>((int)N, (int)R, (int)r0, n_rows, cap, d_vws, d.a.v, d.a.w, d.a.s);
-        HIPCHK(hipGetLastError());
-        if (int rc2 = launch_hist_fit_obs(p, d.a, r0, nr, d_rows)) return rc2;
-        if (curves)                                                            // (the round's rows are still the caller's last answer)
-            if (int rc2 = pt.launch(p, d.a, r0, nr, d_rows)) return rc2;
-    }
-    if (curves)
-        if (int rc = pt.download()) return rc;
-    if (int rc = d.finish(scaling, fractions, out)) return rc;
-    if (curves) pt.unpack(partial);
-    return MCSAS_OK;
+    return no_bad_alloc(who, [&]() -> int {
+        const struct { const char *name; const void *ptr; } needed[] = {{"problem", p}, {"contribs", contribs}, {"d_pset", d_pset}, {"d_rows", d_rows},
+                                                                        {"d_vws", d_vws}, {"rows_cb", (const void *)rows_cb}, {"out", out}};
+        for (const auto &a : needed)
+            if (!a.ptr) return fail(MCSAS_EINVAL, "%s: %s is NULL", who, a.name);
+        if (int rc = check_hist_rows_problem(who, p)) return rc;
+        HistSizes sz;
+        if (int rc = check_hist_set(p, contribs, n_hist, specs, scaling, out, nullptr, &sz)) return fail_within(rc, "%s", who);
+        if (p->n_active < 1 || p->n_active > MCSAS_MAX_ACTIVE) return fail(MCSAS_EINVAL, "%s: n_active %d (1..%d)", who, p->n_active, MCSAS_MAX_ACTIVE);
+        if (capacity_rows < p->n_contrib)
+            return fail(MCSAS_EINVAL, "%s: capacity_rows %lld < %d = n_contrib, the rows of one repetition (mcsas_hip_histogram_rows_shape)", who,
+                        (long long)capacity_rows, p->n_contrib);
+        if (p->smear_nk != 0 || p->smear_locs || p->smear_q_offset || p->smear_weights)
+            return fail(MCSAS_EINVAL, "%s: a smearing table (smear_nk %d) is given, but the rows are the caller's: nothing here would apply it", who, p->smear_nk);
+        HistPartialPlan pl;
+        if (asked)
+            if (int rc = check_hist_partial(p, n_hist, specs, want, partial, &pl)) return rc;
+        DeviceGuard dev_guard;
+        if (int rc = select_device(p->device)) return rc;
+        int dev = 0;
+        HIPCHK(hipGetDevice(&dev));
+        if (int rc = check_device_buffer(who, "d_pset", d_pset, dev)) return rc;
+        if (int rc = check_device_buffer(who, "d_rows", d_rows, dev)) return rc;
+        if (int rc = check_device_buffer(who, "d_vws", d_vws, dev)) return rc;
+        const size_t P = p->n_active, N = p->n_contrib, R = p->n_reps, cap = (size_t)capacity_rows;
+        const size_t per_round = std::min<size_t>({R, cap / N, GRID_Y_MAX});       // (whole repetitions)
+        HistOnDevice d;
+        if (int rc = d.upload(p, contribs, n_hist, specs, sz, per_round, nullptr, d_rows, &pl)) return rc;
+        const int rc = d.run([&](size_t r0, unsigned nr) {
+            const size_t n_rows = nr * N;
+            hist_pset_kernel<<<(unsigned)((n_rows * P + 255) / 256), 256>>>((int)N, (int)P, (int)R, (int)r0, n_rows, d.a.c, d_pset);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(nullptr));                                 // the sets are complete before the caller reads them
+            if (const int cb = rows_cb(user, (int32_t)n_rows)) return fail(MCSAS_ECALLBACK, "%s: rows callback returned %d", who, cb);
+            hist_take_vws_kernel<<<(unsigned)((n_rows + 255) / 256), 256>>>((int)N, (int)R, (int)r0, n_rows, cap, d_vws, d.a.v, d.a.w, d.a.s);
+            HIPCHK(hipGetLastError());
+            return (int)MCSAS_OK;
+        }, d.fit_obs());
+        if (rc) return rc;
+        return d.finish(scaling, fractions, out, partial);
+    });
 }
 extern "C" int mcsas_hip_histogram_device_rows(const mcsas_problem *p, const double *contribs, double *d_pset, double *d_rows, double *d_vws,
                                                int64_t capacity_rows, mcsas_device_rows_callback rows_cb, void *user, int32_t n_hist,
@@ -933,133 +609,127 @@ static int launch_hist_chunk(const std::vector<HistBatchSet> &sets, const HistCh
 extern "C" int mcsas_hip_histogram_batch(int32_t n_sets, const mcsas_problem *problems, const double *const *contribs, const int32_t *n_hist,
                                          const mcsas_histogram_spec *const *specs, double *const *scaling, double *const *fractions,
                                          double *const *out) {
-    if (n_sets < 0) return fail(MCSAS_EINVAL, "histogram_batch: n_sets %d", n_sets);
-    if (n_sets == 0) return MCSAS_OK;
-    if (!problems || !contribs || !n_hist || !specs || !scaling || !out)
-        return fail(MCSAS_EINVAL, "histogram_batch: NULL table (problems, contribs, n_hist, specs, scaling and out are needed; fractions may be NULL)");
-    std::vector<HistBatchSet> sets((size_t)n_sets);
-    const size_t budget = hist_batch_budget();
-    for (int s = 0; s < n_sets; ++s) {
-        HistBatchSet &t = sets[s] = HistBatchSet{&problems[s], contribs[s], n_hist[s], specs[s], scaling[s], fractions ? fractions[s] : nullptr, out[s]};
-        if (t.p->device != problems[0].device)
-            return fail(MCSAS_EINVAL, "histogram_batch: set %d names device %d, set 0 device %d: one device per batch", s, t.p->device, problems[0].device);
-        const int rc = check_hist_set(t.p, t.contribs, t.n_hist, t.specs, t.scaling, t.out, &t.m, &t.sz);
-        if (rc) { const std::string why = g_err; return fail(rc, "histogram_batch: set %d: %s", s, why.c_str()); }
-        t.single = is_plugin_model(t.p->model_id) || t.sz.rows * sizeof(double) > budget;
-    }
-    DeviceGuard dev_guard;
-    if (int rc = select_device(problems[0].device)) return rc;
-    const HistBatchPlan pl = plan_hist_chunks(sets, budget);
-    std::vector<SmearDev> smears(pl.n_rec);                    // (freed after the guard below has waited for the kernels)
-    DevBuf<double> din, dback, drows, dcum, dvws;
-    Pinned hin, hback;
-    SyncGuard sync_guard;
-    if (pl.n_rec) {
-        HIPCHK(din.alloc(pl.in_total())); HIPCHK(dback.alloc(pl.n_back)); HIPCHK(drows.alloc(pl.max_rows)); HIPCHK(dcum.alloc(pl.max_cum)); HIPCHK(dvws.alloc(pl.n_vws));
-        HIPCHK(hin.alloc(pl.in_total())); HIPCHK(hback.alloc(pl.n_back));
-        if (int rc = pack_hist_batch(pl, sets, smears, hin.p)) return rc;
-        HIPCHK(hipMemcpyAsync(din.p, hin.p, hin.bytes, hipMemcpyHostToDevice, nullptr));
-    }
-    const HistBatchDev dev{reinterpret_cast<const HistSetDev *>(din.p + pl.n_in), reinterpret_cast<const ChainRef *>(din.p + pl.n_in + pl.rec_d()),
-                           din.p, dback.p, drows.p, dcum.p, dvws.p};
-    size_t next_chunk = 0;
-    for (int s = 0; s < n_sets; ++s) {
-        const HistBatchSet &t = sets[s];
-        if (t.single) {
-            const int rc = mcsas_hip_histogram(t.p, t.contribs, t.n_hist, t.specs, t.scaling, t.fractions, t.out);
-            if (rc) { const std::string why = g_err; return fail(rc, "histogram_batch: set %d: %s", s, why.c_str()); }
-        } else if (next_chunk < pl.chunks.size() && pl.chunks[next_chunk].first == (size_t)s) {   // (otherwise: inside a chunk already launched)
-            if (int rc = launch_hist_chunk(sets, pl.chunks[next_chunk++], dev)) return rc;
+    return no_bad_alloc("histogram_batch", [&]() -> int {
+        if (n_sets < 0) return fail(MCSAS_EINVAL, "histogram_batch: n_sets %d", n_sets);
+        if (n_sets == 0) return MCSAS_OK;
+        if (!problems || !contribs || !n_hist || !specs || !scaling || !out)
+            return fail(MCSAS_EINVAL, "histogram_batch: NULL table (problems, contribs, n_hist, specs, scaling and out are needed; fractions may be NULL)");
+        std::vector<HistBatchSet> sets((size_t)n_sets);
+        const size_t budget = hist_batch_budget();
+        for (int s = 0; s < n_sets; ++s) {
+            HistBatchSet &t = sets[s] = HistBatchSet{&problems[s], contribs[s], n_hist[s], specs[s], scaling[s], fractions ? fractions[s] : nullptr, out[s]};
+            if (t.p->device != problems[0].device)
+                return fail(MCSAS_EINVAL, "histogram_batch: set %d names device %d, set 0 device %d: one device per batch", s, t.p->device, problems[0].device);
+            if (int rc = check_hist_set(t.p, t.contribs, t.n_hist, t.specs, t.scaling, t.out, &t.m, &t.sz)) return fail_within(rc, "histogram_batch: set %d", s);
+            t.single = is_plugin_model(t.p->model_id) || t.sz.rows * sizeof(double) > budget;
         }
-    }
-    if (pl.n_rec) {
-        HIPCHK(hipMemcpyAsync(hback.p, dback.p, hback.bytes, hipMemcpyDeviceToHost, nullptr));
-        HIPCHK(hipStreamSynchronize(nullptr));
-    }
-    sync_guard.armed = false;
-    for (const HistBatchSet &t : sets)
-        if (!t.single) unpack_hist_set(hback.p + t.back_off, t.sz, t.scaling, t.fractions, t.out);
-    return MCSAS_OK;
+        DeviceGuard dev_guard;
+        if (int rc = select_device(problems[0].device)) return rc;
+        const HistBatchPlan pl = plan_hist_chunks(sets, budget);
+        std::vector<SmearDev> smears(pl.n_rec);                    // (freed after the guard below has waited for the kernels)
+        DevBuf<double> din, dback, drows, dcum, dvws;
+        Pinned hin, hback;
+        SyncGuard sync_guard;
+        if (pl.n_rec) {
+            HIPCHK(din.alloc(pl.in_total())); HIPCHK(dback.alloc(pl.n_back)); HIPCHK(drows.alloc(pl.max_rows)); HIPCHK(dcum.alloc(pl.max_cum)); HIPCHK(dvws.alloc(pl.n_vws));
+            HIPCHK(hin.alloc(pl.in_total())); HIPCHK(hback.alloc(pl.n_back));
+            if (int rc = pack_hist_batch(pl, sets, smears, hin.p)) return rc;
+            HIPCHK(hipMemcpyAsync(din.p, hin.p, hin.bytes, hipMemcpyHostToDevice, nullptr));
+        }
+        const HistBatchDev dev{reinterpret_cast<const HistSetDev *>(din.p + pl.n_in), reinterpret_cast<const ChainRef *>(din.p + pl.n_in + pl.rec_d()),
+                               din.p, dback.p, drows.p, dcum.p, dvws.p};
+        size_t next_chunk = 0;
+        for (int s = 0; s < n_sets; ++s) {
+            const HistBatchSet &t = sets[s];
+            if (t.single) {
+                if (int rc = mcsas_hip_histogram(t.p, t.contribs, t.n_hist, t.specs, t.scaling, t.fractions, t.out)) return fail_within(rc, "histogram_batch: set %d", s);
+            } else if (next_chunk < pl.chunks.size() && pl.chunks[next_chunk].first == (size_t)s) {   // (otherwise: inside a chunk already launched)
+                if (int rc = launch_hist_chunk(sets, pl.chunks[next_chunk++], dev)) return rc;
+            }
+        }
+        if (pl.n_rec) {
+            HIPCHK(hipMemcpyAsync(hback.p, dback.p, hback.bytes, hipMemcpyDeviceToHost, nullptr));
+            HIPCHK(hipStreamSynchronize(nullptr));
+        }
+        sync_guard.armed = false;
+        for (const HistBatchSet &t : sets)
+            if (!t.single) unpack_hist_set(hback.p + t.back_off, t.sz, t.scaling, t.fractions, t.out);
+        return MCSAS_OK;
+    });
 }
 
 
 // ------------------------------------------------------------------------------ two parameters at once: mcsas_hip_histogram2d
 // The joint histogram of two parameter columns from fractions a histogram call returned (include/mcsas_hip.h): no model, no rows.
 // Per axis every rule is hist_bins_body's, so that one y column that holds every value gives that kernel's bins bit for bit.
-#include "hist2d_kernel.h"   // Hist2dSpecDev, hist2d_staged_bytes, hist2d_shared_bytes, hist2d_kernel
-static_assert(HIST2D_MAX_CONTRIBS == HIST_MAX_CONTRIBS, "hist2d_kernel.h: the 1-D cap");
 
 // a histogram's outputs: bins and observability [n_bin_x][n_bin_y][R] each, then the moments [7][R] (hist2d_body)
 static size_t hist2d_out_doubles(size_t cells, size_t R) { return 2 * cells * R + 7 * R; }
-// the n + 1 edges of an axis with bins: finite, and none below the one before it
-static bool hist2d_edges_ok(const double *e, int n) {
-    for (int k = 0; k <= n; ++k)
-        if (!std::isfinite(e[k]) || (k > 0 && e[k] < e[k - 1])) return false;
-    return true;
-}
 
 // One packed upload [contribs | fractions | edges | records], hist2d_kernel on the null stream, one packed download, as HistOnDevice
 // holds a set; every refusal of the arguments comes before a device is touched.
 extern "C" int mcsas_hip_histogram2d(int32_t n_contrib, int32_t n_active, int32_t n_reps, const double *contribs, const double *fractions,
                                      int32_t n_hist, const mcsas_histogram2d_spec *specs, double *out, int32_t device) {
     static const char who[] = "histogram2d";
-    if (n_hist < 0) return fail(MCSAS_EINVAL, "%s: n_hist %d", who, n_hist);
-    if (n_hist == 0) return MCSAS_OK;
-    if (!contribs || !fractions || !specs || !out) return fail(MCSAS_EINVAL, "%s: NULL table (contribs, fractions, specs and out are needed)", who);
-    if (n_contrib < 1 || n_contrib > HIST_MAX_CONTRIBS || n_active < 1 || n_reps < 1)
-        return fail(MCSAS_EINVAL, "%s: n_contrib %d (1..%d: a repetition's contributions are staged in LDS), n_active %d, n_reps %d (each >= 1)", who,
-                    n_contrib, HIST_MAX_CONTRIBS, n_active, n_reps);
-    const size_t N = n_contrib, P = n_active, R = n_reps;
-    if ((size_t)n_hist * R > (size_t)INT32_MAX) return fail(MCSAS_EINVAL, "%s: n_hist %d x n_reps %d blocks", who, n_hist, n_reps);
-    size_t n_edges = 0, n_out = 0, shared = 0;
-    for (int h = 0; h < n_hist; ++h) {
-        const mcsas_histogram2d_spec &sp = specs[h];
-        if (sp.reserved != 0) return fail(MCSAS_EINVAL, "%s: histogram %d: reserved %d (must be 0)", who, h, sp.reserved);
-        if (sp.param_x < 0 || sp.param_x >= n_active || sp.param_y < 0 || sp.param_y >= n_active || sp.weighting < 0 || sp.weighting > 3)
-            return fail(MCSAS_EINVAL, "%s: histogram %d: param_x %d, param_y %d (0..%d), weighting %d (0..3)", who, h, sp.param_x, sp.param_y,
-                        n_active - 1, sp.weighting);
-        if (sp.n_bin_x < 0 || sp.n_bin_y < 0 || (int64_t)sp.n_bin_x * sp.n_bin_y > HIST2D_MAX_CELLS)
-            return fail(MCSAS_EINVAL, "%s: histogram %d: n_bin_x %d, n_bin_y %d (each >= 0, at most %d cells)", who, h, sp.n_bin_x, sp.n_bin_y, HIST2D_MAX_CELLS);
-        if ((sp.n_bin_x > 0 && !sp.edges_x) || (sp.n_bin_y > 0 && !sp.edges_y))
-            return fail(MCSAS_EINVAL, "%s: histogram %d: an axis with bins has no edges", who, h);
-        if ((sp.n_bin_x > 0 && !hist2d_edges_ok(sp.edges_x, sp.n_bin_x)) || (sp.n_bin_y > 0 && !hist2d_edges_ok(sp.edges_y, sp.n_bin_y)))
-            return fail(MCSAS_EINVAL, "%s: histogram %d: edges must be finite and non-decreasing", who, h);
-        const size_t cells = (size_t)sp.n_bin_x * sp.n_bin_y;
-        if (cells) n_edges += (size_t)sp.n_bin_x + sp.n_bin_y + 2;
-        n_out += hist2d_out_doubles(cells, R);
-        shared = std::max(shared, hist2d_shared_bytes(N, sp.n_bin_x, sp.n_bin_y));
-    }
-    DeviceGuard dev_guard;
-    if (int rc = select_device(device)) return rc;
-    const size_t f_off = N * P * R, e_off = f_off + 8 * N * R, s_off = e_off + n_edges, n_in = s_off + (sizeof(Hist2dSpecDev) * (size_t)n_hist + 7) / 8;
-    DevBuf<double> din, dout;
-    Pinned hin, hout;
-    SyncGuard sync_guard;                                      // (after the blocks: it waits before they go back)
-    HIPCHK(din.alloc(n_in)); HIPCHK(dout.alloc(n_out)); HIPCHK(hin.alloc(n_in)); HIPCHK(hout.alloc(n_out));
-    memcpy(hin.p, contribs, sizeof(double) * f_off);
-    memcpy(hin.p + f_off, fractions, sizeof(double) * 8 * N * R);
-    Hist2dSpecDev *hs = reinterpret_cast<Hist2dSpecDev *>(hin.p + s_off);
-    size_t eo = 0, oo = 0;
-    for (int h = 0; h < n_hist; ++h) {
-        const mcsas_histogram2d_spec &sp = specs[h];
-        const size_t cells = (size_t)sp.n_bin_x * sp.n_bin_y;
-        hs[h] = Hist2dSpecDev{sp.param_x, sp.param_y, sp.weighting, sp.n_bin_x, sp.n_bin_y, 0, (int64_t)eo, (int64_t)oo, sp.lower_x, sp.upper_x, sp.lower_y, sp.upper_y};
-        if (cells) {
-            memcpy(hin.p + e_off + eo, sp.edges_x, sizeof(double) * ((size_t)sp.n_bin_x + 1));
-            memcpy(hin.p + e_off + eo + sp.n_bin_x + 1, sp.edges_y, sizeof(double) * ((size_t)sp.n_bin_y + 1));
-            eo += (size_t)sp.n_bin_x + sp.n_bin_y + 2;
+    return no_bad_alloc(who, [&]() -> int {
+        if (n_hist < 0) return fail(MCSAS_EINVAL, "%s: n_hist %d", who, n_hist);
+        if (n_hist == 0) return MCSAS_OK;
+        if (!contribs || !fractions || !specs || !out) return fail(MCSAS_EINVAL, "%s: NULL table (contribs, fractions, specs and out are needed)", who);
+        if (n_contrib < 1 || n_contrib > HIST_MAX_CONTRIBS || n_active < 1 || n_reps < 1)
+            return fail(MCSAS_EINVAL, "%s: n_contrib %d (1..%d: a repetition's contributions are staged in LDS), n_active %d, n_reps %d (each >= 1)", who,
+                        n_contrib, HIST_MAX_CONTRIBS, n_active, n_reps);
+        const size_t N = n_contrib, P = n_active, R = n_reps;
+        if ((size_t)n_hist * R > (size_t)INT32_MAX) return fail(MCSAS_EINVAL, "%s: n_hist %d x n_reps %d blocks", who, n_hist, n_reps);
+        size_t n_edges = 0, n_out = 0, shared = 0;
+        for (int h = 0; h < n_hist; ++h) {
+            const mcsas_histogram2d_spec &sp = specs[h];
+            if (sp.reserved != 0) return fail(MCSAS_EINVAL, "%s: histogram %d: reserved %d (must be 0)", who, h, sp.reserved);
+            if (sp.param_x < 0 || sp.param_x >= n_active || sp.param_y < 0 || sp.param_y >= n_active || sp.weighting < 0 || sp.weighting > 3)
+                return fail(MCSAS_EINVAL, "%s: histogram %d: param_x %d, param_y %d (0..%d), weighting %d (0..3)", who, h, sp.param_x, sp.param_y,
+                            n_active - 1, sp.weighting);
+            if (sp.n_bin_x < 0 || sp.n_bin_y < 0 || (int64_t)sp.n_bin_x * sp.n_bin_y > HIST2D_MAX_CELLS)
+                return fail(MCSAS_EINVAL, "%s: histogram %d: n_bin_x %d, n_bin_y %d (each >= 0, at most %d cells)", who, h, sp.n_bin_x, sp.n_bin_y, HIST2D_MAX_CELLS);
+            if ((sp.n_bin_x > 0 && !sp.edges_x) || (sp.n_bin_y > 0 && !sp.edges_y))
+                return fail(MCSAS_EINVAL, "%s: histogram %d: an axis with bins has no edges", who, h);
+            if ((sp.n_bin_x > 0 && !hist2d_edges_ok(sp.edges_x, sp.n_bin_x)) || (sp.n_bin_y > 0 && !hist2d_edges_ok(sp.edges_y, sp.n_bin_y)))
+                return fail(MCSAS_EINVAL, "%s: histogram %d: edges must be finite and non-decreasing", who, h);
+            const size_t cells = (size_t)sp.n_bin_x * sp.n_bin_y;
+            if (cells) n_edges += (size_t)sp.n_bin_x + sp.n_bin_y + 2;
+            n_out += hist2d_out_doubles(cells, R);
+            shared = std::max(shared, hist2d_shared_bytes(N, sp.n_bin_x, sp.n_bin_y));
         }
-        oo += hist2d_out_doubles(cells, R);
-    }
-    HIPCHK(hipMemcpyAsync(din.p, hin.p, hin.bytes, hipMemcpyHostToDevice, nullptr));
-    const size_t lds = hist2d_staged_bytes(N) + shared;
-    if (lds > LDS_UNRAISED_MAX) HIPCHK(hipFuncSetAttribute((const void *)hist2d_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hist2d_kernel<<<(unsigned)((size_t)n_hist * R), WAVE, lds>>>((int)N, (int)P, (int)R, din.p, din.p + f_off, din.p + e_off,
-                                                                 reinterpret_cast<const Hist2dSpecDev *>(din.p + s_off), dout.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hout.p, dout.p, hout.bytes, hipMemcpyDeviceToHost, nullptr));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    sync_guard.armed = false;
-    memcpy(out, hout.p, sizeof(double) * n_out);
-    return MCSAS_OK;
+        DeviceGuard dev_guard;
+        if (int rc = select_device(device)) return rc;
+        const size_t f_off = N * P * R, e_off = f_off + 8 * N * R, s_off = e_off + n_edges, n_in = s_off + (sizeof(Hist2dSpecDev) * (size_t)n_hist + 7) / 8;
+        DevBuf<double> din, dout;
+        Pinned hin, hout;
+        SyncGuard sync_guard;                                      // (after the blocks: it waits before they go back)
+        HIPCHK(din.alloc(n_in)); HIPCHK(dout.alloc(n_out)); HIPCHK(hin.alloc(n_in)); HIPCHK(hout.alloc(n_out));
+        memcpy(hin.p, contribs, sizeof(double) * f_off);
+        memcpy(hin.p + f_off, fractions, sizeof(double) * 8 * N * R);
+        Hist2dSpecDev *hs = reinterpret_cast<Hist2dSpecDev *>(hin.p + s_off);
+        size_t eo = 0, oo = 0;
+        for (int h = 0; h < n_hist; ++h) {
+            const mcsas_histogram2d_spec &sp = specs[h];
+            const size_t cells = (size_t)sp.n_bin_x * sp.n_bin_y;
+            hs[h] = Hist2dSpecDev{sp.param_x, sp.param_y, sp.weighting, sp.n_bin_x, sp.n_bin_y, 0, (int64_t)eo, (int64_t)oo, sp.lower_x, sp.upper_x, sp.lower_y, sp.upper_y};
+            if (cells) {
+                memcpy(hin.p + e_off + eo, sp.edges_x, sizeof(double) * ((size_t)sp.n_bin_x + 1));
+                memcpy(hin.p + e_off + eo + sp.n_bin_x + 1, sp.edges_y, sizeof(double) * ((size_t)sp.n_bin_y + 1));
+                eo += (size_t)sp.n_bin_x + sp.n_bin_y + 2;
+            }
+            oo += hist2d_out_doubles(cells, R);
+        }
+        HIPCHK(hipMemcpyAsync(din.p, hin.p, hin.bytes, hipMemcpyHostToDevice, nullptr));
+        const size_t lds = hist2d_staged_bytes(N) + shared;
+        if (lds > LDS_UNRAISED_MAX) HIPCHK(hipFuncSetAttribute((const void *)hist2d_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hist2d_kernel<<<(unsigned)((size_t)n_hist * R), WAVE, lds>>>((int)N, (int)P, (int)R, din.p, din.p + f_off, din.p + e_off,
+                                                                     reinterpret_cast<const Hist2dSpecDev *>(din.p + s_off), dout.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(hout.p, dout.p, hout.bytes, hipMemcpyDeviceToHost, nullptr));
+        HIPCHK(hipStreamSynchronize(nullptr));
+        sync_guard.armed = false;
+        memcpy(out, hout.p, sizeof(double) * n_out);
+        return MCSAS_OK;
+    });
 }

@@ -16,6 +16,8 @@
 // ------------------------------------------------------------------------------ error plumbing (host_decide.hip)
 extern thread_local std::string g_err;
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+// an inner check's refusal passed on in the caller's name: "<fmt and its arguments>: <what g_err said>", the code kept
+int fail_within(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 #define HIPCHK(expr)                                                                         \
     do {                                                                                     \
         hipError_t e_ = (expr);                                                              \

@@ -29,7 +29,7 @@ __device__ __forceinline__ Contrib<M> prepared_contrib(const ModelArgs &m, doubl
 }
 
 // min over q of sigma*vf / (A*I_c(q)), I_c != 0 (mcsas.py:582-590), +inf where no point is kept: one wave, `intensity(k)` being
-// I_c(q[k]) — evaluated by observability_kernel, read from the stored row by hist_obs_body (host_hist.hip)
+// I_c(q[k]) — evaluated by observability_kernel, read from the stored row by hist_obs_body (hist_kernels.h)
 template <class Intensity>
 __device__ __forceinline__ void visibility_limit(int nq, const double *sigma, double vf, double A, Intensity intensity, double *min_req) {
     double best = __builtin_inf();

@@ -1,4 +1,4 @@
-"""Shared by test_hist2d_host.py and test_hist2d_gpu.py: the joint histogram of two parameters (csrc/host_hist.hip hist2d_body,
+"""Shared by test_hist2d_host.py and test_hist2d_gpu.py: the joint histogram of two parameters (csrc/hist2d_kernel.h hist2d_body,
 include/mcsas_hip.h mcsas_hip_histogram2d; parameter.Histogram2D.calc is its numpy form) as
   - the cases: contributions, fractions and limits of the test's own choosing, no model behind them,
   - exact values (mpmath, 60 digits) of the discrete operation at those doubles,

@@ -1,5 +1,5 @@
 """Shared by test_hist_exact_host.py and test_hist_exact_gpu.py: what McSAS.histogram() reads off a set of contributions (visibility
-limits, fractions, bins, observability, cumulative distribution, moments: csrc/host_hist.hip hist_obs_body, hist_fractions_body,
+limits, fractions, bins, observability, cumulative distribution, moments: csrc/hist_kernels.h hist_obs_body, hist_fractions_body,
 hist_bins_body), engine.observability (csrc/small_kernels.h observability_kernel; both limits are its visibility_limit) and the
 re-binning of raw data (csrc/host_calls.hip rebin_kernel) as
   - the cases,
@@ -33,7 +33,7 @@ from exact import R, V, gamma, reduced_sum, slots_of, sum_roundings
 from fit_exact import emu_bgfit, exactly, tree
 
 WEIGHTS = ("vol", "num", "int", "surf")
-FRAC8 = ("vf", "nf", "qf", "sf", "mv", "mn", "mq", "ms")          # frac8 = [vf nf qf sf | mv mn mq ms][N][R] (host_hist.hip:85)
+FRAC8 = ("vf", "nf", "qf", "sf", "mv", "mn", "mq", "ms")          # frac8 = [vf nf qf sf | mv mn mq ms][N][R] (hist_kernels.h: hist_fractions_body)
 C_EXP = 0.6666666
 
 

@@ -1,5 +1,5 @@
 """The joint fit of several data sets with ONE scale for all of them (include/mcsas_hip.h: mcsas_hip_analyse_sets_mode with
-MCSAS_SETS_SCALE_SHARED; csrc/chain_sets.h) and the histogram of a joint fit (mcsas_hip_histogram_sets; csrc/host_hist.hip:
+MCSAS_SETS_SCALE_SHARED; csrc/chain_sets.h) and the histogram of a joint fit (mcsas_hip_histogram_sets; csrc/hist_kernels.h:
 hist_fit_sets_kernel, hist_obs_sets_kernel), restated from the parts the other restatements are made of.  A plain module like
 sets_exact.py: nothing in here is collected, nothing is fitted to a device's output.
 

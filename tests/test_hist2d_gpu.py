@@ -1,4 +1,4 @@
-"""The joint histogram of two parameters on the device (csrc/host_hist.hip hist2d_body through engine.histogram2d_device) against
+"""The joint histogram of two parameters on the device (csrc/hist2d_kernel.h hist2d_body through engine.histogram2d_device) against
 exact values, each inside the bound derived for it from the kernel's operation order (tests/hist2d_exact.py; the same cases and
 bounds hold parameter.Histogram2D.calc and the emulation in test_hist2d_host.py, so a device value outside a bound they keep is the
 kernel's).  No assertion here has a tolerance that is not such a bound; membership, empty cells, the NaN -> 0 of a cell, the 0 of an

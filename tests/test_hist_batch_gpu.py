@@ -282,3 +282,27 @@ def test_histogram_prep_equals_the_device_histogram(N, nq, find_background, posi
         assert not np.isnan(prep[0]).any() and not np.isnan(prep[4]).any()
     np.testing.assert_array_equal(prep[0], scaling)
     np.testing.assert_array_equal(prep[4], fractions["vol"][1])
+
+
+def test_histogram_prep_with_a_smearing_table_equals_the_device_histogram():
+    """The same with a smearing table, which both calls hand to the device in the one place that makes the set there: 9
+    contributions (one over the eight-at-a-time column sum), 65 q (one over the 64 lanes), 3 smearing points, 2 repetitions.  The
+    table is a slit's, locs = sqrt(q² + offset²), typed in here; it is in the numbers, and scaling and limits are the same bits."""
+    import types
+    N, nq, R = 9, 65, 2
+    q = np.geomspace(1e8, 3e9, nq)
+    lo, hi = np.pi / 3e9, np.pi / 1e8
+    m = mcsas_amd.Sphere(); m.radius.setActiveRange((lo, hi))
+    rs = np.random.RandomState(965)
+    I, sig = 1.0 + rs.rand(nq), 0.1 + rs.rand(nq)
+    contribs = rs.uniform(lo, hi, (N, 1, R))
+    offset = np.array([0., 4e7, 8e7])
+    smear = types.SimpleNamespace(locs=np.sqrt(q[:, None] ** 2 + offset[None, :] ** 2), q_offset=offset, weights=np.array([1., 0.7, 0.2]))
+    prep = engine.histogram_prep(m.setup(), q, I, sig, contribs, C_EXP, smear=smear)
+    scaling, fractions, hists = engine.histogram_device(m.setup(), q, I, sig, contribs, C_EXP, [], smear=smear)
+    assert prep[0].shape == (2, R) and prep[4].shape == (N, R) and hists == []
+    assert np.isfinite(prep[0]).all() and not np.isnan(prep[4]).any()
+    np.testing.assert_array_equal(prep[0], scaling)
+    np.testing.assert_array_equal(prep[4], fractions["vol"][1])
+    plain = engine.histogram_prep(m.setup(), q, I, sig, contribs, C_EXP)
+    assert (plain[0][0] != prep[0][0]).all() and (plain[4] != prep[4]).any()

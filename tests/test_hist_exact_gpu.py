@@ -1,5 +1,5 @@
 """What McSAS.histogram() reads off a set of contributions on the device — visibility limits, fractions, bins, observability,
-cumulative distribution, moments (csrc/host_hist.hip hist_obs_body, hist_fractions_body, hist_bins_body) — engine.observability and
+cumulative distribution, moments (csrc/hist_kernels.h hist_obs_body, hist_fractions_body, hist_bins_body) — engine.observability and
 the re-binning (csrc/host_calls.hip rebin_kernel) against exact values, each inside the bound derived for it from the kernel's
 operation order (tests/hist_exact.py, tests/exact.py; the same cases and bounds hold the numpy emulations in
 test_hist_exact_host.py, so a device value outside a bound its emulation keeps is the kernel's).  No assertion here has a tolerance

@@ -1,5 +1,5 @@
-"""GPU tests of histogram() on rows the caller fills on the device (mcsas_hip_histogram_device_rows, csrc/host_hist.hip:
-hist_pset_kernel + hist_take_vws_kernel in front of the hist_* kernels of mcsas_hip_histogram).
+"""GPU tests of histogram() on rows the caller fills on the device (mcsas_hip_histogram_device_rows, csrc/host_hist.hip;
+csrc/hist_kernels.h: hist_pset_kernel + hist_take_vws_kernel in front of the hist_* kernels of mcsas_hip_histogram).
 
 Fed the rows, volumes, weights and surfaces of a BUILT-IN model (engine.model_calc: model_rows_kernel is hist_rows_body's text under
 -ffp-contract=off) every array must be mcsas_hip_histogram's of that model bit for bit, however the repetitions are cut into rounds:
@@ -9,6 +9,9 @@ project holds a torch model's histogram to against the built-in's (test_device_r
 on one MI355X, over every array of every case (the tests print it per array): 0 — both paths see the same torch rows and keep
 contribution order in every sum."""
 import ctypes as C
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -311,3 +314,76 @@ def test_failures_leave_the_next_call_intact(sphere):
     assert raw(C.c_void_p(host_rows.ctypes.data), failing) == -1                       # MCSAS_EINVAL
     assert "d_rows is not device memory" in lib.mcsas_hip_last_error().decode() and entered == [300]
     assert_same_triple(engine.histogram_device_rows(*args, good), f["ref"], "after the refusals")
+
+
+# engine.histogram_device of the built-in sphere on the arrays of an .npz, every array of the result into another: run by a fresh
+# process for the test below, and by the test itself
+_PLAIN_CALL = """
+import sys
+import numpy as np
+import mcsas_amd
+from mcsas_amd import engine
+
+def plain_call(g):
+    lo, hi = float(g["lo"]), float(g["hi"])
+    m = mcsas_amd.Sphere(); m.radius.setActiveRange((lo, hi))
+    spec = dict(param_index=0, yweight="vol", edges=g["edges"], lower=lo, upper=hi)
+    sc, fr, hs = engine.histogram_device(m.setup(), g["q"], g["I"], g["sig"], g["contribs"], float(g["c_exp"]), [spec])
+    out = dict(scaling=sc, **{k: hs[0][k] for k in ("bins", "obs", "cdf", "moments")})
+    for k, (frac, limit) in fr.items():
+        out["frac_" + k], out["limit_" + k] = frac, limit
+    return out
+
+if __name__ == "__main__":
+    np.savez(sys.argv[2], **plain_call(np.load(sys.argv[1])))
+"""
+
+
+def test_a_callback_failing_in_a_later_round_leaves_the_plain_call_intact(tmp_path):
+    """8 contributions x 3 q x 3 repetitions with room for one repetition's rows: three rounds, and the callback reports failure in
+    the second, with the first round's kernels and the second's parameter sets behind it.  The call is MCSAS_ECALLBACK, and
+    mcsas_hip_histogram of the same sizes — the same staging blocks from the cache — then gives the bits a process that never saw
+    the failure gives: the set's guard waited before the blocks went back."""
+    N, nq, R = 8, 3, 3
+    rs = np.random.RandomState(83)
+    q = np.geomspace(1e8, 3e9, nq)
+    lo, hi = np.pi / 3e9, np.pi / 1e8
+    inputs = dict(q=q, I=1.0 + rs.rand(nq), sig=0.1 + rs.rand(nq), contribs=rs.uniform(lo, hi, (N, 1, R)), lo=lo, hi=hi,
+                  edges=np.geomspace(lo, hi, 5), c_exp=C_EXP)
+    np.savez(tmp_path / "in.npz", **inputs)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    r = subprocess.run([sys.executable, "-c", _PLAIN_CALL, str(tmp_path / "in.npz"), str(tmp_path / "fresh.npz")], cwd=root, env=env,
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    fresh = np.load(tmp_path / "fresh.npz")
+    assert np.isfinite(fresh["scaling"]).all() and (fresh["bins"] != 0).any()
+
+    lib = _lib.load()
+    m = mcsas_amd.Sphere(); m.radius.setActiveRange((lo, hi))
+    spec = dict(param_index=0, yweight="vol", edges=inputs["edges"], lower=lo, upper=hi)
+    call = engine._HistogramCall(m.setup(), q, inputs["I"], inputs["sig"], inputs["contribs"], 0.0, [spec])
+    call.prob.c.model_id = engine.MODEL_HOST
+    dev = torch.device("cuda", torch.cuda.current_device())
+    pset = torch.zeros((N, 1), dtype=torch.float64, device=dev)
+    rows = torch.ones((N, nq), dtype=torch.float64, device=dev)
+    vws = torch.ones((3, N), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+    entered = []
+
+    def failing_second(user, n):
+        entered.append(n)
+        return 7 if len(entered) == 2 else 0
+    rc = lib.mcsas_hip_histogram_device_rows(C.byref(call.prob.c), _lib.as_dp(call.contribs), C.c_void_p(pset.data_ptr()), C.c_void_p(rows.data_ptr()),
+                                             C.c_void_p(vws.data_ptr()), N, _lib.DeviceRowsCallback(failing_second), None, len(call.specs),
+                                             call.arr, _lib.as_dp(call.sc), _lib.as_dp(call.frac), _lib.as_dp(call.out))
+    assert rc == -6 and entered == [N, N]                                              # MCSAS_ECALLBACK, in round 2 of 3
+    assert "rows callback returned 7" in lib.mcsas_hip_last_error().decode()
+    np.testing.assert_array_equal(pset.cpu().numpy()[:, 0], inputs["contribs"][:, 0, 1])    # (round 2's sets were laid out)
+
+    scope = {"__name__": "plain_call"}
+    exec(_PLAIN_CALL, scope)
+    here = scope["plain_call"](inputs)
+    assert sorted(here) == sorted(fresh.files)
+    for k in here:
+        assert _equal(here[k], fresh[k]), k

@@ -1,4 +1,4 @@
-"""The histogram of a joint fit on the device (mcsas_hip_histogram_sets; csrc/host_hist.hip: hist_fit_sets_kernel,
+"""The histogram of a joint fit on the device (mcsas_hip_histogram_sets; csrc/hist_kernels.h: hist_fit_sets_kernel,
 hist_obs_sets_kernel) against mcsas_hip_histogram where the two must agree bit for bit, and against the exact restatement
 tests/sets_shared_exact.py with the bounds derived there and in tests/hist_exact.py / tests/fit_exact.py.  No assertion has a tolerance
 that is not such a bound; which contribution is in which bin and where NaN, +-inf and an exact 0 stand are compared by equality.

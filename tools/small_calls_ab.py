@@ -5,13 +5,17 @@ after their last device-to-host copy,
   - engine.histogram_device_batch of 8 such sets,
   - engine.histogram_device_rows at the shape of tools/hist_rows_ab.py (100 q x 200 x 10, four 50-bin histograms, a sphere in torch),
   - engine.model_calc for 400 rows x 512 q,
-and prints one JSON line.  Run it in fresh processes alternating between the trees, then hand the lines to --md:
+  - engine.histogram_prep, the call McSAS.histogram() makes, at the benchmark's shape,
+  - engine.histogram_device at that shape with the range and bin curves of its histogram (partial=2),
+  - engine.histogram_sets of that shape's points as two sets (256 + 256 q),
+and prints one JSON line.  With --dump DIR every array of each call's result goes to DIR as well (one .npy each), for
+tools/cmp_dumps.py to compare the trees' bits.  Run it in fresh processes alternating between the trees, then hand the lines to --md:
 
     for t in PARENT . PARENT .; do python tools/small_calls_ab.py --tree $t >> ab.jsonl; done
     python tools/small_calls_ab.py --md profiles/small_calls_refactor_ab.md ab.jsonl
 
 A call counts as unchanged where the difference of the two trees' medians is no larger than the spread (max - min) of the first
-tree's own repeats."""
+tree's own repeats, and as faster where the second tree's median is lower by more than that."""
 import argparse
 import json
 import os
@@ -20,10 +24,24 @@ import time
 
 import numpy as np
 
-CALLS = ("histogram_device", "histogram_device_batch x8", "histogram_device_rows", "model_calc")
+CALLS = ("histogram_device", "histogram_device_batch x8", "histogram_device_rows", "model_calc", "histogram_prep", "histogram_device partial=2",
+         "histogram_sets x2")
 
 
-def measure(tree, repeats, warmup):
+def arrays_of(x, name, out):
+    """every numpy array in a call's result (tuples, lists and dicts of them), named by its place"""
+    if isinstance(x, dict):
+        for k in x:
+            arrays_of(x[k], "%s.%s" % (name, k), out)
+    elif isinstance(x, (tuple, list)):
+        for i, v in enumerate(x):
+            arrays_of(v, "%s.%d" % (name, i), out)
+    elif x is not None:
+        out[name] = np.asarray(x)
+    return out
+
+
+def measure(tree, repeats, warmup, dump=None):
     import torch                                    # (ahead of the library's first load: engine._one_hip_runtime)
     sys.path.insert(0, os.path.abspath(tree))
     import mcsas_amd
@@ -64,11 +82,18 @@ def measure(tree, repeats, warmup):
         lambda: engine.histogram_device(**item),
         lambda: engine.histogram_device_batch([item] * 8),
         lambda: engine.histogram_device_rows(rsetup, rq, rI, rsig, rcontribs, rspecs, torch_sphere),
-        lambda: engine.model_calc(setup, q, pset, 0.6666666, want_rows=True))))
+        lambda: engine.model_calc(setup, q, pset, 0.6666666, want_rows=True),
+        lambda: engine.histogram_prep(setup, q, I, sig, contribs, 0.6666666),
+        lambda: engine.histogram_device(**item, partial=[2]),
+        lambda: engine.histogram_sets(setup, [(q[:256], I[:256], sig[:256]), (q[256:], I[256:], sig[256:])], contribs, 0.6666666, specs))))
     out = dict(tree=tree, device=torch.cuda.get_device_name(0), repeats=repeats, ms={})
     for name, call in calls.items():
         for _ in range(warmup):
-            call()
+            result = call()
+        if dump:
+            os.makedirs(dump, exist_ok=True)
+            for k, a in arrays_of(result, name.replace(" ", "_"), {}).items():
+                np.save(os.path.join(dump, k + ".npy"), a)
         t = []
         for _ in range(repeats):
             torch.cuda.synchronize()
@@ -104,7 +129,7 @@ def table(md, files):
                 f.write("| `%s` | %s | %.3f | %.3f | %.3f | %.3f | %s |\n" % (c, names[t], np.median(ms), ms.min(), ms.max(), np.ptp(ms),
                                                                           " / ".join("%.3f" % np.median(p) for p in per)))
             d = med[trees[1]][0] - med[trees[0]][0]
-            verdicts.append("`%s` %+.3f ms against a spread of %.3f ms: %s" % (c, d, med[trees[0]][1], "within" if abs(d) <= med[trees[0]][1] else "OUTSIDE"))
+            verdicts.append("`%s` %+.3f ms against a spread of %.3f ms: %s" % (c, d, med[trees[0]][1], "within" if abs(d) <= med[trees[0]][1] else ("faster" if d < 0 else "OUTSIDE")))
         f.write("\nDifference of the medians (this tree - parent) against the spread of the parent's own repeats: " + "; ".join(verdicts) + ".\n")
     print(open(md).read())
 
@@ -115,9 +140,10 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=11)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--md", default=None)
+    ap.add_argument("--dump", default=None)
     ap.add_argument("files", nargs="*")
     a = ap.parse_args()
     if a.md:
         table(a.md, a.files)
     else:
-        measure(a.tree or os.path.dirname(os.path.dirname(os.path.abspath(__file__))), a.repeats, a.warmup)
+        measure(a.tree or os.path.dirname(os.path.dirname(os.path.abspath(__file__))), a.repeats, a.warmup, a.dump)
