@@ -29,8 +29,7 @@
 //                      values are lane k of prow (mcsas.py:385-390).  Only the traced kernels (chain_wave.h, chain_wide.h) put anything here
     double *rset = a.rset + (size_t)rep * N * P;
     double *cache = CACHE ? CHAIN_CACHE_PTR(a.cache + (size_t)rep * a.cache_rows * qpad) : nullptr;
-    DrawSource src{a.replay ? a.replay + (size_t)rep * a.replay_len : nullptr, a.replay_len, a.seed,
-                   (uint32_t)(a.rep_offset + rep)};
+    DrawSource src MCSAS_CHAIN_DRAWS(a, rep);
     int overflow = 0;
     CHAIN_STATE
     uint64_t draw_pos = 0;                 // uniforms consumed so far by this rep (all attempts)
@@ -52,22 +51,7 @@
         for (int n0 = 0; n0 < N; n0 += WAVE) {
             const int n = n0 + lane;
             double row[MCSAS_MAX_ACTIVE] = {0., 0., 0., 0.};
-            if (n < N) {
-#pragma unroll
-                for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)
-                    if (p < P) {
-                        if (given) row[p] = rset[(size_t)n * P + p];
-                        else if (a.start_from_min) row[p] = a.start_value[p];    // mcsas.py:310-315
-                        else {
-                            double u = src.at(draw_pos + (uint64_t)p * N + n, overflow);   // parameter-major
-                            row[p] = gen_transform(a.gen_kind[p], u) * (a.gen_hi[p] - a.gen_lo[p]) + a.gen_lo[p];
-                        }
-                        if (CHAIN_FIRST) rset[(size_t)n * P + p] = row[p];
-                    }
-            } else {
-#pragma unroll
-                for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p) row[p] = a.gen_lo[p] > 0. ? a.gen_lo[p] : 1e-9;
-            }
+            MCSAS_INITIAL_ROW(row, n, n < N, given, CHAIN_FIRST, draw_pos, overflow)
             Contrib<M> mine;                                       // (where a chain has several waves, each prepares all 64: the same numbers)
             mine.prepare(a.model, row);
             // model.calc(data, rset, c): rows accumulated in contribution order (scatteringmodel.py:90-101)
@@ -115,14 +99,7 @@
             // P uniforms per step in parameter order (mcsas.py:358)
             double prow[MCSAS_MAX_ACTIVE] = {0., 0., 0., 0.};
             int povf = 0;
-#pragma unroll
-            for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)
-                if (p < P) {
-                    double u = 0.5;
-                    if (num_iter + lane < a.max_iter)
-                        u = src.at(draw_pos + (uint64_t)(num_iter + lane) * P + p, povf);
-                    prow[p] = gen_transform(a.gen_kind[p], u) * (a.gen_hi[p] - a.gen_lo[p]) + a.gen_lo[p];
-                }
+            MCSAS_PROPOSAL_ROW(prow, draw_pos + (uint64_t)(num_iter + lane) * P, num_iter + lane < a.max_iter, povf)
             Contrib<M> prop;
             prop.prepare(a.model, prow);
 

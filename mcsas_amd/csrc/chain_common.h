@@ -141,4 +141,63 @@ struct DrawSource {
     }
 };
 
+// ---------------------------------------------------------------------------------- how a chain draws
+// What every execution mode does with its uniforms, written once: the repetition's stream, a uniform's value, an attempt's initial
+// set, a step's proposal and the number of draws the initial set takes.  draw_value is a function; the rest are macros that stand
+// for the tokens a site would otherwise carry, because a function for any of them was measured to change the kernels' code (DESIGN
+// §4.1a; _Pragma("unroll") is `#pragma unroll` as a macro can say it).  What stays at a site is what differs between the modes:
+// which thread owns which contribution, where the attempt's draws begin, and where an overflow is latched.
+
+// The stream of repetition `rep` of analysis `a`, as DrawSource's initialiser: DrawSource src MCSAS_CHAIN_DRAWS(a, rep);
+#define MCSAS_CHAIN_DRAWS(a, rep) \
+    {a.replay ? a.replay + (size_t)(rep) * a.replay_len : nullptr, a.replay_len, a.seed, (uint32_t)(a.rep_offset + (rep))}
+
+// uniform u as a value of active parameter p: the generator's transform, stretched over the parameter's range
+__device__ __forceinline__ double draw_value(const ChainArgs &a, int p, double u) {
+    return gen_transform(a.gen_kind[p], u) * (a.gen_hi[p] - a.gen_lo[p]) + a.gen_lo[p];
+}
+
+// Uniforms an attempt's initial set consumes (generateParameters(N): N per active parameter; none from the minimum, mcsas.py:310-315).
+// chain_body.inc and chain_sets.h advance draw_pos by it in words of their own (`if (!a.start_from_min) draw_pos += N * P`): this
+// macro and a function in its place both changed their kernels' code (profiles/r34_summary.md).
+#define MCSAS_INITIAL_DRAWS(a, N, P) (a.start_from_min ? 0 : (uint64_t)N * P)
+
+// Contribution `n` of an attempt's initial set into row[] (MCSAS_MAX_ACTIVE doubles, zeroed by the site) and into rset.  From the
+// scope: `a` (ChainArgs), `src` (the chain's DrawSource), `rset` (the repetition's sets), `N`, `P` (a.n_contrib, a.model.n_active).
+//   real     this thread holds a contribution (n < N, and whatever else the mode asks); the others get the padding row, which
+//            any model evaluates without a division by zero and nobody reads
+//   given    the set the host left in rset stands in for the draws (false folds away)
+//   writes   this thread writes row[] to rset
+//   base     where the attempt's draws begin in the stream; the set is drawn parameter-major (scatteringmodel.py:117-127)
+//   ovf      int lvalue: set when a draw lies behind a replay stream's end
+#define MCSAS_INITIAL_ROW(row, n, real, given, writes, base, ovf) \
+    if (real) { \
+        _Pragma("unroll") \
+        for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p) \
+            if (p < P) { \
+                if (given) row[p] = rset[(size_t)(n) * P + p]; \
+                else if (a.start_from_min) row[p] = a.start_value[p];             /* mcsas.py:310-315 */ \
+                else { \
+                    double u = src.at((base) + (uint64_t)p * N + (n), ovf); \
+                    row[p] = draw_value(a, p, u); \
+                } \
+                if (writes) rset[(size_t)(n) * P + p] = row[p]; \
+            } \
+    } else { \
+        _Pragma("unroll") \
+        for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p) row[p] = a.gen_lo[p] > 0. ? a.gen_lo[p] : 1e-9; \
+    }
+
+// A step's proposal into prow[]: generateParameters() draws P uniforms in parameter order (mcsas.py:358), the first of them draw
+// `pos` of the stream; where `live` is false (a step behind max_iter) every uniform is 0.5 and nothing is drawn.  `ovf` as above;
+// `a`, `src`, `P` from the scope.
+#define MCSAS_PROPOSAL_ROW(prow, pos, live, ovf) \
+    _Pragma("unroll") \
+    for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p) \
+        if (p < P) { \
+            double u = 0.5; \
+            if (live) u = src.at((pos) + p, ovf); \
+            prow[p] = draw_value(a, p, u); \
+        }
+
 }  // namespace mcsas

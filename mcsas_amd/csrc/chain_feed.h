@@ -136,8 +136,7 @@ __global__ __launch_bounds__(64) void feed_draw_kernel(const FeedArgs f, double 
     const int n = f.count[rep], kind = f.kind[rep];
     if (n == 0 || kind == FEED_END) return;
     const int N = a.n_contrib, P = a.model.n_active;
-    const DrawSource src{a.replay ? a.replay + (size_t)rep * a.replay_len : nullptr, a.replay_len, a.seed,
-                         (uint32_t)(a.rep_offset + rep)};
+    const DrawSource src MCSAS_CHAIN_DRAWS(a, rep);
     const uint64_t draw_pos = (uint64_t)pos[rep];
     const int64_t num_iter = pos[a.n_reps + rep];
     double *out = pset + (size_t)f.first[rep] * P;
@@ -149,7 +148,7 @@ __global__ __launch_bounds__(64) void feed_draw_kernel(const FeedArgs f, double 
             else {
                 const double u = kind == FEED_INIT ? src.at(draw_pos + (uint64_t)c * N + k, overflow)      // parameter-major
                                                    : src.at(draw_pos + (uint64_t)(num_iter + k) * P + c, overflow);   // mcsas.py:358
-                v = gen_transform(a.gen_kind[c], u) * (a.gen_hi[c] - a.gen_lo[c]) + a.gen_lo[c];
+                v = draw_value(a, c, u);
             }
             out[(size_t)k * P + c] = v;
         }

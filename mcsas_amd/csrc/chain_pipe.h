@@ -100,7 +100,7 @@ __global__ void pipe_reset_kernel(const PipeArgs *pap) {
     PipeSnap s{};
     s.attempt = 0; s.t_init = 0; s.alive = 1;
     s.init_base = 0;
-    s.step_base = a.start_from_min ? 0 : (uint64_t)a.n_contrib * a.model.n_active;
+    s.step_base = MCSAS_INITIAL_DRAWS(a, a.n_contrib, a.model.n_active);
     ch.snap[0] = s; ch.snap[1] = s;
     ch.attempts = 1; ch.chi2 = 0.; ch.A = 1.; ch.t_start = wall_clock64();
     pa.chains[rep] = ch;

@@ -11,8 +11,10 @@
 //
 // Everything else is the chain of chain_body.inc — draw order (N·P at an attempt's start, P per step, retries going on in the
 // stream), round-robin index, ft + (new - old), clip and generator transforms, start_from_minimum, the stop word, Philox keyed by
-// rep_offset + rep — and with one set the sums, X and chi² are the numbers of chain_wave_kernel<M, QPL, true, false>.  The text is
-// this kernel's own: a hook or a template parameter in chain_body.inc changes every existing kernel's object.
+// rep_offset + rep — and with one set the sums, X and chi² are the numbers of chain_wave_kernel<M, QPL, true, false>.  How the chain
+// draws is the text every family shares (chain_common.h: MCSAS_CHAIN_DRAWS, draw_value, MCSAS_INITIAL_ROW,
+// MCSAS_PROPOSAL_ROW); the step, the fits and the outputs are this kernel's own: a hook or a template parameter in chain_body.inc
+// changes every existing kernel's object.
 //
 // Layout: as chain_wave.h (q index i in lane i & 63, register slot i >> 6), and set s is padded to 64 k_s entries (pad: q of the
 // set's first point, w = wI = I = 0), so that a register slot belongs to ONE set for the whole wave.  Bit j of SetsArgs::end_mask
@@ -180,8 +182,7 @@ __global__ __launch_bounds__(64, MCSAS_SETS_MIN_WAVES(QPL)) void chain_sets_kern
 
     double *rset = a.rset + (size_t)rep * N * P;
     double *cache = a.cache + (size_t)rep * a.cache_rows * qpad;
-    DrawSource src{a.replay ? a.replay + (size_t)rep * a.replay_len : nullptr, a.replay_len, a.seed,
-                   (uint32_t)(a.rep_offset + rep)};
+    DrawSource src MCSAS_CHAIN_DRAWS(a, rep);
     int overflow = 0;
     uint64_t draw_pos = 0;                 // uniforms consumed so far by this rep (all attempts)
     const uint64_t t_start = wall_clock64();
@@ -200,21 +201,7 @@ __global__ __launch_bounds__(64, MCSAS_SETS_MIN_WAVES(QPL)) void chain_sets_kern
         for (int n0 = 0; n0 < N; n0 += WAVE) {
             const int n = n0 + lane;
             double row[MCSAS_MAX_ACTIVE] = {0., 0., 0., 0.};
-            if (n < N) {
-#pragma unroll
-                for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)
-                    if (p < P) {
-                        if (a.start_from_min) row[p] = a.start_value[p];             // mcsas.py:310-315
-                        else {
-                            double u = src.at(draw_pos + (uint64_t)p * N + n, overflow);   // parameter-major
-                            row[p] = gen_transform(a.gen_kind[p], u) * (a.gen_hi[p] - a.gen_lo[p]) + a.gen_lo[p];
-                        }
-                        rset[(size_t)n * P + p] = row[p];
-                    }
-            } else {
-#pragma unroll
-                for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p) row[p] = a.gen_lo[p] > 0. ? a.gen_lo[p] : 1e-9;
-            }
+            MCSAS_INITIAL_ROW(row, n, n < N, false, true, draw_pos, overflow)
             Contrib<M> mine;
             mine.prepare(a.model, row);
             // model.calc(data, rset, c): rows accumulated in contribution order (scatteringmodel.py:90-101)
@@ -263,14 +250,7 @@ __global__ __launch_bounds__(64, MCSAS_SETS_MIN_WAVES(QPL)) void chain_sets_kern
             // proposals for the next 64 steps, one per lane: P uniforms per step in parameter order (mcsas.py:358)
             double prow[MCSAS_MAX_ACTIVE] = {0., 0., 0., 0.};
             int povf = 0;
-#pragma unroll
-            for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)
-                if (p < P) {
-                    double u = 0.5;
-                    if (num_iter + lane < a.max_iter)
-                        u = src.at(draw_pos + (uint64_t)(num_iter + lane) * P + p, povf);
-                    prow[p] = gen_transform(a.gen_kind[p], u) * (a.gen_hi[p] - a.gen_lo[p]) + a.gen_lo[p];
-                }
+            MCSAS_PROPOSAL_ROW(prow, draw_pos + (uint64_t)(num_iter + lane) * P, num_iter + lane < a.max_iter, povf)
             Contrib<M> prop;
             prop.prepare(a.model, prow);
 

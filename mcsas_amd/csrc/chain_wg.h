@@ -98,21 +98,7 @@ __device__ __forceinline__ void wg_init_rows(const ChainArgs &a, const WgGeom &g
     for (int nb = 0; nb < N; nb += T) {
         const int n = nb + lane * W + wave;
         double row[MCSAS_MAX_ACTIVE] = {0., 0., 0., 0.};
-        if (n < N) {
-#pragma unroll
-            for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)
-                if (p < P) {
-                    if (a.start_from_min) row[p] = a.start_value[p];
-                    else {
-                        double u = src.at(draw_pos + (uint64_t)p * N + n, ovf_init);
-                        row[p] = gen_transform(a.gen_kind[p], u) * (a.gen_hi[p] - a.gen_lo[p]) + a.gen_lo[p];
-                    }
-                    rset[(size_t)n * P + p] = row[p];
-                }
-        } else {
-#pragma unroll
-            for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p) row[p] = a.gen_lo[p] > 0. ? a.gen_lo[p] : 1e-9;
-        }
+        MCSAS_INITIAL_ROW(row, n, n < N, false, true, draw_pos, ovf_init)
         Contrib<M> mine;
         mine.prepare(a.model, row);
         for (int l = 0; l < WAVE; ++l) {
@@ -136,8 +122,7 @@ __device__ __forceinline__ void wg_producer(const ChainArgs &a, const WgGeom &g,
     const int N = a.n_contrib, P = a.model.n_active, qpad = a.qpad;
     double *rset = a.rset + (size_t)rep * N * P;
     double *cache = a.cache + (size_t)rep * a.cache_rows * qpad;
-    const DrawSource src{a.replay ? a.replay + (size_t)rep * a.replay_len : nullptr, a.replay_len, a.seed,
-                         (uint32_t)(a.rep_offset + rep)};
+    const DrawSource src MCSAS_CHAIN_DRAWS(a, rep);
     const int rpw = K / NP;
     const bool chain_runs = (N > 1);
     uint64_t draw_pos = 0;
@@ -147,7 +132,7 @@ __device__ __forceinline__ void wg_producer(const ChainArgs &a, const WgGeom &g,
         for (int i = tid; i < 2 * K; i += T) sh.stage_slot[i] = N + i;
         __syncthreads();                                // B0: tables / control words in place
         wg_init_rows<M, QPL>(a, g, sh, src, draw_pos, rset, cache);
-        const uint64_t step_base = draw_pos + (a.start_from_min ? 0 : (uint64_t)N * P);
+        const uint64_t step_base = draw_pos + MCSAS_INITIAL_DRAWS(a, N, P);
         __syncthreads();                                // B1: rows of the initial set are in HBM
 
         // wave w owns window slots k = (w-1) + NP*jj; its m-th row overall is step
@@ -169,13 +154,7 @@ __device__ __forceinline__ void wg_producer(const ChainArgs &a, const WgGeom &g,
                         const int64_t ml = m + lane;
                         const int64_t sl = (ml / rpw) * K + (wave - 1) + (int64_t)NP * (ml % rpw);
                         pov = 0;
-#pragma unroll
-                        for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)
-                            if (p < P) {
-                                double u = 0.5;
-                                if (sl < a.max_iter) u = src.at(step_base + (uint64_t)sl * P + p, pov);
-                                prow[p] = gen_transform(a.gen_kind[p], u) * (a.gen_hi[p] - a.gen_lo[p]) + a.gen_lo[p];
-                            }
+                        MCSAS_PROPOSAL_ROW(prow, step_base + (uint64_t)sl * P, sl < a.max_iter, pov)
                         prop.prepare(a.model, prow);
                     }
                     const int bl = __builtin_amdgcn_readfirstlane((int)(m - m0));
@@ -235,8 +214,7 @@ __device__ __forceinline__ void wg_scanner(const ChainArgs &a, const WgGeom &g, 
     const int N = a.n_contrib, P = a.model.n_active, qpad = a.qpad;
     double *rset = a.rset + (size_t)rep * N * P;
     double *cache = a.cache + (size_t)rep * a.cache_rows * qpad;
-    const DrawSource src{a.replay ? a.replay + (size_t)rep * a.replay_len : nullptr, a.replay_len, a.seed,
-                         (uint32_t)(a.rep_offset + rep)};
+    const DrawSource src MCSAS_CHAIN_DRAWS(a, rep);
     const uint64_t t_start = wall_clock64();
     __builtin_amdgcn_s_setprio(3);                      // the latency-critical wave
     const double invSw = 1.0 / a.Sw, SIoSw = a.SI / a.Sw, Scen = a.SII - a.SI * a.SI / a.Sw;
@@ -256,7 +234,7 @@ __device__ __forceinline__ void wg_scanner(const ChainArgs &a, const WgGeom &g, 
         if (lane == 0) { sh.ctl[CTL_DONE] = 0; sh.ctl[CTL_DONE + 1] = 0; if (attempt == 0) sh.ctl[CTL_OVF] = 0; }
         __syncthreads();                                // B0
         wg_init_rows<M, QPL>(a, g, sh, src, draw_pos, rset, cache);
-        const uint64_t step_base = draw_pos + (a.start_from_min ? 0 : (uint64_t)N * P);
+        const uint64_t step_base = draw_pos + MCSAS_INITIAL_DRAWS(a, N, P);
         __syncthreads();                                // B1
 
         double SC, SIC, SCC;

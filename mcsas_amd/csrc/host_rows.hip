@@ -138,7 +138,7 @@ struct FeedRun {
             HostChain &h = hc[r];
             const int kind = m[2 * R + r];
             if (h.phase == 2 || (m[R + r] == 0 && kind != FEED_END)) continue;
-            if (kind == FEED_INIT) { h.phase = 1; h.num_iter = 0; if (!p->start_from_minimum) h.draw_pos += (uint64_t)N * P; }
+            if (kind == FEED_INIT) { h.phase = 1; h.num_iter = 0; if (!p->start_from_minimum) h.draw_pos += (uint64_t)N * P; }   // the host's MCSAS_INITIAL_DRAWS (chain_common.h)
             h.num_iter = hs[r].num_iter;
             if (hs[r].ended) {                                                  // the attempt is over (mcsas.py:424-439)
                 h.total += h.num_iter; h.draw_pos += (uint64_t)h.num_iter * P;
@@ -185,6 +185,8 @@ static int host_rows_run(const mcsas_problem *p, mcsas_rows_callback rows_cb, vo
         for (size_t r = 0; r < R; ++r) {
             const uint64_t draw_pos = (uint64_t)run.pos()[r];
             const int64_t num_iter = run.pos()[R + r];
+            // host code for what the kernels take from chain_common.h ("how a chain draws": MCSAS_INITIAL_ROW, MCSAS_PROPOSAL_ROW,
+            // draw_value as `generate`) and feed_draw_kernel restates for the device (chain_feed.h)
             for (size_t k = 0; k < (size_t)count[r]; ++k)
                 for (size_t c = 0; c < P; ++c) {
                     double v;

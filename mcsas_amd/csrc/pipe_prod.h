@@ -105,8 +105,7 @@ __device__ __forceinline__ void pipe_prod_block(const PipeArgs &pa, const PipeHo
     if constexpr (RQ) { pipe_prod_rowq<M, QPL>(pa, hot, lds, qt, rep, by, gy, t, sn, own); return; }
     auto rset = glb(a.rset) + (size_t)rep * N * P;
     auto cache = glb(a.cache) + (size_t)rep * a.cache_rows * qpad;
-    const DrawSource src{a.replay ? a.replay + (size_t)rep * a.replay_len : nullptr, a.replay_len, a.seed,
-                         (uint32_t)(a.rep_offset + rep)};
+    const DrawSource src MCSAS_CHAIN_DRAWS(a, rep);
     auto slot_of = glb(pa.slot_of) + (size_t)rep * N;
     auto stage = glb(pa.stage_slot) + (size_t)rep * 2 * Kb;
     auto row_valid = glb(pa.row_valid) + (size_t)rep * N;
@@ -121,21 +120,7 @@ __device__ __forceinline__ void pipe_prod_block(const PipeArgs &pa, const PipeHo
         for (int nb = 0; nb < N; nb += nw * WAVE) {
             const int n = nb + lane * nw + gw;
             double row[MCSAS_MAX_ACTIVE] = {0., 0., 0., 0.};
-            if (n < N) {
-#pragma unroll
-                for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)
-                    if (p < P) {
-                        if (a.start_from_min) row[p] = a.start_value[p];
-                        else {
-                            double u = src.at(sn.init_base + (uint64_t)p * N + n, ovf);
-                            row[p] = gen_transform(a.gen_kind[p], u) * (a.gen_hi[p] - a.gen_lo[p]) + a.gen_lo[p];
-                        }
-                        rset[(size_t)n * P + p] = row[p];
-                    }
-            } else {
-#pragma unroll
-                for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p) row[p] = a.gen_lo[p] > 0. ? a.gen_lo[p] : 1e-9;
-            }
+            MCSAS_INITIAL_ROW(row, n, n < N, false, true, sn.init_base, ovf)
             Contrib<M> mine;
             mine.prepare(a.model, row);
             for (int l = 0; l < WAVE; ++l) {
@@ -254,7 +239,7 @@ __device__ __forceinline__ void pipe_prod_block(const PipeArgs &pa, const PipeHo
                 if (p < P) {
                     double u = 0.5;
                     if (prop_thr && sl < max_iter) u = src.at(sn.step_base + (uint64_t)sl * P + p, pov);
-                    const double pv = gen_transform(a.gen_kind[p], u) * (a.gen_hi[p] - a.gen_lo[p]) + a.gen_lo[p];
+                    const double pv = draw_value(a, p, u);
                     if (!old_thr) prow[p] = pv;
                 }
             Contrib<M> prop;

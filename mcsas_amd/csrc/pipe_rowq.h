@@ -44,8 +44,7 @@ __device__ __forceinline__ void pipe_rowq_visit(const PipeArgs &pa, const PipeHo
     double *lq = lds, *lw = lds + qpad, *lwI = lds + 2 * qpad;
     auto rset = glb(a.rset) + (size_t)rep * N * P;
     auto cache = glb(a.cache) + (size_t)rep * a.cache_rows * qpad;
-    const DrawSource src{a.replay ? a.replay + (size_t)rep * a.replay_len : nullptr, a.replay_len, a.seed,
-                         (uint32_t)(a.rep_offset + rep)};
+    const DrawSource src MCSAS_CHAIN_DRAWS(a, rep);
     auto slot_of = glb(pa.slot_of) + (size_t)rep * N;
     auto stage = glb(pa.stage_slot) + (size_t)rep * 2 * Kb;
     auto row_valid = glb(pa.row_valid) + (size_t)rep * N;
@@ -67,21 +66,7 @@ __device__ __forceinline__ void pipe_rowq_visit(const PipeArgs &pa, const PipeHo
             if (n0 < 0 || n0 >= N) break;
             const int n = n0 + lane;
             double row[MCSAS_MAX_ACTIVE] = {0., 0., 0., 0.};
-            if (lane < CH && n < N) {
-#pragma unroll
-                for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)
-                    if (p < P) {
-                        if (a.start_from_min) row[p] = a.start_value[p];
-                        else {
-                            double u = src.at(sn.init_base + (uint64_t)p * N + n, ovf);
-                            row[p] = gen_transform(a.gen_kind[p], u) * (a.gen_hi[p] - a.gen_lo[p]) + a.gen_lo[p];
-                        }
-                        rset[(size_t)n * P + p] = row[p];
-                    }
-            } else {
-#pragma unroll
-                for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p) row[p] = a.gen_lo[p] > 0. ? a.gen_lo[p] : 1e-9;
-            }
+            MCSAS_INITIAL_ROW(row, n, lane < CH && n < N, false, true, sn.init_base, ovf)
             Contrib<M> mine;
             mine.prepare(a.model, row);
             for (int l = 0; l < CH && n0 + l < N; ++l) {
@@ -110,13 +95,7 @@ __device__ __forceinline__ void pipe_rowq_visit(const PipeArgs &pa, const PipeHo
     for (int k = tid; k < Kb; k += PIPE_BLOCK) {
         double prow[MCSAS_MAX_ACTIVE] = {0., 0., 0., 0.};
         int pov = 0;
-#pragma unroll
-        for (int p = 0; p < MCSAS_MAX_ACTIVE; ++p)
-            if (p < P) {
-                double u = 0.5;
-                if (k < nvalid) u = src.at(sn.step_base + (uint64_t)(s0 + k) * P + p, pov);
-                prow[p] = gen_transform(a.gen_kind[p], u) * (a.gen_hi[p] - a.gen_lo[p]) + a.gen_lo[p];
-            }
+        MCSAS_PROPOSAL_ROW(prow, sn.step_base + (uint64_t)(s0 + k) * P, k < nvalid, pov)
         Contrib<M> prop;
         prop.prepare(a.model, prow);
         double cost = -1.0;                                   // (steps behind max_iter: last)

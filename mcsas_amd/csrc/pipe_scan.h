@@ -503,7 +503,7 @@ __device__ __forceinline__ void pipe_scan_block(const PipeArgs &pa, double *lds,
                 next.attempt = sn.attempt + 1;
                 next.t_init = t + 2;
                 next.init_base = draw_pos;
-                next.step_base = draw_pos + (a.start_from_min ? 0 : (uint64_t)N * P);
+                next.step_base = draw_pos + MCSAS_INITIAL_DRAWS(a, N, P);
                 next.alive = 1;
             }
         }

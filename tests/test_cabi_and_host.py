@@ -317,6 +317,34 @@ def test_chain_body_hooks_are_defined_and_undefined_around_every_inclusion(tmp_p
     assert r.returncode == 0, r.stderr[-4000:]
 
 
+def test_how_a_chain_draws_is_written_once():
+    """The repetition's stream, a uniform's value and the start from the minimum are text of chain_common.h ("how a chain draws");
+    the chain and pipeline headers of every execution mode use it and restate none of it.  Text, comments stripped.  A site that
+    keeps words of its own is named in `left_alone` with the number of occurrences it keeps, so the list cannot grow silently:
+    feed_draw_kernel's one loop serves initial sets and steps, and its `kind` decides; chain_body.inc and chain_sets.h advance
+    draw_pos behind the initial set under `!a.start_from_min`, because MCSAS_INITIAL_DRAWS and a function in its place both
+    changed their kernels' code (profiles/r34_summary.md)."""
+    csrc = os.path.join(ROOT, "mcsas_amd", "csrc")
+    code = lambda text: re.sub(r"//[^\n]*", "", text)
+    names = sorted(n for n in os.listdir(csrc) if re.fullmatch(r"(chain|pipe)_\w+\.(h|inc)", n))
+    assert "chain_common.h" in names and "chain_body.inc" in names and "pipe_prod_overlap.inc" in names and len(names) >= 14, names
+    # file -> {needle: occurrences it keeps}
+    left_alone = {"chain_feed.h": {"start_value[": 1, "start_from_min": 1},
+                  "chain_body.inc": {"start_from_min": 1},
+                  "chain_sets.h": {"start_from_min": 1}}
+    for name in names:
+        text = code(open(os.path.join(csrc, name)).read())
+        for needle in ("gen_transform(", "a.replay +", "start_value[", "start_from_min"):
+            if name == "chain_common.h":
+                assert needle in text, needle
+            else:
+                assert text.count(needle) == left_alone.get(name, {}).get(needle, 0), (name, needle)
+    common = code(open(os.path.join(csrc, "chain_common.h")).read())
+    assert common.count("gen_transform(") == 1 and common.count("a.replay +") == 1
+    assert common.count("start_value[") == 2                   # the field of ChainArgs and MCSAS_INITIAL_ROW
+    assert common.count("start_from_min") == 3                 # the field, MCSAS_INITIAL_DRAWS and MCSAS_INITIAL_ROW
+
+
 def test_committed_counter_profiles_describe_the_committed_kernels():
     """bench.py quotes per-step counters (instructions, memory-side bytes) from the newest profiles/rNN_*.json; tools/pmc_summary.py
     stores a hash of the kernel sources they were taken on, and the bench line reports whether it matches the tree.  Committed state:

@@ -149,7 +149,7 @@ def test_the_kernel_is_a_unit_of_its_own_and_leaves_the_shared_chain_text_alone(
         assert "chain_sets_kernel<MCSAS_M, %d>" % qpl in unit
     text = open(os.path.join(CSRC, "chain_sets.h")).read()
     assert "chain_body.inc\"" not in text and "chain_wave_kernel.inc\"" not in text        # its own chain text, no hook
-    for reused in ("Contrib<M>", "RowEval<M, QPL>", "make_qtables<M>", "gen_transform", "DrawSource", "wave_sum3", "stop_requested", "ChainOut"):
+    for reused in ("Contrib<M>", "RowEval<M, QPL>", "make_qtables<M>", "draw_value", "DrawSource", "wave_sum3", "stop_requested", "ChainOut"):
         assert reused in text, reused
 
 

@@ -1,6 +1,7 @@
 """Every instance of the joint fit's kernel (csrc/chain_sets.h: chain_sets_kernel<M, QPL, SHARED>, 8 built-in models x QPL in
 {1, 2, 4, 8, 16} x 2 scale modes = 80) run on the device against exact chains, and the edges of its chain text.  The kernel carries
-its own chain text and shares none with chain_body.inc: the other families' chain tests say nothing about it.
+its own step, fits and outputs; with chain_body.inc it shares only how a chain draws (chain_common.h: the stream, a uniform's value,
+the initial set, a proposal), so the other families' chain tests say nothing about the rest of it.
 
 Against the float64 restatement (tests/sets_exact.py, tests/sets_shared_exact.py) on the generated inputs sets_exact.GENERATED:
 tests/test_sets_host.py and tests/test_sets_shared_host.py hold every one of them to a decisive margin at every step, and
