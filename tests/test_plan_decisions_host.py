@@ -4,7 +4,8 @@ No GPU, nothing loaded into this process.  The recorded plan shapes (tests/golde
 decide_shape with the recording's CU count; the free-memory gate of MCSAS_EXEC_AUTO, which no device of the library's own kind
 exercises, is checked at its threshold; the family table, the trace block's layout and the tick budget against values worked
 out by hand.  Of a joint fit of several sets (mcsas_hip_analyse_sets): where the sets lie in the padded vectors, the vectors and
-each set's constants, its refusals; of every chain run the settings block of the kernels' arguments."""
+each set's constants, its refusals; of every chain run the settings block of the kernels' arguments; of the wave and q-split instance
+matrix (tests/instance_cases.py) the mode, slot count and wave count of every shape."""
 import json
 import os
 import shutil
@@ -142,6 +143,30 @@ def generated_sets_layouts(check):
     assert (int(full[1]), int(full[3], 16) >> 15) == (16, 1)                  # bit 15 of end_mask, no padding slot
 
 
+def instance_matrix_shapes(check):
+    """Every shape of the wave and q-split instance matrix (tests/instance_cases.py; tests/test_instances_gpu.py) selects the mode, the
+    slot count and the wave count its name says.  (The row cache is the device's: Plan.info confirms it there.)"""
+    import instance_cases as IC
+    want, lines = {}, []
+    for tag, qpl, cache in IC.WAVE:
+        name, nq = "wave_%s_q%d_c%d" % (tag, qpl, cache), IC.wave_nq(qpl)
+        want[name] = ("wave", 1, qpl)
+        lines.append(problem_line(name, IC.models(tag)[0], *IC.data(nq), IC.engine_settings(tag, nq, engine.EXEC_WAVE, cache)))
+    for tag, qpl, shape in IC.WIDE:
+        name, (nq, waves) = "wide_%s_q%d_%s" % (tag, qpl, shape), IC.WIDE_SHAPES[qpl][shape]
+        want[name] = ("workgroup", waves, qpl)
+        lines.append(problem_line(name, IC.models(tag)[0], *IC.data(nq), IC.engine_settings(tag, nq, engine.EXEC_WORKGROUP)))
+    assert len(want) == len(lines) == 96 + 45
+    got = {}
+    for line in check("shapes", text="".join(lines)).splitlines():
+        name, kind, rest = line.split(" ", 2)
+        assert kind == "shape", line
+        mode, waves, got_qpl, _ = (int(x) for x in rest.split())
+        got[name] = (MODE_NAMES[mode], waves, got_qpl)
+        print(name, "->", *got[name])
+    assert got == want, sorted(n for n in want if got.get(n) != want[n])
+
+
 def sets_refusals(check):
     """Every row of test_sets_host.REFUSALS through the function that makes them, in the stand-alone program: the same words."""
     from test_sets_host import REFUSALS, _request
@@ -169,6 +194,7 @@ def test_plan_decisions_without_a_device(tmp_path):
     assert check().strip() == "ok"
     sets_layouts(check)
     generated_sets_layouts(check)
+    instance_matrix_shapes(check)
     sets_refusals(check)
     recorded_plan_shapes(check)
     free_memory_gate(check)
